@@ -12,8 +12,13 @@ query with 6 % substitution draws / 2 % deletions / 2 % insertions, band w=128, 
 (BASELINE configs[3]) sharded over the ranks by cells (sedef_amd.dist.shard_tasks), every rank aligns its shard, every
 rank receives every rank's results, and rank 0 checks the union against a single-GPU run of the whole batch.
 
-Prints ONE JSON line (rank 0).  `value` = in-band cells of all ranks / max-over-ranks time; `value_incl_pcie` adds the
-H2D of the packed sequences (untimed extra passes, single GPU).
+Prints ONE JSON line (rank 0).  `value` = in-band cells of all ranks / max-over-ranks time; `ms_per_step` = the wall
+time of one timed step.  A plain run sets up, warms up, times --steps steps and prints that line; everything else it can
+measure or check is an untimed extra behind --full: `value_incl_pcie` (adds the H2D of the packed sequences, single
+GPU), `value_one_call_in_flight`, the roofline block (an isolated launch and a copy-bandwidth run), the CPU baseline, the
+spot check against the CPU checker, the `stage` block, and at N > 1 the checks of the gathered results.
+`--dump-outputs DIR`: rank 0's results of the last timed step as .npy files (dump_outputs); the inputs depend only on
+the arguments, so two builds can be compared output for output.
 """
 import argparse
 import os
@@ -318,6 +323,39 @@ def spot_check(pool, q_off, qlen, t_off, tlen, w, res, cigs, n_sample=64, seed=7
     return {"tasks": int(len(idx)), "checker": kind, "compared": "score + every CIGAR word of the last timed step", "ok": True}
 
 
+# the result-record fields the timed path produces (want = CIGAR + score, include/sedef_hip.h: SDF_WANT_CIGAR /
+# SDF_WANT_SCORE); max, max_q, max_t, mqe and mqe_t are not computed there, cigar_off is where a CIGAR lies in the buffer
+DUMP_FIELDS = ("score", "mte", "mte_q", "zdropped", "n_cigar", "matches", "mismatches", "gaps", "gap_bases")
+
+
+def dump_outputs(d, res, cigs, qlen, tlen, record_bytes=16000000, cigar_bytes=47000000, seed=20240601):
+    """--dump-outputs: what the caller of the timed path received in the last timed step, as float64 .npy files under `d`
+    (every value is an int32 or a uint32: exact in float64), at most 64 * 10^6 bytes in all.
+      task.npy       the tasks whose records are dumped: all of them if their fields fit in `record_bytes`, else a fixed
+                     sample (a prefix of a permutation seeded by `seed`, which depends on the batch size alone), ascending
+      <field>.npy    one value per dumped task, for every field in DUMP_FIELDS
+      cigar_task.npy the tasks whose CIGARs are dumped: the longest prefix of the same permutation whose CIGARs and
+                     indices surely fit in `cigar_bytes` (a CIGAR has at most qlen + tlen runs), ascending; a subset of
+                     task.npy
+      cigar.npy      their CIGAR words (length << 4 | op) one task after the other; n_cigar.npy gives the lengths
+    The sample depends on the inputs only, so two builds' dumps of the same arguments compare file by file."""
+    os.makedirs(d, exist_ok=True)
+    n = len(res)
+    perm = np.random.default_rng(seed).permutation(n)
+    k_rec = min(n, record_bytes // (8 * (len(DUMP_FIELDS) + 1)))
+    bound = 8 * (qlen[perm[:k_rec]].astype(np.int64) + tlen[perm[:k_rec]] + 2)
+    k_cig = int(np.searchsorted(np.cumsum(bound), cigar_bytes, side="right"))
+    rec_tasks = np.sort(perm[:k_rec]) if k_rec < n else np.arange(n)
+    cig_tasks = np.sort(perm[:k_cig])
+    np.save(os.path.join(d, "task.npy"), rec_tasks.astype(np.float64))
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(d, f + ".npy"), res[f][rec_tasks].astype(np.float64))
+    np.save(os.path.join(d, "cigar_task.npy"), cig_tasks.astype(np.float64))
+    off, cnt = res["cigar_off"][cig_tasks].astype(np.int64), res["n_cigar"][cig_tasks].astype(np.int64)
+    idx = np.repeat(off - (np.cumsum(cnt) - cnt), cnt) + np.arange(int(cnt.sum()))
+    np.save(os.path.join(d, "cigar.npy"), cigs[idx].astype(np.float64))
+
+
 
 def stage_block(budget_s=120.0):
     """The STAGE the north star calls the drop-in (`sedef align generate`, reference: src/align_main.cc:285-337), untimed
@@ -577,10 +615,17 @@ def main():
     ap.add_argument("--workspace-gib", type=float, default=48.0)
     ap.add_argument("--inflight", type=int, default=2,
                     help="batch calls in flight, each on a device context and host thread of its own (1: one call after the other)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the untimed extras after the timed steps: PCIe and one-call passes, roofline (isolated launch, "
+                         "copy bandwidth), CPU baseline, spot check, stage block, checks of the gathered results at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's results of the last timed step to DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
     args.inflight = max(1, min(3, args.inflight))
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher: this process starts the N ranks itself -- before anything here
         # has touched the GPU (no torch import, no HIP call so far: a process that has initialised the GPU must not
@@ -790,8 +835,10 @@ def main():
     lb = (step_no[0] - 1) % nsets
     res = h_outs[lb].numpy().view(sedef_amd.RESULT_DTYPE)
     assert int(res["n_cigar"].astype(np.int64).sum()) == used  # what came over PCIe is the whole result
+    if args.dump_outputs and rank == 0:  # (before the extras below: their passes reuse buffer set 0)
+        dump_outputs(args.dump_outputs, res, h_cigs[lb].numpy().view(np.uint32), qlen, tlen)
     union_check = None
-    if gathers:  # every rank holds every rank's results: this rank's own part of the last gather is what it computed
+    if gathers and args.full:  # every rank holds every rank's results: this rank's own part of the last gather is what it computed
         pr, pc = gathers[lb].part(rank)
         assert torch.equal(pr.cpu(), h_outs[lb]) and torch.equal(pc.cpu(), h_cigs[lb][:used])
         if gathers[lb].loopback:  # what came back through the send / receive pair is what went out
@@ -818,95 +865,7 @@ def main():
             union_check = "CIGAR+score checksum of all %d tasks: union of %d shards == single-GPU run" % (len(wqlen), world)
             del wd_pool, wd_out, wd_cig
     if rank == 0:
-        alg = algorithmic_bytes(qlen, tlen, cells_task, res["n_cigar"])
-        # Roofline of the dominant kernel.  The timed steps above run the batch as a pipeline of chunks whose DP
-        # launches overlap each other and the traceback, so a launch's own duration is taken from one extra,
-        # untimed pass of the same batch through a context created with pipeline = 0 (sdf_config): the whole batch in ONE
-        # DP launch on one stream, HIP events around it on that stream (sdf_last_ms(0)).  The committed rocprofv3
-        # summary (profiles/) is of `SDF_PIPELINE=0 python bench.py ...`, the same launch.
-        iso_ms, iso_launches = dp_ms / max(args.steps, 1), max(launches // max(args.steps, 1), 1)
-        roof_mode = "pipelined launches (union of the DP intervals)"
-        headline = world == 1 and not hg19
-        if headline:
-            iso = sedef_amd.Extz2Engine(local, int(args.workspace_gib * (1 << 30)), config=dict(SDF_PIPELINE=0))
-            for _ in range(2):  # warm-up + measured
-                iso.align_batch_device(tasks, d_pool.data_ptr(), d_outs[0].data_ptr(), d_cigs[0].data_ptr(), cig_cap,
-                                       want=want, stream=estream.cuda_stream)
-            iso_ms, iso_launches = iso.last_ms(0), max(iso.last_launches(), 1)
-            roof_mode = "one isolated DP launch of the whole batch (SDF_PIPELINE=0 pass, untimed)"
-            del iso
-        avg_launch_s = iso_ms / 1e3 / iso_launches
-        bytes_per_launch = alg / iso_launches
-        achieved = bytes_per_launch / avg_launch_s / 1e9
-        traffic = None
-        valu = None
-        traffic_note = None
-        tp = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tp) and headline and n == 100000 and w == 128 and args.qlen == 1000:
-            # NOT measured in this run: read from the committed rocprofv3 PMC passes of this exact workload and launch
-            # (profiles/README.md, profiles/collect.sh)
-            pmc = json.load(open(tp))
-            # ... and only while the kernel they were taken on is the kernel that ran: the JSON carries the sha256 of
-            # extz2_pair.hip at collection time (profiles/make_traffic_json.py); after any edit of that file the
-            # counters are stale and the line says null until profiles/collect.sh has run again
-            stale = pmc.get("kernel_source_sha256") != source_sha256("sedef_amd/csrc/extz2_pair.hip")
-            traffic_note = "profiles/hbm_traffic.json is older than sedef_amd/csrc/extz2_pair.hip: counters dropped" if stale else None
-            if not stale:
-                traffic = pmc.get("bytes_per_step") / iso_launches
-            if not stale and pmc.get("valu_insts_per_step"):
-                # What actually bounds the launch: VALU issue.  Counted wavefront VALU instructions over what the SIMDs can
-                # issue in the launch's live-measured duration, against BOTH rates: one per 2 cycles (MI355X_MICROARCH.md:
-                # wave64 on a SIMD-32) and one per 4.2 cycles (the measured rate of the VOP3P / VOP3 / DPP encodings
-                # that make up the row, profiles/r01_ubench_issue_rates.txt; VOP2 issues at 2.5)
-                props = torch.cuda.get_device_properties(local)
-                simds = props.multi_processor_count * 4
-                mhz = (getattr(props, "clock_rate", 0) or 2400000) / 1e3  # (2.4 GHz: MI355X peak engine clock)
-                cycles = simds * mhz * 1e6 * avg_launch_s * iso_launches
-                valu = {"insts_per_step": pmc["valu_insts_per_step"], "simds": simds, "clock_mhz": round(mhz, 1),
-                        "frac_of_issue_peak_2cyc": round(pmc["valu_insts_per_step"] / (cycles / 2.0), 4),
-                        "frac_of_issue_peak_4cyc": round(pmc["valu_insts_per_step"] / (cycles / 4.0), 4),
-                        "frac_of_issue_peak_4p2cyc_measured_vop3p": round(pmc["valu_insts_per_step"] / (cycles / 4.2), 4),
-                        "steady_row_by_encoding": encoding_split(),
-                        "source": "committed profile: " + str(pmc.get("valu_source"))}
         value = cells_all * args.steps / dt / 1e9
-        with torch.cuda.stream(estream):
-            peak_measured = measured_copy_bandwidth(dev)
-        # End to end over PCIe (never `value`): H2D of the packed sequences, the batch, D2H of the results, back to back
-        # without overlap, untimed extra passes (include/sedef_hip.h: sdf_extz2_batch is this plus packing on the host)
-        incl_pcie = None
-        if world == 1 and not args.no_pcie_pass:
-            h_pool = torch.from_numpy(words.view(np.int32)).pin_memory()
-            d_pool2 = torch.empty_like(d_pool)
-            times = []
-            for _ in range(3):
-                torch.cuda.synchronize()
-                tp0 = time.perf_counter()
-                with torch.cuda.stream(estream):
-                    d_pool2.copy_(h_pool, non_blocking=True)
-                    estream.synchronize()
-                    u2 = eng.align_batch_device(tasks, d_pool2.data_ptr(), d_outs[0].data_ptr(), d_cigs[0].data_ptr(),
-                                                cig_cap, want=want, stream=estream.cuda_stream)
-                    h_outs[0].copy_(d_outs[0], non_blocking=True)
-                    h_cigs[0][:u2].copy_(d_cigs[0][:u2], non_blocking=True)
-                    estream.synchronize()
-                times.append(time.perf_counter() - tp0)
-            incl_pcie = round(cells_rank / min(times[1:]) / 1e9, 3)
-        # One call at a time (what `--inflight 1` measures as `value`): the latency-bound figure next to the throughput one,
-        # untimed extra -- every call returns when its stream has drained, its results go out over pinned D2H like in the
-        # timed steps, all waited for inside the clock
-        one_call = None
-        if world == 1 and len(engs) > 1:
-            k1 = max(3, min(args.steps, 10))
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(k1):
-                u1 = engs[0].align_batch_device(tasks, d_pool.data_ptr(), d_outs[0].data_ptr(), d_cigs[0].data_ptr(), cig_cap,
-                                                want=want, stream=estreams[0].cuda_stream)
-                with torch.cuda.stream(cstream):
-                    h_outs[0].copy_(d_outs[0], non_blocking=True)
-                    h_cigs[0][:u1].copy_(d_cigs[0][:u1], non_blocking=True)
-            torch.cuda.synchronize()
-            one_call = round(cells_rank * k1 / (time.perf_counter() - t1) / 1e9, 3)
         if hg19:
             wl = ("configs[3]: hg19-shaped task mixture, %d DP tasks %s, all w=-1 (59 %% <=100 cells, 40 %% <=1e4, 1.2 %% "
                   "500x500, 0.06 %% <=1000^2, 0.06 %% up to 6000^2), affine gap 5/-4/40/1, CIGAR+score+counts"
@@ -920,8 +879,6 @@ def main():
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "i8",
             "data": "synthetic",
-            "value_incl_pcie": incl_pcie,
-            "value_one_call_in_flight": one_call,
             "timed_region": "planning + DP + traceback + CIGAR compaction + result D2H (pinned, double-buffered under the "
                             "next step)" + (" + all-gatherv of records and CIGARs" if dist_on else "") +
                             ("; two batch calls in flight on two device contexts: a step's planning and tail run under the "
@@ -943,56 +900,149 @@ def main():
                                    "compact": round(cp_ms / args.steps, 3),
                                    "host_planning": round(plan_ms / args.steps, 3),
                                    "host_call_total": round(call_ms / args.steps, 3)},
-            # `bound` / `achieved` / `peak` / `frac` are the HBM roofline SURVEY 8(d) defines for this path (algorithmic bytes
-            # over the launch's duration).  It is NOT what limits the launch: `binding_limit` says what does -- the vector
-            # ALUs' issue slots, from the launch's counted VALU instructions at the measured issue cost of their encodings.
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "binding_limit": ({"bound": "valu_issue", "frac": valu["frac_of_issue_peak_4cyc"],
-                                            "how": "counted wavefront VALU instructions of the launch x 4 cycles (a wave64 vector "
-                                                   "instruction holds its SIMD's ALU for four cycles: the rate every DP launch "
-                                                   "of this library that fills the device was measured at, profiles/"
-                                                   "r06_chain_pmc.txt; a lone stream of packed / VOP3 / DPP encodings was "
-                                                   "measured at 4.2, valu_issue.frac_of_issue_peak_4p2cyc_measured_vop3p) over "
-                                                   "SIMDs x nominal clock x the launch's live-measured duration; 1.0 = every "
-                                                   "issue slot of every SIMD taken",
-                                            "hbm_frac_is": "%.2f of the HBM peak because the kernel is bound elsewhere: its HBM "
-                                                           "traffic (`traffic`) is %.2f x the algorithmic bytes, nothing is re-read "
-                                                           "(what exceeds 1.0 is register spills at the starts of 16-row blocks)"
-                                                           % (achieved / HBM_PEAK_GBS, (traffic or 0) / max(bytes_per_launch, 1))}
-                                           if valu else {"bound": "valu_issue", "frac": None,
-                                                         "how": "no committed counters for this workload / kernel source (see "
-                                                                "traffic_source); the DP kernels of this path are VALU-issue "
-                                                                "bound on every profiled shape (DESIGN.md 5)"}),
-                         "peak_measured": round(peak_measured, 1), "frac_of_measured": round(achieved / peak_measured, 5),
-                         "peak_measured_how": "device-to-device copy of 1 GiB in this run, read + write bytes over the best of 5",
-                         "traffic": traffic,
-                         "traffic_source": ("committed profile (profiles/hbm_traffic.json), not measured in this run" if traffic
-                                            else traffic_note),
-                         "kernel": "extz2_pair_kernel<3> (extz2 DP)" if not hg19 else "all DP launches of the mixture",
-                         "measured_on": roof_mode,
-                         "launches": iso_launches, "avg_launch_ms": round(avg_launch_s * 1e3, 4),
-                         "algorithmic_bytes_per_launch": int(bytes_per_launch), "valu_issue": valu},
         }
-        if not args.no_cpu_baseline:
-            # (at every N: rank 0's shard on this box's host cores while the other ranks wait at the barrier below -- the
-            # ratio to quote is value / cpu_baseline.value per cpu_baseline.cores cores)
-            cb = cpu_baseline(pool, q_off, qlen, t_off, tlen, cells_task, w)
-            line["cpu_baseline"] = cb
-            # the north star's ">= 50 x per node" needs a stated denominator: the measured one is `cores` host cores (a
-            # cgroup quota on this pool); the whole-host figure is a LINEAR projection from the per-core rate
-            per_gpu = value / world
-            line["vs_cpu"] = {
-                "x_per_cpu_cores_measured": round(value / cb["value"], 2), "measured_on_cores": cb["cores"],
-                "whole_host_linear_projection_gcells": round(cb["per_core"] * cb["host_cores_total"], 3),
-                "x_vs_whole_host_linear_projection": round(value / (cb["per_core"] * cb["host_cores_total"]), 3),
-                "x_vs_whole_host_at_8_gpus_if_linear": round(8 * per_gpu / (cb["per_core"] * cb["host_cores_total"]), 2),
-                "note": "value / cpu_baseline.value is per `measured_on_cores` cores; the projections assume the reference "
-                        "kernel scales linearly to host_cores_total logical CPUs and the GPUs to 8 (neither measured here)"}
-        if world == 1 and os.environ.get("BENCH_NO_SPOT_CHECK") != "1":
-            line["spot_check"] = spot_check(pool, q_off, qlen, t_off, tlen, w, res, h_cigs[lb].numpy().view(np.uint32))
-        if headline and not args.no_stage and os.environ.get("BENCH_NO_STAGE") != "1":
-            line["stage"] = stage_block()
+        if args.full:  # the untimed extras: none of them is part of `value` or `ms_per_step`
+            alg = algorithmic_bytes(qlen, tlen, cells_task, res["n_cigar"])
+            # Roofline of the dominant kernel.  The timed steps above run the batch as a pipeline of chunks whose DP
+            # launches overlap each other and the traceback, so a launch's own duration is taken from one extra,
+            # untimed pass of the same batch through a context created with pipeline = 0 (sdf_config): the whole batch in ONE
+            # DP launch on one stream, HIP events around it on that stream (sdf_last_ms(0)).  The committed rocprofv3
+            # summary (profiles/) is of `SDF_PIPELINE=0 python bench.py ...`, the same launch.
+            iso_ms, iso_launches = dp_ms / max(args.steps, 1), max(launches // max(args.steps, 1), 1)
+            roof_mode = "pipelined launches (union of the DP intervals)"
+            headline = world == 1 and not hg19
+            if headline:
+                iso = sedef_amd.Extz2Engine(local, int(args.workspace_gib * (1 << 30)), config=dict(SDF_PIPELINE=0))
+                for _ in range(2):  # warm-up + measured
+                    iso.align_batch_device(tasks, d_pool.data_ptr(), d_outs[0].data_ptr(), d_cigs[0].data_ptr(), cig_cap,
+                                           want=want, stream=estream.cuda_stream)
+                iso_ms, iso_launches = iso.last_ms(0), max(iso.last_launches(), 1)
+                roof_mode = "one isolated DP launch of the whole batch (SDF_PIPELINE=0 pass, untimed)"
+                del iso
+            avg_launch_s = iso_ms / 1e3 / iso_launches
+            bytes_per_launch = alg / iso_launches
+            achieved = bytes_per_launch / avg_launch_s / 1e9
+            traffic = None
+            valu = None
+            traffic_note = None
+            tp = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            if os.path.exists(tp) and headline and n == 100000 and w == 128 and args.qlen == 1000:
+                # NOT measured in this run: read from the committed rocprofv3 PMC passes of this exact workload and launch
+                # (profiles/README.md, profiles/collect.sh)
+                pmc = json.load(open(tp))
+                # ... and only while the kernel they were taken on is the kernel that ran: the JSON carries the sha256 of
+                # extz2_pair.hip at collection time (profiles/make_traffic_json.py); after any edit of that file the
+                # counters are stale and the line says null until profiles/collect.sh has run again
+                stale = pmc.get("kernel_source_sha256") != source_sha256("sedef_amd/csrc/extz2_pair.hip")
+                traffic_note = "profiles/hbm_traffic.json is older than sedef_amd/csrc/extz2_pair.hip: counters dropped" if stale else None
+                if not stale:
+                    traffic = pmc.get("bytes_per_step") / iso_launches
+                if not stale and pmc.get("valu_insts_per_step"):
+                    # What actually bounds the launch: VALU issue.  Counted wavefront VALU instructions over what the SIMDs can
+                    # issue in the launch's live-measured duration, against BOTH rates: one per 2 cycles (MI355X_MICROARCH.md:
+                    # wave64 on a SIMD-32) and one per 4.2 cycles (the measured rate of the VOP3P / VOP3 / DPP encodings
+                    # that make up the row, profiles/r01_ubench_issue_rates.txt; VOP2 issues at 2.5)
+                    props = torch.cuda.get_device_properties(local)
+                    simds = props.multi_processor_count * 4
+                    mhz = (getattr(props, "clock_rate", 0) or 2400000) / 1e3  # (2.4 GHz: MI355X peak engine clock)
+                    cycles = simds * mhz * 1e6 * avg_launch_s * iso_launches
+                    valu = {"insts_per_step": pmc["valu_insts_per_step"], "simds": simds, "clock_mhz": round(mhz, 1),
+                            "frac_of_issue_peak_2cyc": round(pmc["valu_insts_per_step"] / (cycles / 2.0), 4),
+                            "frac_of_issue_peak_4cyc": round(pmc["valu_insts_per_step"] / (cycles / 4.0), 4),
+                            "frac_of_issue_peak_4p2cyc_measured_vop3p": round(pmc["valu_insts_per_step"] / (cycles / 4.2), 4),
+                            "steady_row_by_encoding": encoding_split(),
+                            "source": "committed profile: " + str(pmc.get("valu_source"))}
+            with torch.cuda.stream(estream):
+                peak_measured = measured_copy_bandwidth(dev)
+            # End to end over PCIe (never `value`): H2D of the packed sequences, the batch, D2H of the results, back to back
+            # without overlap, untimed extra passes (include/sedef_hip.h: sdf_extz2_batch is this plus packing on the host)
+            incl_pcie = None
+            if world == 1 and not args.no_pcie_pass:
+                h_pool = torch.from_numpy(words.view(np.int32)).pin_memory()
+                d_pool2 = torch.empty_like(d_pool)
+                times = []
+                for _ in range(3):
+                    torch.cuda.synchronize()
+                    tp0 = time.perf_counter()
+                    with torch.cuda.stream(estream):
+                        d_pool2.copy_(h_pool, non_blocking=True)
+                        estream.synchronize()
+                        u2 = eng.align_batch_device(tasks, d_pool2.data_ptr(), d_outs[0].data_ptr(), d_cigs[0].data_ptr(),
+                                                    cig_cap, want=want, stream=estream.cuda_stream)
+                        h_outs[0].copy_(d_outs[0], non_blocking=True)
+                        h_cigs[0][:u2].copy_(d_cigs[0][:u2], non_blocking=True)
+                        estream.synchronize()
+                    times.append(time.perf_counter() - tp0)
+                incl_pcie = round(cells_rank / min(times[1:]) / 1e9, 3)
+            # One call at a time (what `--inflight 1` measures as `value`): the latency-bound figure next to the throughput one,
+            # untimed extra -- every call returns when its stream has drained, its results go out over pinned D2H like in the
+            # timed steps, all waited for inside the clock
+            one_call = None
+            if world == 1 and len(engs) > 1:
+                k1 = max(3, min(args.steps, 10))
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(k1):
+                    u1 = engs[0].align_batch_device(tasks, d_pool.data_ptr(), d_outs[0].data_ptr(), d_cigs[0].data_ptr(), cig_cap,
+                                                    want=want, stream=estreams[0].cuda_stream)
+                    with torch.cuda.stream(cstream):
+                        h_outs[0].copy_(d_outs[0], non_blocking=True)
+                        h_cigs[0][:u1].copy_(d_cigs[0][:u1], non_blocking=True)
+                torch.cuda.synchronize()
+                one_call = round(cells_rank * k1 / (time.perf_counter() - t1) / 1e9, 3)
+            line.update({
+                "value_incl_pcie": incl_pcie,
+                "value_one_call_in_flight": one_call,
+                # `bound` / `achieved` / `peak` / `frac` are the HBM roofline SURVEY 8(d) defines for this path (algorithmic bytes
+                # over the launch's duration).  It is NOT what limits the launch: `binding_limit` says what does -- the vector
+                # ALUs' issue slots, from the launch's counted VALU instructions at the measured issue cost of their encodings.
+                "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5),
+                             "binding_limit": ({"bound": "valu_issue", "frac": valu["frac_of_issue_peak_4cyc"],
+                                                "how": "counted wavefront VALU instructions of the launch x 4 cycles (a wave64 vector "
+                                                       "instruction holds its SIMD's ALU for four cycles: the rate every DP launch "
+                                                       "of this library that fills the device was measured at, profiles/"
+                                                       "r06_chain_pmc.txt; a lone stream of packed / VOP3 / DPP encodings was "
+                                                       "measured at 4.2, valu_issue.frac_of_issue_peak_4p2cyc_measured_vop3p) over "
+                                                       "SIMDs x nominal clock x the launch's live-measured duration; 1.0 = every "
+                                                       "issue slot of every SIMD taken",
+                                                "hbm_frac_is": "%.2f of the HBM peak because the kernel is bound elsewhere: its HBM "
+                                                               "traffic (`traffic`) is %.2f x the algorithmic bytes, nothing is re-read "
+                                                               "(what exceeds 1.0 is register spills at the starts of 16-row blocks)"
+                                                               % (achieved / HBM_PEAK_GBS, (traffic or 0) / max(bytes_per_launch, 1))}
+                                               if valu else {"bound": "valu_issue", "frac": None,
+                                                             "how": "no committed counters for this workload / kernel source (see "
+                                                                    "traffic_source); the DP kernels of this path are VALU-issue "
+                                                                    "bound on every profiled shape (DESIGN.md 5)"}),
+                             "peak_measured": round(peak_measured, 1), "frac_of_measured": round(achieved / peak_measured, 5),
+                             "peak_measured_how": "device-to-device copy of 1 GiB in this run, read + write bytes over the best of 5",
+                             "traffic": traffic,
+                             "traffic_source": ("committed profile (profiles/hbm_traffic.json), not measured in this run" if traffic
+                                                else traffic_note),
+                             "kernel": "extz2_pair_kernel<3> (extz2 DP)" if not hg19 else "all DP launches of the mixture",
+                             "measured_on": roof_mode,
+                             "launches": iso_launches, "avg_launch_ms": round(avg_launch_s * 1e3, 4),
+                             "algorithmic_bytes_per_launch": int(bytes_per_launch), "valu_issue": valu},
+            })
+            if not args.no_cpu_baseline:
+                # (at every N: rank 0's shard on this box's host cores while the other ranks wait at the barrier below -- the
+                # ratio to quote is value / cpu_baseline.value per cpu_baseline.cores cores)
+                cb = cpu_baseline(pool, q_off, qlen, t_off, tlen, cells_task, w)
+                line["cpu_baseline"] = cb
+                # the north star's ">= 50 x per node" needs a stated denominator: the measured one is `cores` host cores (a
+                # cgroup quota on this pool); the whole-host figure is a LINEAR projection from the per-core rate
+                per_gpu = value / world
+                line["vs_cpu"] = {
+                    "x_per_cpu_cores_measured": round(value / cb["value"], 2), "measured_on_cores": cb["cores"],
+                    "whole_host_linear_projection_gcells": round(cb["per_core"] * cb["host_cores_total"], 3),
+                    "x_vs_whole_host_linear_projection": round(value / (cb["per_core"] * cb["host_cores_total"]), 3),
+                    "x_vs_whole_host_at_8_gpus_if_linear": round(8 * per_gpu / (cb["per_core"] * cb["host_cores_total"]), 2),
+                    "note": "value / cpu_baseline.value is per `measured_on_cores` cores; the projections assume the reference "
+                            "kernel scales linearly to host_cores_total logical CPUs and the GPUs to 8 (neither measured here)"}
+            if world == 1 and os.environ.get("BENCH_NO_SPOT_CHECK") != "1":
+                line["spot_check"] = spot_check(pool, q_off, qlen, t_off, tlen, w, res, h_cigs[lb].numpy().view(np.uint32))
+            if headline and not args.no_stage and os.environ.get("BENCH_NO_STAGE") != "1":
+                line["stage"] = stage_block()
         print(json.dumps(line))
     if dist_on:
         dist.barrier(group=quiet) if quiet is not None else dist.barrier()

@@ -6,7 +6,7 @@ cp sedef_amd/lib/libsedef_hip.so /tmp/keep.so
 for rep in 1 2 3; do
   for v in "$@"; do
     cp sedef_amd/lib/ab/$v.so sedef_amd/lib/libsedef_hip.so
-    python3 bench.py --no-stage --no-cpu-baseline --no-pcie-pass --steps 10 --warmup 3 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
+    python3 bench.py --full --no-stage --no-cpu-baseline --no-pcie-pass --steps 10 --warmup 3 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$v', d['value'], d['value_one_call_in_flight'], d['roofline']['avg_launch_ms'], d['spot_check']['ok'])"
   done

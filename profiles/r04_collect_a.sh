@@ -12,7 +12,7 @@ out=gpurun_out/r04a
 mkdir -p $out
 rocprofv3 -L > $out/counters_all.txt 2>&1
 grep -o "SQ_[A-Z0-9_]*\|GRBM_[A-Z0-9_]*\|TCC_[A-Z0-9_]*" $out/counters_all.txt | sort -u > $out/counter_names.txt
-B1="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-pcie-pass"
+B1="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-pcie-pass"
 pmc() {  # pmc <dir> <counters...> -- <cmd...>
   d=$1; shift
   ctr=()
@@ -44,7 +44,7 @@ M3="python3 profiles/mix_probe.py mm8 3000"
 SDF_DEBUG_CLASSES=1 $M3 > $out/mm8_3k_classes.log 2> $out/mm8_3k_classes.err
 grep "^\[class" $out/mm8_3k_classes.err > $out/mm8_3k_classes.txt
 # ---- 3. hg19 mixture: bench line with its own cpu_baseline; its classes; PMC of its kernels ----
-python3 bench.py --workload hg19mix --tasks 1000000 --steps 10 --warmup 3 --no-pcie-pass > $out/hg19_bench.log 2>&1
+python3 bench.py --full --workload hg19mix --tasks 1000000 --steps 10 --warmup 3 --no-pcie-pass > $out/hg19_bench.log 2>&1
 tail -1 $out/hg19_bench.log > $out/hg19_bench.json
 H="python3 profiles/mix_probe.py hg19 1000000"
 SDF_DEBUG_CLASSES=1 $H > $out/hg19_classes.log 2> $out/hg19_classes.err
@@ -53,7 +53,7 @@ pmc hg19_sq SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES S
 pmc hg19_fetch FETCH_SIZE -- $H
 pmc hg19_write WRITE_SIZE -- $H
 # ---- 4. the default bench line on this box ----
-python3 bench.py > $out/bench_default.log 2>&1
+python3 bench.py --full > $out/bench_default.log 2>&1
 tail -1 $out/bench_default.log > $out/bench_default.json
 ls -la $out
 cat $out/pmc_sq1.txt $out/pmc_sq3.txt $out/pmc_grbm.txt | grep "pair_kernel<3"

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp GPU_MAX_HW_QUEUES=8
 out=gpurun_out/r06start; mkdir -p $out
 timeout 900 python3 -m pytest tests -m gpu -x -q > $out/gputest.txt 2>&1; tail -3 $out/gputest.txt
-timeout 300 python3 bench.py > $out/bench.json 2> $out/bench.err; cut -c1-300 $out/bench.json
+timeout 300 python3 bench.py --full > $out/bench.json 2> $out/bench.err; cut -c1-300 $out/bench.json
 timeout 600 python3 profiles/stage_bench.py --chr1 --one-bucket 3 > $out/stage.txt 2>&1; grep "^run" $out/stage.txt
 d=$(ls -d /tmp/sdf_stage_* | head -1)
 SDF_DEBUG_TIMING=1 sedef_amd/bin/sedef align generate -k 11 $d/genome.fa $d/buckets/bucket_0000 > /tmp/o.bed 2> $out/stage_dbg.log

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/stage_pairs_kat.json.gz: what the REFERENCE produces for candidate pairs and whole bucket files.
+"""Generates tests/golden/stage_pairs_kat.json.xz: what the REFERENCE produces for candidate pairs and whole bucket files.
 
 Build container only.  src/chain.cc, src/refine.cc and src/align_main.cc cannot be compiled here (Boost.ICL through
 src/search.h:22-23), so the control flow of fast_align / chain_anchors' sweep / refine_chains / the driver's ordering and
@@ -19,8 +19,8 @@ Sections (inputs and expected outputs only):
              sweep run on the reference's own SegmentTree.
   stages  -- FASTA + .fai + bucket file -> the exact stdout of `sedef align generate`.
 """
-import gzip
 import json
+import lzma
 import os
 import sys
 import tempfile
@@ -82,16 +82,16 @@ def synthetic_chains(ref):
 
 def write(out, obj):
     blob = json.dumps(obj, separators=(",", ":")).encode()
-    with gzip.GzipFile(out, "wb", mtime=0) as f:
-        f.write(blob)
+    with open(out, "wb") as f:  # (xz: the gzip form was over 1 MiB)
+        f.write(lzma.compress(blob, preset=9 | lzma.PRESET_EXTREME))
 
 
 def main():
     ref = ReferenceAlign()
     t0 = time.time()
-    out_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stage_pairs_kat.json.gz")
+    out_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stage_pairs_kat.json.xz")
     if "--synthetic-chains-only" in sys.argv:  # (the pairs and stages sections take minutes: keep them, redo the synthetic chains)
-        with gzip.open(out_path, "rb") as f:
+        with lzma.open(out_path, "rb") as f:
             old = json.loads(f.read().decode())
         old["chains"] = [c for c in old["chains"] if "ties" not in c] + synthetic_chains(ref)
         write(out_path, old)

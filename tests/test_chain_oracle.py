@@ -19,6 +19,7 @@ import pytest
 
 import bruteforce
 import hostgen
+from refcalls import ref_calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -34,15 +35,6 @@ def host():
     from sedef_amd import host as h
     h.load_host()
     return h
-
-
-@pytest.fixture(scope="module")
-def ref_tree():
-    from oracle.binding import ReferenceAlign
-    try:
-        return ReferenceAlign()
-    except (FileNotFoundError, OSError):
-        pytest.skip("reference checkout / oracle/_ref/libref_align.so not available")
 
 
 def _same(got, case):
@@ -103,13 +95,16 @@ def _random_script(rng, n):
     return pts, np.array(ops, np.int32)
 
 
-def test_oracle_and_host_trees_equal_reference_live(oracle, host, ref_tree):
-    rng = np.random.default_rng(7)
-    for it in range(400):
-        pts, ops = _random_script(rng, int(rng.integers(2, 200)))
-        exp = ref_tree.segtree_script(pts, ops)
-        for got in (oracle.segtree_script(pts, ops), host.rangemax_script(pts, ops)):
-            assert np.array_equal(got[0], exp[0]) and np.array_equal(got[1], exp[1]), it
+def test_oracle_and_host_trees_equal_reference_live(oracle, host):
+    """(the reference's SegmentTree: live where oracle/_ref is built, else its recorded answers, tests/refcalls.py)"""
+    from oracle.binding import ReferenceAlign
+    with ref_calls("chain_oracle_segtree", ReferenceAlign) as ref_tree:
+        rng = np.random.default_rng(7)
+        for it in range(400):
+            pts, ops = _random_script(rng, int(rng.integers(2, 200)))
+            exp = ref_tree.segtree_script(pts, ops)
+            for got in (oracle.segtree_script(pts, ops), host.rangemax_script(pts, ops)):
+                assert np.array_equal(got[0], exp[0]) and np.array_equal(got[1], exp[1]), it
 
 
 def _chain_cases(host, rng, n_each):

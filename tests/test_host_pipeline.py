@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import hostgen
+from refcalls import ref_calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -63,23 +64,21 @@ def test_far_gap_of_equal_sides_keeps_its_zero_length_run(host, oracle_dp, host_
 
 
 def test_alignment_live_vs_reference_classes(host, oracle_dp):
+    """(the reference's classes: live where oracle/_ref is built, else their recorded answers, tests/refcalls.py)"""
     from oracle.binding import ReferenceAlign
-    try:
-        ref = ReferenceAlign()
-    except Exception:
-        pytest.skip("oracle/_ref/libref_align.so not built and /root/reference absent")
-    rng = np.random.default_rng(2)
-    for it in range(120):
-        a = hostgen.rseq(rng, int(rng.integers(1, 600)), 0.01 if it % 3 == 0 else 0)
-        b = hostgen.mut(rng, a, rng.random() * 0.2)
-        assert host.alignment_pair(a, b, test_dp=oracle_dp) == ref.alignment_pair(a, b)
-    n = 0
-    while n < 60:
-        c = hostgen.chain_case(rng, host)
-        if c is None:
-            continue
-        n += 1
-        assert host.guide_from_chains(*c, test_dp=oracle_dp) == ref.guide_from_chains(*c)
+    with ref_calls("host_pipeline_alignment", ReferenceAlign) as ref:
+        rng = np.random.default_rng(2)
+        for it in range(120):
+            a = hostgen.rseq(rng, int(rng.integers(1, 600)), 0.01 if it % 3 == 0 else 0)
+            b = hostgen.mut(rng, a, rng.random() * 0.2)
+            assert host.alignment_pair(a, b, test_dp=oracle_dp) == ref.alignment_pair(a, b)
+        n = 0
+        while n < 60:
+            c = hostgen.chain_case(rng, host)
+            if c is None:
+                continue
+            n += 1
+            assert host.guide_from_chains(*c, test_dp=oracle_dp) == ref.guide_from_chains(*c)
 
 
 def test_merge_matches_reference_golden(host, host_golden):
@@ -89,15 +88,13 @@ def test_merge_matches_reference_golden(host, host_golden):
 
 
 def test_merge_live_vs_reference(host):
+    """(the reference's merge: live where oracle/_ref is built, else its recorded answers, tests/refcalls.py)"""
     from oracle.binding import ReferenceAlign
-    try:
-        ref = ReferenceAlign()
-    except Exception:
-        pytest.skip("oracle/_ref/libref_align.so not built and /root/reference absent")
-    rng = np.random.default_rng(8)
-    for _ in range(200):
-        lines, spec = hostgen.merge_case(rng)
-        assert host.merge(lines, 250) == ref.merge(spec, 250)
+    with ref_calls("host_pipeline_merge", ReferenceAlign) as ref:
+        rng = np.random.default_rng(8)
+        for _ in range(200):
+            lines, spec = hostgen.merge_case(rng)
+            assert host.merge(lines, 250) == ref.merge(spec, 250)
 
 
 def test_bucket_stage(host, oracle_dp, tmp_path):

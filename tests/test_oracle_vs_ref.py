@@ -1,26 +1,22 @@
-"""CPU: live fuzz of the oracle against the reference kernel compiled from /root/reference.
-
-Skipped where oracle/_ref/libksw2_ref.so is absent and cannot be built (no reference checkout).
-"""
+"""CPU: fuzz of the oracle against the reference kernel: live where oracle/_ref/libksw2_ref.so is built, else against
+its recorded answers for the same seeded cases (tests/refcalls.py)."""
 import numpy as np
-import pytest
 
 from oracle.binding import Reference, mutate, random_codes, sedef_mat
+from refcalls import ref_calls
 from util import FIELDS
-
-
-@pytest.fixture(scope="module")
-def ref():
-    if not Reference.available():
-        pytest.skip("reference kernel not built (oracle/_ref) and /root/reference absent")
-    return Reference()
 
 
 def _same(a, b):
     return all(a[k] == b[k] for k in FIELDS) and np.array_equal(a["cigar"], b["cigar"])
 
 
-def test_fuzz_sedef_scoring(oracle, ref):
+def test_fuzz_sedef_scoring(oracle):
+    with ref_calls("oracle_vs_ref_sedef_scoring", Reference) as ref:
+        _fuzz_sedef_scoring(oracle, ref)
+
+
+def _fuzz_sedef_scoring(oracle, ref):
     rng = np.random.default_rng(11)
     for _ in range(3000):
         q = random_codes(rng, int(rng.integers(1, 400)), 0.02 if rng.random() < 0.3 else 0.0)
@@ -35,7 +31,12 @@ def test_fuzz_sedef_scoring(oracle, ref):
         assert _same(oracle.extz2(q, t, **kw), ref.extz2(q, t, **kw)), kw
 
 
-def test_fuzz_wrapping_scorings(oracle, ref):
+def test_fuzz_wrapping_scorings(oracle):
+    with ref_calls("oracle_vs_ref_wrapping_scorings", Reference) as ref:
+        _fuzz_wrapping_scorings(oracle, ref)
+
+
+def _fuzz_wrapping_scorings(oracle, ref):
     rng = np.random.default_rng(12)
     for _ in range(3000):
         q = random_codes(rng, int(rng.integers(1, 300)), 0.05 if rng.random() < 0.3 else 0.0)
@@ -48,8 +49,13 @@ def test_fuzz_wrapping_scorings(oracle, ref):
         assert _same(oracle.extz2(q, t, **kw), ref.extz2(q, t, **kw)), kw
 
 
-def test_fuzz_generic_matrix_and_approximate_modes(oracle, ref):
+def test_fuzz_generic_matrix_and_approximate_modes(oracle):
     """KSW_EZ_GENERIC_SC with a matrix whose wildcard row / column is not zero, KSW_EZ_APPROX_MAX / APPROX_DROP."""
+    with ref_calls("oracle_vs_ref_generic_matrix", Reference) as ref:
+        _fuzz_generic_matrix(oracle, ref)
+
+
+def _fuzz_generic_matrix(oracle, ref):
     rng = np.random.default_rng(13)
     mat = np.array([6, -3, -5, -3, -1, -3, 6, -3, -5, -1, -5, -3, 6, -3, -1, -3, -5, -3, 6, -1, -1, -1, -1, -1, 1], np.int8)
     for _ in range(2000):

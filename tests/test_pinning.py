@@ -12,6 +12,7 @@ import pytest
 
 import bruteforce
 import hostgen
+from refcalls import ref_calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -66,26 +67,24 @@ def test_sequence_ctor_matches_reference_golden(host, host_golden):
 
 
 def test_fasta_and_extend_live_vs_reference(host, tmp_path):
+    """(the reference's classes: live where oracle/_ref is built, else their recorded answers, tests/refcalls.py)"""
     from oracle.binding import ReferenceAlign
-    try:
-        ref = ReferenceAlign()
-    except Exception:
-        pytest.skip("oracle/_ref/libref_align.so not built and /root/reference absent")
-    rng = np.random.default_rng(99)
-    for k, (lb, nchr) in enumerate(((61, 2), (13, 4), (80, 1))):
-        text, entries = hostgen.fasta_text(rng, nchr, lb)
-        fa = _write_fasta(tmp_path, dict(text=text, entries=entries), k)
-        bare = tmp_path / ("bare%d.fa" % k)  # the reference driver needs a FASTA without .fai (see ref_fasta_get)
-        bare.write_text(text)
-        for (name, length, offset, lb_, ll) in entries:
-            for (a, b) in hostgen.fasta_queries(rng, length, lb_):
-                assert host.fasta_get(fa, name, a, b) == ref.fasta_get(str(bare), name, length, offset, lb_, ll, a, b)
-    for _ in range(300):
-        io = [int(x) for x in rng.integers(0, 50000, 4)]
-        io[1] += io[0] + 1
-        io[3] += io[2] + 1
-        f, mx = float(rng.uniform(0.1, 6)), int(rng.integers(1, 20000))
-        assert host.hit_extend(*io, f, mx) == ref.hit_extend(*io, f, mx)
+    with ref_calls("pinning_fasta_extend", ReferenceAlign) as ref:
+        rng = np.random.default_rng(99)
+        for k, (lb, nchr) in enumerate(((61, 2), (13, 4), (80, 1))):
+            text, entries = hostgen.fasta_text(rng, nchr, lb)
+            fa = _write_fasta(tmp_path, dict(text=text, entries=entries), k)
+            bare = tmp_path / ("bare%d.fa" % k)  # the reference driver needs a FASTA without .fai (see ref_fasta_get)
+            bare.write_text(text)
+            for (name, length, offset, lb_, ll) in entries:
+                for (a, b) in hostgen.fasta_queries(rng, length, lb_):
+                    assert host.fasta_get(fa, name, a, b) == ref.fasta_get(str(bare), name, length, offset, lb_, ll, a, b)
+        for _ in range(300):
+            io = [int(x) for x in rng.integers(0, 50000, 4)]
+            io[1] += io[0] + 1
+            io[3] += io[2] + 1
+            f, mx = float(rng.uniform(0.1, 6)), int(rng.integers(1, 20000))
+            assert host.hit_extend(*io, f, mx) == ref.hit_extend(*io, f, mx)
 
 
 # ---------------------------------------------------------------- C1: anchors vs. brute force

@@ -1,19 +1,21 @@
 """fast_align / chain_anchors' sweep / refine_chains / the stage driver against fixtures made with the REFERENCE's own classes.
 
-tests/golden/stage_pairs_kat.json.gz (generator: tests/golden/make_golden_stage_pairs.py) holds what a definition-level
+tests/golden/stage_pairs_kat.json.xz (generator: tests/golden/make_golden_stage_pairs.py) holds what a definition-level
 model of src/chain.cc:103-268, src/refine.cc:23-193 and src/align_main.cc:200-337 (tests/bruteforce.py: StageModel, control
 flow only) produces when every alignment, merge, guide alignment, tree query, FASTA fetch and BED line on the way is made by
 the reference's Alignment / Hit / SegmentTree / FastaReference classes compiled unmodified.  The product's host pipeline
 (sedef_amd/csrc/host/pipeline.cc, chain.cc) has to reproduce it byte for byte: with the CPU test hook here, through the GPU
 provider and the CLI under -m gpu."""
 import ctypes as C
-import gzip
 import json
+import lzma
 import os
 import subprocess
 
 import numpy as np
 import pytest
+
+from refcalls import ref_calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,7 +42,7 @@ def cpu_dp(oracle):
 
 @pytest.fixture(scope="module")
 def golden():
-    with gzip.open(os.path.join(ROOT, "tests", "golden", "stage_pairs_kat.json.gz"), "rb") as f:
+    with lzma.open(os.path.join(ROOT, "tests", "golden", "stage_pairs_kat.json.xz"), "rb") as f:
         return json.loads(f.read().decode())
 
 
@@ -114,14 +116,15 @@ def test_stage_output_matches_reference_fixture(host, cpu_dp, golden, tmp_path):
 
 
 def test_model_live_against_the_host_pipeline(host, cpu_dp):
-    """The same comparison on fresh seeded pairs when the reference classes are here (build container): the fixture is
-    not the only place the model and the product meet."""
+    """The same comparison on fresh seeded pairs, the model driving the reference's classes (live where oracle/_ref is
+    built, else their recorded answers, tests/refcalls.py): the fixture is not the only place the model and the product
+    meet."""
     from oracle.binding import ReferenceAlign
-    try:
-        ref = ReferenceAlign()
-        ref.lib.ref_tab_open
-    except Exception:
-        pytest.skip("oracle/_ref/libref_align.so not built and /root/reference absent")
+    with ref_calls("stage_pairs_model", ReferenceAlign) as ref:
+        _model_live(host, cpu_dp, ref)
+
+
+def _model_live(host, cpu_dp, ref):
     import bruteforce
     import hostgen
 

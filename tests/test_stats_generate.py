@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import hostgen
+from refcalls import ref_calls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -46,17 +47,16 @@ def test_double_formatting_fixed_values(host):
 
 
 def test_double_formatting_equals_reference_fmt_live(host):
+    """(the reference's fmt: live where oracle/_ref is built, else its recorded answers, tests/refcalls.py)"""
     from oracle.binding import ReferenceAlign
-    try:
-        ref = ReferenceAlign()
-    except (FileNotFoundError, OSError):
-        pytest.skip("reference checkout / oracle/_ref/libref_align.so not available")
-    rng = np.random.default_rng(3)
-    xs = [x for x, _ in FIXED] + [-0.75 * math.log(1.0 - 4.0 / 3 * p) for p in rng.random(200) * 0.74] + \
-        list(rng.random(300)) + list(10.0 ** rng.uniform(-12, 12, 300)) + [1 - k / 997.0 for k in range(0, 997, 7)]
-    for x in xs:
-        assert host.format_double(x) == ref.fmt_double(x), x
-    assert host.format_double(math.log(-1.0) if False else float("nan")).lstrip("-") == ref.fmt_double(float("nan")).lstrip("-")
+    with ref_calls("stats_generate_fmt_double", ReferenceAlign) as ref:
+        rng = np.random.default_rng(3)
+        xs = [x for x, _ in FIXED] + [-0.75 * math.log(1.0 - 4.0 / 3 * p) for p in rng.random(200) * 0.74] + \
+            list(rng.random(300)) + list(10.0 ** rng.uniform(-12, 12, 300)) + [1 - k / 997.0 for k in range(0, 997, 7)]
+        for x in xs:
+            assert host.format_double(x) == ref.fmt_double(x), x
+        assert host.format_double(math.log(-1.0) if False else float("nan")).lstrip("-") == \
+            ref.fmt_double(float("nan")).lstrip("-")
 
 
 # ---- the reference's algorithm on column strings (independent of the product's run-length form) ----------------------

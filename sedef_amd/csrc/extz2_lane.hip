@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void lane_plan_kernel(const LaneRec *__restric
   t.out_idx = (int32_t)r.out_idx;
   t.cig_cap = (r.flag & SDF_FLAG_SCORE_ONLY) ? 0 : t.qlen + t.tlen + 2;
   t.nreg = 1;
-  t.pad_ = 8;  // direction-flag layout 5 (traceback.hip)
+  t.kind = kTaskLane;  // direction-flag layout 5 (traceback.hip)
   plan[p] = t;
 }
 
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void lane_place_kernel(const LaneRec *__restri
   t.out_idx = (int32_t)r.out_idx;
   t.cig_cap = (r.flag & SDF_FLAG_SCORE_ONLY) ? 0 : t.qlen + t.tlen + 2;
   t.nreg = 1;
-  t.pad_ = 8;  // direction-flag layout 5 (traceback.hip)
+  t.kind = kTaskLane;  // direction-flag layout 5 (traceback.hip)
   plan[p] = t;
 }
 

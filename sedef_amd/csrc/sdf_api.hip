@@ -49,31 +49,6 @@ int usable_cpus() {
 }
 }  // namespace
 
-// the context's fields the planner and the launcher read, from its configuration (one place; the context's settings do
-// not change afterwards)
-static void apply_config(sdf_ctx *ctx) {
-  const sdf_config &c = ctx->cfg;
-  ctx->force_general = c.force_general != 0;
-  ctx->no_pair = c.no_pair != 0;
-  ctx->no_mixed = c.no_mixed != 0;
-  ctx->mixed_min = (size_t)c.mixed_min;
-  ctx->stripe_claim = c.stripe_claim != 0;
-  ctx->chain_min = (size_t)c.chain_min;
-  ctx->self_pair_max = (size_t)c.self_pair_max;
-  ctx->stats_items = (unsigned)c.stats_items;
-  ctx->no_stripe = c.no_stripe != 0;
-  ctx->stripe_min = (int)c.stripe_min;
-  ctx->bstripe_min_rows = (int)c.bstripe_min_rows;
-  ctx->stripe_spin_cap = (int)c.stripe_spin_cap;
-  ctx->strip_enabled = c.no_strip == 0;
-  ctx->strip_always = c.strip_always != 0;
-  ctx->strip_cols = (int)c.strip_cols;
-  ctx->lane_enabled = c.no_lane == 0;
-  ctx->lane_min = (size_t)c.lane_min;
-  ctx->pipeline = c.pipeline != 0;
-  if (c.debug_timing) g_debug_timing.store(true, std::memory_order_relaxed);
-}
-
 extern "C" const sdf_config *sdf_get_config(const sdf_ctx *ctx) { return ctx ? &ctx->cfg : nullptr; }
 
 extern "C" sdf_ctx *sdf_create(int device, size_t workspace_bytes) { return sdf_create_cfg(device, workspace_bytes, nullptr); }
@@ -111,7 +86,8 @@ extern "C" sdf_ctx *sdf_create_cfg(int device, size_t workspace_bytes, const sdf
   sdf_ctx *ctx = new sdf_ctx();
   ctx->device = device;
   ctx->cfg = cfg;
-  apply_config(ctx);
+  ctx->pipeline_ok = cfg.pipeline != 0;
+  if (cfg.debug_timing) g_debug_timing.store(true, std::memory_order_relaxed);
   if (cfg.debug_plan) {
     std::string dump(sdf_config_dump(&cfg, nullptr, 0), '\0');
     sdf_config_dump(&cfg, &dump[0], dump.size());
@@ -138,73 +114,39 @@ extern "C" sdf_ctx *sdf_create_cfg(int device, size_t workspace_bytes, const sdf
   if (cfg.workspace_gib > 0) budget = (size_t)(cfg.workspace_gib * 1073741824.0);  // (overrides the caller's figure: experiments with the stage driver)
   if (free_b && budget > free_b / 2) budget = free_b / 2;
   ctx->ws_budget = budget;
-  // allow the general kernel its full 160 KiB of LDS
+  // Every kernel that takes dynamic LDS may have up to 160 KiB of it.  The first five, the general kernel's LDS-resident
+  // instantiations, decide what the planner may ask for: max_dyn_lds is raised only when all of them accept it.
   const int want_lds = 160 * 1024;
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_general_kernel<64, false, false>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, want_lds) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_general_kernel<256, false, false>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, want_lds) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_general_kernel<1024, false, false>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, want_lds) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_general_kernel<1024, false, true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, want_lds) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_general_kernel<256, false, true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, want_lds) == hipSuccess)
-    ctx->max_dyn_lds = want_lds;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<1, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<1, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<2, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<2, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<3, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<3, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<6, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<6, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<4, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<4, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<8, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_wave_kernel<8, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-#define SDF_PAIR_ATTR(N)                                                                   \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_pair_kernel<N, false, false>),  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);         \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_pair_kernel<N, true, false>),   \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  SDF_PAIR_ATTR(1) SDF_PAIR_ATTR(2) SDF_PAIR_ATTR(3) SDF_PAIR_ATTR(4) SDF_PAIR_ATTR(6) SDF_PAIR_ATTR(8)
-#undef SDF_PAIR_ATTR
-  for (const void *f : {reinterpret_cast<const void *>(&extz2_pair_kernel<3, true, true>),
-                        reinterpret_cast<const void *>(&extz2_pair_kernel<6, true, true>),
-                        reinterpret_cast<const void *>(&extz2_pair_mixed_kernel<2>),
-                        reinterpret_cast<const void *>(&extz2_pair_mixed_kernel<3>),
-                        reinterpret_cast<const void *>(&extz2_pair_mixed_kernel<4>),
-                        reinterpret_cast<const void *>(&extz2_pair_mixed_kernel<5>),
-                        reinterpret_cast<const void *>(&extz2_pair_mixed_kernel<6>),
-                        reinterpret_cast<const void *>(&extz2_pair_mixed_kernel<8>),
-                        reinterpret_cast<const void *>(&extz2_pair_mixed_kernel<9>)})
-    (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
+#define SDF_K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+  const void *const dyn_lds_kernels[] = {
+      SDF_K(extz2_general_kernel<64, false, false>), SDF_K(extz2_general_kernel<256, false, false>),
+      SDF_K(extz2_general_kernel<1024, false, false>), SDF_K(extz2_general_kernel<1024, false, true>),
+      SDF_K(extz2_general_kernel<256, false, true>),
+      SDF_K(extz2_wave_kernel<1, false>), SDF_K(extz2_wave_kernel<1, true>), SDF_K(extz2_wave_kernel<2, false>),
+      SDF_K(extz2_wave_kernel<2, true>), SDF_K(extz2_wave_kernel<3, false>), SDF_K(extz2_wave_kernel<3, true>),
+      SDF_K(extz2_wave_kernel<6, false>), SDF_K(extz2_wave_kernel<6, true>), SDF_K(extz2_wave_kernel<4, false>),
+      SDF_K(extz2_wave_kernel<4, true>), SDF_K(extz2_wave_kernel<8, false>), SDF_K(extz2_wave_kernel<8, true>),
+      SDF_K(extz2_pair_kernel<1, false, false>), SDF_K(extz2_pair_kernel<1, true, false>),
+      SDF_K(extz2_pair_kernel<2, false, false>), SDF_K(extz2_pair_kernel<2, true, false>),
+      SDF_K(extz2_pair_kernel<3, false, false>), SDF_K(extz2_pair_kernel<3, true, false>),
+      SDF_K(extz2_pair_kernel<4, false, false>), SDF_K(extz2_pair_kernel<4, true, false>),
+      SDF_K(extz2_pair_kernel<6, false, false>), SDF_K(extz2_pair_kernel<6, true, false>),
+      SDF_K(extz2_pair_kernel<8, false, false>), SDF_K(extz2_pair_kernel<8, true, false>),
+      SDF_K(extz2_pair_kernel<3, true, true>), SDF_K(extz2_pair_kernel<6, true, true>),
+      SDF_K(extz2_pair_mixed_kernel<2>), SDF_K(extz2_pair_mixed_kernel<3>), SDF_K(extz2_pair_mixed_kernel<4>),
+      SDF_K(extz2_pair_mixed_kernel<5>), SDF_K(extz2_pair_mixed_kernel<6>), SDF_K(extz2_pair_mixed_kernel<8>),
+      SDF_K(extz2_pair_mixed_kernel<9>),
+      SDF_K(extz2_stripe_kernel<1>), SDF_K(extz2_stripe_kernel<2>), SDF_K(extz2_stripe_kernel<4>),
+      SDF_K(extz2_bstripe_kernel<1>), SDF_K(extz2_bstripe_kernel<2>), SDF_K(extz2_bstripe_kernel<4>),
+      SDF_K(extz2_strip_kernel), SDF_K(extz2_lane_kernel)};
+#undef SDF_K
+  bool general_ok = true;
+  for (size_t i = 0; i < sizeof(dyn_lds_kernels) / sizeof(dyn_lds_kernels[0]); ++i) {
+    const bool ok = hipFuncSetAttribute(dyn_lds_kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, want_lds) == hipSuccess;
+    if (i < 5) general_ok = general_ok && ok;
+  }
+  if (general_ok) ctx->max_dyn_lds = want_lds;
   (void)hipGetLastError();
-  for (const void *f : {reinterpret_cast<const void *>(&extz2_stripe_kernel<1>),
-                        reinterpret_cast<const void *>(&extz2_stripe_kernel<2>),
-                        reinterpret_cast<const void *>(&extz2_stripe_kernel<4>),
-                        reinterpret_cast<const void *>(&extz2_bstripe_kernel<1>),
-                        reinterpret_cast<const void *>(&extz2_bstripe_kernel<2>),
-                        reinterpret_cast<const void *>(&extz2_bstripe_kernel<4>)})
-    (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, want_lds);
-  (void)hipGetLastError();
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_strip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            want_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&extz2_lane_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            want_lds);
   // (per context, hence per device: a process-wide once-flag would leave a second GPU's copy of the kernel at 64 KiB)
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sdf::chain_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             std::max(ctx->max_dyn_lds, 65536));
@@ -214,7 +156,7 @@ extern "C" sdf_ctx *sdf_create_cfg(int device, size_t workspace_bytes, const sdf
       hipStreamCreateWithFlags(&ctx->dp_stream[1], hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&ctx->tb_stream, hipStreamNonBlocking) != hipSuccess) {
     (void)hipGetLastError();
-    ctx->pipeline = false;
+    ctx->pipeline_ok = false;
   }
   // (three streams of our own: the runtime multiplexes streams onto GPU_MAX_HW_QUEUES -- default 4 -- hardware
   // queues, and two of ours landing on one queue serialises what the pipeline wants side by side; with the
@@ -351,7 +293,7 @@ extern "C" long long sdf_last_lane_tasks(const sdf_ctx *ctx) { return ctx ? ctx-
 
 namespace {
 
-int make_scorek(sdf_ctx *ctx, const sdf_scoring *sc, ScoreK &k, bool &degenerate) {
+int make_scorek(sdf_ctx *ctx, const sdf_scoring *sc, ScoreK &k) {
   if (!sc || sc->m != 5) {
     ctx->err = "scoring: the GPU path implements the 5-letter alphabet (ACGT + wildcard) only";
     return SDF_ERR_UNSUPPORTED;
@@ -367,21 +309,38 @@ int make_scorek(sdf_ctx *ctx, const sdf_scoring *sc, ScoreK &k, bool &degenerate
   k.sc_mis = (uint8_t)sc->mat[1];
   k.wild = (uint8_t)(sc->m - 1);
   memcpy(k.mat, sc->mat, 25);
-  int min_sc = sc->mat[1];
-  for (int t = 1; t < sc->m * sc->m; ++t) min_sc = std::min<int>(min_sc, sc->mat[t]);
-  degenerate = -min_sc > 2 * (q + e);  // reference returns before any work (:81)
   return SDF_OK;
 }
 
-// The scoring's share of the planning environment (the batch entry points and sdf_debug_plan).
-// The register-resident window kernels take three differences of the recurrence with 32-bit subtracts (extz2_wave.hip:
-// SDF_CORE), which needs every fresh score byte z0 = score + 2 (q + e) in q .. 127: SEDEF's scoring and every sane one.
-// Anything else -- bytes that wrap, a mismatch below -(q + 2 e) -- runs on the general kernel, which emulates the reference's
-// bytes one by one.
-static void scoring_gates(const sdf_scoring *sc, PlanEnv &env) {
+// The planning environment of a batch call -- batch_part's and sdf_debug_plan's, which plans exactly like it: the
+// settings, and what the scoring (validated by make_scorek) and the request allow.  The lane kernel needs the records its
+// scan fills as well (env.lane_recs: pinned memory of a context), which batch_part adds.
+static PlanEnv plan_env(const sdf_config &cfg, const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want,
+                        int max_dyn_lds) {
+  PlanEnv env;
+  env.cfg = &cfg;
+  env.tasks = tasks;
+  env.n = n;
+  env.want = want;
+  int min_sc = sc->mat[1];
+  for (int t = 1; t < sc->m * sc->m; ++t) min_sc = std::min<int>(min_sc, sc->mat[t]);
+  env.degenerate = -min_sc > 2 * (sc->gapo + sc->gape);  // reference returns before any work (:81)
+  env.gapo = sc->gapo;
+  env.max_dyn_lds = max_dyn_lds;
+  // The register-resident window kernels take three differences of the recurrence with 32-bit subtracts (extz2_wave.hip:
+  // SDF_CORE), which needs every fresh score byte z0 = score + 2 (q + e) in q .. 127: SEDEF's scoring and every sane one.
+  // Anything else -- bytes that wrap, a mismatch below -(q + 2 e) -- runs on the general kernel, which emulates the
+  // reference's bytes one by one.
   const int qe2 = 2 * (sc->gapo + sc->gape), zm = sc->mat[0] + qe2, zx = sc->mat[1] + qe2;
   const bool core32_ok = sc->gapo >= 0 && sc->gape >= 0 && zm <= 127 && zx <= 127 && zm >= sc->gapo && zx >= sc->gapo;
-  if (!core32_ok) env.force_general = true;
+  env.force_general = cfg.force_general != 0 || !core32_ok;
+  // the lane and strip kernels: a tame scoring (every byte of the reference's state stays in 0..127: no wrap-around, no
+  // signed / unsigned or sign-extension artefacts); the lane kernel: nothing but CIGAR / score / mte wanted, the strip
+  // kernels: zx - q >= 0 (they take z - q with a 32-bit subtract on packed halves, extz2_strip.hip)
+  const bool tame = !env.degenerate && sc->gapo >= 0 && sc->gape >= 0 && zm >= 0 && zm <= 127 && zx >= 0 && zx <= 127;
+  env.lane_ok = cfg.no_lane == 0 && cfg.force_general == 0 && tame && !(want & SDF_WANT_EXT) && n >= (size_t)cfg.lane_min;
+  env.strip_ok = cfg.no_strip == 0 && cfg.force_general == 0 && tame && zx - sc->gapo >= 0 && sc->mat[0] >= 0;
+  return env;
 }
 
 // Plans the chunks of a cut, in launch order, on `nthreads` worker threads; wait(ci) blocks until chunk ci is planned.
@@ -461,44 +420,15 @@ static int batch_part(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks
   run.d_out = d_out;
 
   // ---- validate, cut into chunks ----
-  PlanEnv env;
-  env.cfg = &ctx->cfg;
-  env.tasks = tasks;
-  env.n = n;
-  env.want = want;
-  env.want_cigar = (want & SDF_WANT_CIGAR) != 0;
-  if (int rc = make_scorek(ctx, sc, run.sk, env.degenerate)) return rc;
-  env.gapo = sc->gapo;
-  env.max_dyn_lds = ctx->max_dyn_lds;
-  env.force_general = ctx->force_general;
-  scoring_gates(sc, env);
-  env.no_pair = ctx->no_pair;
-  env.self_pair_max = ctx->self_pair_max;
-  env.no_mixed = ctx->no_mixed;
-  env.mixed_min = ctx->mixed_min;
-  env.no_stripe = ctx->no_stripe;
-  env.stripe_min = ctx->stripe_min;
-  env.bstripe_min_rows = ctx->bstripe_min_rows;
-  // lane kernel: a tame scoring (every byte of the reference's state stays in 0..127: no wrap-around, no signed /
-  // unsigned or sign-extension artefacts) and nothing but CIGAR / score / mte wanted
-  {
-    const int qe2 = 2 * (sc->gapo + sc->gape), zm = sc->mat[0] + qe2, zx = sc->mat[1] + qe2;
-    env.lane_ok = ctx->lane_enabled && ctx->pipeline && !ctx->force_general && !env.degenerate && !(want & SDF_WANT_EXT) &&
-                  sc->gapo >= 0 && sc->gape >= 0 && zm >= 0 && zm <= 127 && zx >= 0 && zx <= 127 && n >= ctx->lane_min;
-    env.lane_min = ctx->lane_min;
-    env.strip_always = ctx->strip_always;
-    env.strip_cols = ctx->strip_cols;
-    env.chain_min = ctx->chain_min;
-    // (zx - q >= 0: the strip kernels take z - q with a 32-bit subtract on packed halves, extz2_strip.hip)
-    env.strip_ok = ctx->strip_enabled && !ctx->force_general && !env.degenerate && sc->gapo >= 0 && sc->gape >= 0 && zm >= 0 &&
-                   zm <= 127 && zx >= 0 && zx <= 127 && zx - sc->gapo >= 0 && sc->mat[0] >= 0;
-    if (env.lane_ok) {
-      SDF_HIP(ctx->host_lane.reserve(n * sizeof(LaneRec)));
-      env.lane_recs = (LaneRec *)ctx->host_lane.p;
-    }
+  if (int rc = make_scorek(ctx, sc, run.sk)) return rc;
+  PlanEnv env = plan_env(ctx->cfg, sc, tasks, n, want, ctx->max_dyn_lds);
+  env.lane_ok = env.lane_ok && ctx->pipeline_ok;  // (the lane kernel runs on a stream of its own)
+  if (env.lane_ok) {
+    SDF_HIP(ctx->host_lane.reserve(n * sizeof(LaneRec)));
+    env.lane_recs = (LaneRec *)ctx->host_lane.p;
   }
   ctx->lane_tasks = 0;
-  run.want_cigar = env.want_cigar;
+  run.want_cigar = env.want_cigar();
   run.scoring = sc;
   run.tasks = tasks;
   run.want = want;
@@ -607,7 +537,7 @@ static int batch_part(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks
   {
     const char *msg = nullptr;
     const bool early_on = ctx->cfg.early_heavy != 0;  // (0: the heavy chunks wait for the whole cut, as every other chunk)
-    const int crc = cut_batch(env, ctx->pipeline, ctx->ws_budget, cut, &msg, ctx->pool, early_on && !ctx->is_part ? &early : nullptr);
+    const int crc = cut_batch(env, ctx->pipeline_ok, ctx->ws_budget, cut, &msg, ctx->pool, early_on && !ctx->is_part ? &early : nullptr);
     run.more_chunks = false;
     if (crc) {
       if (ctx->err.empty()) ctx->err = msg ? msg : "invalid batch";
@@ -721,7 +651,7 @@ extern "C" int sdf_extz2_batch_device(sdf_ctx *ctx, const sdf_scoring *sc, const
   BatchRun run, first;
   BatchRun *head = nullptr;
   size_t n_first = 0;
-  if (ctx->pipeline && (split_default || split_asked) && !ctx->is_part) {
+  if (ctx->pipeline_ok && (split_default || split_asked) && !ctx->is_part) {
     if (!ctx->part_ctx) {
       sdf_config pc = ctx->cfg;  // (the parent's settings, whatever the environment says now)
       pc.workspace_gib = 0;
@@ -1154,7 +1084,7 @@ extern "C" int sdf_reserve(sdf_ctx *ctx, size_t max_tasks, size_t max_bases, siz
   // up -- the stage's first two rounds spent 35 ms on five of them)
   lap("sort / scan scratch");
   if (flags & SDF_RESERVE_FEW_STREAMS) ctx->aux_limit = 0;
-  if (ctx->pipeline) {
+  if (ctx->pipeline_ok) {
     for (hipStream_t *q : {&ctx->lane_stream, &ctx->aux_stream[0], &ctx->aux_stream[1], &ctx->aux_stream[2], &ctx->aux_stream[3]}) {
       if (q != &ctx->lane_stream && (size_t)(q - &ctx->aux_stream[0]) >= ctx->aux_limit) continue;
       if (!*q && (q == &ctx->lane_stream ? create_lane_stream(ctx, q) : hipStreamCreateWithFlags(q, hipStreamNonBlocking)) != hipSuccess) {
@@ -1655,7 +1585,7 @@ extern "C" int sdf_stats_columns_device(sdf_ctx *ctx, const sdf_stats_task *d_ta
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   // the list for the segments of long alignments (stats_cols.hip): 2^18 segments of 512 runs; an alignment that finds it
   // full is counted by its own wavefront
-  const unsigned kItems = ctx->stats_items;
+  const unsigned kItems = (unsigned)ctx->cfg.stats_items;
   SDF_HIP(ctx->st_items.reserve((size_t)kItems * sizeof(sdf::StatsItem) + 64));
   unsigned *d_counter = reinterpret_cast<unsigned *>((char *)ctx->st_items.p + (size_t)kItems * sizeof(sdf::StatsItem));
   SDF_HIP(hipMemsetAsync(d_counter, 0, sizeof(unsigned), st));
@@ -1795,38 +1725,23 @@ extern "C" void sdf_ksw_extz2(void * /*km*/, int qlen, const uint8_t *query, int
 }
 
 // ---- planner without a device (not part of the public header; tests/test_planner.py) -------------------------------
-// Cuts and plans a batch exactly like sdf_extz2_batch_device does (same code, same thread pool) and reports, per input
-// task: chunk index (-1: not run), launch class `bs`, nreg, pad_, dir_off, cig_slot, partner (index of the task it
-// shares a wavefront with, -1 none), and per chunk {heavy, tasks, launches, dir_bytes, region capacity}.
+// Cuts and plans a batch exactly like sdf_extz2_batch_device does (same code, same settings -- the environment's, like a
+// context made now would get --, same thread pool; no lane kernel: its records need a device) and reports, per input
+// task: chunk index (-1: not run), launch class (LaunchClass::code), nreg, kind (TaskKind), dir_off, cig_slot, partner
+// (index of the task it shares a wavefront with, -1 none), and per chunk {heavy, tasks, launches, dir_bytes, region
+// capacity}.
 extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want, size_t ws_budget,
                               int max_dyn_lds, int nthreads, int64_t *per_task /* n x 7 */, int64_t *per_chunk /* cap x 5 */,
                               size_t chunk_cap, size_t *nchunks) {
-  sdf_ctx tmp;  // only err / flags are used: no HIP call is made here
-  tmp.max_dyn_lds = max_dyn_lds;
-  PlanEnv env;
-  env.tasks = tasks;
-  env.n = n;
-  env.want = want;
-  env.want_cigar = (want & SDF_WANT_CIGAR) != 0;
-  sdf_config dcfg;  // (no context here: the environment's settings, like a context made now would get)
+  sdf_config dcfg;
   {
     char why[256];
     if (sdf_config_from_env(&dcfg, why, sizeof why) != SDF_OK) return SDF_ERR_INVALID;
   }
-  env.cfg = &dcfg;
+  sdf_ctx tmp;  // only err is used: no HIP call is made here
   ScoreK sk;
-  if (int rc = make_scorek(&tmp, sc, sk, env.degenerate)) return rc;
-  env.gapo = sc->gapo;
-  scoring_gates(sc, env);
-  env.max_dyn_lds = max_dyn_lds;
-  {  // the strip kernels as a context made now would plan them (batch_part; the lane kernel's records need a device)
-    const int qe2 = 2 * (sc->gapo + sc->gape), zm = sc->mat[0] + qe2, zx = sc->mat[1] + qe2;
-    env.strip_always = dcfg.strip_always != 0;
-    env.strip_cols = (int)dcfg.strip_cols;
-    env.chain_min = (size_t)dcfg.chain_min;
-    env.strip_ok = dcfg.no_strip == 0 && dcfg.force_general == 0 && !env.degenerate && sc->gapo >= 0 && sc->gape >= 0 && zm >= 0 &&
-                   zm <= 127 && zx >= 0 && zx <= 127 && zx - sc->gapo >= 0 && sc->mat[0] >= 0;
-  }
+  if (int rc = make_scorek(&tmp, sc, sk)) return rc;
+  const PlanEnv env = plan_env(dcfg, sc, tasks, n, want, max_dyn_lds);
   BatchCut cut;
   const char *msg = nullptr;
   const auto tc0 = std::chrono::steady_clock::now();
@@ -1877,9 +1792,9 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
       o[4] = (int64_t)(c.heavy ? cut.heavy_need : cut.region_need);
     }
     for (const Launch &L : c.launches) {
-      const bool pair = (L.bs >= 100 && L.bs < 200) || L.bs == 500;  // (500: strip kernel, two tasks of any geometry)
-      const bool chained = L.bs == 604 || L.bs == 608;               // (an entry per block of a pair of tasks: the listed one's partner through zdrop)
-      const bool stripes = (L.bs >= 300 && L.bs < 500) || chained;
+      const bool pair = L.lc.two_per_entry();
+      const bool chained = L.lc.fam == LaunchClass::Family::Chain;  // (an entry per block of a pair of tasks: the listed one's partner through zdrop)
+      const bool stripes = L.lc.per_stripe();
       for (size_t e = 0; e < L.cnt; ++e) {
         int32_t rel = order[c.ob + L.off + e];
         if (stripes) {  // one entry per stripe: the task is reported at its stripe 0
@@ -1893,9 +1808,9 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
           int64_t *o = per_task + 7 * (size_t)p.out_idx;
           if (o[0] >= 0 && !(pair && o[6] == p.out_idx)) return SDF_ERR_INVALID;  // listed twice (only a self-pair may be)
           o[0] = (int64_t)ci;
-          o[1] = L.bs;
+          o[1] = L.lc.code();
           o[2] = p.nreg;
-          o[3] = p.pad_;
+          o[3] = p.kind;
           o[4] = p.dir_off;
           o[5] = p.cig_slot;
           o[6] = pair ? plan[c.pb + order[c.ob + L.off + (e ^ 1)]].out_idx : chained ? plan[c.pb + p.zdrop].out_idx : -1;

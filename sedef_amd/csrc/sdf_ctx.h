@@ -314,7 +314,7 @@ using sdf::DevBuf;
 using sdf::HostBuf;
 
 struct sdf_ctx {
-  sdf_config cfg;  // the context's settings, fixed when it is made (sdf_config.hip; sdf_api.hip: apply_config)
+  sdf_config cfg;  // the context's settings, fixed when it is made (sdf_config.hip): every setting is read from here
   int device = 0;
   hipStream_t stream = nullptr;
   size_t ws_budget = 0;
@@ -330,7 +330,6 @@ struct sdf_ctx {
   DevBuf st_tasks, st_pool, st_cig, st_out;  // sdf_stats_columns_batch
   DevBuf claim_buf;                          // stripe launches: eight entry counters each (stripe_claim), zeroed per call
   DevBuf st_items;                           // sdf_stats_columns_device: segments of long alignments + their counter
-  unsigned stats_items = 1u << 18;           // ... capacity of that list (SDF_STATS_ITEMS)
   DevBuf h_pool, h_out, h_cig;  // device buffers of the host-buffer entry point
   DevBuf h_brief;               // ... 16-byte result records (sdf_extz2_batch_brief)
   std::vector<sdf_task> host_tasks;  // ... the task array with word offsets
@@ -343,11 +342,6 @@ struct sdf_ctx {
   DevBuf ln_recs, ln_keys, ln_vals, ln_sizes, ln_tmp;
   DevBuf ln_bins;  // ... second form of the lane planning: per-key counts, ranks, prefixes (extz2_lane.hip: lane_hist_kernel and on)
   hipStream_t lane_stream = nullptr;
-  bool strip_enabled = true;  // SDF_NO_STRIP=1: full-band tasks of 257..8192 target bases stay on the window / stripe kernels
-  bool strip_always = false;  // SDF_STRIP_ALWAYS=1 (tests): the strip kernels whatever the number of tasks
-  int strip_cols = 0;         // SDF_STRIP_COLS=4|8 (tests)
-  bool lane_enabled = true;   // SDF_NO_LANE=1: small full-band tasks stay on the window kernels
-  size_t lane_min = 8192;     // SDF_LANE_MIN: eligible tasks a batch must hold for the lane kernel to take them
   long long lane_tasks = 0;   // tasks of the last batch call the lane kernel took
   sdf::WorkerPool *pool = nullptr;  // planning threads, started with the first batch large enough to use them
   sdf::BatchCut *cut = nullptr;  // chunk list and planning scratch of the last batch call (sdf_plan.hip)
@@ -357,20 +351,8 @@ struct sdf_ctx {
   int launches = 0;
   long long paired = 0;  // tasks of the last batch that ran two per wavefront (extz2_pair.hip)
   std::string err;
-  int max_dyn_lds = 64 * 1024;
-  bool force_general = false;  // SDF_FORCE_GENERAL=1: route everything to the LDS-resident kernel
-  bool pipeline = true;        // SDF_PIPELINE=0: one chunk on one stream (isolated kernel timing)
-  int stripe_min = 400;       // SDF_STRIPE_MIN: targets longer than this (and full band) take the stripe kernel
-  int bstripe_min_rows = 4000;  // SDF_BSTRIPE_MIN_ROWS: banded tasks of this many anti-diagonals or more take the banded
-                               // stripe kernel (extz2_bstripe.hip); 0: never
-  bool no_stripe = false;      // SDF_NO_STRIPE=1: wide full-band tasks stay on the general kernel (extz2_stripe.hip off)
-  size_t self_pair_max = 512;  // SDF_SELF_PAIR_MAX: see PlanEnv
-  size_t chain_min = 3072;     // SDF_CHAIN_MIN: see PlanEnv
-  bool stripe_claim = true;    // SDF_STRIPE_CLAIM=0: the stripe kernels' workgroups take launch-order entry blockIdx.x
-  bool no_pair = false;        // SDF_NO_PAIR=1: never pack two tasks into one wavefront (extz2_pair.hip)
-  bool no_mixed = false;       // SDF_NO_MIXED=1: no mixed pairs (banded tasks of different lengths in one wavefront)
-  size_t mixed_min = 4096;     // SDF_MIXED_MIN: see PlanEnv
-  int stripe_spin_cap = 1 << 24;  // SDF_STRIPE_SPIN_CAP: polls before a stripe's wait gives its task up (extz2_stripe.hip)
+  int max_dyn_lds = 64 * 1024;  // dynamic LDS the general kernels may ask for (raised in sdf_create where the device allows)
+  bool pipeline_ok = true;      // cfg.pipeline, and the pipeline's streams could be created (else one chunk on one stream)
   sdf_ctx *part_ctx = nullptr;    // second context of this device: the first part of a very large batch (sdf_api.hip)
   hipEvent_t part_ev = nullptr;
   bool is_part = false, pool_shared = false;

@@ -1,5 +1,6 @@
 // Internal types shared by the host C-ABI layer and the gfx950 kernels.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/sedef_hip.h"
@@ -21,6 +22,21 @@ struct ScoreK {
   int8_t pad2_[3];
 };
 
+// The DP kernel the planner gave a task (PlanTask::kind).
+enum TaskKind : int32_t {
+  kTaskGeneral = 0,     // general kernel (extz2_general.hip), state in LDS; with nreg > 0 the wave kernel (extz2_wave.hip)
+  kTaskGeneralHbm = 1,  // general kernel with its state in an HBM slab
+  kTaskPair = 2,        // pair kernel (extz2_pair.hip): nreg counts 64-slot registers, the flags are per-task uint2 records
+  kTaskPlain = 3,       // general kernel, PLAIN flavour (packed recurrence, H along the band edge only), state in LDS
+  kTaskPlainHbm = 4,    // ... state in an HBM slab
+  kTaskStripe = 5,      // stripe kernel (extz2_stripe.hip)
+  kTaskTrack = 6,       // planning only: the pair kernel's TRACK flavour, made kTaskPair before the launch classes are formed
+  kTaskBStripe = 7,     // banded stripe kernel (extz2_bstripe.hip)
+  kTaskLane = 8,        // lane kernel (extz2_lane.hip), planned on the device
+  kTaskStrip = 9,       // strip kernel (extz2_strip.hip)
+  kTaskChain = 10,      // chained strips (extz2_strip.hip)
+};
+
 // One planned task as the kernels see it.
 struct PlanTask {
   int64_t q_word;    // word offset of the packed query in the pool
@@ -35,11 +51,17 @@ struct PlanTask {
   int32_t out_idx;   // index of the result record
   int32_t cig_cap;   // words in the staging slot
   int32_t nreg;      // 0: general kernel, byte-per-cell direction rows; >0: wave kernel with nreg
-                     // packed registers, direction flags in 16-row x 128-slot bit blocks
-  int32_t pad_;      // 1: general kernel with its state in an HBM slab; 2: pair kernel (extz2_pair.hip): nreg counts
-                     // 64-slot registers and the flags are per-task uint2 records; 3 / 4: general kernel, PLAIN
-                     // flavour (packed recurrence, H along the band edge only), state in LDS / in an HBM slab
+                     // packed registers, direction flags in 16-row x 128-slot bit blocks (or what `kind` says)
+  TaskKind kind;
 };
+static_assert(sizeof(PlanTask) == 72 && offsetof(PlanTask, kind) == 68, "PlanTask is uploaded as it is");
+
+// Direction-flag layout of a planned task (traceback.hip: LAYOUT): 0 byte rows, 1 wave-kernel bit blocks, 2 pair-kernel
+// records, 3 stripes, 4 banded stripes, 5 lane kernel, 6 strips.
+__host__ __device__ inline int dir_layout(const PlanTask &t) {
+  return t.nreg == 0 ? 0 : t.kind == kTaskPair ? 2 : t.kind == kTaskStripe ? 3 : t.kind == kTaskBStripe ? 4
+         : t.kind == kTaskLane ? 5 : (t.kind == kTaskStrip || t.kind == kTaskChain) ? 6 : 1;
+}
 
 // Per-anti-diagonal band geometry (reference: extern/ksw2_extz2_sse.cc:101-115).
 struct Band {

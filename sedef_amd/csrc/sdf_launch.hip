@@ -75,8 +75,9 @@ static void drain_streams(sdf_ctx *ctx, hipStream_t st) {
   (void)hipGetLastError();
 }
 
-// One DP launch of a planned class.  slabs: HBM state of the very long tasks (HBM-state classes only).
-static void launch_dp(const Launch &L, hipStream_t sdp, const PlanTask *lp, const int32_t *lo, const uint32_t *d_pool,
+// One DP launch of a planned class; false: no kernel instantiation serves the class (a planner slip, not launched).
+// slabs: HBM state of the very long tasks (HBM-state classes only).
+static bool launch_dp(const Launch &L, hipStream_t sdp, const PlanTask *lp, const int32_t *lo, const uint32_t *d_pool,
                       const ScoreK &sk, uint8_t *dir_reg, sdf_result *d_out, uint8_t *slabs, unsigned long long *gave_up,
                       int spin_cap, unsigned *claim = nullptr) {
   const dim3 one((unsigned)L.cnt), half((unsigned)(L.cnt / 2));
@@ -100,78 +101,108 @@ static void launch_dp(const Launch &L, hipStream_t sdp, const PlanTask *lp, cons
     hipLaunchKernelGGL(bstripe_finish_kernel, dim3((unsigned)((L.cnt + 63) / 64)), dim3(64), 0, sdp, lp, lo,     \
                        (int)L.cnt, N, dir_reg, d_out);                                                            \
   }
+#define SDF_CHAIN(C) /* chained strips: edge columns and row-0 sums reset first */                                   \
+  {                                                                                                               \
+    hipLaunchKernelGGL(strip_chain_init_kernel, one, dim3(64), 0, sdp, lp, lo, dir_reg);                          \
+    hipLaunchKernelGGL(extz2_strip_chain_kernel<C>, one, dim3(64), 0, sdp, lp, lo, d_pool, sk, dir_reg, d_out, gave_up, spin_cap, claim); \
+  }
 #define SDF_GENERAL(BS, PLAIN)                                                                                      \
   hipLaunchKernelGGL((extz2_general_kernel<BS, false, PLAIN>), one, dim3(BS), L.lds, sdp, lp, lo, d_pool, sk, dir_reg, \
                      d_out, (uint8_t *)nullptr, (size_t)0)
 #define SDF_GENERAL_HBM(BS, PLAIN) /* L.lds = per-workgroup slab bytes in HBM */                                    \
   hipLaunchKernelGGL((extz2_general_kernel<BS, true, PLAIN>), one, dim3(BS), 512, sdp, lp, lo, d_pool, sk, dir_reg, \
                      d_out, slabs, L.lds)
-  switch (L.bs) {
-    case 1: SDF_WAVE(1, false); break;
-    case 11: SDF_WAVE(1, true); break;
-    case 2: SDF_WAVE(2, false); break;
-    case 12: SDF_WAVE(2, true); break;
-    case 3: SDF_WAVE(3, false); break;
-    case 13: SDF_WAVE(3, true); break;
-    case 6: SDF_WAVE(6, false); break;
-    case 16: SDF_WAVE(6, true); break;
-    case 4: SDF_WAVE(4, false); break;
-    case 14: SDF_WAVE(4, true); break;
-    case 8: SDF_WAVE(8, false); break;
-    case 18: SDF_WAVE(8, true); break;
-    case 101: SDF_PAIR(1, false); break;
-    case 111: SDF_PAIR(1, true); break;
-    case 102: SDF_PAIR(2, false); break;
-    case 112: SDF_PAIR(2, true); break;
-    case 103: SDF_PAIR(3, false); break;
-    case 113: SDF_PAIR(3, true); break;
-    case 104: SDF_PAIR(4, false); break;
-    case 114: SDF_PAIR(4, true); break;
-    case 106: SDF_PAIR(6, false); break;
-    case 116: SDF_PAIR(6, true); break;
-    case 108: SDF_PAIR(8, false); break;
-    case 118: SDF_PAIR(8, true); break;
-    case 132: SDF_PAIR_MIXED(2); break;
-    case 133: SDF_PAIR_MIXED(3); break;
-    case 134: SDF_PAIR_MIXED(4); break;
-    case 135: SDF_PAIR_MIXED(5); break;
-    case 136: SDF_PAIR_MIXED(6); break;
-    case 138: SDF_PAIR_MIXED(8); break;
-    case 139: SDF_PAIR_MIXED(9); break;
-    case 123: SDF_PAIR_TRACK(3); break;
-    case 126: SDF_PAIR_TRACK(6); break;
-    case 608: /* chained strips: edge columns and row-0 sums reset first */
-      hipLaunchKernelGGL(strip_chain_init_kernel, one, dim3(64), 0, sdp, lp, lo, dir_reg);
-      hipLaunchKernelGGL(extz2_strip_chain_kernel<8>, one, dim3(64), 0, sdp, lp, lo, d_pool, sk, dir_reg, d_out, gave_up, spin_cap, claim);
+#define SDF_WAVE_OF(N) \
+  case N:             \
+    if (K.stream) SDF_WAVE(N, true); else SDF_WAVE(N, false); return true;
+#define SDF_PAIR_OF(N) \
+  case N:             \
+    if (K.stream) SDF_PAIR(N, true); else SDF_PAIR(N, false); return true;
+  using Family = LaunchClass::Family;
+  const LaunchClass &K = L.lc;
+  switch (K.fam) {
+    case Family::Wave:
+      switch (K.nreg) { SDF_WAVE_OF(1) SDF_WAVE_OF(2) SDF_WAVE_OF(3) SDF_WAVE_OF(6) SDF_WAVE_OF(4) SDF_WAVE_OF(8) }
       break;
-    case 604:
-      hipLaunchKernelGGL(strip_chain_init_kernel, one, dim3(64), 0, sdp, lp, lo, dir_reg);
-      hipLaunchKernelGGL(extz2_strip_chain_kernel<4>, one, dim3(64), 0, sdp, lp, lo, d_pool, sk, dir_reg, d_out, gave_up, spin_cap, claim);
+    case Family::Pair:
+      switch (K.nreg) { SDF_PAIR_OF(1) SDF_PAIR_OF(2) SDF_PAIR_OF(3) SDF_PAIR_OF(4) SDF_PAIR_OF(6) SDF_PAIR_OF(8) }
       break;
-    case 500:
+    case Family::PairMixed:
+      switch (K.nreg) {
+        case 2: SDF_PAIR_MIXED(2); return true;
+        case 3: SDF_PAIR_MIXED(3); return true;
+        case 4: SDF_PAIR_MIXED(4); return true;
+        case 5: SDF_PAIR_MIXED(5); return true;
+        case 6: SDF_PAIR_MIXED(6); return true;
+        case 8: SDF_PAIR_MIXED(8); return true;
+        case 9: SDF_PAIR_MIXED(9); return true;
+      }
+      break;
+    case Family::PairTrack:
+      switch (K.nreg) {
+        case 3: SDF_PAIR_TRACK(3); return true;
+        case 6: SDF_PAIR_TRACK(6); return true;
+      }
+      break;
+    case Family::Chain:
+      switch (K.nreg) {
+        case 8: SDF_CHAIN(8) return true;
+        case 4: SDF_CHAIN(4) return true;
+      }
+      break;
+    case Family::Strip:
       hipLaunchKernelGGL(extz2_strip_kernel, half, dim3(64), L.lds, sdp, lp, lo, d_pool, sk, dir_reg, d_out);
+      return true;
+    case Family::Stripe:
+      switch (K.nreg) {
+        case 1: SDF_STRIPE(1) return true;
+        case 2: SDF_STRIPE(2) return true;
+        case 4: SDF_STRIPE(4) return true;
+      }
       break;
-    case 301: SDF_STRIPE(1) break;
-    case 302: SDF_STRIPE(2) break;
-    case 304: SDF_STRIPE(4) break;
-    case 401: SDF_BSTRIPE(1) break;
-    case 402: SDF_BSTRIPE(2) break;
-    case 404: SDF_BSTRIPE(4) break;
-    case 64: SDF_GENERAL(64, false); break;
-    case 256: SDF_GENERAL(256, false); break;
-    case 1024: SDF_GENERAL(1024, false); break;
-    case 2256: SDF_GENERAL(256, true); break;
-    case 3024: SDF_GENERAL(1024, true); break;
-    case 2001: SDF_GENERAL_HBM(1024, true); break;
-    case 1001: SDF_GENERAL_HBM(1024, false); break;
-    default: SDF_GENERAL_HBM(256, false); break;  // 1000
+    case Family::BStripe:
+      switch (K.nreg) {
+        case 1: SDF_BSTRIPE(1) return true;
+        case 2: SDF_BSTRIPE(2) return true;
+        case 4: SDF_BSTRIPE(4) return true;
+      }
+      break;
+    case Family::General:
+      switch (K.block) {
+        case 64: SDF_GENERAL(64, false); return true;
+        case 256: SDF_GENERAL(256, false); return true;
+        case 1024: SDF_GENERAL(1024, false); return true;
+      }
+      break;
+    case Family::GeneralPlain:
+      switch (K.block) {
+        case 256: SDF_GENERAL(256, true); return true;
+        case 1024: SDF_GENERAL(1024, true); return true;
+      }
+      break;
+    case Family::GeneralPlainHbm:
+      if (K.block == 1024) {
+        SDF_GENERAL_HBM(1024, true);
+        return true;
+      }
+      break;
+    case Family::GeneralHbm:
+      switch (K.block) {
+        case 1024: SDF_GENERAL_HBM(1024, false); return true;
+        case 256: SDF_GENERAL_HBM(256, false); return true;
+      }
+      break;
   }
+  return false;
+#undef SDF_WAVE_OF
+#undef SDF_PAIR_OF
 #undef SDF_WAVE
 #undef SDF_PAIR
 #undef SDF_PAIR_MIXED
 #undef SDF_PAIR_TRACK
 #undef SDF_STRIPE
 #undef SDF_BSTRIPE
+#undef SDF_CHAIN
 #undef SDF_GENERAL
 #undef SDF_GENERAL_HBM
 }
@@ -225,7 +256,7 @@ static int launch_chunk(BatchRun &run, size_t ci) {
   // A chunk of several mixed-pair launches (banded tasks of all lengths, extz2_pair.hip MIXED): each of them ends with its
   // longest chain of rows whatever else runs, so they must START together -- eight more streams, four per chunk parity
   size_t n_mixed_launches = 0;
-  for (const Launch &L : c.launches) n_mixed_launches += L.bs >= 130 && L.bs < 140;
+  for (const Launch &L : c.launches) n_mixed_launches += L.lc.mixed();
   if (pipelined && n_mixed_launches >= 2 && !run.have_heavy)
     for (size_t a = 0; a < 8; ++a)
       if (!ctx->wide_stream[a] && hipStreamCreateWithFlags(&ctx->wide_stream[a], hipStreamNonBlocking) != hipSuccess) {
@@ -278,7 +309,7 @@ static int launch_chunk(BatchRun &run, size_t ci) {
   {  // HBM state slabs of the very long tasks of this chunk: one allocation, a slice per launch
     size_t gs_total = 0;
     for (const Launch &L : c.launches)
-      if (L.bs == 1000 || L.bs == 1001 || L.bs == 2001) gs_total += L.lds * L.cnt;
+      if (L.lc.hbm_state()) gs_total += L.lds * L.cnt;
     if (gs_total > ctx->gstate_buf.cap) {  // growing frees the old slabs: nothing may be using them
       for (hipStream_t q : Q)
         if (q) SDF_HIP(hipStreamSynchronize(q));
@@ -292,7 +323,6 @@ static int launch_chunk(BatchRun &run, size_t ci) {
   const bool dbg_cls = ctx->cfg.debug_classes != 0;
   if (dbg_cls) {  // what each launch class of the chunk holds: tasks, anti-diagonals, in-band cells (profiles/r04_mm8_classes.txt)
     for (const Launch &L : c.launches) {
-      const bool striped = (L.bs >= 300 && L.bs < 500) || L.bs == 604 || L.bs == 608;
       long long nt = 0, rows = 0, cells = 0;
       int32_t prev = -1;
       auto add = [&](int32_t rel) {
@@ -303,18 +333,18 @@ static int launch_chunk(BatchRun &run, size_t ci) {
       };
       for (size_t j = 0; j < L.cnt; ++j) {
         const int32_t e = run.order[ob + L.off + j];
-        if (striped) {
+        if (L.lc.per_stripe()) {
           if (((uint32_t)e >> 24) != 0) continue;  // (one entry per stripe: the first stands for the task)
           const int32_t rel = e & 0xffffff;
           add(rel);
-          if (L.bs >= 600 && run.plan[pb + rel].zdrop != rel) add(run.plan[pb + rel].zdrop);  // (chained strips: the partner)
+          if (L.lc.fam == LaunchClass::Family::Chain && run.plan[pb + rel].zdrop != rel) add(run.plan[pb + rel].zdrop);  // (chained strips: the partner)
         } else if (e != prev) {  // (a task paired with itself is listed twice)
           add(e);
           prev = e;
         }
       }
       fprintf(stderr, "[class chunk %zu%s bs %d entries %zu tasks %lld rows %lld cells %lld lds %zu]\n", ci, c.heavy ? " (heavy)" : "",
-              L.bs, L.cnt, nt, rows, cells, L.lds);
+              L.lc.code(), L.cnt, nt, rows, cells, L.lds);
     }
   }
   for (const Launch &L : c.launches) {
@@ -322,9 +352,13 @@ static int launch_chunk(BatchRun &run, size_t ci) {
     // milliseconds each), the others for the ordinary chunks, which would otherwise queue behind them
     int qi = 0;
     if (pipelined) {
-      const bool mixed_cls = L.bs >= 130 && L.bs < 140;  // (long and short banded tasks in one launch: it ends with its longest chain,
-                                                         // and runs next to the chunk's other launches rather than behind them)
-      if (piped && L.cnt >= 2048 && (L.bs < 300 || L.bs == 500) && !mixed_cls) {  // (a stripe class counts stripes, and lasts as long as its longest task)
+      // a big launch of one-wavefront tasks: the wave, pair (not mixed: long and short banded tasks in one launch end with
+      // their longest chain, and run next to the chunk's other launches rather than behind them) and strip kernels, and the
+      // general kernel's 64- and 256-thread workgroups (a stripe class counts stripes, and lasts as long as its longest task)
+      using Family = LaunchClass::Family;
+      const bool big = (L.lc.fam == Family::Wave || (L.lc.two_per_entry() && !L.lc.mixed()) ||
+                        (L.lc.fam == Family::General && L.lc.block <= 256));
+      if (piped && L.cnt >= 2048 && big) {
         qi = ui;
       } else {  // least estimated work queued; with heavy tasks in the batch Q[0], Q[1], Q[4], Q[5] are theirs
         // Without heavy tasks, consecutive ordinary chunks keep to disjoint sets of queues -- Q[1], Q[4], Q[5] and Q[2],
@@ -352,17 +386,20 @@ static int launch_chunk(BatchRun &run, size_t ci) {
       if (region_ev) SDF_HIP(hipStreamWaitEvent(sdp, region_ev, 0));
     }
     uint8_t *slabs = nullptr;
-    if (L.bs == 1000 || L.bs == 1001 || L.bs == 2001) {
+    if (L.lc.hbm_state()) {
       slabs = (uint8_t *)ctx->gstate_buf.p + gs_off;
       gs_off += L.lds * L.cnt;
     }
     unsigned *claim = nullptr;  // a stripe launch's entry counters (stripe_claim): one set of eight per launch of the call
-    if (((L.bs >= 300 && L.bs < 500) || L.bs == 604 || L.bs == 608) && ctx->stripe_claim && L.cnt % 8 == 0 &&
+    if (L.lc.per_stripe() && ctx->cfg.stripe_claim && L.cnt % 8 == 0 &&
         run.claim_sets < kClaimSets)
       claim = (unsigned *)ctx->claim_buf.p + 8 * run.claim_sets++;
-    launch_dp(L, sdp, run.d_plan + pb, run.d_order + ob + L.off, run.d_pool, run.sk, dir_reg, run.d_out, slabs,
-              (unsigned long long *)ctx->misc_buf.p + 1, ctx->stripe_spin_cap, claim);
-    if ((L.bs >= 300 && L.bs < 500) || L.bs == 604 || L.bs == 608) run.any_stripe = true;
+    if (!launch_dp(L, sdp, run.d_plan + pb, run.d_order + ob + L.off, run.d_pool, run.sk, dir_reg, run.d_out, slabs,
+                   (unsigned long long *)ctx->misc_buf.p + 1, (int)ctx->cfg.stripe_spin_cap, claim)) {
+      ctx->err = "internal: no kernel for launch class " + std::to_string(L.lc.code());
+      return SDF_ERR_INVALID;
+    }
+    if (L.lc.per_stripe()) run.any_stripe = true;
     ++ctx->launches;
   }
   for (int q = 0; q < NQ; ++q) {  // the traceback stream collects every stream the chunk's DP ran on

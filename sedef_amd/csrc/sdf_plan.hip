@@ -29,40 +29,81 @@ inline const sdf_config *default_config() {  // (a PlanEnv nobody gave a context
   return &c;
 }
 
+// What the planner reads: the context's settings (cfg, sdf_config.hip) and what is derived from them, the scoring and
+// the request per call (sdf_api.hip: plan_env fills it).
 struct PlanEnv {
-  const sdf_config *cfg = default_config();  // the context's settings (sdf_config.hip); the fields below are derived per call
+  const sdf_config *cfg = default_config();
   const sdf_task *tasks = nullptr;
   size_t n = 0;
   uint32_t want = 0;
-  bool want_cigar = false;
   bool degenerate = false;  // scoring for which the reference returns before any work (:81)
   int gapo = 0;
   int max_dyn_lds = 64 * 1024;
-  bool force_general = false, no_pair = false, no_stripe = false;
-  size_t self_pair_max = 512;  // more tasks without a partner than this in a chunk: the wave kernel instead of pairing them with themselves (SDF_SELF_PAIR_MAX)
-  // mixed pairs (extz2_pair.hip, MIXED): banded tasks of one (w, flag) and different lengths two to a wavefront -- a
-  // throughput kernel: a chunk must hold `mixed_min` candidates (SDF_MIXED_MIN), and then its long banded tasks whose
-  // band reaches the end take it too, instead of the banded stripe kernel (SDF_NO_MIXED=1: off)
-  bool no_mixed = false;
-  size_t mixed_min = 4096;
-  int stripe_min = 400;
-  int bstripe_min_rows = 4000;  // banded tasks with at least this many anti-diagonals: banded stripe kernel (0: off)
+  bool force_general = false;  // SDF_FORCE_GENERAL, or a scoring the window kernels do not take
+  bool strip_ok = false;       // strip kernels (extz2_strip.hip) allowed: the scoring is tame
   // lane kernel (extz2_lane.hip): small full-band tasks leave the host's planning altogether when the batch holds at least
-  // `lane_min` of them (fewer do not fill the device: a lane walks its matrix alone, ~100 cycles per cell)
-  bool strip_ok = false;    // strip kernel (extz2_strip.hip): the scoring is tame
-  bool strip_always = false;  // SDF_STRIP_ALWAYS=1 (tests): ... whatever the number of tasks
-  int strip_cols = 0;         // SDF_STRIP_COLS (tests): columns per lane of the chained strips
-  size_t chain_min = 3072;    // chain wavefronts a chunk must hold for the chained strips (SDF_CHAIN_MIN)
-  bool lane_ok = false;     // the scoring is tame and only CIGAR / score / mte are wanted
-  size_t lane_min = 8192;
-  LaneRec *lane_recs = nullptr;  // pinned, one per task of the batch: filled by the scan
+  // SDF_LANE_MIN of them (fewer do not fill the device: a lane walks its matrix alone, ~100 cycles per cell)
+  bool lane_ok = false;          // the scoring is tame and only CIGAR / score / mte are wanted
+  LaneRec *lane_recs = nullptr;  // pinned, one per task of the batch: filled by the scan (none: no lane kernel)
+  bool want_cigar() const { return (want & SDF_WANT_CIGAR) != 0; }
+};
+
+// Launch class: the kernel instantiation a launch runs (sdf_launch.hip: launch_dp).
+struct LaunchClass {
+  enum class Family { Wave, Pair, PairTrack, PairMixed, Stripe, BStripe, Strip, Chain, General, GeneralPlain, GeneralHbm, GeneralPlainHbm };
+  Family fam;
+  int nreg = 0;         // window registers (wave, pair kernels), stripe width (stripe kernels), columns per lane (chains)
+  bool stream = false;  // wave / pair kernel: the streamed-window instantiation (sequences longer than the LDS windows)
+  int block = 0;        // general kernels: threads per workgroup
+  bool operator==(const LaunchClass &o) const { return fam == o.fam && nreg == o.nreg && stream == o.stream && block == o.block; }
+  bool operator!=(const LaunchClass &o) const { return !(*this == o); }
+  // one launch-order entry per stripe, (stripe << 24) | task (chains: per block of a pair of tasks)
+  bool per_stripe() const { return fam == Family::Stripe || fam == Family::BStripe || fam == Family::Chain; }
+  // an entry holds two tasks: a task and its partner (itself, when it has none), one wavefront
+  bool two_per_entry() const { return fam == Family::Pair || fam == Family::PairTrack || fam == Family::PairMixed || fam == Family::Strip; }
+  bool hbm_state() const { return fam == Family::GeneralHbm || fam == Family::GeneralPlainHbm; }  // lds = slab bytes per workgroup
+  bool mixed() const { return fam == Family::PairMixed; }  // long and short banded tasks in one launch
+  // rough cells per unit of time of one workgroup (the duration estimate of a class)
+  double rate() const {
+    switch (fam) {
+      case Family::Wave: return 0.13;
+      case Family::Pair: case Family::PairTrack: case Family::PairMixed: return 0.25;
+      case Family::Stripe: return 1.0;
+      case Family::BStripe: return 0.3;
+      case Family::Strip: return 0.5;
+      case Family::Chain: return 2.0;
+      case Family::General: return block == 64 ? 0.03 : block == 256 ? 0.1 : 0.6;
+      case Family::GeneralPlain: return block == 256 ? 0.3 : 0.85;
+      case Family::GeneralHbm: return 0.08;
+      case Family::GeneralPlainHbm: return 0.3;
+    }
+    return 0.13;
+  }
+  // The number SDF_DEBUG_CLASSES prints and sdf_debug_plan reports: 1..8 wave kernel with NREG (+10 streamed windows), 100 +
+  // NREG pair kernel (+10 streamed; 120 + NREG TRACK, 130 + NREG MIXED flavour), 300 / 400 + NREG stripe / banded stripe
+  // kernel, 500 strip kernel, 600 + columns per lane chained strips, 64 / 256 / 1024 general kernel with that many threads
+  // (+2000 PLAIN flavour), 1000 / 1001 / 2001 general kernel with its state in HBM (256 / 1024 threads, PLAIN).
+  int code() const {
+    switch (fam) {
+      case Family::Wave: return nreg + (stream ? 10 : 0);
+      case Family::Pair: return 100 + nreg + (stream ? 10 : 0);
+      case Family::PairTrack: return 120 + nreg;
+      case Family::PairMixed: return 130 + nreg;
+      case Family::Stripe: return 300 + nreg;
+      case Family::BStripe: return 400 + nreg;
+      case Family::Strip: return 500;
+      case Family::Chain: return 600 + nreg;
+      case Family::General: return block;
+      case Family::GeneralPlain: return 2000 + block;
+      case Family::GeneralHbm: return block == 1024 ? 1001 : 1000;
+      case Family::GeneralPlainHbm: return 2001;
+    }
+    return -1;
+  }
 };
 
 struct Launch {
-  int bs;  // 64 / 256 / 1024: general kernel with that many threads (+2000: PLAIN flavour); 1, 2, 3, 4, 6, 8: wave kernel with
-           // NREG (+10: streamed windows); 100 + NREG: pair kernel (+10: streamed; 120 + NREG: TRACK flavour);
-           // 300 + NREG: stripe kernel, 400 + NREG: banded stripe kernel (one launch-order entry per stripe);
-           // 1000 / 1001 / 2001: general kernel with its state in HBM
+  LaunchClass lc;
   size_t lds;  // dynamic LDS bytes of the launch (HBM-state classes: slab bytes per workgroup)
   size_t off, cnt;  // entries of the chunk's launch order
   double est;       // duration estimate: the launch's longest task
@@ -162,7 +203,7 @@ inline int bstripe_nreg(int tlen, const int forced) {  // forced: sdf_config.bst
 inline bool task_runs(const sdf_task &t, bool degenerate) { return t.qlen > 0 && t.tlen > 0 && !degenerate; }
 
 struct Cls {
-  int bs;
+  LaunchClass lc;
   size_t lds;       // class key
   size_t need_max;  // largest real requirement in the class: what the launch asks for
   std::vector<int32_t> idx;
@@ -225,7 +266,7 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
   const bool dbg_cut = env.cfg->debug_plan != 0;
   const auto tc0 = std::chrono::steady_clock::now();
   std::vector<uint32_t> &bound = cut.bound, &cap = cut.cap;
-  const bool lane_scan = env.lane_ok && env.lane_recs && n >= env.lane_min;
+  const bool lane_scan = env.lane_ok && env.lane_recs && n >= (size_t)env.cfg->lane_min;
   if (lane_scan && cut.lane.size() < n) cut.lane.resize(n);
   // (not cleared: 8 MB of memset per million tasks, on this thread, before anything else can start -- the scan below
   // writes both words of every task, runnable or not)
@@ -240,13 +281,13 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
   const size_t nblk = (n + SDF_CUT_BLOCK - 1) / SDF_CUT_BLOCK;
   cut.blocks.assign(nblk, BatchCut::Block());
   auto banded_long = [&](const sdf_task &t) {  // (a superset of what plan_chunk gives to the banded stripe kernel)
-    return env.bstripe_min_rows > 0 && t.w >= 1 && t.qlen + t.tlen - 1 >= env.bstripe_min_rows && plan_detail::bstripe_nreg(t.tlen, (int)env.cfg->bstripe_nreg) > 0;
+    return env.cfg->bstripe_min_rows > 0 && t.w >= 1 && t.qlen + t.tlen - 1 >= env.cfg->bstripe_min_rows && plan_detail::bstripe_nreg(t.tlen, (int)env.cfg->bstripe_nreg) > 0;
   };
   auto order_entries = [&](const sdf_task &t) -> uint32_t {  // a task paired with itself is listed twice, a stripe task
     // (chained strips take full-band targets of 513..65536 bases whatever stripe_min is: eight idle entries of padding per
     // block at most -- ADVICE r3: with SDF_STRIPE_MIN above 512 their launch order overflowed)
     const bool chain = env.strip_ok && t.tlen > kStripMaxT && t.tlen <= kStripChainMaxT;
-    return 2 + (t.tlen > env.stripe_min && t.tlen <= kStripeMaxT ? (uint32_t)(t.tlen + 127) / 128 : chain ? 8u * (uint32_t)strip_blocks(t.tlen, 4) : 0u) +  // once per stripe
+    return 2 + (t.tlen > env.cfg->stripe_min && t.tlen <= kStripeMaxT ? (uint32_t)(t.tlen + 127) / 128 : chain ? 8u * (uint32_t)strip_blocks(t.tlen, 4) : 0u) +  // once per stripe
            (banded_long(t) ? (uint32_t)(t.tlen + 15 + 127) / 128 : 0u);
   };
   {
@@ -290,7 +331,7 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
       // A task that wants no CIGAR needs no direction flags -- except on the stripe kernels, whose progress words,
       // hand-over values and edge columns live in HBM right behind the task's flag blocks: those tasks reserve the
       // whole layout whatever they want.
-      const bool with_dir = env.want_cigar && !(t.flag & SDF_FLAG_SCORE_ONLY);
+      const bool with_dir = env.want_cigar() && !(t.flag & SDF_FLAG_SCORE_ONLY);
       words = with_dir ? (uint32_t)(t.qlen + t.tlen + 2) : 0u;
       cap[k] |= words;
       blk.sw += words;
@@ -315,9 +356,9 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
         // own bounds follow below: 0.5-0.8 bytes per cell against the byte rows' two per cell of a square matrix).  The
         // far-gap round of the chr1-sized stage -- 10,813 tasks, 9.5e9 cells -- was cut into two chunks of one 7 ms chain each
         // by that bound; one chunk: DP 14.4 -> see profiles/r06_stage_dp2.txt.
-        const bool striped_always = !env.force_general && !env.no_stripe && !(env.want & SDF_WANT_EXT) && t.zdrop < 0 && env.gapo >= 0 &&
+        const bool striped_always = !env.force_general && !env.cfg->no_stripe && !(env.want & SDF_WANT_EXT) && t.zdrop < 0 && env.gapo >= 0 &&
                                     !(t.flag & (SDF_FLAG_RIGHT | SDF_FLAG_EXTZ_ONLY | SDF_FLAG_GENERIC_SC | SDF_FLAG_APPROX_MAX | SDF_FLAG_APPROX_DROP)) &&
-                                    w >= std::max(t.qlen, t.tlen) && t.tlen > env.stripe_min && t.tlen <= kStripeMaxT &&
+                                    w >= std::max(t.qlen, t.tlen) && t.tlen > env.cfg->stripe_min && t.tlen <= kStripeMaxT &&
                                     stripe_lds_bytes(t.qlen, 4) <= (size_t)env.max_dyn_lds;
         if (!bits_only && !striped_always) bd = hvb;
         // (the wave kernel's blocks: 1 KiB per register of 128 slots -- 1, 2, 3, 4, 6 or 8 of them; the pair kernels' 512 B per
@@ -336,7 +377,7 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
           bd = std::max(bd, (nrow + 15) / 16 * (size_t)nreg * 512);
         }
       }
-      if (t.tlen > env.stripe_min && t.tlen <= kStripeMaxT && w >= std::max(t.qlen, t.tlen))  // (stripe kernel, any width)
+      if (t.tlen > env.cfg->stripe_min && t.tlen <= kStripeMaxT && w >= std::max(t.qlen, t.tlen))  // (stripe kernel, any width)
         for (int nr = 1; nr <= 4; nr *= 2)
           bd = std::max(bd, (stripe_dir_bytes(t.qlen, t.tlen, nr) + stripe_sync_bytes(t.qlen, t.tlen, nr) + 255) & ~(size_t)255);
       if (banded_long(t)) {
@@ -356,7 +397,7 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
         // (a chain's blocks are four columns per lane wide when its chunk holds few of them -- plan_chunk decides, unless
         // SDF_STRIP_COLS=8 does --: twice the blocks, a record per PAIR of steps -- the same bytes, one block of rounding
         // apart, whichever plan_chunk picks)
-        bd = std::max(bd, t.tlen > kStripMaxT && env.strip_cols != 8
+        bd = std::max(bd, t.tlen > kStripMaxT && env.cfg->strip_cols != 8
                               ? ((size_t)std::max(strip_blocks(t.tlen, 4), 2 * strip_blocks(t.tlen, 8)) *
                                      (size_t)(t.qlen * 27 / 50 + 60) * 260 + 512 + 255) & ~(size_t)255
                               : ((size_t)strip_blocks(t.tlen, 8) * (size_t)(t.qlen * 27 / 50 + 60) * 520 + 512 + 255) & ~(size_t)255);
@@ -412,7 +453,7 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
         if (lane_scan && t.qlen <= kLaneMaxLen && t.tlen <= kLaneMaxLen && (int64_t)t.qlen * t.tlen <= kLaneMaxCells &&
             (t.w < 0 || t.w >= std::max(t.qlen, t.tlen)) && t.zdrop < 0 && !(t.flag & ~(SDF_FLAG_SCORE_ONLY | SDF_FLAG_REV_CIGAR)) &&
             (uint64_t)t.q_off < 0xffffffffull && (uint64_t)t.t_off < 0xffffffffull) {
-          const bool with_dir = env.want_cigar && !(t.flag & SDF_FLAG_SCORE_ONLY);
+          const bool with_dir = env.want_cigar() && !(t.flag & SDF_FLAG_SCORE_ONLY);
           BatchCut::Block &blk = cut.blocks[k / SDF_CUT_BLOCK];
           cut.lane[k] = 1;
           LaneRec &lr = env.lane_recs[k];
@@ -591,7 +632,7 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
         for (int c = 0; c < 4; ++c) cut.lane_cls[c] += blk.lcls[c];
       }
       // (a quarter of the workspace in 4-bit flags would be more than 10^10 cells of small tasks)
-      cut.use_lane = cut.n_lane >= env.lane_min && cut.lane_dir_bytes + 256 <= ws_budget / 4;
+      cut.use_lane = cut.n_lane >= (size_t)env.cfg->lane_min && cut.lane_dir_bytes + 256 <= ws_budget / 4;
       if (!cut.use_lane && cut.n_lane) {  // too few of them after all: they are ordinary tasks
         for (size_t k = 0; k < n; ++k)
           if (cut.lane[k]) {
@@ -719,8 +760,9 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
 static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, PlanTask *plan, int32_t *order,
                        PlanScratch &sx) {
   using plan_detail::Cls;
+  using Family = LaunchClass::Family;
   const sdf_task *tasks = env.tasks;
-  const bool want_cigar = env.want_cigar;
+  const bool want_cigar = env.want_cigar();
   const bool dbg_pc = env.cfg->debug_plan != 0;
   const auto tp0 = std::chrono::steady_clock::now();
   auto tp1 = tp0, tp2 = tp0, tp3 = tp0;
@@ -739,7 +781,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
   // the device: 1,024 one-wavefront tasks, 3,072 chain wavefronts (1,024 for the heavy tasks of a large batch).
   bool use_strip = false, use_chain = false;
   if (env.strip_ok) {
-    const bool force = env.strip_always;  // (tests: whatever the count)
+    const bool force = env.cfg->strip_always != 0;  // (tests: whatever the count)
     size_t n9 = 0, w10 = 0;
     for (size_t pos = c.s; pos < c.e; ++pos) {
       const size_t k = c.heavy ? cut.heavy_idx[pos] : pos;
@@ -754,7 +796,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     // (the heavy tasks of a large batch share the device with everything else it holds: what counts there is the work per
     // cell, not the pace of a lone chain -- the hg19 mixture's 608 long tasks, 2,900 chain wavefronts: 13.5-14.0 ms as chains
     // against 14.2-15.2 on the stripe kernel; the same tasks alone: 10-15 % slower as chains)
-    const size_t chain_min = c.heavy && cut.n_heavy * 16 <= env.n ? std::min<size_t>(env.chain_min, 1024) : env.chain_min;
+    const size_t chain_min = c.heavy && cut.n_heavy * 16 <= env.n ? std::min<size_t>((size_t)env.cfg->chain_min, 1024) : (size_t)env.cfg->chain_min;
     use_chain = force || w10 / 2 >= chain_min;
   }
   // A FEW tasks much longer than the rest of a chunk of chains: a chain's step is ~1 us on blocks of 256 columns, a stripe's row
@@ -763,10 +805,10 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
   // 1.7 kb: the round's DP 21 -> see profiles/r04_stage.txt).
   size_t n_long = 0;
   auto long_task = [&](const sdf_task &t) {
-    return t.qlen + t.tlen >= 12000 && t.tlen > env.stripe_min && t.tlen <= kStripeMaxT && (t.w < 0 || t.w >= std::max(t.qlen, t.tlen)) &&
+    return t.qlen + t.tlen >= 12000 && t.tlen > env.cfg->stripe_min && t.tlen <= kStripeMaxT && (t.w < 0 || t.w >= std::max(t.qlen, t.tlen)) &&
            stripe_lds_bytes(t.qlen, 4) <= (size_t)env.max_dyn_lds;
   };
-  if (use_chain && !env.strip_always && !env.no_stripe) {
+  if (use_chain && !env.cfg->strip_always && !env.cfg->no_stripe) {
     for (size_t pos = c.s; pos < c.e; ++pos) {
       const size_t k = c.heavy ? cut.heavy_idx[pos] : pos;
       const sdf_task &t = c.heavy ? cut.heavy_tasks[pos] : tasks[k];
@@ -793,7 +835,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     nc = (std::min(nc, p.w + 1) + 15) / 16 + 1;
     p.ncol16 = nc * 16;
     p.out_idx = (int32_t)k;
-    p.pad_ = 0;
+    p.kind = kTaskGeneral;
     // register-resident wave kernel when only CIGAR/score/mte are wanted and the shape fits
     p.nreg = 0;
     int wneed = 0;
@@ -816,13 +858,13 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       const int bstripe_all = (int)env.cfg->bstripe_all;  // (tests: every long banded task)
       constexpr int bstripe_plain_min = 192;  // (measured on the mm8-like mixture: 384 -> 47 ms, 192 -> 29-34 ms, 128 -> 36-39 ms)
       const int bneed = std::min(p.ncol16 + 32, (t.tlen + 15) / 16 * 16);
-      if (simple && !env.force_general && env.bstripe_min_rows > 0 && nrow >= env.bstripe_min_rows && p.w >= 1 &&
+      if (simple && !env.force_general && env.cfg->bstripe_min_rows > 0 && nrow >= env.cfg->bstripe_min_rows && p.w >= 1 &&
           p.w < std::max(t.qlen, t.tlen) && (bstripe_all || bneed > bstripe_plain_min || !band_whole)) {
         const int nr = plan_detail::bstripe_nreg(t.tlen, (int)env.cfg->bstripe_nreg);
         if (nr && bstripe_lds_bytes(p.w, nr) <= (size_t)env.max_dyn_lds) {
           p.nreg = nr;
-          p.pad_ = 7;
-          if (plain_ok && bneed <= kMixedMaxNeed && !env.no_pair && !env.no_mixed) {  // (band_whole: a mixed pair can take it)
+          p.kind = kTaskBStripe;
+          if (plain_ok && bneed <= kMixedMaxNeed && !env.cfg->no_pair && !env.cfg->no_mixed) {  // (band_whole: a mixed pair can take it)
             const int wn = bneed <= 128 ? 1 : bneed <= 256 ? 2 : bneed <= 384 ? 3 : bneed <= 512 ? 4 : 6;
             if (wave_lds_bytes(t.qlen, t.tlen, wn) <= (size_t)env.max_dyn_lds) {
               sx.bs_alt.push_back((int32_t)(np - c.pb));
@@ -835,7 +877,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       // the same request on a band that runs out before the end of both sequences: the pair kernel's TRACK flavour
       // (exact H of every cell, best cell for the traceback), the task paired with itself; windows up to 384 slots
       const bool runs_out = !band_whole && p.w >= 1 && nrow > 1;
-      if (p.pad_ != 7 && runs_out && !env.force_general && !env.no_pair && !(env.want & SDF_WANT_EXT) && t.zdrop < 0 &&
+      if (p.kind != kTaskBStripe && runs_out && !env.force_general && !env.cfg->no_pair && !(env.want & SDF_WANT_EXT) && t.zdrop < 0 &&
           !(t.flag & general_only) && env.gapo >= 0) {
         const int need = std::min(p.ncol16 + 32, (t.tlen + 15) / 16 * 16);
         // (wider windows stay on the general kernel: ten registers on one wavefront were measured no faster per row
@@ -843,10 +885,10 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
         const int nreg = need <= 192 ? 3 : need <= 384 ? 6 : 0;
         if (nreg && pair_lds_bytes(t.qlen, t.tlen, nreg) <= (size_t)env.max_dyn_lds) {
           p.nreg = nreg;
-          p.pad_ = 6;  // (becomes layout 2 below; 6 marks the TRACK launch class until then)
+          p.kind = kTaskTrack;  // (a kTaskPair paired with itself below; marks the TRACK launch class until then)
         }
       }
-      if (plain_ok && p.pad_ != 7) {
+      if (plain_ok && p.kind != kTaskBStripe) {
         // window slots: one 16-row block of slack below, the score refresh overshoot above -- but never
         // beyond the target's last 16-cell block (cells past it are not part of any window)
         const int need = std::min(p.ncol16 + 32, (t.tlen + 15) / 16 * 16);
@@ -862,27 +904,27 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     p.cig_cap = (p.flag & SDF_FLAG_SCORE_ONLY) ? 0 : t.qlen + t.tlen + 2;
     p.cig_slot = stage_words;
     stage_words += p.cig_cap;
-    if (use_strip && p.pad_ != 7 && plain_ok && p.w >= std::max(t.qlen, t.tlen) && t.tlen > 256 && t.tlen <= kStripMaxT &&
+    if (use_strip && p.kind != kTaskBStripe && plain_ok && p.w >= std::max(t.qlen, t.tlen) && t.tlen > 256 && t.tlen <= kStripMaxT &&
         t.qlen >= 64 && t.qlen < (1 << 18)) {
       // full band, a few hundred target bases: row-major strips, two tasks per wavefront
       p.nreg = 8;  // (columns per lane)
-      p.pad_ = 9;
+      p.kind = kTaskStrip;
       win_need.back() = 0;
-    } else if ((use_chain || (env.strip_ok && t.tlen > kStripeMaxT)) && !(long_to_stripes && long_task(t)) && !env.no_stripe &&
-               p.pad_ != 7 && plain_ok && p.w >= std::max(t.qlen, t.tlen) && t.tlen > kStripMaxT && t.tlen <= kStripChainMaxT &&
+    } else if ((use_chain || (env.strip_ok && t.tlen > kStripeMaxT)) && !(long_to_stripes && long_task(t)) && !env.cfg->no_stripe &&
+               p.kind != kTaskBStripe && plain_ok && p.w >= std::max(t.qlen, t.tlen) && t.tlen > kStripMaxT && t.tlen <= kStripChainMaxT &&
                t.qlen >= 64 && t.qlen < (1 << 18)) {
       // ... wider: the same strips, a wavefront per block of columns, chained through HBM.  Targets beyond the stripe
       // kernel's 32,512 bases are chains however few they are: the alternative is the workgroup kernel walking its window
       // through LDS at ~3 us per row (a 61,440 x 61,440 task alone: 2,070 ms there, 80 ms here)
       p.nreg = 8;  // (columns per lane: 8, or 4 when the chunk has few chains -- decided below)
-      p.pad_ = 10;
+      p.kind = kTaskChain;
       win_need.back() = 0;
-    } else if (p.pad_ != 7 && plain_ok && !env.no_stripe && p.w >= std::max(t.qlen, t.tlen) &&
-        t.tlen > env.stripe_min && t.tlen <= kStripeMaxT) {
+    } else if (p.kind != kTaskBStripe && plain_ok && !env.cfg->no_stripe && p.w >= std::max(t.qlen, t.tlen) &&
+        t.tlen > env.cfg->stripe_min && t.tlen <= kStripeMaxT) {
       // wide full-band task: one wavefront per stripe of 128 * nreg target positions (nreg: after this pass)
       if (stripe_lds_bytes(t.qlen, 4) <= (size_t)env.max_dyn_lds) {
         p.nreg = 4;
-        p.pad_ = 5;
+        p.kind = kTaskStripe;
         ++n_stripe_tasks;
         stripe_cells += (double)t.qlen * (double)t.tlen;
         stripe_rows = std::max(stripe_rows, t.qlen + t.tlen);
@@ -894,9 +936,9 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       // is wide enough for the 256- or 1024-thread instantiation
       const bool hbm = general_lds_bytes(t.qlen, t.tlen) > (size_t)env.max_dyn_lds;
       const int width = std::min(p.ncol16, (t.tlen + 15) / 16 * 16);
-      if (plain_ok && !hbm && width > 256) p.pad_ = 3;
-      else if (plain_ok && hbm && width > 1024) p.pad_ = 4;
-      else p.pad_ = hbm ? 1 : 0;
+      if (plain_ok && !hbm && width > 256) p.kind = kTaskPlain;
+      else if (plain_ok && hbm && width > 1024) p.kind = kTaskPlainHbm;
+      else p.kind = hbm ? kTaskGeneralHbm : kTaskGeneral;
     }
     plan[np++] = p;
   }
@@ -935,12 +977,12 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     }
     for (size_t k = 0; k < cnt; ++k) {
       PlanTask &p = cp[k];
-      if (p.pad_ != 5) continue;
+      if (p.kind != kTaskStripe) continue;
       p.nreg = nr;
       if ((p.tlen + 128 * nr - 1) / (128 * nr) > 254) {  // (entry encoding: 8 bits of stripe index, 255 = idle)
         p.nreg = 0;
         const bool hbm = general_lds_bytes(p.qlen, p.tlen) > (size_t)env.max_dyn_lds;
-        p.pad_ = hbm ? 4 : 3;
+        p.kind = hbm ? kTaskPlainHbm : kTaskPlain;
       }
     }
   }
@@ -952,15 +994,15 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
   bool use_mixed = false;
   std::vector<char> &mixedf = sx.mixedf;
   mixedf.assign(cnt, 0);
-  if (!env.no_pair && !env.no_mixed && !env.force_general) {
+  if (!env.cfg->no_pair && !env.cfg->no_mixed && !env.force_general) {
     size_t ncand = sx.bs_alt.size() / 3;
     for (size_t k = 0; k < cnt; ++k)
-      ncand += cp[k].nreg && cp[k].pad_ == 0 && win_need[k] > 0 && win_need[k] <= kMixedMaxNeed && cp[k].w < std::max(cp[k].qlen, cp[k].tlen);
-    use_mixed = ncand >= env.mixed_min;
+      ncand += cp[k].nreg && cp[k].kind == kTaskGeneral && win_need[k] > 0 && win_need[k] <= kMixedMaxNeed && cp[k].w < std::max(cp[k].qlen, cp[k].tlen);
+    use_mixed = ncand >= (size_t)env.cfg->mixed_min;
     if (use_mixed)
       for (size_t j = 0; j + 2 < sx.bs_alt.size(); j += 3) {
         PlanTask &p = cp[sx.bs_alt[j]];
-        p.pad_ = 0;
+        p.kind = kTaskGeneral;
         p.nreg = sx.bs_alt[j + 1];
         win_need[sx.bs_alt[j]] = sx.bs_alt[j + 2];
       }
@@ -973,19 +1015,19 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
   std::vector<char> &tracked = sx.tracked;
   tracked.assign(cnt, 0);
   for (size_t k = 0; k < cnt; ++k)
-    if (cp[k].pad_ == 6) {
-      cp[k].pad_ = 2;
+    if (cp[k].kind == kTaskTrack) {
+      cp[k].kind = kTaskPair;
       partner[k] = (int32_t)k;
       tracked[k] = 1;
     }
-  if (!env.no_pair && !env.force_general) {
+  if (!env.cfg->no_pair && !env.force_general) {
     auto &table = sx.table;
     size_t cap = 64;
     while (cap < 2 * cnt) cap *= 2;
     table.assign(cap, {-1, -1});
     for (size_t k = 0; k < cnt; ++k) {
       PlanTask &y = cp[k];
-      if (!y.nreg || y.pad_ != 0 || win_need[k] > 512) continue;  // wave-kernel tasks only
+      if (!y.nreg || y.kind != kTaskGeneral || win_need[k] > 512) continue;  // wave-kernel tasks only
       uint64_t h = ((uint64_t)(uint32_t)y.qlen * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(uint32_t)y.tlen * 0xC2B2AE3D27D4EB4Full) ^
                    ((uint64_t)(uint32_t)y.w * 0x165667B19E3779F9ull) ^ ((uint64_t)(uint32_t)y.flag << 40);
       h ^= h >> 29;
@@ -1006,7 +1048,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
         const int nreg = regs <= 4 ? regs : regs <= 6 ? 6 : 8;
         if (pair_lds_bytes(y.qlen, y.tlen, nreg) > (size_t)env.max_dyn_lds) break;
         z.nreg = y.nreg = nreg;
-        z.pad_ = y.pad_ = 2;
+        z.kind = y.kind = kTaskPair;
         partner[k] = e.second;
         partner[e.second] = (int32_t)k;
         c.paired += 2;
@@ -1030,7 +1072,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       for (auto &e : table)
         if (e.second >= 0) add_key((size_t)e.second);
       for (size_t k = 0; k < cnt; ++k)
-        if (cp[k].nreg && cp[k].pad_ == 0 && win_need[k] > 512 && win_need[k] <= kMixedMaxNeed) add_key(k);
+        if (cp[k].nreg && cp[k].kind == kTaskGeneral && win_need[k] > 512 && win_need[k] <= kMixedMaxNeed) add_key(k);
       // (a batch of few geometries -- the headline's 100,000 tasks of ~50 target lengths -- leaves a handful without a
       // partner: they are paired with themselves inside the tuned launch, as before, not given a launch of their own)
       if (keys.size() * 16 < cnt) keys.clear();
@@ -1052,7 +1094,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
           continue;
         }
         x.nreg = y.nreg = nreg;
-        x.pad_ = y.pad_ = 2;
+        x.kind = y.kind = kTaskPair;
         partner[a] = (int32_t)b;
         partner[b] = (int32_t)a;
         mixedf[a] = mixedf[b] = 1;
@@ -1074,7 +1116,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
         const int nreg = regs <= 2 ? 2 : regs <= 6 ? regs : regs <= 8 ? 8 : 9;
         if (pair_mixed_lds_bytes(x.qlen, x.tlen, nreg) > (size_t)env.max_dyn_lds) continue;
         x.nreg = nreg;
-        x.pad_ = 2;
+        x.kind = kTaskPair;
         partner[a] = (int32_t)a;
         mixedf[a] = 1;
       }
@@ -1083,11 +1125,11 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       // its tuned instantiations
       size_t n_exact = 0;
       for (size_t k = 0; k < cnt; ++k)
-        n_exact += cp[k].pad_ == 2 && !mixedf[k] && !tracked[k] && partner[k] >= 0 && partner[k] != (int32_t)k && cp[k].w < std::max(cp[k].qlen, cp[k].tlen);
+        n_exact += cp[k].kind == kTaskPair && !mixedf[k] && !tracked[k] && partner[k] >= 0 && partner[k] != (int32_t)k && cp[k].w < std::max(cp[k].qlen, cp[k].tlen);
       if (n_exact * 4 <= n_mixed)
         for (size_t k = 0; k < cnt; ++k) {
           PlanTask &x = cp[k];
-          if (x.pad_ != 2 || mixedf[k] || tracked[k] || partner[k] <= (int32_t)k || x.w >= std::max(x.qlen, x.tlen)) continue;
+          if (x.kind != kTaskPair || mixedf[k] || tracked[k] || partner[k] <= (int32_t)k || x.w >= std::max(x.qlen, x.tlen)) continue;
           const int regs = (win_need[k] + 63) / 64;
           const int nreg = regs <= 2 ? 2 : regs <= 6 ? regs : regs <= 8 ? 8 : 9;
           if (pair_mixed_lds_bytes(x.qlen, x.tlen, nreg) > (size_t)env.max_dyn_lds) continue;
@@ -1100,7 +1142,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       for (size_t j = 0; j + 2 < sx.bs_alt.size(); j += 3) {
         const int32_t k = sx.bs_alt[j];
         if (partner[k] >= 0) continue;
-        cp[k].pad_ = 7;
+        cp[k].kind = kTaskBStripe;
         cp[k].nreg = plan_detail::bstripe_nreg(cp[k].tlen, (int)env.cfg->bstripe_nreg);
         win_need[k] = 0;
         for (auto &e : table)
@@ -1114,13 +1156,13 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     size_t n_left = 0;
     for (auto &e : table) n_left += e.second >= 0;
     for (auto &e : table) {
-      if (e.second < 0 || n_left > env.self_pair_max) continue;
+      if (e.second < 0 || n_left > (size_t)env.cfg->self_pair_max) continue;
       PlanTask &y = cp[e.second];
       const int regs = (win_need[e.second] + 63) / 64;
       const int nreg = regs <= 4 ? regs : regs <= 6 ? 6 : 8;
       if (pair_lds_bytes(y.qlen, y.tlen, nreg) > (size_t)env.max_dyn_lds) continue;
       y.nreg = nreg;
-      y.pad_ = 2;
+      y.kind = kTaskPair;
       partner[e.second] = e.second;
     }
   }
@@ -1135,10 +1177,10 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     // tasks of a batch: fewer wavefronts than the device has slots for) take four columns per lane, many take eight
     // (less per-step overhead per cell).  One width per chunk: one launch.
     {
-      const int force_cols = env.strip_cols;
+      const int force_cols = (int)env.cfg->strip_cols;
       size_t chain_waves = 0;
       for (size_t k = 0; k < cnt; ++k)
-        if (cp[k].pad_ == 10) chain_waves += (size_t)strip_blocks(cp[k].tlen, 8);
+        if (cp[k].kind == kTaskChain) chain_waves += (size_t)strip_blocks(cp[k].tlen, 8);
       // (measured, profiles/r03_strip.txt: four columns shorten a lone chain -- 5.3 against 6.5 ms for 6000 x 6000 -- but
       // cost throughput -- 1,364 against 1,612 Gcell/s on 20,000 x 1000 x 1000 --, and lone chains are the stripe
       // kernel's anyway: eight unless SDF_STRIP_COLS says otherwise)
@@ -1147,10 +1189,10 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       // 1,000,000-task batch, its DP 9.3-10.8 against 11.6-11.9 ms)
       const int cols = force_cols == 4 || force_cols == 8 ? force_cols : chain_waves / 2 <= 4096 ? 4 : 8;  // (two tasks a wavefront)
       for (size_t k = 0; k < cnt; ++k)
-        if (cp[k].pad_ == 10) cp[k].nreg = cols;
+        if (cp[k].kind == kTaskChain) cp[k].nreg = cols;
     }
     for (size_t k = 0; k < cnt; ++k)
-      if (cp[k].pad_ == 9 || cp[k].pad_ == 10) {
+      if (cp[k].kind == kTaskStrip || cp[k].kind == kTaskChain) {
         // (blocks, rows, columns within the last block, index): 8 + 18 + 9 + 24 bits -- up to 256 blocks; a one-wavefront
         // task has one block and a chain at least two, so the two kinds stay apart
         const int bw = 64 * cp[k].nreg;
@@ -1185,7 +1227,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       const int32_t x = sl[q];
       int32_t y = x;  // the next one, if it has as many column blocks and at most an eighth as many rows again (+ 64: the
                       // flag bound of cut_batch counts on it)
-      if (q + 1 < sl.size() && cp[sl[q + 1]].pad_ == cp[x].pad_ &&
+      if (q + 1 < sl.size() && cp[sl[q + 1]].kind == cp[x].kind &&
           strip_blocks(cp[sl[q + 1]].tlen, cp[x].nreg) == strip_blocks(cp[x].tlen, cp[x].nreg) &&
           cp[sl[q + 1]].qlen <= cp[x].qlen + cp[x].qlen / 8 + 64)
         y = sl[q + 1];
@@ -1195,7 +1237,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       partner[hi] = lo;
       // (the rows the wavefront steps through: the traceback finds a block's records by it)
       cp[lo].ncol16 = cp[hi].ncol16 = std::max(cp[lo].qlen, cp[hi].qlen) | (lo == hi ? 1 << 30 : 0);  // (bit 30: no partner)
-      if (cp[lo].pad_ == 10) {  // (the chain kernel finds a task's partner through its plan record)
+      if (cp[lo].kind == kTaskChain) {  // (the chain kernel finds a task's partner through its plan record)
         cp[lo].zdrop = hi;
         cp[hi].zdrop = lo;
       }
@@ -1212,7 +1254,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     {
       size_t need = 0;
       // (the stripe kernels keep their inter-stripe words behind the flag blocks: reserved for score-only tasks as well)
-      if (p.pad_ == 9 || p.pad_ == 10) {
+      if (p.kind == kTaskStrip || p.kind == kTaskChain) {
         // one flag region per wavefront: task A's words are the even, its partner's the odd ones of the same records
         if (partner[k] < (int32_t)k) {
           need = 0;  // (placed with its partner, below)
@@ -1220,72 +1262,73 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
           const PlanTask &pb = cp[partner[k]];
           const int qm = std::max(p.qlen, pb.qlen), tm = std::max(p.tlen, pb.tlen);
           need = (strip_dir_bytes(qm, tm, p.nreg, partner[k] == (int32_t)k) + 255) & ~(size_t)255;
-          if (p.pad_ == 10) need += strip_chain_sync_bytes(qm, tm, p.nreg);
+          if (p.kind == kTaskChain) need += strip_chain_sync_bytes(qm, tm, p.nreg);
           if (partner[k] != (int32_t)k) cp[partner[k]].dir_off = (int64_t)dir_acc + 4;
         }
-      } else if (p.pad_ == 5)
+      } else if (p.kind == kTaskStripe)
         need = (stripe_dir_bytes(p.qlen, p.tlen, p.nreg) + stripe_sync_bytes(p.qlen, p.tlen, p.nreg) + 255) & ~(size_t)255;
-      else if (p.pad_ == 7)
+      else if (p.kind == kTaskBStripe)
         need = (bstripe_dir_bytes(p.qlen, p.tlen, p.w, p.nreg) + bstripe_sync_bytes(p.qlen, p.tlen, p.w, p.nreg) + 255) & ~(size_t)255;
       else if (!(p.flag & SDF_FLAG_SCORE_ONLY)) {
         const size_t nblk = (size_t)((p.qlen + p.tlen - 1 + 15) / 16);
-        if (p.pad_ == 2) need = nblk * (size_t)p.nreg * 512;
+        if (p.kind == kTaskPair) need = nblk * (size_t)p.nreg * 512;
         else if (p.nreg) need = nblk * (size_t)p.nreg * 1024;
         else need = ((size_t)(p.qlen + p.tlen - 1) * (size_t)p.ncol16 + 16 + 255) & ~(size_t)255;
       }
-      if (!((p.pad_ == 9 || p.pad_ == 10) && partner[k] < (int32_t)k)) p.dir_off = (int64_t)dir_acc;
+      if (!((p.kind == kTaskStrip || p.kind == kTaskChain) && partner[k] < (int32_t)k)) p.dir_off = (int64_t)dir_acc;
       dir_acc += need;
     }
-    c.layouts |= 1u << (p.nreg == 0 ? 0 : p.pad_ == 2 ? 2 : p.pad_ == 5 ? 3 : p.pad_ == 7 ? 4 : (p.pad_ == 9 || p.pad_ == 10) ? 6 : 1);
+    c.layouts |= 1u << dir_layout(p);
     const int width = std::min(p.ncol16, (p.tlen + 15) / 16 * 16);
-    int bs = width > 1024 ? 1024 : width > 256 ? 256 : 64;  // 4 cells per thread and pass over the row
+    const int block = width > 1024 ? 1024 : width > 256 ? 256 : 64;  // 4 cells per thread and pass over the row
+    LaunchClass lc{Family::General};
     size_t lds = 2048, need;
-    if (p.pad_ == 10) {
+    if (p.kind == kTaskChain) {
       if (partner[k] < (int32_t)k) continue;  // (its partner's entry stands for both)
-      bs = 600 + p.nreg;  // chained strips: one wavefront (workgroup) per block of 64 x nreg columns of a pair of tasks
+      lc = {Family::Chain, p.nreg};  // chained strips: one wavefront (workgroup) per block of 64 x nreg columns of a pair of tasks
       need = 16;
       lds = 1024;
-    } else if (p.pad_ == 9) {
+    } else if (p.kind == kTaskStrip) {
       if (partner[k] < (int32_t)k) continue;  // placed together with its partner
-      bs = 500;  // strip kernel, one wavefront per pair of tasks
+      lc = {Family::Strip};  // strip kernel, one wavefront per pair of tasks
       need = strip_lds_bytes(std::max(p.qlen, cp[partner[k]].qlen), std::max(p.tlen, cp[partner[k]].tlen));
       lds = 1024;
       while (lds < need) lds *= 2;
-    } else if (p.pad_ == 2) {
+    } else if (p.kind == kTaskPair) {
       if (partner[k] < (int32_t)k) continue;  // placed together with its partner
-      // 100 + NREG; + 10 for the streamed-window instantiation (sequences longer than the LDS windows)
-      bs = tracked[k] ? 120 + p.nreg : mixedf[k] ? 130 + p.nreg : 100 + p.nreg + (pair_fits_whole(p.qlen, p.tlen, p.nreg) ? 0 : 10);
+      lc = tracked[k] ? LaunchClass{Family::PairTrack, p.nreg} : mixedf[k] ? LaunchClass{Family::PairMixed, p.nreg}
+                      : LaunchClass{Family::Pair, p.nreg, !pair_fits_whole(p.qlen, p.tlen, p.nreg)};
       need = mixedf[k] ? pair_mixed_lds_bytes(std::max(p.qlen, cp[partner[k]].qlen), std::max(p.tlen, cp[partner[k]].tlen), p.nreg)
                        : pair_lds_bytes(p.qlen, p.tlen, p.nreg);
       lds = 8192;
       while (lds < need) lds *= 2;
-    } else if (p.pad_ == 5) {
-      bs = 300 + p.nreg;  // stripe kernel, one wavefront (workgroup) per stripe
+    } else if (p.kind == kTaskStripe) {
+      lc = {Family::Stripe, p.nreg};  // stripe kernel, one wavefront (workgroup) per stripe
       need = stripe_lds_bytes(p.qlen, p.nreg);
       lds = 8192;
       while (lds < need) lds *= 2;
-    } else if (p.pad_ == 7) {
-      bs = 400 + p.nreg;  // banded stripe kernel, one wavefront (workgroup) per stripe
+    } else if (p.kind == kTaskBStripe) {
+      lc = {Family::BStripe, p.nreg};  // banded stripe kernel, one wavefront (workgroup) per stripe
       need = bstripe_lds_bytes(p.w, p.nreg);
       lds = 8192;
       while (lds < need) lds *= 2;
     } else if (p.nreg) {
-      // NREG; + 10 for the streamed-window instantiation (sequences longer than the LDS windows)
-      bs = p.nreg + (wave_fits_whole(p.qlen, p.tlen, p.nreg) ? 0 : 10);
+      lc = {Family::Wave, p.nreg, !wave_fits_whole(p.qlen, p.tlen, p.nreg)};
       // one class for everything up to 6 KiB (>= 6 waves/SIMD either way), powers of two above
       need = wave_lds_bytes(p.qlen, p.tlen, p.nreg);
       lds = 6144;
       while (lds < need) lds *= 2;
-    } else if (p.pad_ == 1 || p.pad_ == 4) {  // HBM-resident state: one class, slab = largest requirement
-      bs = p.pad_ == 4 ? 2001 : width > 1024 ? 1001 : 1000;
+    } else if (p.kind == kTaskGeneralHbm || p.kind == kTaskPlainHbm) {  // HBM-resident state: one class, slab = largest requirement
+      lc = p.kind == kTaskPlainHbm ? LaunchClass{Family::GeneralPlainHbm, 0, false, 1024}
+                                   : LaunchClass{Family::GeneralHbm, 0, false, width > 1024 ? 1024 : 256};
       need = general_lds_bytes(p.qlen, p.tlen);
       lds = (size_t)1 << 40;
     } else {
-      if (p.pad_ == 3) bs += 2000;  // PLAIN flavour: 2256 / 3024
+      lc = {p.kind == kTaskPlain ? Family::GeneralPlain : Family::General, 0, false, block};
       need = general_lds_bytes(p.qlen, p.tlen);
       while (lds < need) lds *= 2;
     }
-    const bool hbm_cls = bs == 1000 || bs == 1001 || bs == 2001;
+    const bool hbm_cls = lc.hbm_state();
     if (!hbm_cls && need > (size_t)env.max_dyn_lds) {  // every kernel choice above checked its LDS need
       c.err = "internal: launch class needs more LDS than the device offers";
       return;
@@ -1293,19 +1336,15 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
     if (!hbm_cls && lds > (size_t)env.max_dyn_lds) lds = env.max_dyn_lds;
     Cls *cl = nullptr;
     for (auto &x : cls)
-      if (x.bs == bs && x.lds == lds) cl = &x;
+      if (x.lc == lc && x.lds == lds) cl = &x;
     if (!cl) {
-      cls.push_back({bs, lds, 0, {}});
+      cls.push_back({lc, lds, 0, {}});
       cl = &cls.back();
     }
     cl->need_max = std::max(cl->need_max, need);
-    {  // rough per-workgroup rates: general 64 / 256 / 1024 threads, HBM state, wave, pair
-      const double rate = bs == 64 ? 0.03 : bs == 256 ? 0.1 : bs == 1024 ? 0.6 : bs == 2256 ? 0.3 : bs == 3024 ? 0.85
-                          : bs == 2001 ? 0.3 : bs >= 1000 ? 0.08 : bs >= 600 ? 2.0 : bs >= 500 ? 0.5 : bs >= 400 ? 0.3 : bs >= 300 ? 1.0 : bs >= 200 ? 2.2 : bs >= 100 ? 0.25 : 0.13;  // (pair classes are 100..126)
-      cl->est = std::max(cl->est, (double)(p.qlen + p.tlen) * (double)p.ncol16 / rate);
-    }
+    cl->est = std::max(cl->est, (double)(p.qlen + p.tlen) * (double)p.ncol16 / lc.rate());
     cl->idx.push_back((int32_t)k);
-    if (p.pad_ == 2 || p.pad_ == 9) cl->idx.push_back(partner[k]);
+    if (p.kind == kTaskPair || p.kind == kTaskStrip) cl->idx.push_back(partner[k]);
   }
   c.dir_bytes = dir_acc;
   if (dir_acc > (c.heavy ? cut.heavy_need : cut.region_need)) {
@@ -1317,7 +1356,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
   for (size_t a = 0; a < cls.size(); ++a) {
     if (cls[a].idx.empty() || cls[a].idx.size() >= 2048) continue;
     for (size_t b = a + 1; b < cls.size(); ++b) {
-      if (cls[b].bs != cls[a].bs || cls[b].idx.empty() || cls[b].idx.size() >= 2048) continue;
+      if (cls[b].lc != cls[a].lc || cls[b].idx.empty() || cls[b].idx.size() >= 2048) continue;
       cls[a].lds = std::max(cls[a].lds, cls[b].lds);
       cls[a].need_max = std::max(cls[a].need_max, cls[b].need_max);
       cls[a].est = std::max(cls[a].est, cls[b].est);
@@ -1329,8 +1368,8 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
   // inside a launch of few tasks the longest go first too (workgroups are dispatched in order: a long task that
   // starts last is the tail of the launch); pair-kernel entries move as (task, partner) units
   for (auto &x : cls) {
-    const bool mixed_cls = x.bs >= 130 && x.bs < 140;  // (long and short tasks in one launch: the long chains start first)
-    if ((x.idx.size() >= 8192 && !mixed_cls) || x.idx.size() < 3) continue;
+    // (a mixed class -- long and short tasks in one launch -- however large: the long chains start first)
+    if ((x.idx.size() >= 8192 && !x.lc.mixed()) || x.idx.size() < 3) continue;
     auto work = [&](int32_t k) { return (int64_t)(cp[k].qlen + cp[k].tlen) * cp[k].ncol16; };
     int64_t wmin = work(x.idx[0]), wmax = wmin;
     for (int32_t k : x.idx) {
@@ -1339,7 +1378,7 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       wmax = std::max(wmax, wk);
     }
     if (wmax < 2 * wmin) continue;  // tasks of one size: the order does not matter
-    if ((x.bs >= 100 && x.bs < 200) || x.bs == 500) {
+    if (x.lc.two_per_entry()) {
       std::vector<std::pair<int32_t, int32_t>> pr(x.idx.size() / 2);
       for (size_t q = 0; q < pr.size(); ++q) pr[q] = {x.idx[2 * q], x.idx[2 * q + 1]};
       std::stable_sort(pr.begin(), pr.end(), [&](const std::pair<int32_t, int32_t> &a, const std::pair<int32_t, int32_t> &b) {
@@ -1358,9 +1397,8 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
   std::sort(cls.begin(), cls.end(), [](const Cls &a, const Cls &b) { return a.est > b.est; });
   size_t cursor = 0;
   for (auto &x : cls) {
-    const bool hbm_cls = x.bs == 1000 || x.bs == 1001 || x.bs == 2001;
-    const size_t lds_bytes = hbm_cls ? ((x.need_max + 255) & ~(size_t)255) : std::min(x.lds, (x.need_max + 511) & ~(size_t)511);
-    if ((x.bs >= 300 && x.bs < 500) || x.bs == 604 || x.bs == 608) {
+    const size_t lds_bytes = x.lc.hbm_state() ? ((x.need_max + 255) & ~(size_t)255) : std::min(x.lds, (x.need_max + 511) & ~(size_t)511);
+    if (x.lc.per_stripe()) {
       // Stripe kernel: one entry per stripe, (stripe << 24) | task.  Workgroup i runs on XCD i mod 8 and workgroups
       // are dispatched in index order.  The tasks are dealt to the eight residues (most stripes first, to the residue
       // with the fewest so far): a task's stripes share an XCD (its L2 carries their edge words).  A task is a chain:
@@ -1374,9 +1412,9 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
       // (chained strips, extz2_strip.hip: an entry stands for a PAIR of tasks -- the one listed and its partner --, a
       // "stripe" is a block of 512 columns of the wider of the two, 64 steps behind the block to its left, and the chain
       // is as long as the rows of the longer plus 64 per block)
-      const bool chained = x.bs >= 600;
-      const bool banded = !chained && x.bs >= 400;  // (banded stripe kernel: stripes over the padded target, 2 * 128 * nreg rows apart)
-      const int nreg = chained ? x.bs - 600 : x.bs - (banded ? 400 : 300);
+      const bool chained = x.lc.fam == Family::Chain;
+      const bool banded = x.lc.fam == Family::BStripe;  // (banded stripe kernel: stripes over the padded target, 2 * 128 * nreg rows apart)
+      const int nreg = x.lc.nreg;
       const size_t first = cursor;
       const int nslot = chained ? 64 : banded ? 256 * nreg : 128 * nreg;  // rows between the starts of consecutive stripes
       auto stripes_of = [&](int32_t rel) {
@@ -1430,11 +1468,11 @@ static void plan_chunk(const PlanEnv &env, const BatchCut &cut, ChunkPlan &c, Pl
         }
         cursor = first + (size_t)longest * 8;
       }
-      c.launches.push_back({x.bs, lds_bytes, first, cursor - first, x.est});
+      c.launches.push_back({x.lc, lds_bytes, first, cursor - first, x.est});
       for (int32_t rel : x.idx) c.launches.back().rmax = std::max(c.launches.back().rmax, cp[rel].qlen + cp[rel].tlen);
       continue;
     }
-    c.launches.push_back({x.bs, lds_bytes, cursor, x.idx.size(), x.est});
+    c.launches.push_back({x.lc, lds_bytes, cursor, x.idx.size(), x.est});
     std::copy(x.idx.begin(), x.idx.end(), order + c.ob + cursor);
     cursor += x.idx.size();
   }

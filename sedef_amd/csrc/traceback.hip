@@ -18,8 +18,8 @@ __device__ __forceinline__ uint32_t code_at(const uint32_t *codes, const uint32_
 }
 
 // ---- one cell of the direction matrix ----------------------------------------------------------------------
-// LAYOUT: 0 = byte rows (general kernel), 1 = wave-kernel bit blocks, 2 = pair-kernel bit blocks, 3 = wave-kernel
-// bit blocks per target stripe (extz2_stripe.hip).  A cell outside the block range the reference stored for its
+// LAYOUT: the task's dir_layout (sdf_internal.h) -- 0 = byte rows (general kernel), 1 = wave-kernel bit blocks, 2 =
+// pair-kernel bit blocks, 3 = bit blocks per target stripe (extz2_stripe.hip), ...  A cell outside the block range the reference stored for its
 // anti-diagonal has no flags: the walk is forced there (reference: extern/ksw2.h:128-130) -- state 2 below the
 // range, 1 above it.
 struct TbAddr {
@@ -147,8 +147,7 @@ __global__ __launch_bounds__(64) void traceback_kernel(const PlanTask *__restric
   const int k = (int)blockIdx.x * PER + lane / G;
   bool active = k < n;
   PlanTask tk = plan[active ? k : 0];
-  active = active && (tk.nreg == 0 ? 0 : tk.pad_ == 2 ? 2 : tk.pad_ == 5 ? 3 : tk.pad_ == 7 ? 4 : tk.pad_ == 8 ? 5 : (tk.pad_ == 9 || tk.pad_ == 10) ? 6 : 1) == LAYOUT &&
-           !(tk.flag & SDF_FLAG_SCORE_ONLY);
+  active = active && dir_layout(tk) == LAYOUT && !(tk.flag & SDF_FLAG_SCORE_ONLY);
   sdf_result rr = res[tk.out_idx];
   active = active && rr.n_cigar != -1;  // (-1: a stripe kernel gave the task up -- nothing to walk; it is run again)
   int i = -1, j = -1;  // (sequences are shorter than 2^31)

@@ -1,7 +1,7 @@
 """GPU fuzz against the oracle over SCORINGS (not collected by pytest: run by hand on a GPU box, e.g.
     SEED=1 ROUNDS=40 python tests/fuzz/fuzz_scorings.py
 Round 5: the register-resident kernels take three differences of the recurrence with 32-bit subtracts, which is exact when both
-fresh score bytes match + 2 (q + e) and mismatch + 2 (q + e) lie in q .. 127 (sedef_amd/csrc/sdf_api.hip: scoring_gates);
+fresh score bytes match + 2 (q + e) and mismatch + 2 (q + e) lie in q .. 127 (sedef_amd/csrc/sdf_api.hip: plan_env);
 every other scoring runs on the general kernel.  Each round draws ONE scoring -- a third of them on the edges of that
 condition (mismatch + q + 2 e = 0 / -1, match + 2 (q + e) = 127 / 128, q = 0, e = 0), the rest anywhere the reference accepts
 -- and a batch of banded and full-band tasks of all shapes; every task's score, mte, mte_q, zdropped and CIGAR (and the best

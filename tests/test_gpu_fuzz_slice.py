@@ -1,7 +1,7 @@
 """A slice of the hand-run fuzz campaigns (tests/fuzz/, profiles/r0N_fuzz.txt) inside `pytest -m gpu`: 500,000 random tasks,
 every kernel of the path forced in turn through the library's configuration struct, twenty scorings -- a third of them on the
 edges of the condition that decides between the register-resident kernels' 32-bit differences and the general kernel
-(sedef_amd/csrc/sdf_api.hip: scoring_gates) -- every task's score and every CIGAR word against the CPU checker: the
+(sedef_amd/csrc/sdf_api.hip: plan_env) -- every task's score and every CIGAR word against the CPU checker: the
 reference's own ksw_extz2_sse where oracle/_ref travels with the repository (extern/ksw2_extz2_sse.cc compiled unmodified),
 else the scalar oracle.  VERDICT r5: the campaigns were logs of scripts run by hand; this is the part of them the driver's own
 run carries (budget: about a minute)."""

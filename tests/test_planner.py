@@ -132,7 +132,7 @@ def test_kernel_choice_by_request():
     assert rc == -3  # SDF_ERR_UNSUPPORTED: not a flag of this kernel
     rc, pt, _ = _plan(_tasks([300, 0], [300, 5]), mat=np.array([1] + [-100] * 24, np.int8), gapo=1, gape=1)
     assert rc == 0 and (pt[:, 0] == -1).all()  # degenerate scoring: the reference returns before any work
-    # the window kernels' 32-bit differences want every fresh score byte in q .. 127 (sdf_api.hip: scoring_gates)
+    # the window kernels' 32-bit differences want every fresh score byte in q .. 127 (sdf_api.hip: plan_env)
     from sedef_amd import extz2
     t2 = _tasks([300, 300, 1000, 1000], [300, 300, 1000, 1000], w=[-1, -1, 128, 128])
     for (ma, mi, go, ge), fast in (((5, -10, 10, 0), True), ((5, -11, 10, 0), False), ((5, -4, 60, 1), True),
@@ -194,6 +194,30 @@ def test_two_pass_cut_with_early_heavy_chunks(monkeypatch):
     in_heavy, in_heavy0 = np.isin(pt[:, 0], heavy), np.isin(pt0[:, 0], np.flatnonzero(pc0[:, 0]))
     assert in_heavy.sum() >= 650 and (in_heavy == in_heavy0).all()
     assert ((pt[:, 0] >= 0) == (pt0[:, 0] >= 0)).all()  # the same tasks run
+
+
+_GENERAL_CLASSES = (64, 256, 1024, 2256, 3024, 1000, 1001, 2001)
+
+
+@pytest.mark.parametrize("var, turned_off", [
+    ("SDF_FORCE_GENERAL", lambda c: ~np.isin(c, _GENERAL_CLASSES)),  # every task on the general kernel
+    ("SDF_NO_PAIR", lambda c: (c >= 100) & (c < 200)),               # no pair kernel, of any flavour
+    ("SDF_NO_STRIPE", lambda c: (c >= 300) & (c < 400)),             # no stripe kernel
+], ids=["force_general", "no_pair", "no_stripe"])
+def test_debug_plan_follows_the_kernel_settings(monkeypatch, var, turned_off):
+    """sdf_debug_plan plans with every setting a context made now would get (sdf_api.hip: plan_env): a batch whose default
+    plan uses the kernels a setting turns off plans without them once the setting is in the environment."""
+    rng = np.random.default_rng(7)
+    q = np.r_[np.full(2000, 1000), np.full(20, 6000)]
+    tl = np.r_[1000 + rng.integers(-25, 25, 2000), np.full(20, 6000)]
+    t = _tasks(q, tl, w=np.r_[np.full(2000, 128), np.full(20, -1)])
+    rc, pt, _ = _plan(t)
+    assert rc == 0 and turned_off(pt[:, 1]).any()
+    monkeypatch.setenv(var, "1")
+    rc, pt, pc = _plan(t)
+    assert rc == 0 and (pt[:, 0] >= 0).all()
+    assert not turned_off(pt[:, 1]).any(), np.unique(pt[:, 1])
+    _check(t, pt, pc)
 
 
 def _mm8_like(rng, n):

@@ -32,10 +32,9 @@ static void fake_dp(int qlen, const uint8_t *, int tlen, const uint8_t *, int, c
 struct ProfProvider : sdfh::DpProvider {
   std::unique_ptr<sdfh::DpProvider> inner = sdfh::make_test_provider(fake_dp);
   std::vector<std::vector<sdfh::Anchor>> cache;
-  std::vector<sdfh::Cigar> run(const std::vector<sdfh::DpRequest> &reqs, const sdfh::Params &p) override {
-    auto r = inner->run(reqs, p);
+  void run(const std::vector<sdfh::DpRequest> &reqs, const sdfh::Params &p, Raw &raw) override {
+    inner->run(reqs, p, raw);
     tasks = inner->tasks, cells = inner->cells;
-    return r;
   }
   bool anchors(const std::vector<AnchorJob> &jobs, int kmer, AnchorBatch &out) override {
     if (cache.size() != jobs.size()) {

@@ -156,7 +156,7 @@ static int alignment_pair_impl(const Params &p, const char *fa, const char *fb, 
     DpSession rec;
     rec.requests = &reqs;
     { Alignment tmp(sa, sb, rec); }
-    std::vector<Cigar> res = dp->run(reqs, p);
+    std::vector<Cigar> res = dp->run_cigars(reqs, p);
     DpSession rep;
     rep.recording = false;
     rep.results = &res;
@@ -206,7 +206,7 @@ int sdfh_guide_alignment(const char *qstr_, const char *rstr_, int n, const int 
       DpSession rec;
       rec.requests = &reqs;
       body_rec(rec);
-      std::vector<Cigar> res = dp->run(reqs, p);
+      std::vector<Cigar> res = dp->run_cigars(reqs, p);
       DpSession rep;
       rep.recording = false;
       rep.results = &res;
@@ -269,7 +269,7 @@ int sdfh_guide_from_chains(const char *qstr_, const char *rstr_, const char *spe
       DpSession rec;
       rec.requests = &reqs;
       body(rec);  // recording pass (callers pass bodies that work on copies)
-      return dp->run(reqs, p);
+      return dp->run_cigars(reqs, p);
     };
     auto qs = std::make_shared<Sequence>("QRY", qstr);
     auto rs = std::make_shared<Sequence>("REF", rstr);
@@ -352,7 +352,7 @@ int sdfh_fast_align(const char *query_, const char *ref_, const char *qname, con
     for (;;) {
       std::vector<DpRequest> reqs = job.advance(results);
       if (reqs.empty()) break;
-      results = dp->run(reqs, p);
+      results = dp->run_cigars(reqs, p);
     }
     std::string out;
     char nums[160];

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <future>
 #include <mutex>
 #include <set>
 #include <thread>
@@ -56,9 +57,12 @@ struct AlignCodes {  // align_dna (src/common.h:60-70,91): ACGT of either case 0
   }
 };
 const AlignCodes kCodes;
-void expand(const std::vector<DpRequest> &reqs, const Params &p, std::vector<TaskRef> &tasks, TaskPool &pool) {
+// (`first`: per request (+1), its first task, as Raw::first_task)
+void expand(const std::vector<DpRequest> &reqs, const Params &p, std::vector<TaskRef> &tasks, TaskPool &pool,
+            std::vector<size_t> &first) {
   const size_t n = reqs.size(), step = (size_t)p.max_ksw_seq_len;
-  std::vector<size_t> off(n + 1, 0), first(n + 1, 0);
+  std::vector<size_t> off(n + 1, 0);
+  first.assign(n + 1, 0);
   for (size_t k = 0; k < n; k++) {
     const DpRequest &r = reqs[k];
     off[k + 1] = off[k] + (size_t)r.qlen + (size_t)r.tlen;
@@ -159,7 +163,7 @@ class GpuProvider : public DpProvider {
       spare_threads_.emplace_back([this, i, n, max_batch_bytes] {
         try {
           spares_[(size_t)i].reset(new GpuProvider(spare_dev_[(size_t)i], 0, std::vector<int>(), max_batch_bytes, n + 1));
-        } catch (std::string &) {  // (no room for another context: clone() will try again, the lane does without)
+        } catch (...) {  // (no room for another context: clone() will try again, the lane does without)
         }
       });
     }
@@ -219,28 +223,16 @@ class GpuProvider : public DpProvider {
   void ready() {
     if (reserve_thread_.joinable()) reserve_thread_.join();
   }
-  std::vector<Cigar> run(const std::vector<DpRequest> &reqs, const Params &p) override {
-    std::vector<Cigar> out(reqs.size());
-    Raw raw;
-    run_raw(reqs, p, raw);
-    const auto tp2 = std::chrono::steady_clock::now();
-    for (size_t r = 0; r < reqs.size(); r++) out[r] = raw.cigar(r);
-    t_unpack += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp2).count();
-    return out;
-  }
-
-  bool run_raw(const std::vector<DpRequest> &reqs, const Params &p, Raw &raw) override {
+  void run(const std::vector<DpRequest> &reqs, const Params &p, Raw &raw) override {
     raw.first_task.assign(reqs.size() + 1, 0);
     raw.recs = nullptr;
     raw.words = nullptr;
-    if (reqs.empty()) return true;
+    if (reqs.empty()) return;
     std::vector<TaskRef> tr;
     TaskPool pool;
     const auto tp0 = std::chrono::steady_clock::now();
-    expand(reqs, p, tr, pool);
-    for (auto &t : tr) raw.first_task[t.req + 1]++;  // tasks are in request order
-    for (size_t r = 0; r < reqs.size(); r++) raw.first_task[r + 1] += raw.first_task[r];
-    if (tr.empty()) return true;
+    expand(reqs, p, tr, pool, raw.first_task);
+    if (tr.empty()) return;
     const size_t nt = tr.size();
     std::unique_ptr<sdf_task[]> tasks(new sdf_task[nt]);
     const size_t tblock = 16384, ntb = (nt + tblock - 1) / tblock;
@@ -249,7 +241,6 @@ class GpuProvider : public DpProvider {
         tasks[k] = make_task((int64_t)tr[k].q_off, (int64_t)tr[k].t_off, tr[k].qlen, tr[k].tlen);
     });
     call_batch(tasks.get(), nt, &pool, p, raw, tp0);
-    return true;
   }
 
   // The same round on ranges of the character pool the last anchors() call left on the device: nothing is cut out, coded,
@@ -512,14 +503,13 @@ struct OracleResult {  // layout of sdfo_result (oracle/extz2_oracle.h)
 class TestProvider : public DpProvider {
  public:
   explicit TestProvider(test_dp_fn fn) : fn_(fn) {}
-  std::vector<Cigar> run(const std::vector<DpRequest> &reqs, const Params &p) override {
-    std::vector<Cigar> out(reqs.size());
+  void run(const std::vector<DpRequest> &reqs, const Params &p, Raw &raw) override {
     std::vector<TaskRef> tr;
     TaskPool pool;
-    expand(reqs, p, tr, pool);
+    expand(reqs, p, tr, pool, raw.first_task);
     int8_t mat[25];
     fill_mat(p, mat);
-    // the hook is re-entrant (like ksw_extz2_sse): tasks run on all host threads, CIGARs are appended in task order
+    // the hook is re-entrant (like ksw_extz2_sse): tasks run on all host threads, their CIGAR words land in task order
     std::vector<OracleResult> res(tr.size());
     parallel_for((int)tr.size(), [&](int k) {
       const TaskRef &t = tr[(size_t)k];
@@ -527,13 +517,21 @@ class TestProvider : public DpProvider {
       fn_(t.qlen, pool.data() + t.q_off, t.tlen, pool.data() + t.t_off, 5, mat, -p.gap_open, -p.gap_extend, -1, -1,
           0, &res[(size_t)k]);
     });
+    size_t words = 0;
+    for (auto &r : res) words += (size_t)r.n_cigar;
+    raw.own_recs.reset(new Raw::Rec[std::max<size_t>(tr.size(), 1)]);
+    raw.own_words.reset(new uint32_t[std::max<size_t>(words, 1)]);
+    words = 0;
     for (size_t k = 0; k < tr.size(); k++) {
-      append_ops(out[tr[k].req], res[k].cigar, res[k].n_cigar);
+      raw.own_recs[k] = {(int64_t)words, (int32_t)res[k].n_cigar, -1};  // (the oracle counts no matches)
+      std::copy(res[k].cigar, res[k].cigar + res[k].n_cigar, raw.own_words.get() + words);
+      words += (size_t)res[k].n_cigar;
       free(res[k].cigar);
       tasks++;
       cells += (int64_t)tr[k].qlen * tr[k].tlen;
     }
-    return out;
+    raw.recs = raw.own_recs.get();
+    raw.words = raw.own_words.get();
   }
   // (lanes of super-batches and of buckets work with the hook as with the device: the hook is re-entrant)
   std::unique_ptr<DpProvider> clone(int /*device*/ = -1) override { return std::unique_ptr<DpProvider>(new TestProvider(fn_)); }
@@ -549,9 +547,19 @@ Cigar DpProvider::Raw::cigar(size_t req) const {
   c.matches = 0;
   for (size_t k = first_task[req]; k < first_task[req + 1]; k++) {
     append_ops(c, words + recs[k].off, recs[k].cnt);
-    c.matches += recs[k].match;
+    c.matches = c.matches < 0 || recs[k].match < 0 ? -1 : c.matches + recs[k].match;
   }
   return c;
+}
+
+std::vector<Cigar> DpProvider::run_cigars(const std::vector<DpRequest> &reqs, const Params &p) {
+  Raw raw;
+  run(reqs, p, raw);
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<Cigar> out(reqs.size());
+  for (size_t r = 0; r < reqs.size(); r++) out[r] = raw.cigar(r);
+  t_unpack += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return out;
 }
 
 std::unique_ptr<DpProvider> make_gpu_provider(int device) { return std::unique_ptr<DpProvider>(new GpuProvider(device)); }
@@ -973,6 +981,38 @@ void set_stage_settings(const StageSettings &s) {
   g_stage_settings = s;
 }
 
+namespace {
+// The first failure of the threads that work for one caller: recorded in their catch blocks -- whatever was thrown --, rethrown
+// on the caller's thread, once they have all returned, as the std::string message the stage's callers handle.
+class FirstError {
+ public:
+  void set() {  // (inside a catch block)
+    std::string msg;
+    try {
+      throw;
+    } catch (std::string &s) {
+      msg = s.empty() ? std::string("error") : s;
+    } catch (std::exception &e) {
+      msg = e.what();
+    } catch (...) {
+      msg = "unknown error";
+    }
+    std::lock_guard<std::mutex> g(mu_);
+    if (!failed_) msg_ = msg;
+    failed_ = true;
+  }
+  bool failed() const { return failed_; }
+  void rethrow() const {
+    if (failed_) throw msg_;
+  }
+
+ private:
+  std::mutex mu_;
+  std::atomic<bool> failed_{false};
+  std::string msg_;
+};
+}  // namespace
+
 static void parallel_for(int n, const std::function<void(int)> &body) {
   const int nthreads = [] {
     const int asked = stage_settings().host_threads;
@@ -1001,15 +1041,13 @@ static void parallel_for(int n, const std::function<void(int)> &body) {
     const std::function<void(int)> *body;
     int n;
     std::atomic<int> next{0}, done{0};
-    std::mutex err_mu;
-    std::string error;
+    FirstError error;
     void run() {
       for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
         try {
           (*body)(i);
-        } catch (std::string &s) {
-          std::lock_guard<std::mutex> g(err_mu);
-          if (error.empty()) error = s.empty() ? std::string("error") : s;
+        } catch (...) {
+          error.set();
         }
         if (done.fetch_add(1) + 1 == n) {  // the last item: wake the caller if it is waiting
           std::lock_guard<std::mutex> g(fin_mu);
@@ -1069,7 +1107,7 @@ static void parallel_for(int n, const std::function<void(int)> &body) {
     std::unique_lock<std::mutex> g(region->fin_mu);
     region->fin_cv.wait(g, [&] { return region->done.load() >= n; });
   }
-  if (!region->error.empty()) throw region->error;
+  region->error.rethrow();
 }
 
 static std::vector<Hit> read_schedule(const std::string &bed_path, FILE *log) {  // src/align_main.cc:200-283, nbins=1
@@ -1101,105 +1139,101 @@ static std::vector<Hit> read_schedule(const std::string &bed_path, FILE *log) { 
   return order;
 }
 
-GenerateStats generate_alignments(const std::string &ref_path, const std::string &bed_path, int kmer_size,
-                                  const Params &p_in, DpProvider &dp0, FILE *out, FILE *log, int super_batch) {
-  const auto t0 = std::chrono::steady_clock::now();
-  Params p = p_in;
-  p.kmer = kmer_size;
-  set_alignment_scoring(p);
-  GenerateStats st;
-  struct Acc {  // wall seconds of the phases of one lane of the driver
-    double dp_secs = 0, anchor_secs = 0, t_fetch = 0, t_adv = 0, t_longest = 0, t_sum = 0, t_collect = 0, t_out = 0;
-    int rounds = 0;
-  };
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count();
-  };
-  g_us_chain = 0;
-  g_us_rest = 0;
-  // SDF_DEBUG_TIMING: one line per phase of every super-batch, milliseconds since the stage clock started
-  const bool dbg_tl = stage_settings().debug_timing;
-  auto mark = [&](int base, const char *what) {
-    if (dbg_tl) fprintf(stderr, "[stage %7.1f ms] batch@%d %s\n", since(t0) * 1e3, base, what);
-  };
-  std::vector<Hit> schedule = read_schedule(bed_path, log);
-  mark(-1, "schedule read");
-  FastaReference fr(ref_path);
-  mark(-1, "fasta index open");
-  fprintf(log, "Using k-mer size %d\n", kmer_size);
-  const int total = (int)schedule.size();
+namespace {
+using Clock = std::chrono::steady_clock;
+double since(Clock::time_point a) { return std::chrono::duration<double>(Clock::now() - a).count(); }
 
-  struct Item {
-    Hit h;
-    SeqView fa, fb;  // in the super-batch's pool (the provider's pinned staging, or the lane's own memory)
-    std::unique_ptr<PairJob> job;
-    std::vector<DpRequest> pending;
-  };
-  // Pairs per super-batch: every round of a super-batch is one device batch call (planning, launches, one
-  // synchronisation), so few large super-batches beat many small ones; bounded by the sequence bytes held at once.
-  // Lanes: super-batches are independent, so two or three of them are in flight, each on its own device context -- while
-  // one waits for the device, the host threads work on the other.  A second context costs ~0.1 s to set up, so
-  // small inputs stay on one lane; medium ones are cut into at least two super-batches per lane.
-  std::vector<int> devices;
-  int nlanes = stage_lane_count(total, &devices);
-  super_batch = stage_super_batch(total, nlanes, super_batch);
-  std::vector<std::pair<int, int>> batches;  // (first pair, pairs)
-  int64_t max_batch_bytes = 0;
-  for (int base = 0, n = 0; base < total; base += n) {
-    int64_t bytes = 0;
-    n = 0;
-    while (base + n < total && n < super_batch && bytes < ((int64_t)1 << 30)) {
-      const Hit &h = schedule[base + n];
-      bytes += (int64_t)(h.query_end - h.query_start) + (h.ref_end - h.ref_start);
-      ++n;
-    }
-    batches.push_back({base, n});
-    max_batch_bytes = std::max(max_batch_bytes, bytes);
+struct Acc {  // wall seconds of the phases of one lane of the driver
+  double dp_secs = 0, anchor_secs = 0, t_fetch = 0, t_adv = 0, t_longest = 0, t_sum = 0, t_collect = 0, t_out = 0;
+  int rounds = 0;
+  Acc &operator+=(const Acc &o) {
+    dp_secs += o.dp_secs, anchor_secs += o.anchor_secs, t_fetch += o.t_fetch, t_adv += o.t_adv;
+    t_longest += o.t_longest, t_sum += o.t_sum, t_collect += o.t_collect, t_out += o.t_out;
+    rounds += o.rounds;
+    return *this;
   }
-  dp0.prepare((size_t)max_batch_bytes);
-  auto zero_counters = [](DpProvider &d) {  // (a provider serves bucket after bucket of one process: the figures below are this run's)
-    d.tasks = d.cells = 0;
-    d.t_pack = d.t_call = d.t_unpack = 0;
-  };
-  zero_counters(dp0);
+};
 
+// What the super-batches of one run of the stage share.
+struct StageRun {
+  const Clock::time_point t0 = Clock::now();
+  const bool dbg = stage_settings().debug_timing;
+  Params p;
+  std::vector<Hit> schedule;
+  std::unique_ptr<FastaReference> fr;
   std::mutex cleanup_mu;
-  std::vector<std::thread> cleanup;
-  struct JoinAll {  // (also on the way out with an exception)
-    std::vector<std::thread> &v;
-    ~JoinAll() {
-      for (auto &t : v)
-        if (t.joinable()) t.join();
-    }
-  } join_cleanup{cleanup};
-  // One super-batch from the sequences to its formatted output lines (one string per pair, schedule order).
-  auto do_batch = [&](int base, int n, DpProvider &dp, Acc &a, std::vector<std::string> &lines, std::vector<int> &nhits,
-                      std::unique_ptr<char[]> &own_pool, size_t &own_pool_cap) {
-    std::vector<Item> items(n);
-    mark(base, "start");
-    const auto tf = now();
+  std::vector<std::thread> cleanup;  // (threads that free the items of finished super-batches)
+  // SDF_DEBUG_TIMING: one line per phase of every super-batch, milliseconds since the stage clock started
+  void mark(int base, const char *what) const {
+    if (dbg) fprintf(stderr, "[stage %7.1f ms] batch@%d %s\n", since(t0) * 1e3, base, what);
+  }
+  void join_cleanup() {
+    for (auto &t : cleanup)
+      if (t.joinable()) t.join();
+    cleanup.clear();
+  }
+  ~StageRun() { join_cleanup(); }  // (also on the way out with an exception)
+};
+
+// A lane of the driver: its provider, its clocks, and the sequence pool of its super-batches when the provider has none
+// (kept from super-batch to super-batch).
+struct Lane {
+  DpProvider *dp = nullptr;
+  std::unique_ptr<DpProvider> own;  // (a lane after the first: its clone of the first lane's provider)
+  Acc acc;
+  std::unique_ptr<char[]> own_pool;
+  size_t own_pool_cap = 0;
+};
+
+struct Item {
+  Hit h;
+  SeqView fa, fb;  // in the super-batch's pool (the provider's pinned staging, or the lane's own memory)
+  std::unique_ptr<PairJob> job;
+  std::vector<DpRequest> pending;
+};
+
+// One super-batch from the sequences to its formatted output lines (one string per pair, schedule order), phase by phase:
+// fetch(), seed_anchors(), dp_rounds(), format().
+struct SuperBatch {
+  StageRun &run;
+  Lane &lane;
+  const int base, n;
+  DpProvider &dp = *lane.dp;
+  Acc &a = lane.acc;
+  std::vector<Item> items = std::vector<Item>((size_t)n);
+  std::vector<size_t> slot;  // pair k's query at pool + slot[2k], its reference at pool + slot[2k + 1]
+  bool provider_pool = false;
+  std::vector<DpProvider::AnchorBatch> seeds;  // (live until the jobs have taken their copies: their first advance)
+  std::vector<int64_t> q_base = std::vector<int64_t>((size_t)n, 0), r_base = q_base;  // resident: the pairs in the device pool
+  bool resident = false;
+  std::vector<char> advanced = std::vector<char>((size_t)n, 0);  // pairs whose first advance() has run (requests in `pending`)
+  std::atomic<long long> pre_us{0};
+
+  void fetch() {
+    run.mark(base, "start");
+    const auto tf = Clock::now();
     // src/align_main.cc:299-306.  The bases of the whole super-batch go into ONE pool -- the provider's pinned staging when it
     // has one: the anchors call uploads from there without another copy, and the DP rounds name ranges of it -- a slot per
     // sequence as long as the bytes its range spans in the file (line ends included: the bound known before the copy).
     std::vector<FastaReference::Span> span(2 * (size_t)n);
-    std::vector<size_t> slot(2 * (size_t)n + 1, 0);
+    slot.assign(2 * (size_t)n + 1, 0);
     for (int k = 0; k < n; k++) {
       Item &it = items[k];
-      it.h = schedule[base + k];
-      span[2 * k] = fr.locate(it.h.query->name, it.h.query_start, &it.h.query_end);
-      span[2 * k + 1] = fr.locate(it.h.ref->name, it.h.ref_start, &it.h.ref_end);
+      it.h = run.schedule[base + k];
+      span[2 * k] = run.fr->locate(it.h.query->name, it.h.query_start, &it.h.query_end);
+      span[2 * k + 1] = run.fr->locate(it.h.ref->name, it.h.ref_start, &it.h.ref_end);
       slot[2 * k + 1] = slot[2 * k] + span[2 * k].bytes;
       slot[2 * k + 2] = slot[2 * k + 1] + span[2 * k + 1].bytes;
     }
-    char *pool = dp.pool_host(slot[2 * (size_t)n] + 1);
-    const bool provider_pool = pool != nullptr;
+    const size_t bytes = slot[2 * (size_t)n];
+    char *pool = dp.pool_host(bytes + 1);
+    provider_pool = pool != nullptr;
     if (!pool) {
-      if (own_pool_cap < slot[2 * (size_t)n] + 1) {
-        own_pool_cap = slot[2 * (size_t)n] + 1 + slot[2 * (size_t)n] / 8;
-        own_pool.reset(new char[own_pool_cap]);
+      if (lane.own_pool_cap < bytes + 1) {
+        lane.own_pool_cap = bytes + 1 + bytes / 8;
+        lane.own_pool.reset(new char[lane.own_pool_cap]);
       }
-      pool = own_pool.get();
+      pool = lane.own_pool.get();
     }
     parallel_for(n, [&](int k) {
       Item &it = items[k];
@@ -1207,177 +1241,149 @@ GenerateStats generate_alignments(const std::string &ref_path, const std::string
       it.fa = SeqView(qa, FastaReference::extract(span[2 * k], qa));
       it.fb = SeqView(ra, FastaReference::extract(span[2 * k + 1], ra));
       if (it.h.ref->is_rc) rc_inplace(ra, it.fb.size());
-      it.job.reset(new PairJob(it.fa, it.fb, it.h, p));
+      it.job.reset(new PairJob(it.fa, it.fb, it.h, run.p));
     });
     a.t_fetch += since(tf);
-    dp.pool_ready(slot[2 * (size_t)n]);  // (the whole pool to the device, asynchronously)
-    mark(base, "sequences fetched");
-    // Seed anchors on the device, when the provider offers it -- in PARTS of about equal bytes (two from 16 MB of sequences,
-    // four from 64 MB): while the device finds the anchors of part i + 1, the host threads chain part i (a pair's first
-    // advance(): src/chain.cc:203-258 up to the requests of its round-A stitch), which is the longest host phase of a
-    // super-batch (20 of 85 ms in the chr1-sized run).  Every part's anchors are appended behind those of the parts before
-    // it in the provider's staging (anchors_more), which stay valid until their jobs have taken their copies.
-    std::vector<DpProvider::AnchorBatch> seeds;  // (live until the jobs have taken their copies: their first advance)
-    std::vector<int64_t> q_base((size_t)n, 0), r_base((size_t)n, 0);
-    bool resident = false;
-    std::vector<char> advanced((size_t)n, 0);  // pairs whose first advance() has run (their requests wait in `pending`)
-    std::atomic<long long> pre_us(0);
-    {
-      std::vector<DpProvider::AnchorJob> aj(n);
-      for (int k = 0; k < n; k++) {
-        const Hit &h = items[k].h;
-        aj[k] = {items[k].fa, items[k].fb, h.query->name == h.ref->name && h.query->is_rc == h.ref->is_rc,
-                 h.ref_start - h.query_start};
-      }
-      // (only where the sequences lie in the PROVIDER's pool: a provider that copies them replaces its pool with every call)
-      const size_t total = slot[2 * (size_t)n];
-      int parts = 1;
-      if (provider_pool && n >= 64 && total >= ((size_t)16 << 20)) parts = 2;  // (small super-batches: one call)
-      if (provider_pool && n >= 256 && total >= ((size_t)64 << 20)) parts = 4;
-      if (stage_settings().anchor_parts > 0 && provider_pool) parts = std::min(stage_settings().anchor_parts, std::max(n / 16, 1));
-      std::vector<int> cut((size_t)parts + 1, n);  // part i: pairs [cut[i], cut[i + 1])
-      cut[0] = 0;
-      for (int i = 1, k = 0; i < parts; i++) {
-        while (k < n && slot[2 * (size_t)k] < total / (size_t)parts * (size_t)i) ++k;
-        cut[(size_t)i] = k;
-      }
-      for (int i = 0; i < parts; i++)
-        if (cut[(size_t)i + 1] - cut[(size_t)i] < 16) {  // (a part of a few pairs: one call for everything)
-          parts = 1;
-          cut.assign(2, n);
-          cut[0] = 0;
-          break;
-        }
-      seeds.resize((size_t)parts);
-      auto first_advance = [&](int lo, int hi, const DpProvider::AnchorBatch &sd) {
-        parallel_for(hi - lo, [&](int i) {
-          const int k = lo + i;
-          Item &it = items[k];
-          const auto tj = std::chrono::steady_clock::now();
-          it.job->set_anchors(sd.data() + sd.off[i], (size_t)(sd.off[i + 1] - sd.off[i]));
-          it.pending = it.job->advance(std::vector<Cigar>());
-          advanced[(size_t)k] = 1;
-          pre_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tj).count();
-        });
-      };
-      auto part_jobs = [&](int i) {
-        return std::vector<DpProvider::AnchorJob>(aj.begin() + cut[(size_t)i], aj.begin() + cut[(size_t)i + 1]);
-      };
-      const auto ta = now();
-      if (dp.anchors(part_jobs(0), p.kmer, seeds[0])) {
-        resident = seeds[0].resident;
-        auto take_bases = [&](int i) {
-          for (int k = cut[(size_t)i]; k < cut[(size_t)i + 1]; k++) {
-            q_base[k] = resident ? seeds[(size_t)i].q_base[k - cut[(size_t)i]] : 0;
-            r_base[k] = resident ? seeds[(size_t)i].r_base[k - cut[(size_t)i]] : 0;
-          }
-        };
-        take_bases(0);
-        if (parts == 1) {
-          for (int k = 0; k < n; k++)
-            items[k].job->set_anchors(seeds[0].data() + seeds[0].off[k], (size_t)(seeds[0].off[k + 1] - seeds[0].off[k]));
-        } else {
-          size_t keep = (size_t)seeds[0].off[cut[1]];  // anchors in the staging so far
-          bool have = true;                            // part i's anchors are there
-          for (int i = 0; i < parts; i++) {
-            const bool more = i + 1 < parts;
-            bool ok_next = false;
-            std::string err_next;
-            std::vector<DpProvider::AnchorJob> next_jobs;
-            std::thread next;
-            if (more) {
-              next_jobs = part_jobs(i + 1);
-              next = std::thread([&] {
-                try {
-                  ok_next = dp.anchors_more(next_jobs, p.kmer, keep, seeds[(size_t)i + 1]);
-                } catch (std::string &e) {
-                  err_next = e.empty() ? std::string("error") : e;
-                }
-              });
-            }
-            struct Join {
-              std::thread &t;
-              ~Join() {
-                if (t.joinable()) t.join();
-              }
-            } join_next{next};
-            if (i == 0) mark(base, "anchors of the first part done");
-            // (a part without anchors from the device: its jobs find theirs on the host, in their first advance below)
-            if (have) first_advance(cut[(size_t)i], cut[(size_t)i + 1], seeds[(size_t)i]);
-            if (!more) break;
-            next.join();
-            if (!err_next.empty()) throw err_next;
-            // (no room behind the anchors of the parts before, or a part the device does not cover: the ordinary call, now
-            // that the earlier parts' jobs have taken their copies -- it starts the staging over)
-            bool fresh = false;
-            if (!ok_next) ok_next = fresh = dp.anchors(next_jobs, p.kmer, seeds[(size_t)i + 1]);
-            have = ok_next;
-            if (!ok_next) resident = false;  // (its pairs have no place in the resident pool the requests could name)
-            if (ok_next && seeds[(size_t)i + 1].resident != resident) resident = false;  // (the parts disagree about where the
-                                                                                        // sequences are: the pointer form for everybody)
-            if (ok_next && resident) take_bases(i + 1);
-            if (ok_next) keep = (fresh ? 0 : keep) + (size_t)seeds[(size_t)i + 1].off[cut[(size_t)i + 2] - cut[(size_t)i + 1]];
-          }
-          mark(base, "anchors done");
-        }
-        a.anchor_secs += since(ta);
-      }
+    dp.pool_ready(bytes);  // (the whole pool to the device, asynchronously)
+    run.mark(base, "sequences fetched");
+  }
+
+  // The parts the seed anchors are found in: part i holds pairs [cut[i], cut[i + 1]) -- parts of about equal bytes, two from
+  // 16 MB of sequences, four from 64 MB (SDF_ANCHOR_PARTS), only where the sequences lie in the PROVIDER's pool (a provider
+  // that copies them replaces its pool with every call).
+  std::vector<int> part_cuts() const {
+    const size_t total = slot[2 * (size_t)n];
+    int parts = 1;
+    if (provider_pool && n >= 64 && total >= ((size_t)16 << 20)) parts = 2;  // (small super-batches: one call)
+    if (provider_pool && n >= 256 && total >= ((size_t)64 << 20)) parts = 4;
+    if (stage_settings().anchor_parts > 0 && provider_pool) parts = std::min(stage_settings().anchor_parts, std::max(n / 16, 1));
+    std::vector<int> cut((size_t)parts + 1, n);
+    cut[0] = 0;
+    for (int i = 1, k = 0; i < parts; i++) {
+      while (k < n && slot[2 * (size_t)k] < total / (size_t)parts * (size_t)i) ++k;
+      cut[i] = k;
     }
-    mark(base, "anchors done, parts chained");
-    // rounds: every unfinished job advances; all their DP requests go to the GPU as one batch.
-    // Results of the previous round: Cigars per pair (provider without a raw form), or the raw device words
-    // and each pair's first request in them -- then the pair's own thread builds (and later frees) its Cigars
-    std::vector<std::vector<Cigar>> results(n);
-    DpProvider::Raw raw;
-    bool have_raw = false;
-    std::vector<size_t> first_req(n, 0), n_req(n, 0);
-    for (;;) {
-      std::vector<DpRequest> batch;
-      std::vector<DpProvider::ResidentReq> rbatch;
-      std::vector<std::pair<int, size_t>> owners;
-      bool any = false;
-      const auto tadv = now();
-      std::atomic<long long> longest_us(0), sum_us(0);
-      parallel_for(n, [&](int k) {
-        Item &it = items[k];
-        if (advanced[(size_t)k]) {  // (its first advance ran next to the second half's anchors: the requests are waiting)
-          advanced[(size_t)k] = 0;
-          return;
-        }
-        it.pending.clear();
-        if (it.job->done()) return;
-        const auto tj = std::chrono::steady_clock::now();
-        if (have_raw) {
-          std::vector<Cigar> mine(n_req[k]);
-          for (size_t r = 0; r < n_req[k]; r++) mine[r] = raw.cigar(first_req[k] + r);
-          it.pending = it.job->advance(mine);
-        } else {
-          it.pending = it.job->advance(results[k]);
-          results[k].clear();
-        }
-        const long long us =
-            std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tj).count();
-        sum_us += us;
-        long long cur = longest_us.load();
-        while (us > cur && !longest_us.compare_exchange_weak(cur, us)) {
-        }
-      });
-      a.t_adv += since(tadv);
-      a.t_longest += longest_us.load() / 1e6;
-      a.t_sum += (sum_us.load() + pre_us.exchange(0)) / 1e6;
-      const auto tc = now();
-      std::vector<size_t> first(n + 1, 0);
-      for (int k = 0; k < n; k++) {
-        first[k + 1] = first[k] + items[k].pending.size();
-        if (!items[k].pending.empty()) {
-          owners.push_back({k, items[k].pending.size()});
-          any = true;
-        }
+    for (int i = 0; i < parts; i++)
+      if (cut[i + 1] - cut[i] < 16) return {0, n};  // (a part of a few pairs: one call for everything)
+    return cut;
+  }
+
+  // The first advance() of pairs [lo, hi) -- chaining up to the requests of their round-A stitch (src/chain.cc:203-258) --
+  // on the anchors `sd` holds for them.
+  void first_advance(int lo, int hi, const DpProvider::AnchorBatch &sd) {
+    parallel_for(hi - lo, [&](int i) {
+      const int k = lo + i;
+      const auto tj = Clock::now();
+      items[k].job->set_anchors(sd.data() + sd.off[i], (size_t)(sd.off[i + 1] - sd.off[i]));
+      items[k].pending = items[k].job->advance(std::vector<Cigar>());
+      advanced[k] = 1;
+      pre_us += std::chrono::duration_cast<std::chrono::microseconds>(Clock::now() - tj).count();
+    });
+  }
+
+  // Seed anchors on the device, when the provider offers it -- in parts (part_cuts): while the device finds the anchors of
+  // part i + 1, the host threads chain part i, which is the longest host phase of a super-batch (20 of 85 ms in the
+  // chr1-sized run).  Every part's anchors are appended behind those of the parts before it in the provider's staging
+  // (anchors_more), which stay valid until their jobs have taken their copies.  Without anchors from the device the jobs
+  // find theirs on the host, in their first advance.
+  void seed_anchors() {
+    std::vector<DpProvider::AnchorJob> aj(n);
+    for (int k = 0; k < n; k++) {
+      const Hit &h = items[k].h;
+      aj[k] = {items[k].fa, items[k].fb, h.query->name == h.ref->name && h.query->is_rc == h.ref->is_rc,
+               h.ref_start - h.query_start};
+    }
+    const std::vector<int> cut = part_cuts();
+    const int parts = (int)cut.size() - 1;
+    seeds.resize(parts);
+    auto part_jobs = [&](int i) { return std::vector<DpProvider::AnchorJob>(aj.begin() + cut[i], aj.begin() + cut[i + 1]); };
+    auto take_bases = [&](int i) {
+      for (int k = cut[i]; k < cut[i + 1]; k++) {
+        q_base[k] = resident ? seeds[i].q_base[k - cut[i]] : 0;
+        r_base[k] = resident ? seeds[i].r_base[k - cut[i]] : 0;
       }
+    };
+    const auto ta = Clock::now();
+    if (dp.anchors(part_jobs(0), run.p.kmer, seeds[0])) {
+      resident = seeds[0].resident;
+      take_bases(0);
+      if (parts == 1) {
+        for (int k = 0; k < n; k++)
+          items[k].job->set_anchors(seeds[0].data() + seeds[0].off[k], (size_t)(seeds[0].off[k + 1] - seeds[0].off[k]));
+      } else {
+        size_t keep = (size_t)seeds[0].off[cut[1]];  // anchors in the staging so far
+        bool have = true;                            // part i's anchors are there
+        for (int i = 0; i < parts; i++) {
+          const bool more = i + 1 < parts;
+          const std::vector<DpProvider::AnchorJob> next_jobs = more ? part_jobs(i + 1) : std::vector<DpProvider::AnchorJob>();
+          // (the next part's anchors on a thread of its own: whatever it throws arrives with get(), and the future waits for
+          // the thread also on the way out with an exception)
+          std::future<bool> next;
+          if (more)
+            next = std::async(std::launch::async, [&] { return dp.anchors_more(next_jobs, run.p.kmer, keep, seeds[i + 1]); });
+          if (i == 0) run.mark(base, "anchors of the first part done");
+          // (a part without anchors from the device: its jobs find theirs on the host, in their first advance)
+          if (have) first_advance(cut[i], cut[i + 1], seeds[i]);
+          if (!more) break;
+          bool ok_next = next.get();
+          // (no room behind the anchors of the parts before, or a part the device does not cover: the ordinary call, now
+          // that the earlier parts' jobs have taken their copies -- it starts the staging over)
+          bool fresh = false;
+          if (!ok_next) ok_next = fresh = dp.anchors(next_jobs, run.p.kmer, seeds[i + 1]);
+          have = ok_next;
+          if (!ok_next) resident = false;  // (its pairs have no place in the resident pool the requests could name)
+          if (ok_next && seeds[i + 1].resident != resident) resident = false;  // (the parts disagree about where the
+                                                                              // sequences are: the pointer form for everybody)
+          if (ok_next && resident) take_bases(i + 1);
+          if (ok_next) keep = (fresh ? 0 : keep) + (size_t)seeds[i + 1].off[cut[i + 2] - cut[i + 1]];
+        }
+        run.mark(base, "anchors done");
+      }
+      a.anchor_secs += since(ta);
+    }
+    run.mark(base, "anchors done, parts chained");
+  }
+
+  // Every unfinished job advances on the results of the previous round: pair k's are requests [first[k], first[k + 1]) of
+  // `raw`, turned into Cigars on the pair's own thread (which later frees them).
+  void advance_jobs(const DpProvider::Raw &raw, const std::vector<size_t> &first) {
+    const auto tadv = Clock::now();
+    std::atomic<long long> longest_us(0), sum_us(0);
+    parallel_for(n, [&](int k) {
+      Item &it = items[k];
+      if (advanced[k]) {  // (its first advance ran next to a later part's anchors: the requests are waiting)
+        advanced[k] = 0;
+        return;
+      }
+      it.pending.clear();
+      if (it.job->done()) return;
+      const auto tj = Clock::now();
+      std::vector<Cigar> mine(first[k + 1] - first[k]);
+      for (size_t r = 0; r < mine.size(); r++) mine[r] = raw.cigar(first[k] + r);
+      it.pending = it.job->advance(mine);
+      const long long us = std::chrono::duration_cast<std::chrono::microseconds>(Clock::now() - tj).count();
+      sum_us += us;
+      long long cur = longest_us.load();
+      while (us > cur && !longest_us.compare_exchange_weak(cur, us)) {
+      }
+    });
+    a.t_adv += since(tadv);
+    a.t_longest += longest_us.load() / 1e6;
+    a.t_sum += (sum_us.load() + pre_us.exchange(0)) / 1e6;
+  }
+
+  // Rounds: every unfinished job advances; all their DP requests go to the provider as one batch.
+  void dp_rounds() {
+    DpProvider::Raw raw;
+    std::vector<size_t> first((size_t)n + 1, 0);  // pair k's requests of the round: [first[k], first[k + 1])
+    for (;;) {
+      advance_jobs(raw, first);
+      const auto tc = Clock::now();
+      for (int k = 0; k < n; k++) first[k + 1] = first[k] + items[k].pending.size();
       // (requests are four words each; with the pairs' characters on the device they become offsets of that pool, on the
       // host threads: 708,600 of them in the first round of the chr1-sized run)
-      if (resident) rbatch.resize(first[n]);
-      else batch.resize(first[n]);
+      std::vector<DpRequest> batch(resident ? 0 : first[n]);
+      std::vector<DpProvider::ResidentReq> rbatch(resident ? first[n] : 0);
       std::atomic<bool> outside(false);
       parallel_for(n, [&](int k) {
         Item &it = items[k];
@@ -1395,35 +1401,24 @@ GenerateStats generate_alignments(const std::string &ref_path, const std::string
       });
       if (outside.load()) throw std::string("internal: a DP request outside its pair's sequences");
       a.t_collect += since(tc);
-      if (!any) break;
+      if (first[n] == 0) break;
       a.rounds++;
-      mark(base, "jobs advanced, requests collected");
-      const auto td = now();
-      std::vector<Cigar> got;
-      have_raw = resident ? dp.run_resident(rbatch, p, raw) : dp.run_raw(batch, p, raw);
-      if (resident && !have_raw) throw std::string("internal: the provider lost its resident sequences");
-      if (!have_raw) got = dp.run(batch, p);
+      run.mark(base, "jobs advanced, requests collected");
+      const auto td = Clock::now();
+      if (!resident) dp.run(batch, run.p, raw);
+      else if (!dp.run_resident(rbatch, run.p, raw)) throw std::string("internal: the provider lost its resident sequences");
       a.dp_secs += since(td);
-      mark(base, "DP round done");
-      const auto tc2 = now();
-      size_t cur = 0;
-      std::fill(n_req.begin(), n_req.end(), 0);
-      for (auto &o : owners) {
-        if (have_raw) {
-          first_req[o.first] = cur;
-          n_req[o.first] = o.second;
-        } else {
-          results[o.first].assign(std::make_move_iterator(got.begin() + cur),
-                                  std::make_move_iterator(got.begin() + cur + o.second));
-        }
-        cur += o.second;
-      }
-      a.t_collect += since(tc2);
+      run.mark(base, "DP round done");
     }
-    const auto tout = now();
-    lines.assign(n, std::string());  // formatted on the host threads, written in schedule order
-    nhits.assign(n, 0);
-    parallel_for(n, [&](int k) {  // src/align_main.cc:314-331
+  }
+
+  // The output lines (src/align_main.cc:314-331), formatted on the host threads; returns the hits.  The items go to the
+  // cleanup thread.
+  int format(std::vector<std::string> &lines) {
+    const auto tout = Clock::now();
+    lines.assign(n, std::string());
+    std::atomic<int> hits(0);
+    parallel_for(n, [&](int k) {
       Item &it = items[k];
       const std::string tail = "\t" + it.h.to_bed(false) + "\n";
       for (auto &hh : it.job->hits()) {
@@ -1440,138 +1435,167 @@ GenerateStats generate_alignments(const std::string &ref_path, const std::string
         }
         hh.query->name = it.h.query->name;
         hh.ref->name = it.h.ref->name;
-        nhits[k]++;
+        hits++;
         lines[k] += hh.to_bed(false);
         lines[k] += tail;
       }
     });
     a.t_out += since(tout);
-    mark(base, "output formatted");
+    run.mark(base, "output formatted");
     // (the pairs' jobs hold hundreds of megabytes in small pieces: freeing them took a lane 15-50 ms between two
     // super-batches -- a thread of its own does it while the lane fetches the next one's sequences)
     auto *gone = new std::vector<Item>(std::move(items));
-    std::lock_guard<std::mutex> g(cleanup_mu);
-    cleanup.emplace_back([gone] { delete gone; });
-  };
-  auto write_batch = [&](int base, int n, const std::vector<std::string> &lines, const std::vector<int> &nhits) {
-    for (int k = 0; k < n; k++) {
-      st.lines++;
-      st.total_written += nhits[k];
-      if (!lines[k].empty()) fwrite(lines[k].data(), 1, lines[k].size(), out);
-    }
-    fprintf(log, "\r Processing %d out of %d (%.1f%%)", std::min(base + n, total), total,
-            100.0 * std::min(base + n, total) / std::max(total, 1));
-  };
+    std::lock_guard<std::mutex> g(run.cleanup_mu);
+    run.cleanup.emplace_back([gone] { delete gone; });
+    return hits;
+  }
+};
 
-  // Output is written in schedule order whatever lane produced it.  Every lane but the first creates its own device
-  // context (~0.1 s) on its own thread while the first one is already working; the super-batches are handed out as the
-  // lanes ask for them, so a lane that starts late, or cannot get a context at all, just takes fewer.
+// Pairs per super-batch: every round of a super-batch is one device batch call (planning, launches, one synchronisation), so
+// few large super-batches beat many small ones; bounded by the sequence bytes held at once.
+struct Batch {
+  int first, n;   // pairs [first, first + n) of the schedule
+  int64_t bytes;  // their sequence
+};
+std::vector<Batch> cut_super_batches(const std::vector<Hit> &schedule, int super_batch) {
+  std::vector<Batch> batches;
+  const int total = (int)schedule.size();
+  for (int base = 0, n = 0; base < total; base += n) {
+    int64_t bytes = 0;
+    n = 0;
+    while (base + n < total && n < super_batch && bytes < ((int64_t)1 << 30)) {
+      const Hit &h = schedule[(size_t)(base + n)];
+      bytes += (int64_t)(h.query_end - h.query_start) + (h.ref_end - h.ref_start);
+      ++n;
+    }
+    batches.push_back({base, n, bytes});
+  }
+  return batches;
+}
+
+// body(0) on the calling thread, body(1 .. n - 1) on threads of their own, until all have returned; the first failure of any
+// of them is left in `failure` (which tells the others that one has failed) for the caller to rethrow.
+void run_lanes(int n, FirstError &failure, const std::function<void(int)> &body) {
+  auto one = [&](int l) {
+    try {
+      body(l);
+    } catch (...) {
+      failure.set();
+    }
+  };
+  std::vector<std::thread> threads;
+  for (int l = 1; l < n; l++) threads.emplace_back(one, l);
+  one(0);
+  for (auto &t : threads) t.join();
+}
+
+void zero_counters(DpProvider &d) {  // (a provider serves bucket after bucket of one process: the figures are this run's)
+  d.tasks = d.cells = 0;
+  d.t_pack = d.t_call = d.t_unpack = 0;
+}
+}  // namespace
+
+GenerateStats generate_alignments(const std::string &ref_path, const std::string &bed_path, int kmer_size,
+                                  const Params &p_in, DpProvider &dp0, FILE *out, FILE *log, int super_batch) {
+  StageRun run;
+  run.p = p_in;
+  run.p.kmer = kmer_size;
+  set_alignment_scoring(run.p);
+  GenerateStats st;
+  g_us_chain = 0;
+  g_us_rest = 0;
+  run.schedule = read_schedule(bed_path, log);
+  run.mark(-1, "schedule read");
+  run.fr.reset(new FastaReference(ref_path));
+  run.mark(-1, "fasta index open");
+  fprintf(log, "Using k-mer size %d\n", kmer_size);
+  const int total = (int)run.schedule.size();
+
+  // Lanes: super-batches are independent, so two or three of them are in flight, each on its own device context -- while
+  // one waits for the device, the host threads work on the other.  A second context costs ~0.1 s to set up, so
+  // small inputs stay on one lane; medium ones are cut into at least two super-batches per lane.
+  std::vector<int> devices;
+  int nlanes = stage_lane_count(total, &devices);
+  super_batch = stage_super_batch(total, nlanes, super_batch);
+  const std::vector<Batch> batches = cut_super_batches(run.schedule, super_batch);
+  int64_t max_batch_bytes = 0;
+  for (const Batch &b : batches) max_batch_bytes = std::max(max_batch_bytes, b.bytes);
+  dp0.prepare((size_t)max_batch_bytes);
+  zero_counters(dp0);
+
+  // Output is written in schedule order whatever lane produced it: a finished super-batch keeps its lines until every earlier
+  // one of the schedule has been written.  The first lane runs on the calling thread; every other one creates its own device
+  // context (~0.1 s) on its own thread while the first one is already working; the super-batches are handed out as the lanes
+  // ask for them, so a lane that starts late, or cannot get a context at all, just takes fewer.
   nlanes = std::min<int>(nlanes, (int)batches.size());
-  std::vector<std::unique_ptr<DpProvider>> extra((size_t)std::max(nlanes, 1));
-  std::vector<DpProvider *> prov((size_t)std::max(nlanes, 1), nullptr);
-  prov[0] = &dp0;
-  std::vector<Acc> acc((size_t)std::max(nlanes, 1));
-  if (nlanes <= 1) {
+  std::vector<Lane> lanes((size_t)std::max(nlanes, 1));
+  lanes[0].dp = &dp0;
+  // (several lanes take the super-batches with the most sequence first: the schedule is sorted by size, its last super-batch
+  // is the heaviest, and taken last it ran on alone while the other lanes had nothing left; one lane keeps schedule order)
+  std::vector<size_t> turn(batches.size());
+  for (size_t b = 0; b < turn.size(); b++) turn[b] = b;
+  if (nlanes > 1)
+    std::stable_sort(turn.begin(), turn.end(), [&](size_t a, size_t b) { return batches[a].bytes > batches[b].bytes; });
+  struct Done {  // a finished super-batch's output, until every earlier one has been written
     std::vector<std::string> lines;
-    std::vector<int> nhits;
-    std::unique_ptr<char[]> own_pool;  // (the lane's sequence pool when its provider has none: kept from batch to batch)
-    size_t own_pool_cap = 0;
-    for (auto &b : batches) {
-      do_batch(b.first, b.second, dp0, acc[0], lines, nhits, own_pool, own_pool_cap);
-      write_batch(b.first, b.second, lines, nhits);
+    int hits = 0;
+    bool ready = false;
+  };
+  std::vector<Done> done(batches.size());
+  std::mutex mu;
+  size_t next_write = 0;
+  std::atomic<size_t> next_batch(0);
+  FirstError failure;
+  run_lanes((int)lanes.size(), failure, [&](int l) {
+    Lane &lane = lanes[(size_t)l];
+    if (l > 0) {
+      try {
+        lane.own = dp0.clone(devices.empty() ? -1 : devices[(size_t)l % devices.size()]);
+      } catch (...) {  // no room for another device context: one lane fewer
+      }
+      lane.dp = lane.own.get();
+      run.mark(-2 - l, "lane's device context ready");
+      if (!lane.dp) return;
+      zero_counters(*lane.dp);
+      lane.dp->prepare((size_t)max_batch_bytes);
     }
-  } else {
-    // The super-batches with the most sequence first (the schedule is sorted by size: its last super-batch is the
-    // heaviest, and taken last it ran on alone while the other lanes had nothing left); a finished super-batch keeps its
-    // lines until every earlier one of the schedule has been written.
-    std::vector<size_t> turn(batches.size());
-    {
-      std::vector<int64_t> weight(batches.size(), 0);
-      for (size_t b = 0; b < batches.size(); b++)
-        for (int k = 0; k < batches[b].second; k++) {
-          const Hit &h = schedule[(size_t)(batches[b].first + k)];
-          weight[b] += (int64_t)(h.query_end - h.query_start) + (h.ref_end - h.ref_start);
-        }
-      for (size_t b = 0; b < turn.size(); b++) turn[b] = b;
-      std::stable_sort(turn.begin(), turn.end(), [&](size_t a, size_t b) { return weight[a] > weight[b]; });
+    for (size_t ti = next_batch++; ti < batches.size() && !failure.failed(); ti = next_batch++) {
+      const size_t bi = turn[ti];
+      SuperBatch sb{run, lane, batches[bi].first, batches[bi].n};
+      sb.fetch();
+      sb.seed_anchors();
+      sb.dp_rounds();
+      const int hits = sb.format(done[bi].lines);
+      std::lock_guard<std::mutex> g(mu);
+      if (failure.failed()) return;
+      done[bi].hits = hits;
+      done[bi].ready = true;
+      // (whoever completes the next one in line writes)
+      for (; next_write < batches.size() && done[next_write].ready; ++next_write) {
+        const int end = batches[next_write].first + batches[next_write].n;
+        st.lines += batches[next_write].n;
+        st.total_written += done[next_write].hits;
+        for (const std::string &line : done[next_write].lines)
+          if (!line.empty()) fwrite(line.data(), 1, line.size(), out);
+        std::vector<std::string>().swap(done[next_write].lines);
+        fprintf(log, "\r Processing %d out of %d (%.1f%%)", end, total, 100.0 * end / std::max(total, 1));
+      }
     }
-    std::vector<std::vector<std::string>> done_lines(batches.size());
-    std::vector<std::vector<int>> done_nhits(batches.size());
-    std::vector<char> is_done(batches.size(), 0);
-    std::mutex mu;
-    size_t next_write = 0;
-    std::atomic<size_t> next_batch(0);
-    std::string failure;
-    bool failed = false;
-    std::vector<std::thread> lanes;
-    for (int l = 0; l < nlanes; l++)
-      lanes.emplace_back([&, l] {
-        if (l > 0) {
-          try {
-            extra[(size_t)l] = dp0.clone(devices.empty() ? -1 : devices[(size_t)l % devices.size()]);
-          } catch (std::string &) {  // no room for another device context: one lane fewer
-          }
-          prov[(size_t)l] = extra[(size_t)l].get();
-          mark(-2 - l, "lane's device context ready");
-          if (!prov[(size_t)l]) return;
-          zero_counters(*prov[(size_t)l]);
-          prov[(size_t)l]->prepare((size_t)max_batch_bytes);
-        }
-        std::vector<std::string> lines;
-        std::vector<int> nhits;
-        std::unique_ptr<char[]> own_pool;
-        size_t own_pool_cap = 0;
-        for (;;) {
-          const size_t ti = next_batch.fetch_add(1);
-          if (ti >= batches.size()) return;
-          const size_t bi = turn[ti];
-          try {
-            do_batch(batches[bi].first, batches[bi].second, *prov[(size_t)l], acc[(size_t)l], lines, nhits, own_pool, own_pool_cap);
-          } catch (std::string &e) {
-            std::lock_guard<std::mutex> g(mu);
-            if (!failed) failure = e.empty() ? std::string("error") : e;
-            failed = true;
-            return;
-          }
-          std::lock_guard<std::mutex> g(mu);
-          if (failed) return;
-          done_lines[bi].swap(lines);
-          done_nhits[bi].swap(nhits);
-          is_done[bi] = 1;
-          while (next_write < batches.size() && is_done[next_write]) {  // (whoever completes the next one in line writes)
-            write_batch(batches[next_write].first, batches[next_write].second, done_lines[next_write], done_nhits[next_write]);
-            std::vector<std::string>().swap(done_lines[next_write]);
-            ++next_write;
-          }
-        }
-      });
-    for (auto &t : lanes) t.join();
-    if (failed) throw failure;
-  }
-  const double secs = since(t0);  // (the output is complete; what is left is giving memory back)
-  for (auto &t : cleanup) t.join();
-  cleanup.clear();
+  });
+  failure.rethrow();
+  const double secs = since(run.t0);  // (the output is complete; what is left is giving memory back)
+  run.join_cleanup();
   Acc a;
-  for (int l = 0; l < nlanes; l++) {
-    a.dp_secs += acc[l].dp_secs;
-    a.anchor_secs += acc[l].anchor_secs;
-    a.t_fetch += acc[l].t_fetch;
-    a.t_adv += acc[l].t_adv;
-    a.t_longest += acc[l].t_longest;
-    a.t_sum += acc[l].t_sum;
-    a.t_collect += acc[l].t_collect;
-    a.t_out += acc[l].t_out;
-    a.rounds += acc[l].rounds;
-  }
+  for (const Lane &l : lanes) a += l.acc;
   st.rounds = a.rounds;
   double t_pack = 0, t_call = 0, t_unpack = 0;
-  for (DpProvider *d : prov) {
-    if (!d) continue;
-    st.dp_tasks += d->tasks;
-    st.dp_cells += d->cells;
-    t_pack += d->t_pack;
-    t_call += d->t_call;
-    t_unpack += d->t_unpack;
+  for (const Lane &l : lanes) {
+    if (!l.dp) continue;
+    st.dp_tasks += l.dp->tasks;
+    st.dp_cells += l.dp->cells;
+    t_pack += l.dp->t_pack;
+    t_call += l.dp->t_call;
+    t_unpack += l.dp->t_unpack;
   }
   fprintf(log, "\nFinished BED %s in %.2fs (%d lines, generated %d hits)\n", bed_path.c_str(), secs, st.lines,
           st.total_written);
@@ -1585,8 +1609,8 @@ GenerateStats generate_alignments(const std::string &ref_path, const std::string
           a.t_fetch, a.t_adv, a.t_longest, a.t_sum, a.t_collect, a.t_out, t_pack, t_call, t_unpack);
   // (the extra lanes' providers go back to the one they came from: the next bucket of this process takes them again, and the
   // first provider gives all their device contexts back side by side when it goes)
-  for (auto &e : extra)
-    if (e) dp0.give_back(std::move(e));
+  for (Lane &l : lanes)
+    if (l.own) dp0.give_back(std::move(l.own));
   return st;
 }
 
@@ -1634,6 +1658,48 @@ StageHint stage_hint_many(const std::vector<std::string> &beds, int super_batch)
   return all;
 }
 
+// One bucket of generate_many: its lines to `<bed><out_suffix>`, its log to `<log_dir>/<basename>.log` with a log directory,
+// else to `log` -- with `buffer_log` (buckets in flight at once, whose progress lines would interleave on the shared log)
+// through a buffer that reaches `log` in one piece when the bucket is over, also when it failed.  A file that cannot be
+// opened throws before the bucket starts.
+static GenerateStats run_bucket(const std::string &ref_path, const std::string &bed, int kmer_size, const Params &p,
+                                DpProvider &dp, const std::string &out_suffix, const std::string &log_dir, FILE *log,
+                                int super_batch, std::mutex &log_mu, bool buffer_log) {
+  typedef std::unique_ptr<FILE, int (*)(FILE *)> File;
+  const std::string out_path = bed + out_suffix;
+  File out(fopen(out_path.c_str(), "w"), fclose), blog(nullptr, fclose);
+  if (!out) throw std::string("Cannot open file ") + out_path + " for writing";
+  if (!log_dir.empty()) {
+    const size_t slash = bed.find_last_of('/');
+    const std::string lp = log_dir + "/" + (slash == std::string::npos ? bed : bed.substr(slash + 1)) + ".log";
+    blog.reset(fopen(lp.c_str(), "w"));
+    if (!blog) throw std::string("Cannot open file ") + lp + " for writing";
+  }
+  struct MemLog {
+    FILE *f, *to;
+    std::mutex &mu;
+    char *buf = nullptr;
+    size_t len = 0;
+    ~MemLog() {
+      if (!f) return;
+      fclose(f);
+      std::lock_guard<std::mutex> g(mu);
+      if (len) fwrite(buf, 1, len, to);
+      free(buf);
+    }
+  } mem{nullptr, log, log_mu};
+  if (!blog && buffer_log) mem.f = open_memstream(&mem.buf, &mem.len);
+  FILE *blog_or_log = blog ? blog.get() : mem.f ? mem.f : log;
+  const GenerateStats st = generate_alignments(ref_path, bed, kmer_size, p, dp, out.get(), blog_or_log, super_batch);
+  out.reset();
+  if (blog) {
+    blog.reset();
+    std::lock_guard<std::mutex> g(log_mu);
+    fprintf(log, "Finished BED %s (%d lines, generated %d hits)\n", bed.c_str(), st.lines, st.total_written);
+  }
+  return st;
+}
+
 std::vector<GenerateStats> generate_many(const std::string &ref_path, const std::vector<std::string> &beds, int kmer_size,
                                          const Params &p, DpProvider &dp, const std::string &out_suffix,
                                          const std::string &log_dir, FILE *log, int super_batch) {
@@ -1648,112 +1714,35 @@ std::vector<GenerateStats> generate_many(const std::string &ref_path, const std:
     for (const std::string &bed : beds) one_lane = one_lane && stage_hint(bed, super_batch).lanes <= 1;
     if (one_lane) conc = std::min<size_t>((size_t)stage_settings().bucket_lanes, beds.size());
   }
-  if (conc > 1) {
-    Params pk = p;
-    pk.kmer = kmer_size;
-    set_alignment_scoring(pk);  // (before the threads: generate_alignments finds it in place)
-    std::vector<GenerateStats> all(beds.size());
-    std::vector<std::unique_ptr<DpProvider>> extra(conc);
-    std::atomic<size_t> next(0);
-    std::mutex mu;
-    std::string failure;
-    bool failed = false;
-    auto run_lane = [&](size_t l) {
-      DpProvider *d = &dp;
-      if (l > 0) {
-        try {
-          extra[l] = dp.clone(-1);
-        } catch (std::string &) {  // (no room for another device context: one bucket lane fewer)
-        }
-        d = extra[l].get();
-        if (!d) return;
-      }
-      for (;;) {
-        const size_t bi = next.fetch_add(1);
-        if (bi >= beds.size()) return;
-        {
-          std::lock_guard<std::mutex> g(mu);
-          if (failed) return;
-        }
-        const std::string &bed = beds[bi];
-        const std::string out_path = bed + out_suffix;
-        FILE *out = fopen(out_path.c_str(), "w");
-        FILE *blog = nullptr;
-        std::string err;
-        if (!out) err = std::string("Cannot open file ") + out_path + " for writing";
-        if (err.empty() && !log_dir.empty()) {
-          const size_t slash = bed.find_last_of('/');
-          const std::string lp = log_dir + "/" + (slash == std::string::npos ? bed : bed.substr(slash + 1)) + ".log";
-          blog = fopen(lp.c_str(), "w");
-          if (!blog) err = std::string("Cannot open file ") + lp + " for writing";
-        }
-        // (without --log-dir the buckets' own progress lines would interleave on the shared log: they go to a buffer that is
-        // written in one piece when the bucket is done)
-        char *membuf = nullptr;
-        size_t memlen = 0;
-        FILE *mlog = (!blog && err.empty()) ? open_memstream(&membuf, &memlen) : nullptr;
-        if (err.empty()) {
-          try {
-            all[bi] = generate_alignments(ref_path, bed, kmer_size, p, *d, out, blog ? blog : mlog ? mlog : log, super_batch);
-          } catch (std::string &e) {
-            err = e.empty() ? std::string("error") : e;
-          } catch (std::exception &e) {
-            err = e.what();
-          }
-        }
-        if (out) fclose(out);
-        if (blog) fclose(blog);
-        if (mlog) fclose(mlog);
-        std::lock_guard<std::mutex> g(mu);
-        if (membuf) {
-          if (memlen) fwrite(membuf, 1, memlen, log);
-          free(membuf);
-        }
-        if (!err.empty()) {
-          if (!failed) failure = err;
-          failed = true;
-          return;
-        }
-        if (blog) fprintf(log, "Finished BED %s (%d lines, generated %d hits)\n", bed.c_str(), all[bi].lines, all[bi].total_written);
-      }
-    };
-    std::vector<std::thread> lanes;
-    for (size_t l = 1; l < conc; l++) lanes.emplace_back(run_lane, l);
-    run_lane(0);
-    for (auto &t : lanes) t.join();
-    for (auto &e : extra)
-      if (e) dp.give_back(std::move(e));
-    if (failed) throw failure;
+  std::vector<GenerateStats> all(beds.size());
+  std::mutex log_mu;
+  if (conc <= 1) {
+    for (size_t bi = 0; bi < beds.size(); bi++)
+      all[bi] = run_bucket(ref_path, beds[bi], kmer_size, p, dp, out_suffix, log_dir, log, super_batch, log_mu, false);
     return all;
   }
-  std::vector<GenerateStats> all;
-  for (const std::string &bed : beds) {
-    const std::string out_path = bed + out_suffix;
-    FILE *out = fopen(out_path.c_str(), "w");
-    if (!out) throw std::string("Cannot open file ") + out_path + " for writing";
-    FILE *blog = nullptr;
-    if (!log_dir.empty()) {
-      const size_t slash = bed.find_last_of('/');
-      const std::string lp = log_dir + "/" + (slash == std::string::npos ? bed : bed.substr(slash + 1)) + ".log";
-      blog = fopen(lp.c_str(), "w");
-      if (!blog) {
-        fclose(out);
-        throw std::string("Cannot open file ") + lp + " for writing";
+  Params pk = p;
+  pk.kmer = kmer_size;
+  set_alignment_scoring(pk);  // (before the threads: generate_alignments finds it in place)
+  std::vector<std::unique_ptr<DpProvider>> extra(conc);
+  std::atomic<size_t> next(0);
+  FirstError failure;
+  run_lanes((int)conc, failure, [&](int l) {
+    DpProvider *d = &dp;
+    if (l > 0) {
+      try {
+        extra[(size_t)l] = dp.clone(-1);
+      } catch (...) {  // (no room for another device context: one bucket lane fewer)
       }
+      d = extra[(size_t)l].get();
+      if (!d) return;
     }
-    try {
-      all.push_back(generate_alignments(ref_path, bed, kmer_size, p, dp, out, blog ? blog : log, super_batch));
-    } catch (...) {
-      fclose(out);
-      if (blog) fclose(blog);
-      throw;
-    }
-    fclose(out);
-    if (blog) {
-      fclose(blog);
-      fprintf(log, "Finished BED %s (%d lines, generated %d hits)\n", bed.c_str(), all.back().lines, all.back().total_written);
-    }
-  }
+    for (size_t bi = next++; bi < beds.size() && !failure.failed(); bi = next++)
+      all[bi] = run_bucket(ref_path, beds[bi], kmer_size, p, *d, out_suffix, log_dir, log, super_batch, log_mu, true);
+  });
+  for (auto &e : extra)
+    if (e) dp.give_back(std::move(e));
+  failure.rethrow();
   return all;
 }
 

@@ -119,30 +119,31 @@ struct DpRequest {
   int qlen, tlen;
 };
 
-// Runs a batch of align_helper-equivalent requests; returns one CIGAR (ops M/D/I) per request.
+// Runs a batch of align_helper-equivalent requests.
 class DpProvider {
  public:
   virtual ~DpProvider() {}
-  virtual std::vector<Cigar> run(const std::vector<DpRequest> &reqs, const Params &p) = 0;
-  // Optional raw form: the device's CIGAR words of every DP task, and the tasks of every request; the caller turns
-  // them into Cigars where it consumes them (the stage driver does that on the thread that owns the pair, so that
-  // the memory of a pair is allocated and freed by one thread).  Returns false if the provider has no raw form.
+  // The results of a batch: the CIGAR words of every DP task, and the tasks of every request.  The caller turns them into
+  // Cigars where it consumes them (the stage driver does that on the thread that owns the pair, so that the memory of a
+  // pair is allocated and freed by one thread).
   struct Raw {
     struct Rec {       // per task (the layout of sdf_result_brief)
       int64_t off;     // first word
       int32_t cnt;     // number of words
-      int32_t match;   // match columns (sdf_result.matches)
+      int32_t match;   // match columns (sdf_result.matches); -1: unknown
     };
     // records and words either in memory of this object or where the provider's device copies landed (its pinned
     // staging: valid until the provider's next DP call -- the driver has consumed a round's results by then)
     const Rec *recs = nullptr;
-    const uint32_t *words = nullptr;
+    const uint32_t *words = nullptr;  // ksw_extz2's CIGAR encoding: length << 4 | op
     std::unique_ptr<Rec[]> own_recs;
     std::unique_ptr<uint32_t[]> own_words;
     std::vector<size_t> first_task;  // per request (+1): its tasks are [first_task[r], first_task[r+1])
-    Cigar cigar(size_t req) const;
+    Cigar cigar(size_t req) const;   // ops M/D/I; matches = -1 when a task's counter is unknown
   };
-  virtual bool run_raw(const std::vector<DpRequest> &, const Params &, Raw &) { return false; }
+  virtual void run(const std::vector<DpRequest> &reqs, const Params &p, Raw &raw) = 0;
+  // run() with one Cigar per request
+  std::vector<Cigar> run_cigars(const std::vector<DpRequest> &reqs, const Params &p);
   // Optional: the same for requests named as ranges of the character pool the provider's last anchors() call left on the
   // device (AnchorBatch::resident; offsets = q_base / r_base of the pair + the range's start in the pair's sequence).
   struct ResidentReq {
@@ -189,7 +190,7 @@ class DpProvider {
   // Optional: the first `bytes` of the pool_host() buffer are complete (the provider may send them to the device now).
   virtual void pool_ready(size_t /*bytes*/) {}
   int64_t tasks = 0, cells = 0;  // statistics
-  double t_pack = 0, t_call = 0, t_unpack = 0;  // wall seconds inside run(): request packing, device call, unpacking
+  double t_pack = 0, t_call = 0, t_unpack = 0;  // wall seconds: request packing and device call (run), unpacking (run_cigars)
 };
 
 // The product provider: sdf_extz2_batch on a HIP device.  Throws std::string when no device / library.

@@ -249,6 +249,23 @@ def test_generate_stage_gpu_equals_cpu_hook(host, oracle_dp, tmp_path):
         _check_bedpe(r.stdout.splitlines(), genome)
 
 
+def test_generate_stage_lanes_keep_schedule_order_cpu_hook(host, oracle_dp, tmp_path, monkeypatch, capfd):
+    """The driver's lane loop on the CPU hook (its providers clone like the device's): one, two and three lanes of
+    super-batches write the same bytes in the same order."""
+    fa = str(tmp_path / "genome.fa")
+    hostgen.make_genome(fa, seed=9, glen=150000, nsd=14)
+    monkeypatch.setenv("SDF_SUPER_BATCH", "2")  # 14 pairs -> 7 super-batches
+    got = []
+    for lanes in ("1", "2", "3"):
+        monkeypatch.setenv("SDF_LANES", lanes)
+        path = str(tmp_path / ("lanes%s.bed" % lanes))
+        stats = host.generate(fa, fa + ".bed", 11, path, test_dp=oracle_dp)
+        assert "%s lane(s)" % lanes in capfd.readouterr().err
+        got.append(open(path, "rb").read())
+        assert stats[0] == 14 and got[-1].count(b"\n") == stats[1] > 0
+    assert got[1] == got[0] and got[2] == got[0]
+
+
 @pytest.mark.gpu
 def test_generate_stage_two_lanes_keep_schedule_order(host, oracle_dp, tmp_path, monkeypatch):
     """Super-batches on two device contexts at once (SDF_LANES): same bytes, same line order as one lane."""

@@ -40,6 +40,14 @@ extern "C" {
 #define SDF_FLAG_APPROX_DROP 0x10 /* with APPROX_MAX: z-drop test on the followed value */
 #define SDF_FLAG_EXTZ_ONLY 0x40  /* traceback from the best extension cell */
 #define SDF_FLAG_REV_CIGAR 0x80  /* leave the CIGAR reversed */
+/* strand bits of a RESIDENT task, outside the KSW_EZ_* range: valid in sdf_extz2_batch_pairs, _pairs_full and _pairs_view only
+ * (an unknown flag, SDF_ERR_UNSUPPORTED, everywhere else).  That side of the task is the reverse complement of its range:
+ * base i = rev_dna(pool[off + len - 1 - i]) (reference: src/common.h:72-77,93 -- what rc() applies, src/align_main.cc:305-306);
+ * q_off / t_off keep naming the first byte of the range in pool order.
+ * Since these bits exist, every batch entry point answers SDF_ERR_UNSUPPORTED ("unknown task flag") to ANY flag bit beyond
+ * 0xff; before, only 0x100 / 0x200 (KSW_EZ_SPLICE_FOR / _REV) were refused and higher bits were ignored. */
+#define SDF_TASK_Q_RC 0x10000
+#define SDF_TASK_T_RC 0x20000
 
 /* error codes */
 #define SDF_OK 0
@@ -235,10 +243,33 @@ int sdf_extz2_batch_brief(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *t
  *                                   copies land -- the context's pinned staging -- instead of receiving a second copy in
  *                                   arrays of its own (the stage driver: 17 MB of records and CIGAR words per round, 34 MB of
  *                                   anchors per super-batch).  *out / *cigar_pool are valid until the context's next call of
- *                                   the same kind. */
+ *                                   the same kind.
+ *
+ * Resident chromosomes: a caller that serves many batches of one genome uploads each FASTA record once, as the file has
+ * it, with sdf_pool_append_fasta, and names (base offset, length, strand) afterwards: SDF_TASK_Q_RC / SDF_TASK_T_RC on the
+ * DP tasks, r_rc on the anchor pairs (sdf_anchors_batch_strand).  A forward and a reverse-strand pair on one region share
+ * the one resident copy. */
 char *sdf_pool_host(sdf_ctx *ctx, size_t bytes);
 int sdf_pool_upload(sdf_ctx *ctx, const char *chars, size_t bytes);
 size_t sdf_pool_bytes(const sdf_ctx *ctx); /* characters resident at this moment */
+/* Appends the bases of one FASTA record to the resident pool.  `bytes` are the record's sequence lines as they lie in
+ * the file (nbytes of them, starting at the .fai offset): line_bases bases, then line_bytes - line_bases line-end
+ * bytes, repeated; the last line may be short, and its line end may be missing.  The device drops the line ends (characters
+ * stay as they are: case, N); *base_off receives the pool offset of the record's base 0, so base x of the record is pool byte
+ * *base_off + x, and sdf_pool_bytes() grows by n_bases.  reset != 0: the pool is emptied first.  SDF_ERR_INVALID, with the
+ * pool as it was: a geometry that is none (line_bases < 1, line_bytes < line_bases, line_bytes == line_bases in a record of
+ * more than one line), nbytes that does not fit n_bases, a record that does not fit the device's free memory (a pool that
+ * grows moves: the old and the new buffer exist side by side for the copy).  SDF_ERR_NOMEM, with the pool EMPTY
+ * (sdf_pool_bytes() == 0): the allocation failed although the free memory sufficed.  Enqueued on the context's stream like
+ * sdf_pool_upload, from any host memory (sdf_pool_host's pinned buffer: one asynchronous DMA per 64 MiB piece); `bytes`
+ * must stay unchanged until the next call on this context that returns data, or until sdf_pool_sync() has returned -- a
+ * loader that stages record after record in the one buffer of sdf_pool_host calls sdf_pool_sync before it overwrites the
+ * buffer.  While bases are resident, sdf_pool_host only sizes the staging and leaves the pool in HBM alone. */
+int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nbytes, int64_t n_bases, int32_t line_bases,
+                          int32_t line_bytes, int reset, int64_t *base_off);
+/* Waits until everything enqueued on the context's stream has run: the uploads of sdf_pool_upload / sdf_pool_append_fasta
+ * have left their host buffers. */
+int sdf_pool_sync(sdf_ctx *ctx);
 int sdf_extz2_batch_pairs(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks, size_t n, sdf_result_brief *out,
                           uint32_t *cigar_pool, size_t cigar_cap, size_t *cigar_used);
 int sdf_extz2_batch_pairs_full(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want,
@@ -311,6 +342,18 @@ int sdf_anchors_batch_view(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n,
  * staging does not grow here: SDF_ERR_CIGAR_OVERFLOW when it has no room (*out_used: the anchors there would be). */
 int sdf_anchors_batch_more(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, size_t pool_bytes, int kmer, size_t keep,
                            const sdf_anchor **out, int64_t *out_off, size_t *out_used);
+
+/* The three calls with a strand per pair: r_rc[i] != 0 (r_rc: n bytes, or NULL = all forward) reads pair i's REFERENCE
+ * range reverse-complemented, rev_dna(pool[r_off + rlen - 1 - x]) as base x (reference: fb = rc(fb), src/align_main.cc:305-306).
+ * The anchors are exactly those, in that order, of the plain call on a pool that holds the reverse-complemented bytes of
+ * the range; their r are positions in the reverse-complemented sequence.  r_off names the first byte of the range in pool
+ * order; same_chr and delta mean what they mean above.  The plain calls are these with r_rc = NULL. */
+int sdf_anchors_batch_strand(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, const char *seq_pool,
+                             size_t pool_bytes, int kmer, sdf_anchor *out, size_t out_cap, int64_t *out_off, size_t *out_used);
+int sdf_anchors_batch_view_strand(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, const char *seq_pool,
+                                  size_t pool_bytes, int kmer, const sdf_anchor **out, int64_t *out_off, size_t *out_used);
+int sdf_anchors_batch_more_strand(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, size_t pool_bytes,
+                                  int kmer, size_t keep, const sdf_anchor **out, int64_t *out_off, size_t *out_used);
 
 /* ---- anchor chaining on the GPU ---------------------------------------------------------------
  * Replaces chain_anchors (reference: src/chain.cc:103-199) for a batch of pairs whose anchors are laid out as

@@ -21,15 +21,33 @@ namespace sdf {
 struct AnchorPairDev {
   int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool
   int32_t qlen, rlen;
-  int32_t same_chr, delta;  // near-diagonal filter of self comparisons (:67-69)
+  int32_t same_chr, delta;  // near-diagonal filter of self comparisons (:67-69); same_chr: kPairSameChr | kPairRefRc
   int64_t rk_start, qk_start;  // first global k-mer index of this pair's reference / query
 };
+
+// AnchorPairDev::same_chr holds two truth values (sdf_anchor_pair::same_chr is one, and stays one)
+constexpr int32_t kPairSameChr = 1;
+constexpr int32_t kPairRefRc = 2;  // the reference range is read reverse-complemented (sdf_anchors_batch_strand: r_rc)
 
 __device__ __forceinline__ int up(int c) { return (c >= 'a' && c <= 'z') ? c - 32 : c; }
 __device__ __forceinline__ bool is_upper(int c) { return c >= 'A' && c <= 'Z'; }
 __device__ __forceinline__ int base2(int c) {  // hash_dna (src/common.h:69,89): ACGT -> 0..3, anything else 0
   c = up(c);
   return c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 0;
+}
+// rev_dna (reference: src/common.h:72-77,93; the table behind rc(), src/util.cc:43-48): the complement of ACGT in its own
+// case, 'N' for every other index of the 128-entry table
+__device__ __forceinline__ int rev_char(int c) {
+  c &= 127;
+  const int u = c & 0x5f, low = c & 0x20;
+  return u == 'A' ? ('T' | low) : u == 'C' ? ('G' | low) : u == 'G' ? ('C' | low) : u == 'T' ? ('A' | low) : 'N';
+}
+// Character i of a pair's reference sequence as the caller means it: of the range itself, or of its reverse complement
+// (RC: the call has such pairs at all -- the kernels of a call without one are the ones without the test)
+template <bool RC>
+__device__ __forceinline__ int ref_char(const AnchorPairDev &p, const char *R, int i) {
+  if (RC && (p.same_chr & kPairRefRc)) return rev_char(R[p.rlen - 1 - i]);
+  return R[i];
 }
 // hash of the k-mer starting at s; returns false if the window holds an N
 __device__ __forceinline__ bool kmer_at(const char *s, int k, uint32_t &h) {
@@ -42,8 +60,21 @@ __device__ __forceinline__ bool kmer_at(const char *s, int k, uint32_t &h) {
   }
   return ok;
 }
+// ... of the k-mer starting at base i of the reverse complement of R[0, rlen): the bytes R[rlen - 1 - i] downwards
+__device__ __forceinline__ bool kmer_at_rc(const char *R, int rlen, int i, int k, uint32_t &h) {
+  h = 0;
+  bool ok = true;
+  const char *s = R + (rlen - 1 - i);
+  for (int j = 0; j < k; j++) {
+    const int c = rev_char(s[-j]);
+    ok = ok && c != 'N';
+    h = (h << 2) | (uint32_t)base2(c);
+  }
+  return ok;
+}
 
 // (grid: x = 32 blocks over a pair's k-mers, y x z = the pairs, 65,535 rows per layer; pos_bits: bits of the position field)
+template <bool RC>
 __global__ __launch_bounds__(256) void ref_keys_kernel(const AnchorPairDev *pairs, int npairs, const char *pool, int k,
                                                        int pos_bits, unsigned long long *keys) {
   const unsigned pr = blockIdx.z * 65535u + blockIdx.y;
@@ -52,7 +83,7 @@ __global__ __launch_bounds__(256) void ref_keys_kernel(const AnchorPairDev *pair
   const int nk = p.rlen - k + 1;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += gridDim.x * blockDim.x) {
     uint32_t h;
-    const bool ok = kmer_at(pool + p.r_off + i, k, h);
+    const bool ok = RC && (p.same_chr & kPairRefRc) ? kmer_at_rc(pool + p.r_off, p.rlen, i, k, h) : kmer_at(pool + p.r_off + i, k, h);
     keys[p.rk_start + i] = ok ? (((unsigned long long)pr << (2 * k + pos_bits)) | ((unsigned long long)h << pos_bits) | (unsigned)i)
                               : ~0ull;
   }
@@ -122,6 +153,7 @@ struct CandOut {
   int32_t q, r, l, has_u;
 };
 
+template <bool RC>
 __global__ __launch_bounds__(256) void candidates_kernel(const AnchorPairDev *pairs, const char *pool, int k,
                                                          const unsigned long long *keys, const uint32_t *qlo,
                                                          const uint32_t *qcnt, const unsigned long long *cand_off,
@@ -141,12 +173,12 @@ __global__ __launch_bounds__(256) void candidates_kernel(const AnchorPairDev *pa
   const int j = (int)((unsigned long long)c - cand_off[g]);
   const int r = (int)(keys[qlo[g] + j] & ((1ull << pos_bits) - 1));
   const char *Q = pool + p.q_off, *R = pool + p.r_off;
-  bool start = !(p.same_chr && abs(p.delta + r - q) <= k);
+  bool start = !((RC ? (p.same_chr & kPairSameChr) : p.same_chr) && abs(p.delta + r - q) <= k);  // (!RC: the field is 0 or 1)
   // an earlier enabled k-mer of the same match run on this diagonal already covers this one
   for (int s = 1; start; s++) {
     const int qq = q - s, rr = r - s;
     if (qq < 0 || rr < 0) break;
-    const int cq = up(Q[qq]), cr = up(R[rr]);
+    const int cq = up(Q[qq]), cr = up(ref_char<RC>(p, R, rr));
     if (cq == 'N' || cr == 'N' || cq != cr) break;
     if (qcnt[g - s] < 1000) start = false;  // enabled: its anchor (or an even earlier one) extends over q
   }
@@ -155,7 +187,7 @@ __global__ __launch_bounds__(256) void candidates_kernel(const AnchorPairDev *pa
     int len = 0;
     bool hu = false;
     for (; q + len < p.qlen && r + len < p.rlen; len++) {
-      const int a = Q[q + len], b = R[r + len];
+      const int a = Q[q + len], b = ref_char<RC>(p, R, r + len);
       if (up(a) == 'N' || up(b) == 'N' || up(a) != up(b)) break;
       hu = hu || is_upper(a) || is_upper(b);
     }

@@ -198,6 +198,7 @@ extern "C" void sdf_destroy(sdf_ctx *ctx) {
   ctx->host_an.release();
   ctx->host_chars.release();
   ctx->pk_recs.release();
+  ctx->fa_raw.release();
   if (ctx->rerun_ctx) sdf_destroy(ctx->rerun_ctx);
   if (ctx->part_ctx) sdf_destroy(ctx->part_ctx);
   if (ctx->part_ev) (void)hipEventDestroy(ctx->part_ev);
@@ -891,7 +892,9 @@ extern "C" char *sdf_pool_host(sdf_ctx *ctx, size_t bytes) {
     ctx->err = "cannot pin the character pool's staging";
     return nullptr;
   }
-  (void)ctx->an_pool.reserve(bytes + 64);  // (its place in HBM with it: a first upload of 180 MB waited 8 ms for this)
+  // (its place in HBM with it: a first upload of 180 MB waited 8 ms for this -- but only while nothing is resident: a grown
+  // buffer starts empty, and the records sdf_pool_append_fasta left must stay where they are)
+  if (!ctx->pool_bytes) (void)ctx->an_pool.reserve(bytes + 64);
   if (ctx->cfg.debug_timing && ctx->host_chars.cap != had)
     fprintf(stderr, "[sdf_pool_host %zu MiB %s in %.1f ms]\n", ctx->host_chars.cap >> 20, ctx->host_chars.registered ? "registered huge pages" : "hipHostMalloc",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -916,6 +919,88 @@ extern "C" int sdf_pool_upload(sdf_ctx *ctx, const char *chars, size_t bytes) {
 
 extern "C" size_t sdf_pool_bytes(const sdf_ctx *ctx) { return ctx ? ctx->pool_bytes : 0; }
 
+// The context's stream drained: every upload enqueued so far has left its host buffer (include/sedef_hip.h)
+extern "C" int sdf_pool_sync(sdf_ctx *ctx) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  SDF_HIP(hipSetDevice(ctx->device));
+  SDF_HIP(hipStreamSynchronize(ctx->stream));
+  return SDF_OK;
+}
+
+// A FASTA record's sequence lines -> its bases behind the ones resident (include/sedef_hip.h; seq_pack.hip: fasta_gather_kernel).
+// The lines cross PCIe as they are, in pieces of whole lines through one scratch buffer (everything is enqueued on the context's
+// stream, so a piece's upload waits for the gather of the piece before it), and the device drops the line ends.
+extern "C" int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nbytes, int64_t n_bases, int32_t line_bases,
+                                     int32_t line_bytes, int reset, int64_t *base_off) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  auto invalid = [&](const char *why) {
+    ctx->err = std::string("sdf_pool_append_fasta: ") + why;
+    return SDF_ERR_INVALID;
+  };
+  if (!base_off || n_bases < 0 || (!bytes && nbytes)) return invalid("invalid arguments");
+  // line_bases bases, then line_bytes - line_bases line-end bytes; a record of one line may come without a line end at all
+  if (line_bases < 1 || line_bytes < line_bases) return invalid("a line holds at least one base and line_bytes >= line_bases");
+  const size_t gap = (size_t)(line_bytes - line_bases);
+  if (gap == 0 && n_bases > line_bases) return invalid("lines without line ends (line_bytes == line_bases) in a record of several lines");
+  // n_bases bases and the line ends between them, with or without the last line's own
+  const size_t least = (size_t)n_bases + (n_bases ? (size_t)((n_bases - 1) / line_bases) * gap : 0);
+  if (nbytes < least || nbytes > least + gap) return invalid("nbytes does not fit n_bases bases in lines of this geometry");
+  const size_t at = reset ? 0 : ctx->pool_bytes, need = at + (size_t)n_bases;
+  SDF_HIP(hipSetDevice(ctx->device));
+  // pieces of whole lines, 64 MiB or so each (the gather's indices within a piece are 32-bit)
+  const size_t piece_lines = std::max<size_t>(1, ((size_t)64 << 20) / (size_t)line_bytes);
+  const size_t piece_raw = std::min(nbytes, piece_lines * (size_t)line_bytes);
+  // Growth has to fit beside what is resident (the pool moves: old and new buffer live side by side for the copy).  With room
+  // to spare the pool grows with DevBuf's headroom, so that a genome's records do not move it once each; without, to the byte.
+  const bool grow_pool = need + 64 > ctx->an_pool.cap, grow_raw = piece_raw + 64 > ctx->fa_raw.cap;
+  bool headroom = false;
+  if (grow_pool || grow_raw) {
+    size_t free_b = 0, total_b = 0;
+    SDF_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t exact = (grow_pool ? need + 64 : 0) + (grow_raw ? piece_raw + 64 : 0);
+    if (exact > free_b || exact < need) return invalid("the record does not fit the device's free memory beside the resident pool");
+    headroom = grow_pool && exact + std::min<size_t>((need + 64) / 2, (size_t)8 << 30) + ((size_t)64 << 20) <= free_b;
+  }
+  ctx->an_pool.new_call();
+  ctx->fa_raw.new_call();
+  if (grow_pool) {  // (the bases resident move to the larger buffer; the outgrown one is retired, not freed: DevBuf)
+    const void *old = ctx->an_pool.p;
+    ctx->pool_bytes = 0;  // (nothing is resident until the move has been enqueued: a failure below leaves an empty pool)
+    const hipError_t e = headroom ? ctx->an_pool.reserve(need + 64) : ctx->an_pool.reserve_exact(need + 64);
+    if (e != hipSuccess || (at && std::find(ctx->an_pool.retired.begin(), ctx->an_pool.retired.end(), old) == ctx->an_pool.retired.end())) {
+      (void)hipGetLastError();
+      ctx->err = "sdf_pool_append_fasta: out of device memory while growing the pool (the pool is empty now)";
+      return SDF_ERR_NOMEM;
+    }
+    if (at) SDF_HIP(hipMemcpyAsync(ctx->an_pool.p, old, at, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  ctx->pool_bytes = at;
+  SDF_HIP(ctx->fa_raw.reserve_exact(piece_raw + 64));
+  const auto t0 = std::chrono::steady_clock::now();
+  for (size_t b0 = 0, x0 = 0; x0 < (size_t)n_bases; b0 += piece_raw, x0 += piece_lines * (size_t)line_bases) {
+    const size_t nb = std::min(piece_raw, nbytes - b0), nx = std::min(piece_lines * (size_t)line_bases, (size_t)n_bases - x0);
+    SDF_HIP(hipMemcpyAsync(ctx->fa_raw.p, bytes + b0, nb, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(sdf::fasta_gather_kernel, dim3((unsigned)((nx / 16 + 2 + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const char *)ctx->fa_raw.p, (char *)ctx->an_pool.p + at + x0, (uint32_t)nx, (uint32_t)line_bases, (uint32_t)gap);
+  }
+  SDF_HIP(hipGetLastError());
+  if (ctx->cfg.debug_timing) {
+    SDF_HIP(hipStreamSynchronize(ctx->stream));
+    fprintf(stderr, "[sdf_pool_append_fasta %zu bytes -> %lld bases at %zu] %.2f ms\n", nbytes, (long long)n_bases, at,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+  ctx->pool_bytes = need;
+  *base_off = (int64_t)at;
+  return SDF_OK;
+}
+
+// The strand bits of a resident task (include/sedef_hip.h) are consumed where characters become codes (seq_pack.hip): this is
+// the flag word the planner gets.  Every other entry point hands its flags over as they are, where the bits are unknown ones.
+constexpr int32_t kStrandBits = SDF_TASK_Q_RC | SDF_TASK_T_RC;
+static inline int32_t planner_flag(int32_t flag) { return flag & ~kStrandBits; }
+
 static int batch_pairs(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want, sdf_result *out,
                        sdf_result_brief *brief, uint32_t *cigar_pool, size_t cigar_cap, size_t *cigar_used,
                        ResultView *view = nullptr) {
@@ -939,7 +1024,7 @@ static int batch_pairs(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *task
   PackRec *recs = (PackRec *)ctx->host_pool.p;
   const size_t block = 32768, nb = (n + block - 1) / block, pool_bytes = ctx->pool_bytes;
   std::vector<size_t> bwords(nb + 1, 0), bcap(nb, 0);
-  std::atomic<bool> bad(false);
+  std::atomic<bool> bad(false), any_rc(false);
   const unsigned thr_cap = g_live_contexts.load() > 1 ? 4u : (unsigned)std::max(1, std::min(8, usable_cpus() / 2));
   const int nthr = (int)std::min<size_t>(nb, thr_cap);
   auto on_blocks = [&](const std::function<void(size_t)> &f) {
@@ -977,28 +1062,34 @@ static int batch_pairs(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *task
   const size_t words = bwords[nb];
   on_blocks([&](size_t b) {
     size_t w = bwords[b];
+    int32_t block_rc = 0;  // (one store per block: the threads share the flag's cache line)
     for (size_t k = b * block; k < std::min(n, (b + 1) * block); ++k) {
       const sdf_task &t = tasks[k];
       PackRec &r = recs[k];
       r.q_byte = t.q_off;
       r.t_byte = t.t_off;
       r.q_word = (int64_t)w;
-      r.qlen = t.qlen;
-      r.tlen = t.tlen;
+      r.qlen = (int32_t)((uint32_t)t.qlen | ((t.flag & SDF_TASK_Q_RC) ? sdf::kPackRc : 0u));
+      r.tlen = (int32_t)((uint32_t)t.tlen | ((t.flag & SDF_TASK_T_RC) ? sdf::kPackRc : 0u));
+      block_rc |= t.flag;
       t2[k] = t;
+      t2[k].flag = planner_flag(t.flag);  // (the strand is the packing's alone: the planner and the DP kernels never see it)
       t2[k].q_off = (int64_t)w;
       w += sdf_packed_words(t.qlen);
       t2[k].t_off = (int64_t)w;
       w += sdf_packed_words(t.tlen);
     }
+    if (block_rc & kStrandBits) any_rc.store(true, std::memory_order_relaxed);
   });
   const auto dbg1 = std::chrono::steady_clock::now();
   for (DevBuf *b : {&ctx->pk_recs}) b->new_call();
   SDF_HIP(ctx->h_pool.reserve(std::max<size_t>(words, 1) * 4));
   SDF_HIP(ctx->pk_recs.reserve(n * sizeof(PackRec)));
   SDF_HIP(hipMemcpyAsync(ctx->pk_recs.p, recs, n * sizeof(PackRec), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(sdf::pack_chars_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, ctx->stream,
-                     (const PackRec *)ctx->pk_recs.p, (long long)(2 * n), (const char *)ctx->an_pool.p, (uint32_t *)ctx->h_pool.p);
+  // (a batch without a reversed side -- every batch of the stage driver -- runs the forward-only kernel)
+  hipLaunchKernelGGL(any_rc.load() ? sdf::pack_chars_kernel<true> : sdf::pack_chars_kernel<false>, dim3((unsigned)((2 * n + 15) / 16)),
+                     dim3(256), 0, ctx->stream, (const PackRec *)ctx->pk_recs.p, (long long)(2 * n), (const char *)ctx->an_pool.p,
+                     (uint32_t *)ctx->h_pool.p);
   return batch_host_tail(ctx, sc, t2.data(), n, words, want, out, brief, cigar_pool, cigar_cap, cigar_used, nthr, dbg0, dbg1,
                          "sdf_extz2_batch_pairs", view);
 }
@@ -1165,7 +1256,7 @@ extern "C" size_t sdf_device_bytes(const sdf_ctx *ctx) {
                           &ctx->h_pool, &ctx->h_out, &ctx->h_brief, &ctx->h_cig, &ctx->rr_out, &ctx->rr_cig, &ctx->rr_map, &ctx->ln_recs,
                           &ctx->ln_keys, &ctx->ln_vals, &ctx->ln_sizes, &ctx->ln_tmp, &ctx->pk_recs,
                           // the anchors / chaining / stats entry points
-                          &ctx->an_pool, &ctx->an_pairs, &ctx->an_keys, &ctx->an_keys2, &ctx->an_q, &ctx->an_off, &ctx->an_flag, &ctx->an_pos,
+                          &ctx->an_pool, &ctx->fa_raw, &ctx->an_pairs, &ctx->an_keys, &ctx->an_keys2, &ctx->an_q, &ctx->an_off, &ctx->an_flag, &ctx->an_pos,
                           &ctx->an_cand, &ctx->an_out, &ctx->an_tmp, &ctx->an_outoff, &ctx->ch_an, &ctx->ch_off, &ctx->ch_wsoff, &ctx->ch_work,
                           &ctx->ch_path, &ctx->ch_bounds, &ctx->ch_nb, &ctx->ch_which, &ctx->st_tasks, &ctx->st_pool, &ctx->st_cig, &ctx->st_out})
     sum += b->held_bytes();
@@ -1175,8 +1266,8 @@ extern "C" size_t sdf_device_bytes(const sdf_ctx *ctx) {
 }
 
 // ---- seed anchors (reference: src/chain.cc:24-101) ---------------------------------------------------
-static int anchors_range(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, const char *d_pool, int kmer, int pos_bits,
-                         sdf_anchor *out, size_t out_cap, int64_t *out_off, size_t *out_used, hipStream_t st) {
+static int anchors_range(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, const char *d_pool, int kmer,
+                         int pos_bits, sdf_anchor *out, size_t out_cap, int64_t *out_off, size_t *out_used, hipStream_t st) {
   using namespace sdf;
   const auto lt0 = std::chrono::steady_clock::now();
   auto lap = [&, last = lt0](const char *what) mutable {  // (SDF_DEBUG_TIMING: host milliseconds of the call's sections)
@@ -1190,13 +1281,15 @@ static int anchors_range(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, c
   const int key_bits = std::min(64, pair_bits + 2 * kmer + pos_bits);  // (the sort looks at the bits in use only)
   std::vector<AnchorPairDev> hp(n);
   long long nrk = 0, nqk = 0;
+  bool any_rc = false;  // (a call without a reversed reference runs the kernels without the strand test)
   for (size_t i = 0; i < n; i++) {
     AnchorPairDev &d = hp[i];
     d.q_off = pairs[i].q_off;
     d.r_off = pairs[i].r_off;
     d.qlen = pairs[i].qlen;
     d.rlen = pairs[i].rlen;
-    d.same_chr = pairs[i].same_chr;
+    d.same_chr = (pairs[i].same_chr ? kPairSameChr : 0) | (r_rc && r_rc[i] ? kPairRefRc : 0);
+    any_rc = any_rc || (r_rc && r_rc[i]);
     d.delta = pairs[i].delta;
     d.rk_start = nrk;
     d.qk_start = nqk;
@@ -1219,7 +1312,7 @@ static int anchors_range(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, c
   lap("pair records, buffers");
   SDF_HIP(hipMemcpyAsync(d_pairs, hp.data(), n * sizeof(AnchorPairDev), hipMemcpyHostToDevice, st));
   const dim3 grid(32, (unsigned)std::min<size_t>(n, 65535), (unsigned)((n + 65534) / 65535));
-  hipLaunchKernelGGL(ref_keys_kernel, grid, dim3(256), 0, st, d_pairs, (int)n, d_pool, kmer, pos_bits, d_keys);
+  hipLaunchKernelGGL(any_rc ? ref_keys_kernel<true> : ref_keys_kernel<false>, grid, dim3(256), 0, st, d_pairs, (int)n, d_pool, kmer, pos_bits, d_keys);
   size_t tmp_bytes = 0;
   SDF_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_keys, d_keys2, (int)nrk, pos_bits, key_bits, st));
   size_t scan_bytes = 0;
@@ -1249,7 +1342,7 @@ static int anchors_range(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, c
   unsigned long long *d_pos = (unsigned long long *)ctx->an_pos.p;
   CandOut *d_cand = (CandOut *)ctx->an_cand.p;
   const unsigned nb = (unsigned)((ncand + 255) / 256);
-  hipLaunchKernelGGL(candidates_kernel, dim3(nb), dim3(256), 0, st, d_pairs, d_pool, kmer, d_keys2, d_qlo, d_qcnt, d_off,
+  hipLaunchKernelGGL(any_rc ? candidates_kernel<true> : candidates_kernel<false>, dim3(nb), dim3(256), 0, st, d_pairs, d_pool, kmer, d_keys2, d_qlo, d_qcnt, d_off,
                      d_qpair, nqk, (long long)ncand, d_flag, d_cand, pos_bits);
   SDF_HIP(hipMemsetAsync(d_flag + ncand, 0, 4, st));
   size_t scan2 = 0;
@@ -1304,9 +1397,9 @@ static int anchors_range(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, c
   return SDF_OK;
 }
 
-extern "C" int sdf_anchors_batch(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, const char *seq_pool,
-                                 size_t pool_bytes, int kmer, sdf_anchor *out, size_t out_cap, int64_t *out_off,
-                                 size_t *out_used) {
+extern "C" int sdf_anchors_batch_strand(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, const char *seq_pool,
+                                        size_t pool_bytes, int kmer, sdf_anchor *out, size_t out_cap, int64_t *out_off,
+                                        size_t *out_used) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
   if (out_used) *out_used = 0;
@@ -1375,7 +1468,7 @@ extern "C" int sdf_anchors_batch(sdf_ctx *ctx, const sdf_anchor_pair *pairs, siz
     }
     size_t used = 0;
     const int64_t first = out_off[s];
-    rc = anchors_range(ctx, pairs + s, e - s, (const char *)ctx->an_pool.p, kmer, pos_bits, out ? out + used_total : nullptr,
+    rc = anchors_range(ctx, pairs + s, r_rc ? r_rc + s : nullptr, e - s, (const char *)ctx->an_pool.p, kmer, pos_bits, out ? out + used_total : nullptr,
                        out_cap > used_total ? out_cap - used_total : 0, out_off + s, &used, ctx->stream);
     for (size_t i = s; i <= e; i++) out_off[i] += first;  // (the range's offsets start at 0)
     if (rc == SDF_ERR_CIGAR_OVERFLOW) {  // the caller wants the size needed: count the remaining ranges too
@@ -1383,7 +1476,7 @@ extern "C" int sdf_anchors_batch(sdf_ctx *ctx, const sdf_anchor_pair *pairs, siz
       for (size_t s2 = e; s2 < n;) {
         size_t e2 = std::min(n, s2 + range_max), u2 = 0;
         std::vector<int64_t> tmp_off(e2 - s2 + 1);
-        (void)anchors_range(ctx, pairs + s2, e2 - s2, (const char *)ctx->an_pool.p, kmer, pos_bits, nullptr, 0, tmp_off.data(), &u2,
+        (void)anchors_range(ctx, pairs + s2, r_rc ? r_rc + s2 : nullptr, e2 - s2, (const char *)ctx->an_pool.p, kmer, pos_bits, nullptr, 0, tmp_off.data(), &u2,
                             ctx->stream);
         more += u2;
         s2 = e2;
@@ -1402,8 +1495,14 @@ extern "C" int sdf_anchors_batch(sdf_ctx *ctx, const sdf_anchor_pair *pairs, siz
   return rc;
 }
 
-extern "C" int sdf_anchors_batch_view(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, const char *seq_pool, size_t pool_bytes,
-                                      int kmer, const sdf_anchor **out, int64_t *out_off, size_t *out_used) {
+extern "C" int sdf_anchors_batch(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, const char *seq_pool,
+                                 size_t pool_bytes, int kmer, sdf_anchor *out, size_t out_cap, int64_t *out_off,
+                                 size_t *out_used) {
+  return sdf_anchors_batch_strand(ctx, pairs, nullptr, n, seq_pool, pool_bytes, kmer, out, out_cap, out_off, out_used);
+}
+
+extern "C" int sdf_anchors_batch_view_strand(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, const char *seq_pool,
+                                             size_t pool_bytes, int kmer, const sdf_anchor **out, int64_t *out_off, size_t *out_used) {
   if (!ctx || !out) return SDF_ERR_INVALID;
   *out = nullptr;
   if (hipSetDevice(ctx->device) != hipSuccess || ctx->host_an.reserve_pinned(ctx->cfg.pin_register >= 2, (size_t)48 << 20) != hipSuccess) {
@@ -1411,7 +1510,7 @@ extern "C" int sdf_anchors_batch_view(sdf_ctx *ctx, const sdf_anchor_pair *pairs
     ctx->err = "cannot pin the anchors' staging";
     return SDF_ERR_NOMEM;
   }
-  int rc = sdf_anchors_batch(ctx, pairs, n, seq_pool, pool_bytes, kmer, (sdf_anchor *)ctx->host_an.p, ctx->host_an.cap / sizeof(sdf_anchor),
+  int rc = sdf_anchors_batch_strand(ctx, pairs, r_rc, n, seq_pool, pool_bytes, kmer, (sdf_anchor *)ctx->host_an.p, ctx->host_an.cap / sizeof(sdf_anchor),
                              out_off, out_used);
   if (rc == SDF_ERR_CIGAR_OVERFLOW) {  // more anchors than the staging holds: once more with room for all of them
     if (ctx->host_an.reserve_pinned(ctx->cfg.pin_register >= 2, (*out_used + 1024) * sizeof(sdf_anchor)) != hipSuccess) {
@@ -1420,18 +1519,23 @@ extern "C" int sdf_anchors_batch_view(sdf_ctx *ctx, const sdf_anchor_pair *pairs
       return SDF_ERR_NOMEM;
     }
     // (the characters are resident since the first attempt)
-    rc = sdf_anchors_batch(ctx, pairs, n, nullptr, pool_bytes, kmer, (sdf_anchor *)ctx->host_an.p, ctx->host_an.cap / sizeof(sdf_anchor),
+    rc = sdf_anchors_batch_strand(ctx, pairs, r_rc, n, nullptr, pool_bytes, kmer, (sdf_anchor *)ctx->host_an.p, ctx->host_an.cap / sizeof(sdf_anchor),
                            out_off, out_used);
   }
   if (rc == SDF_OK) *out = (const sdf_anchor *)ctx->host_an.p;
   return rc;
 }
 
+extern "C" int sdf_anchors_batch_view(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, const char *seq_pool, size_t pool_bytes,
+                                      int kmer, const sdf_anchor **out, int64_t *out_off, size_t *out_used) {
+  return sdf_anchors_batch_view_strand(ctx, pairs, nullptr, n, seq_pool, pool_bytes, kmer, out, out_off, out_used);
+}
+
 // ... of MORE pairs of the resident pool, written behind the first `keep` anchors of the staging (which stay where they are: a
 // caller that is still reading them -- the stage driver chains the first half of a super-batch while the device finds the
 // anchors of the second -- is not disturbed).  No growth: SDF_ERR_CIGAR_OVERFLOW when the staging has no room for them.
-extern "C" int sdf_anchors_batch_more(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, size_t pool_bytes, int kmer, size_t keep,
-                                      const sdf_anchor **out, int64_t *out_off, size_t *out_used) {
+extern "C" int sdf_anchors_batch_more_strand(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, size_t pool_bytes,
+                                             int kmer, size_t keep, const sdf_anchor **out, int64_t *out_off, size_t *out_used) {
   if (!ctx || !out) return SDF_ERR_INVALID;
   *out = nullptr;
   const size_t cap = ctx->host_an.cap / sizeof(sdf_anchor);
@@ -1440,9 +1544,14 @@ extern "C" int sdf_anchors_batch_more(sdf_ctx *ctx, const sdf_anchor_pair *pairs
     return SDF_ERR_INVALID;
   }
   sdf_anchor *at = (sdf_anchor *)ctx->host_an.p + keep;
-  const int rc = sdf_anchors_batch(ctx, pairs, n, nullptr, pool_bytes, kmer, at, cap - keep, out_off, out_used);
+  const int rc = sdf_anchors_batch_strand(ctx, pairs, r_rc, n, nullptr, pool_bytes, kmer, at, cap - keep, out_off, out_used);
   if (rc == SDF_OK) *out = at;
   return rc;
+}
+
+extern "C" int sdf_anchors_batch_more(sdf_ctx *ctx, const sdf_anchor_pair *pairs, size_t n, size_t pool_bytes, int kmer, size_t keep,
+                                      const sdf_anchor **out, int64_t *out_off, size_t *out_used) {
+  return sdf_anchors_batch_more_strand(ctx, pairs, nullptr, n, pool_bytes, kmer, keep, out, out_off, out_used);
 }
 
 // ---- anchor chaining (reference: src/chain.cc:103-199) ---------------------------------------------------
@@ -1741,6 +1850,15 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
   sdf_ctx tmp;  // only err is used: no HIP call is made here
   ScoreK sk;
   if (int rc = make_scorek(&tmp, sc, sk)) return rc;
+  // Tasks as sdf_extz2_batch_pairs takes them may carry strand bits: the planner gets the flag word that call hands over
+  std::vector<sdf_task> handed;
+  for (size_t k = 0; k < n; ++k)
+    if (tasks[k].flag & kStrandBits) {
+      handed.assign(tasks, tasks + n);
+      for (sdf_task &t : handed) t.flag = planner_flag(t.flag);
+      tasks = handed.data();
+      break;
+    }
   const PlanEnv env = plan_env(dcfg, sc, tasks, n, want, max_dyn_lds);
   BatchCut cut;
   const char *msg = nullptr;
@@ -1826,4 +1944,13 @@ extern "C" int sdf_debug_copy_dir(sdf_ctx *ctx, void *host, size_t bytes) {
   if (!ctx || !ctx->dir_ws.p) return SDF_ERR_INVALID;
   if (bytes > ctx->dir_ws.cap) bytes = ctx->dir_ws.cap;
   return hipMemcpy(host, ctx->dir_ws.p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? SDF_OK : SDF_ERR_HIP;
+}
+
+// ---- debugging aid (not part of the public header): the resident pool's characters [off, off + bytes) as they lie in HBM ----
+extern "C" int sdf_debug_pool_read(sdf_ctx *ctx, size_t off, size_t bytes, char *host) {
+  if (!ctx || !host || off > ctx->pool_bytes || bytes > ctx->pool_bytes - off) return SDF_ERR_INVALID;
+  if (!bytes) return SDF_OK;
+  SDF_HIP(hipSetDevice(ctx->device));
+  SDF_HIP(hipStreamSynchronize(ctx->stream));
+  return hipMemcpy(host, (const char *)ctx->an_pool.p + off, bytes, hipMemcpyDeviceToHost) == hipSuccess ? SDF_OK : SDF_ERR_HIP;
 }

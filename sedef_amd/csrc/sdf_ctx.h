@@ -338,6 +338,7 @@ struct sdf_ctx {
   HostBuf host_chars;      // pinned staging of a super-batch's FASTA characters (sdf_pool_host)
   size_t pool_bytes = 0;   // characters resident in an_pool (sdf_pool_upload / sdf_anchors_batch): what sdf_extz2_batch_pairs may name
   DevBuf pk_recs;          // ... one PackRec per task of such a call (seq_pack.hip)
+  DevBuf fa_raw;           // a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta)
   HostBuf host_an;  // pinned staging of the anchors call's output (sdf_reserve with SDF_RESERVE_ANCHORS; a pageable copy runs at ~3 GB/s)
   DevBuf ln_recs, ln_keys, ln_vals, ln_sizes, ln_tmp;
   DevBuf ln_bins;  // ... second form of the lane planning: per-key counts, ranks, prefixes (extz2_lane.hip: lane_hist_kernel and on)

@@ -436,7 +436,8 @@ static int cut_batch(const PlanEnv &env, bool pipeline_enabled, size_t ws_budget
         } else if (mode == 2 && is_big(t)) {
           continue;
         }
-        if (t.flag & 0x300) {  // (not KSW_EZ_* bits of the extz2 kernel)
+        if (t.flag & ~0xff) {  // (not KSW_EZ_* bits of the extz2 kernel: the splice bits, and everything beyond the KSW_EZ_* range --
+                               // the strand bits of a resident task never get here, sdf_api.hip: planner_flag)
           pt.bad = true;
           return;
         }

@@ -13,27 +13,61 @@
 namespace sdf {
 
 struct PackRec {     // one DP task's two character ranges and where its packed words go (32 bytes)
-  int64_t q_byte;    // first character of the query range in the pool
+  int64_t q_byte;    // first character of the query range in the pool (the first byte in pool order, whatever the strand)
   int64_t t_byte;
   int64_t q_word;    // first packed word of the query; the target's words follow the query's
-  int32_t qlen, tlen;
+  int32_t qlen, tlen;  // bit 31 (kPackRc): the side is read reverse-complemented -- base i = rev(pool[byte + len - 1 - i])
 };
+// The two strand bits of a task (SDF_TASK_Q_RC / SDF_TASK_T_RC) travel in the sign bits of the lengths, which are never
+// negative: the record stays 32 bytes.  Only pack_chars_kernel<true> decodes them; a batch without a reversed side is
+// packed by pack_chars_kernel<false>, the kernel as it was.
+constexpr uint32_t kPackRc = 0x80000000u;
+static_assert(sizeof(PackRec) == 32, "PackRec: two records per 64-byte line");
 
 // Sixteen lanes per sequence (a task is two sequences), a lane per group of 32 bases -- two code words and a mask word.
 // SEDEF's tasks are short (708,600 of ~25 bases in a round of the chr1-sized run) with a few of up to 60,000 bases
 // (Align::MAX_KSW_SEQ_LEN): the lanes of a group stride over a long sequence.
+// REV: some side of some task is reversed.  Such a side is walked from its far end: group g of the task's bases is the 32
+// bytes that END at byte len - 32 g of the range, so the sixteen lanes of a step still read 512 contiguous bytes, a lane its
+// own 32, as on the forward side; rev_dna (reference: src/common.h:72-77,93) then align_dna give 3 - code for ACGT of either
+// case and the wildcard for everything else.
+template <bool REV>
 __global__ void __launch_bounds__(256) pack_chars_kernel(const PackRec *__restrict__ recs, long long n_seq,
                                                          const char *__restrict__ pool, uint32_t *__restrict__ out) {
   const int sub = threadIdx.x & 15;
   const long long seq = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
   if (seq >= n_seq) return;
-  const PackRec r = recs[seq >> 1];
+  PackRec r = recs[seq >> 1];
   const bool is_t = (seq & 1) != 0;
+  bool rc = false;
+  if (REV) {
+    rc = ((uint32_t)(is_t ? r.tlen : r.qlen) & kPackRc) != 0;
+    r.qlen = (int32_t)((uint32_t)r.qlen & ~kPackRc);
+    r.tlen = (int32_t)((uint32_t)r.tlen & ~kPackRc);
+  }
   const int len = is_t ? r.tlen : r.qlen;
   const char *src = pool + (is_t ? r.t_byte : r.q_byte);
   const int q_words = ((r.qlen + 15) >> 4) + ((r.qlen + 31) >> 5);
   uint32_t *dst = out + r.q_word + (is_t ? q_words : 0);
   const int ncode = (len + 15) >> 4;
+  if (REV && rc) {
+    const char *last = src + len - 1;  // base 0 of the reversed side
+    for (int g = sub; 32 * g < len; g += 16) {
+      uint32_t c0 = 0, c1 = 0, m = 0;
+      const int lim = min(32, len - 32 * g);
+      for (int b = 0; b < lim; ++b) {
+        const unsigned c = (unsigned char)last[-(32 * g + b)] & 0x5fu;
+        const unsigned code = c == 'T' ? 0u : c == 'G' ? 1u : c == 'C' ? 2u : c == 'A' ? 3u : 4u;
+        if (code == 4u) m |= 1u << b;
+        else if (b < 16) c0 |= code << (2 * b);
+        else c1 |= code << (2 * (b - 16));
+      }
+      dst[2 * g] = c0;
+      if (32 * g + 16 < len) dst[2 * g + 1] = c1;
+      dst[ncode + g] = m;
+    }
+    return;
+  }
   for (int g = sub; 32 * g < len; g += 16) {
     uint32_t c0 = 0, c1 = 0, m = 0;
     const int lim = min(32, len - 32 * g);
@@ -47,6 +81,41 @@ __global__ void __launch_bounds__(256) pack_chars_kernel(const PackRec *__restri
     dst[2 * g] = c0;
     if (32 * g + 16 < len) dst[2 * g + 1] = c1;
     dst[ncode + g] = m;
+  }
+}
+
+// ---- FASTA layout: a record's sequence lines as they lie in the file -> its bases, back to back, in the resident pool ----
+// Base x of the record lies at byte x + (x / line_bases) * (line_bytes - line_bases) of its lines (what a .fai index says;
+// reference: src/fasta.cc reads through the same arithmetic), so the gather needs no scan.  `raw` holds whole lines from a line
+// start (a piece of the record: sdf_pool_append_fasta streams a long record through a scratch buffer), n bases of them go to
+// dst[0..n).  A thread owns one 16-byte-aligned 16-byte slot of the DESTINATION: one vector store; its 16 source bytes
+// are contiguous unless a line ends among them (one in four threads at 60 bases a line), then -- and on the ragged first and last
+// slot -- it walks byte by byte.  One pass, nothing reused: bound by HBM.
+typedef uint32_t u32x4_unaligned __attribute__((ext_vector_type(4), aligned(1)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(256) fasta_gather_kernel(const char *__restrict__ raw, char *__restrict__ dst, uint32_t n,
+                                                           uint32_t line_bases, uint32_t gap) {
+  const uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);  // bases before the first aligned slot
+  const long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // slot 0: the head
+  const long long x0l = slot == 0 ? 0 : (long long)head + 16 * (slot - 1);
+  if (x0l >= (long long)n) return;
+  const uint32_t x0 = (uint32_t)x0l;
+  const uint32_t cnt = slot == 0 ? min(head, n) : min(16u, n - x0);
+  if (cnt == 0) return;
+  const uint32_t line = x0 / line_bases, col = x0 - line * line_bases;
+  const char *s = raw + (size_t)x0 + (size_t)line * gap;
+  if (cnt == 16 && col + 16 <= line_bases) {
+    *(u32x4 *)(dst + x0) = *(const u32x4_unaligned *)s;
+    return;
+  }
+  uint32_t c = col;
+  for (uint32_t i = 0; i < cnt; ++i) {
+    dst[x0 + i] = *s++;
+    if (++c == line_bases) {
+      c = 0;
+      s += gap;
+    }
   }
 }
 

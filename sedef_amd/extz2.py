@@ -13,6 +13,8 @@ from .build import LIB_PATH
 
 NEG_INF = -0x40000000
 WANT_CIGAR, WANT_SCORE, WANT_EXT, WANT_ALL = 1, 2, 4, 7
+# strand bits of a resident task (include/sedef_hip.h: SDF_TASK_Q_RC / SDF_TASK_T_RC; align_batch_pairs only)
+TASK_Q_RC, TASK_T_RC = 0x10000, 0x20000
 
 TASK_DTYPE = np.dtype([("q_off", "<i8"), ("t_off", "<i8"), ("qlen", "<i4"), ("tlen", "<i4"),
                        ("w", "<i4"), ("zdrop", "<i4"), ("flag", "<i4"), ("pad_", "<i4")])
@@ -92,6 +94,23 @@ def load_library():
     L.sdf_extz2_batch_pairs_full.restype = C.c_int
     L.sdf_extz2_batch_pairs_full.argtypes = [C.c_void_p, C.POINTER(_Scoring), C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sdf_extz2_batch_pairs_view.restype = C.c_int
+    L.sdf_extz2_batch_pairs_view.argtypes = [C.c_void_p, C.POINTER(_Scoring), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.sdf_pool_append_fasta.restype = C.c_int
+    L.sdf_pool_append_fasta.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int32, C.c_int32, C.c_int,
+                                        C.POINTER(C.c_int64)]
+    L.sdf_pool_sync.restype = C.c_int
+    L.sdf_pool_sync.argtypes = [C.c_void_p]
+    L.sdf_anchors_batch_strand.restype = C.c_int
+    L.sdf_anchors_batch_strand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.sdf_anchors_batch_view_strand.restype = C.c_int
+    L.sdf_anchors_batch_view_strand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int,
+                                                C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_size_t)]
+    L.sdf_anchors_batch_more_strand.restype = C.c_int
+    L.sdf_anchors_batch_more_strand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t,
+                                                C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_size_t)]
     L.sdf_reserve.restype = C.c_int
     L.sdf_reserve.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32]
     L.sdf_device_bytes.restype = C.c_size_t
@@ -306,12 +325,46 @@ class Extz2Engine:
             self._check(self.lib.sdf_pool_upload(self.ctx, buf.ctypes.data, len(buf)))
         return int(self.lib.sdf_pool_bytes(self.ctx))
 
-    def align_batch_pairs(self, tasks, mat=None, gapo=40, gape=1, want=None, cigar_cap=None):
+    def pool_append_fasta(self, raw, n_bases, line_bases, line_bytes, reset=False):
+        """sdf_pool_append_fasta: one FASTA record's sequence lines as the file has them (bytes from the .fai offset: line_bases
+        bases, then line_bytes - line_bases line-end bytes, repeated) -> its bases behind the ones resident; the device drops
+        the line ends.  Returns the pool offset of the record's base 0."""
+        buf = np.frombuffer(raw, np.uint8)
+        self._keep = buf  # (unchanged until the next call that returns data)
+        off = C.c_int64(-1)
+        self._check(self.lib.sdf_pool_append_fasta(self.ctx, buf.ctypes.data if len(buf) else None, len(buf), int(n_bases),
+                                                   int(line_bases), int(line_bytes), int(bool(reset)), C.byref(off)))
+        return int(off.value)
+
+    def pool_sync(self):
+        """sdf_pool_sync: the uploads enqueued so far have left their host buffers."""
+        self._check(self.lib.sdf_pool_sync(self.ctx))
+
+    def pool_bytes(self):
+        return int(self.lib.sdf_pool_bytes(self.ctx))
+
+    def align_batch_pairs(self, tasks, mat=None, gapo=40, gape=1, want=None, cigar_cap=None, q_rc=None, t_rc=None, view=False):
         """sdf_extz2_batch_pairs (want=None: 16-byte records) / sdf_extz2_batch_pairs_full: q_off / t_off of the tasks are byte
-        offsets into the resident character pool; align_dna and the packing happen on the device."""
+        offsets into the resident character pool; align_dna and the packing happen on the device.  q_rc / t_rc: per task (or
+        one for all), that side is the reverse complement of its range (TASK_Q_RC / TASK_T_RC are or-ed into the flags).
+        view=True: sdf_extz2_batch_pairs_view, results copied out of the context's staging."""
         tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
+        if q_rc is not None or t_rc is not None:
+            tasks = tasks.copy()
+            for side, bit in ((q_rc, TASK_Q_RC), (t_rc, TASK_T_RC)):
+                if side is not None:
+                    tasks["flag"] |= np.where(np.broadcast_to(np.asarray(side, bool), tasks.shape), bit, 0).astype(np.int32)
         n = len(tasks)
         sc = _scoring(sedef_mat() if mat is None else mat, gapo, gape)
+        if view:
+            pb, pc, used = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+            self._check(self.lib.sdf_extz2_batch_pairs_view(self.ctx, C.byref(sc), tasks.ctypes.data, n, C.byref(pb), C.byref(pc),
+                                                            C.byref(used)))
+            out = np.frombuffer((C.c_char * (n * BRIEF_DTYPE.itemsize)).from_address(pb.value), BRIEF_DTYPE).copy() if n else \
+                np.zeros(0, BRIEF_DTYPE)
+            cig = np.frombuffer((C.c_char * (used.value * 4)).from_address(pc.value), np.uint32).copy() if used.value else \
+                np.zeros(0, np.uint32)
+            return out, cig
         if cigar_cap is None:
             cigar_cap = int((tasks["qlen"].astype(np.int64) + tasks["tlen"] + 2).sum()) + 1
         cig = np.zeros(cigar_cap, np.uint32)
@@ -345,9 +398,44 @@ class Extz2Engine:
         self._check(rc)
         return used.value
 
-    def anchors_batch(self, pairs, kmer=11):
+    def anchors_batch_resident(self, desc, kmer=11, r_rc=None, pool_bytes=None, mode="copy", keep=0):
+        """sdf_anchors_batch_strand / _view_strand / _more_strand (mode "copy" / "view" / "more") on the resident pool.  desc: an
+        ANCHOR_PAIR_DTYPE array whose offsets are pool bytes; r_rc: per pair, the reference range is read reverse-complemented
+        (None: all forward).  Returns (anchors, out_off) as arrays; `more` writes behind the first `keep` anchors of the staging."""
+        desc = np.ascontiguousarray(desc, dtype=ANCHOR_PAIR_DTYPE)
+        n = len(desc)
+        rc_arr = None if r_rc is None else np.ascontiguousarray(np.asarray(r_rc) != 0, dtype=np.uint8)
+        rc_p = None if rc_arr is None else rc_arr.ctypes.data
+        if pool_bytes is None:
+            pool_bytes = self.pool_bytes()
+        offs = np.zeros(n + 1, np.int64)
+        used = C.c_size_t(0)
+        if mode == "copy":
+            cap = 1 << 16
+            while True:
+                out = np.zeros(cap, ANCHOR_DTYPE)
+                rc = self.lib.sdf_anchors_batch_strand(self.ctx, desc.ctypes.data, rc_p, n, None, pool_bytes, kmer, out.ctypes.data,
+                                                       cap, offs.ctypes.data, C.byref(used))
+                if rc == -5:
+                    cap = used.value
+                    continue
+                self._check(rc)
+                return out[:used.value], offs
+        p = C.c_void_p()
+        if mode == "view":
+            self._check(self.lib.sdf_anchors_batch_view_strand(self.ctx, desc.ctypes.data, rc_p, n, None, pool_bytes, kmer,
+                                                               C.byref(p), offs.ctypes.data, C.byref(used)))
+        else:
+            self._check(self.lib.sdf_anchors_batch_more_strand(self.ctx, desc.ctypes.data, rc_p, n, pool_bytes, kmer, int(keep),
+                                                               C.byref(p), offs.ctypes.data, C.byref(used)))
+        out = np.frombuffer((C.c_char * (used.value * 16)).from_address(p.value), ANCHOR_DTYPE).copy() if used.value else \
+            np.zeros(0, ANCHOR_DTYPE)
+        return out, offs
+
+    def anchors_batch(self, pairs, kmer=11, r_rc=None):
         """GPU generate_anchors.  pairs: list of (query str, ref str, same_chr, delta).  Returns one list of
-        (q, r, l, has_u) per pair (include/sedef_hip.h: sdf_anchors_batch)."""
+        (q, r, l, has_u) per pair (include/sedef_hip.h: sdf_anchors_batch).  r_rc: per pair, the anchors are those of the
+        reverse complement of `ref str` (sdf_anchors_batch_strand)."""
         n = len(pairs)
         desc = np.zeros(n, ANCHOR_PAIR_DTYPE)
         chunks, off = [], 0
@@ -362,8 +450,14 @@ class Extz2Engine:
             out = np.zeros(cap, ANCHOR_DTYPE)
             offs = np.zeros(n + 1, np.int64)
             used = C.c_size_t(0)
-            rc = self.lib.sdf_anchors_batch(self.ctx, desc.ctypes.data, n, pool, len(pool), kmer, out.ctypes.data, cap,
-                                            offs.ctypes.data, C.byref(used))
+            if r_rc is None:
+                rc = self.lib.sdf_anchors_batch(self.ctx, desc.ctypes.data, n, pool, len(pool), kmer, out.ctypes.data, cap,
+                                                offs.ctypes.data, C.byref(used))
+            else:
+                strand = np.ascontiguousarray(np.asarray(r_rc) != 0, dtype=np.uint8)
+                assert len(strand) == n
+                rc = self.lib.sdf_anchors_batch_strand(self.ctx, desc.ctypes.data, strand.ctypes.data, n, pool, len(pool), kmer,
+                                                       out.ctypes.data, cap, offs.ctypes.data, C.byref(used))
             if rc == -5:
                 cap = used.value
                 continue

@@ -30,8 +30,8 @@ def build_library(force=False, verbose=False):
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-Wall",
-           "-Wno-unused-function"] + EXTRA_FLAGS + os.environ.get("SDF_HIPCC_FLAGS", "").split() + \
+    cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-Wall"] + \
+          EXTRA_FLAGS + os.environ.get("SDF_HIPCC_FLAGS", "").split() + \
           ["-o", LIB_PATH, os.path.join(SRC_DIR, "sdf_unity.hip")]
     if verbose:
         print(" ".join(cmd))

@@ -14,20 +14,9 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include "sdf_internal.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
-
-struct AnchorPairDev {
-  int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool
-  int32_t qlen, rlen;
-  int32_t same_chr, delta;  // near-diagonal filter of self comparisons (:67-69); same_chr: kPairSameChr | kPairRefRc
-  int64_t rk_start, qk_start;  // first global k-mer index of this pair's reference / query
-};
-
-// AnchorPairDev::same_chr holds two truth values (sdf_anchor_pair::same_chr is one, and stays one)
-constexpr int32_t kPairSameChr = 1;
-constexpr int32_t kPairRefRc = 2;  // the reference range is read reverse-complemented (sdf_anchors_batch_strand: r_rc)
 
 __device__ __forceinline__ int up(int c) { return (c >= 'a' && c <= 'z') ? c - 32 : c; }
 __device__ __forceinline__ bool is_upper(int c) { return c >= 'A' && c <= 'Z'; }
@@ -148,10 +137,6 @@ __global__ __launch_bounds__(256) void query_lookup_kernel(const AnchorPairDev *
     qpair[g] = pr;
   }
 }
-
-struct CandOut {
-  int32_t q, r, l, has_u;
-};
 
 template <bool RC>
 __global__ __launch_bounds__(256) void candidates_kernel(const AnchorPairDev *pairs, const char *pool, int k,

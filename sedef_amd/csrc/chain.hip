@@ -9,7 +9,8 @@
 // host restatement (sedef_amd/csrc/host/chain.cc), compared in tests/test_host_pipeline.py.
 #include <hip/hip_runtime.h>
 
-#include "sdf_internal.h"
+#include "extz2_geom.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
 
@@ -366,13 +367,6 @@ __device__ __forceinline__ void chain_sort_u64(unsigned long long *a, const int 
       __syncthreads();
     }
   }
-}
-
-__host__ __device__ inline size_t chain_wave_lds_bytes(int m) {
-  if (m <= 0) return 16;
-  int bits = 0;
-  for (unsigned v = (unsigned)m - 1u; v; v >>= 1) ++bits;
-  return (size_t)64 * m + (size_t)16 * ((size_t)2 << bits) + 3 * 48 * 4 + 64;
 }
 
 // grid: one workgroup of 64 lanes per entry of `which` (pair indices, those whose arrays fit `lds_cap`)

@@ -23,60 +23,21 @@
 // or where the band runs out).  Direction flags: bit blocks per stripe, block index relative to
 // the stripe's first row block, slot = t - T0 (traceback layout 4).
 //
-// Compiled inside sdf_unity.hip after extz2_wave.hip and extz2_general.hip (helpers, BestCell).
+// Sizes and the stripes' rows: extz2_geom.h (bstripe_*); the recurrence, score tables and BestCell order: extz2_dev.h; the
+// protocol between the stripes: stripe_sync.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "sdf_internal.h"
+#include "extz2_dev.h"
+#include "sdf_kernels.h"
+#include "stripe_sync.h"
 
 namespace sdf {
 
 #ifndef SDF_BS_FIRST_SLEEP
 #define SDF_BS_FIRST_SLEEP 100
 #endif
-
-struct BStripeGeom {
-  int nslot, nst, blocks_cap, col_len;
-  size_t flag_bytes;  // per stripe
-};
-__host__ __device__ inline BStripeGeom bstripe_geom(int qlen, int tlen, int w, int nreg) {
-  BStripeGeom g;
-  g.nslot = 128 * nreg;
-  const int t16 = (tlen + 15) / 16 * 16;
-  g.nst = (t16 + g.nslot - 1) / g.nslot;
-  const int rows = 2 * g.nslot + 2 * w < g.nslot + qlen ? 2 * g.nslot + 2 * w : g.nslot + qlen;
-  g.blocks_cap = (rows + 32 + 15) / 16 + 2;
-  g.col_len = g.blocks_cap * 16 + 64;
-  g.flag_bytes = (size_t)g.blocks_cap * nreg * 1024;
-  return g;
-}
-// First / last anti-diagonal of the stripe [T0, T1) (band not cut by its end).  The last one is the last on which it
-// has a computed cell; the first one is sixteen columns early: the score refresh runs in 16-cell strides from the band
-// START (:124-138), so it reaches up to fifteen cells past the last computed block -- into the first columns of a
-// stripe that computes nothing yet, and a cell computed later as part of a widened block may still hold that score.
-__host__ __device__ inline int bstripe_first_row(int T0, int w) {
-  const int t = T0 >= 16 ? T0 - 16 : 0;
-  return t > 2 * t - w ? t : 2 * t - w;
-}
-__host__ __device__ inline int bstripe_last_row(int T1, int qlen, int tlen, int w) {
-  int z = qlen + tlen - 2;
-  if (z > T1 + qlen - 2) z = T1 + qlen - 2;
-  if (z > 2 * T1 + w - 2) z = 2 * T1 + w - 2;
-  return z;
-}
-// bytes of a task's direction flags / of what lies behind them: a 64-byte record per stripe, then the edge columns
-__host__ __device__ inline size_t bstripe_dir_bytes(int qlen, int tlen, int w, int nreg) {
-  const BStripeGeom g = bstripe_geom(qlen, tlen, w, nreg);
-  return (size_t)g.nst * g.flag_bytes;
-}
-__host__ __device__ inline size_t bstripe_sync_bytes(int qlen, int tlen, int w, int nreg) {
-  const BStripeGeom g = bstripe_geom(qlen, tlen, w, nreg);
-  return (size_t)g.nst * 64 + (size_t)(g.nst > 1 ? g.nst - 1 : 0) * (size_t)g.col_len * 8;
-}
-__host__ __device__ inline size_t bstripe_lds_bytes(int w, int nreg) {
-  return ((size_t)2 * (size_t)(6 * 128 * nreg + 2 * w + 256) + 15) & ~(size_t)15;  // reversed-query window, byte pairs
-}
 
 struct BStripeRec {  // what a stripe leaves for the finishing kernel
   int32_t bestH, bestR, bestKey, bestT;
@@ -148,7 +109,7 @@ __global__ __launch_bounds__(64, 2) void extz2_bstripe_kernel(const PlanTask *__
       uint32_t v0 = (e0 >= 0 && e0 < qlen) ? pool_code16(qw, qn, qlen - 1 - e0, sc.wild) : 0u;
       uint32_t v1 = (e1 >= 0 && e1 < qlen) ? pool_code16(qw, qn, qlen - 1 - e1, sc.wild) : 0u;
       n_seen |= (v0 | v1) >> 8;
-      W[i] = qsel_pair(v0, v1);  // (selector form: extz2_wave.hip, SDF_SCORE2)
+      W[i] = qsel_pair(v0, v1);  // (selector form: extz2_dev.h, SDF_SCORE_PERM)
     }
 #pragma unroll
     for (int k = 0; k < NREG; ++k) {
@@ -312,7 +273,7 @@ __global__ __launch_bounds__(64, 2) void extz2_bstripe_kernel(const PlanTask *__
             vt1[k] = __builtin_amdgcn_perm(V[k], ps, 0x05040302u);
           }
 #pragma unroll
-          for (int k = 0; k < NREG; ++k) SDF_SCORE2(S[k], k, qc[k], false)
+          for (int k = 0; k < NREG; ++k) SDF_SCORE_PERM(S[k], k, qc[k], false)
           if (has_n) {  // (an N in the query: the selector picked 0xff)
 #pragma unroll
             for (int k = 0; k < NREG; ++k) {
@@ -485,7 +446,7 @@ __global__ __launch_bounds__(64, 2) void extz2_bstripe_kernel(const PlanTask *__
               vt1[k] &= keep;
             }
             unsigned z;
-            SDF_SCORE2(z, k, qc[k], has_n)
+            SDF_SCORE_PERM(z, k, qc[k], has_n)
             if (TOP) {
               sel_lo_below(S[k], z, b1 - 64 * k, lane);
               sel_hi_below(S[k], z, b0 - 64 * k, lane);
@@ -690,7 +651,7 @@ __global__ __launch_bounds__(64, 2) void extz2_bstripe_kernel(const PlanTask *__
         // scores: refreshed in 16-cell strides from lo0 (:124-138)
         {
           unsigned z;
-          SDF_SCORE2(z, k, qc[k], has_n)
+          SDF_SCORE_PERM(z, k, qc[k], has_n)
           const int ra = lo0 - tb, rbe = ra + ((hi0 - lo0) & ~15) + 16;
           sel_lo_rng(S[k], z, (ra + 1) >> 1, (rbe + 1) >> 1, lane);
           sel_hi_rng(S[k], z, ra >> 1, rbe >> 1, lane);

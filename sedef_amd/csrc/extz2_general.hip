@@ -18,33 +18,10 @@
 // kernel (extz2_wave.hip) does not take.
 #include <hip/hip_runtime.h>
 
-#include "sdf_internal.h"
+#include "extz2_dev.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
-
-struct BestCell {
-  int32_t H, r, key, t;
-};
-
-// a beats b: larger H; then earlier anti-diagonal; then the reference's in-row scan order
-__device__ __forceinline__ bool beats(const BestCell &a, const BestCell &b) {
-  if (a.H != b.H) return a.H > b.H;
-  if (a.r != b.r) return a.r < b.r;
-  return a.key < b.key;
-}
-
-__device__ __forceinline__ BestCell wave_best(BestCell c) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    BestCell o;
-    o.H = __shfl_xor(c.H, off);
-    o.r = __shfl_xor(c.r, off);
-    o.key = __shfl_xor(c.key, off);
-    o.t = __shfl_xor(c.t, off);
-    if (beats(o, c)) c = o;
-  }
-  return c;
-}
 
 template <int BS>
 __device__ __forceinline__ BestCell block_best(BestCell c, BestCell *red) {
@@ -60,13 +37,6 @@ __device__ __forceinline__ BestCell block_best(BestCell c, BestCell *red) {
     __syncthreads();
   }
   return c;  // valid in thread 0
-}
-
-__device__ __forceinline__ uint32_t packed_code(const uint32_t *codes, const uint32_t *nmask, int k,
-                                                uint32_t wild) {
-  uint32_t c = (codes[k >> 4] >> ((k & 15) * 2)) & 3u;
-  uint32_t n = (nmask[k >> 5] >> (k & 31)) & 1u;
-  return n ? wild : c;
 }
 
 // GLOBAL: the arena and H[] of tasks too long for LDS (> ~14k) live in an HBM scratch slab per workgroup;
@@ -102,8 +72,8 @@ __global__ __launch_bounds__(BS) void extz2_general_kernel(
   {
     const uint32_t *tw = pool + tk.t_word, *tn = tw + (tlen + 15) / 16;
     const uint32_t *qw = pool + tk.q_word, *qn = qw + (qlen + 15) / 16;
-    for (int k = tid; k < tlen; k += BS) SF[k] = (uint8_t)packed_code(tw, tn, k, sc.wild);
-    for (int k = tid; k < qlen; k += BS) QR[k] = (uint8_t)packed_code(qw, qn, qlen - 1 - k, sc.wild);
+    for (int k = tid; k < tlen; k += BS) SF[k] = (uint8_t)pool_code<0u>(tw, tn, k, sc.wild);
+    for (int k = tid; k < qlen; k += BS) QR[k] = (uint8_t)pool_code<0u>(qw, qn, qlen - 1 - k, sc.wild);
   }
   __syncthreads();
 
@@ -467,26 +437,17 @@ __global__ __launch_bounds__(BS) void extz2_general_kernel(
   }
 }
 
-template __global__ void extz2_general_kernel<64, false, false>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-template __global__ void extz2_general_kernel<256, false, false>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-template __global__ void extz2_general_kernel<1024, false, false>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-template __global__ void extz2_general_kernel<1024, true, false>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-template __global__ void extz2_general_kernel<256, true, false>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-template __global__ void extz2_general_kernel<1024, false, true>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-template __global__ void extz2_general_kernel<1024, true, true>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-template __global__ void extz2_general_kernel<256, false, true>(const PlanTask *, const int32_t *, const uint32_t *,
-                                                                ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
-
-size_t general_lds_bytes(int qlen, int tlen) {
-  const size_t T16 = (size_t)(tlen + 15) / 16 * 16, Q16 = (size_t)(qlen + 15) / 16 * 16;
-  return 6 * T16 + Q16 + 16 + 4 * T16 + 16 * sizeof(BestCell) + 16;
-}
+#define SDF_GENERAL_INST(BS, GLOBAL, PLAIN)                                                                            \
+  template __global__ void extz2_general_kernel<BS, GLOBAL, PLAIN>(const PlanTask *, const int32_t *, const uint32_t *, \
+                                                                   ScoreK, uint8_t *, sdf_result *, uint8_t *, size_t);
+SDF_GENERAL_INST(64, false, false)
+SDF_GENERAL_INST(256, false, false)
+SDF_GENERAL_INST(1024, false, false)
+SDF_GENERAL_INST(1024, true, false)
+SDF_GENERAL_INST(256, true, false)
+SDF_GENERAL_INST(1024, false, true)
+SDF_GENERAL_INST(1024, true, true)
+SDF_GENERAL_INST(256, false, true)
+#undef SDF_GENERAL_INST
 
 }  // namespace sdf

@@ -26,27 +26,12 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include "sdf_internal.h"
+#include "extz2_geom.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
 
-struct LaneRec {      // what the host uploads per task of the batch (16 bytes; invalid: flag = 0xffff)
-  uint32_t q_word, t_word;  // word offsets of the packed sequences in the pool
-  uint32_t out_idx;
-  uint8_t qlen_m1, tlen_m1;  // lengths - 1 (1 .. 256)
-  uint16_t flag;             // SDF_FLAG_SCORE_ONLY | SDF_FLAG_REV_CIGAR
-};
-
-constexpr int kLaneMaxLen = 256;      // longest sequence of a lane task
-constexpr int kLaneMaxCells = 16384;  // most cells of a lane task: a lane alone on its row costs ~100 cycles per cell
-
-// direction flags of a task: per column tile of 16 target positions one 8-byte record per query position (four 16-bit flag planes: a bit per
-// cell), the records of a tile back to back -- a lane writes its region front to back, 8 bytes per row of a tile
-__host__ __device__ inline size_t lane_dir_bytes(int qlen, int tlen) { return (size_t)((tlen + 15) >> 4) * (size_t)qlen * 8; }
-// launch classes by query length: the LDS of a wavefront is 128 bytes per query position of its longest task
-__host__ __device__ inline int lane_class(int qlen) { return qlen <= 32 ? 0 : qlen <= 64 ? 1 : qlen <= 128 ? 2 : 3; }
-__host__ __device__ inline size_t lane_lds_bytes(int cls) { return (size_t)128 * (size_t)((32 << cls) + 2); }
-
+// (LaneRec: sdf_kernels.h; the limits, flag bytes and launch classes of a lane task: extz2_geom.h)
 __device__ __forceinline__ int lane_wave_max(int v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
@@ -114,7 +99,6 @@ __global__ __launch_bounds__(256) void lane_plan_kernel(const LaneRec *__restric
 // a histogram, one scan over the BINS (count, staging words, flag bytes: three sums at once) and a pass that gives every
 // task its rank in its bin by an atomic add and writes its plan record.  Tasks of a bin are interchangeable (same matrix
 // size), so their order inside the bin does not matter to anything but the layout of the workspace.
-constexpr int kLaneKeyBits = 19, kLaneBins = 1 << kLaneKeyBits, kLaneScanBlock = 1024;
 __device__ __forceinline__ uint32_t lane_key(const LaneRec &r) {
   return ((uint32_t)lane_class(r.qlen_m1 + 1) << 17) | ((r.flag & SDF_FLAG_SCORE_ONLY) ? 1u << 16 : 0u) | ((uint32_t)r.qlen_m1 << 8) | r.tlen_m1;
 }

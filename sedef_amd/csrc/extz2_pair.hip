@@ -17,24 +17,22 @@
 //   * direction flags leave as 8 bytes per lane per task per 16 rows (four 16-bit row masks),
 //     0.5 B per slot as before.
 //
-// This file is compiled inside sdf_unity.hip after extz2_wave.hip and uses its helpers
-// (pk_*, SDF_OPQ, SDF_CORE).  Special rows (first rows, captured carries, the sign-extension
-// artefact of the reference's carry-in) are data dependent: if either task needs the general row,
-// both take it -- it is exact for every row.
+// Special rows (first rows, captured carries, the sign-extension artefact of the reference's
+// carry-in) are data dependent: if either task needs the general row, both take it -- it is exact
+// for every row.  The recurrence (SDF_CORE), the packed forms and the score permute are in
+// extz2_dev.h, the sizes of the LDS windows and the rows two tasks share in extz2_geom.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "sdf_internal.h"
+#include "extz2_dev.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
 
 // byte code of a base: 0..3, or 0x80|wild for N
-__device__ __forceinline__ uint32_t pool_code8(const uint32_t *codes, const uint32_t *nmask, int k,
-                                               uint32_t wild) {
-  const uint32_t c = (codes[k >> 4] >> ((k & 15) * 2)) & 3u;
-  const uint32_t n = (nmask[k >> 5] >> (k & 31)) & 1u;
-  return n ? (0x80u | wild) : c;
+__device__ __forceinline__ uint32_t pool_code8(const uint32_t *codes, const uint32_t *nmask, int k, uint32_t wild) {
+  return pool_code<0x80u>(codes, nmask, k, wild);
 }
 
 // lanes [a, b) (a >= 0)
@@ -59,55 +57,18 @@ __device__ __forceinline__ unsigned sign_smear(unsigned c) {
   return ((c & 0x8000u) ? 0xff00u : 0u) | ((c & 0x80000000u) ? 0xff000000u : 0u);
 }
 
-// entries of the LDS sequence windows: the whole (padded) sequence when it is short, else the window slots plus
-// 1024 entries of slack (multiples of 4 keep the query window dword aligned behind the target window)
-__host__ __device__ inline int pair_tcap(int tlen, int nreg) {
-  const int whole = (tlen + 15) / 16 * 16 + 64 * nreg + 32, win = 64 * nreg + 1024 + 64;
-  return whole < win ? whole : win;
-}
-__host__ __device__ inline int pair_qcap(int qlen, int nreg) {
-  const int whole = qlen + 64 * nreg + 36, win = 64 * nreg + 1024 + 68;
-  return whole < win ? whole : win;
-}
-
-// Fresh (score + 2(q+e)) << 8 of the lane's cell of both tasks: ONE byte permute.  The lane keeps, per window register, a
+// SDF_SCORE_PERM (extz2_dev.h) as this kernel uses it, with the window entry itself as the selector:
+// fresh (score + 2(q+e)) << 8 of the lane's cell of both tasks: ONE byte permute.  The lane keeps, per window register, a
 // table of four score bytes per task -- its target base against query base 0..3 (an N in the target: the wildcard's score
 // four times) -- and the query window holds the row's bases as the permute's selector: byte 1 = task A's base (a byte of
 // TA), byte 3 = 4 + task B's (a byte of TB), bytes 0 and 2 = 0x0c (zero): the result is 0, zA, 0, zB.  An N in the query
 // selects 0xff -- a negative half, patched to the wildcard's score where the sequences hold any N at all (WITH_N).
 // (Until the end of round 6: xor, min, multiply-add per cell and row.  The kernel issues a vector instruction on 98 % of
 // its SIMD cycles at four cycles each: what counts is their number -- profiles/r06_pair_kernel_pmc.txt.)
-#define SDF_PFRESH(z, k, qword, WITH_N)                                 \
-  {                                                                     \
-    z = __builtin_amdgcn_perm(TB[k], TA[k], (qword));                   \
-    if (WITH_N) {                                                       \
-      unsigned nn_ = pk_ashr15(z);                                      \
-      SDF_OPQ(nn_);                                                     \
-      z = (z_wild & nn_) | (z & ~nn_);                                  \
-    }                                                                   \
-  }
+
 // a query window entry from the two tasks' byte codes (0..3, N: bit 7)
 __device__ __forceinline__ uint32_t pair_qsel(uint32_t ca, uint32_t cb) {
   return 0x000c000cu | (((ca & 0x80u) ? 0xffu : ca) << 8) | (((cb & 0x80u) ? 0xffu : cb + 4u) << 24);
-}
-
-// Mixed pairs (round 4): the band schedule of the reference, lo0 = max(0, r - qlen + 1, (r - w + 1) >> 1), hi0 = min(tlen - 1, r,
-// (r + w) >> 1) (extern/ksw2_extz2_sse.cc:101-115), depends on the lengths only where the r - qlen + 1 / tlen - 1 clips bite:
-// on the last ~w anti-diagonals of a task.  Two tasks of the same (w, flag) but different lengths therefore share every lane
-// predicate and every scalar decision up to the first row at which a clip bites for either of them.
-// pair_clip_free: the last anti-diagonal r such that on ALL rows 0..r neither clip changes the band of a (qlen, tlen, w)
-// task AND the top cell is not yet the target's last column (min(r, (r + w) >> 1) < tlen - 1: the row code tests that too).
-__host__ __device__ inline int pair_clip_free(int qlen, int tlen, int w) {
-  const int a = 2 * qlen - w - 2;  // r - qlen + 1 <= (r - w + 1) >> 1 for every r up to here (and r - qlen + 1 <= 0 while that is negative)
-  const int b = tlen - 2 > 2 * tlen - w - 3 ? tlen - 2 : 2 * tlen - w - 3;  // min(r, (r + w) >> 1) < tlen - 1
-  return a < b ? a : b;
-}
-// rows [0, shared) of two tasks with band w run side by side in one wavefront: a multiple of 16 (the kernel works in
-// 16-row blocks), and row `shared` itself is still clip-free for both (a row looks one row ahead for its top cell)
-__host__ __device__ inline int pair_shared_rows(int qa, int ta, int qb, int tb, int w) {
-  const int ca = pair_clip_free(qa, ta, w), cb = pair_clip_free(qb, tb, w);
-  const int c = ca < cb ? ca : cb;
-  return c >= 16 ? c / 16 * 16 : 0;
 }
 
 // STREAM: the sequences do not fit the LDS windows whole (long tasks); without it the window code compiles out.
@@ -413,7 +374,7 @@ __device__ __forceinline__ void pair_body(
         if (b_ > 0 && a_ < 64) {
           const unsigned qc = W[cq - we0 + 64 * k + lane];
           unsigned z;
-          SDF_PFRESH(z, k, qc, has_n)
+          SDF_SCORE_PERM(z, k, qc, has_n)
           if (a_ <= 0 && b_ >= 64) S[k] = z;
           else if (lane_in(lane, a_ < 0 ? 0 : a_, b_)) S[k] = z;
         }
@@ -516,14 +477,14 @@ __device__ __forceinline__ void pair_body(
         const int b_ = rbe - 64 * k;
         if (STEADY) {
           unsigned z;
-          SDF_PFRESH(z, k, qcur[k], HASN)
+          SDF_SCORE_PERM(z, k, qcur[k], HASN)
           if (NREG == 1) S[0] = in_mask(lane_mask(ra, b_)) ? z : S[0];
           else if (k == 0) S[0] = in_mask(~0ull << ra) ? z : S[0];  // (steady: 0 <= ra < 32 -- one scalar shift, not lane_mask's six)
           else if (k == KT) S[k] = in_mask(b_ <= 0 ? 0ull : ~0ull >> (64 - (b_ < 64 ? b_ : 64))) ? z : S[k];
           else S[k] = z;
         } else if (b_ > 0) {
           unsigned z;
-          SDF_PFRESH(z, k, qcur[k], HASN)
+          SDF_SCORE_PERM(z, k, qcur[k], HASN)
           if (k == 0) {
             if (b_ >= 64) S[0] = lane >= ra ? z : S[0];
             else S[0] = lane_in(lane, ra, b_) ? z : S[0];
@@ -993,19 +954,5 @@ SDF_PAIR_MIXED_INST(6)
 SDF_PAIR_MIXED_INST(8)
 SDF_PAIR_MIXED_INST(9)
 #undef SDF_PAIR_MIXED_INST
-
-// LDS of a mixed pair: the windows of (max qlen, max tlen) and, behind them, the five state registers of half B per lane
-size_t pair_mixed_lds_bytes(int qmax, int tmax, int nreg) {
-  return ((2 * (size_t)pair_tcap(tmax, nreg) + 4 * (size_t)pair_qcap(qmax, nreg) + 15) & ~(size_t)15) + (size_t)5 * nreg * 256;
-}
-
-// the windows hold the sequences whole?
-bool pair_fits_whole(int qlen, int tlen, int nreg) {
-  return pair_tcap(tlen, nreg) == (tlen + 15) / 16 * 16 + 64 * nreg + 32 && pair_qcap(qlen, nreg) == qlen + 64 * nreg + 36;
-}
-
-size_t pair_lds_bytes(int qlen, int tlen, int nreg) {
-  return 2 * (size_t)pair_tcap(tlen, nreg) + 4 * (size_t)pair_qcap(qlen, nreg);
-}
 
 }  // namespace sdf

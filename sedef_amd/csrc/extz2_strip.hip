@@ -27,26 +27,11 @@
 // column (v): score, mte (:226-267).
 #include <hip/hip_runtime.h>
 
-#include "sdf_internal.h"
+#include "extz2_dev.h"
+#include "sdf_kernels.h"
+#include "stripe_sync.h"
 
 namespace sdf {
-
-// columns per lane: 8 (a block of 512 columns per wavefront), or 4 for chains of few wavefronts -- a step of four cells
-// is half as long, and a chain of blocks runs at the pace of its steps
-constexpr int kStripMaxT = 512;        // widest target of the one-wavefront kernel: one block of 8 columns per lane
-constexpr int kStripChainMaxT = 65536;  // ... of a chain of wavefronts, one per block (extz2_strip_chain_kernel): the block index
-                                       // of a launch entry has eight bits (256 blocks of 256 columns); the stage's tasks end at 60 kb
-
-__host__ __device__ inline int strip_blocks(int tlen, int cols = 8) { return (tlen + 64 * cols - 1) / (64 * cols); }
-__host__ __device__ inline int strip_records(int qlen, int cols) {  // records per block: one per step, or per pair of steps
-  return cols == 4 ? (qlen + 64) >> 1 : qlen + 63;
-}
-__host__ __device__ inline size_t strip_dir_bytes(int qlen, int tlen, int cols = 8, bool solo = false) {
-  return (size_t)strip_blocks(tlen, cols) * (size_t)strip_records(qlen, cols) * (solo ? 256 : 512);
-}
-__host__ __device__ inline size_t strip_lds_bytes(int qlen, int tlen) {
-  return strip_blocks(tlen) > 1 ? ((size_t)(qlen + 66) * 4 + 15) & ~(size_t)15 : 16;
-}
 
 // packed code of position k of tasks A | B << 16: 0..3, N = 4; 0 beyond a task's end
 __device__ __forceinline__ unsigned strip_code2(const uint32_t *wa, const uint32_t *na, int lena, const uint32_t *wb,
@@ -371,10 +356,6 @@ __global__ __launch_bounds__(64) void extz2_strip_kernel(const PlanTask *__restr
 // finished; a wait that runs out of polls abandons both tasks (stripe_abandon) and the batch call runs them again.
 // A block's partial exact-H values (the first row's sum of u; the last column's running H) are added up through three
 // words per task behind the edge columns.
-__host__ __device__ inline size_t strip_chain_sync_bytes(int qmax, int tmax, int cols) {
-  return ((size_t)(strip_blocks(tmax, cols) - 1) * (size_t)(qmax + 64) * 4 + 64 + 255) & ~(size_t)255;
-}
-
 __global__ __launch_bounds__(64) void strip_chain_init_kernel(const PlanTask *__restrict__ plan, const int32_t *__restrict__ order,
                                                               uint8_t *__restrict__ dirbase) {
   const int32_t entry = order[blockIdx.x];

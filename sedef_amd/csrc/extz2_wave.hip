@@ -33,237 +33,13 @@
 
 #include <type_traits>
 
-#include "sdf_internal.h"
+#include "extz2_dev.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
 
-// lane mask with bits [lo, hi) set (0 <= lo, hi; clamped to 64)
-__device__ __forceinline__ unsigned long long lane_range(int lo, int hi) {
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > 64 ? 64 : hi;
-  if (hi <= lo) return 0ull;
-  const unsigned long long top = hi >= 64 ? ~0ull : ((1ull << hi) - 1ull);
-  return top & ~((1ull << lo) - 1ull);
-}
-
-// dst half <- src half where the lane's bit in `mask` is set (SDWA keeps the other half)
-__device__ __forceinline__ void sel_lo16(unsigned &dst, unsigned src, unsigned long long mask) {
-  asm volatile(
-      "s_mov_b64 vcc, %2\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\ts_nop 0"
-      : "+v"(dst)
-      : "v"(src), "s"(mask)
-      : "vcc");
-}
-__device__ __forceinline__ void sel_hi16(unsigned &dst, unsigned src, unsigned long long mask) {
-  asm volatile(
-      "s_mov_b64 vcc, %2\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1\n\ts_nop 0"
-      : "+v"(dst)
-      : "v"(src), "s"(mask)
-      : "vcc");
-}
-
-// value of slot `s` (0..127) of a packed register, as its 16-bit half
-__device__ __forceinline__ unsigned slot_half(unsigned reg, int s) {
-  const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)reg, s >> 1);
-  return (s & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
-// S half <- z half in the lanes where `thr <= lane` (GE) or `lane < thr` (LT); the compare writes
-// VCC and the SDWA select consumes it (no wait state needed between them on gfx9).
-__device__ __forceinline__ void sel_lo_ge(unsigned &dst, unsigned src, int thr, int lane) {
-  asm volatile(
-      "v_cmp_le_i32 vcc, %2, %3\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\ts_nop 0"
-      : "+v"(dst) : "v"(src), "s"(thr), "v"(lane) : "vcc");
-}
-__device__ __forceinline__ void sel_hi_ge(unsigned &dst, unsigned src, int thr, int lane) {
-  asm volatile(
-      "v_cmp_le_i32 vcc, %2, %3\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1\n\ts_nop 0"
-      : "+v"(dst) : "v"(src), "s"(thr), "v"(lane) : "vcc");
-}
-__device__ __forceinline__ void sel_lo_lt(unsigned &dst, unsigned src, int thr, int lane) {
-  asm volatile(
-      "v_cmp_gt_i32 vcc, %2, %3\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\ts_nop 0"
-      : "+v"(dst) : "v"(src), "s"(thr), "v"(lane) : "vcc");
-}
-__device__ __forceinline__ void sel_hi_lt(unsigned &dst, unsigned src, int thr, int lane) {
-  asm volatile(
-      "v_cmp_gt_i32 vcc, %2, %3\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1\n\ts_nop 0"
-      : "+v"(dst) : "v"(src), "s"(thr), "v"(lane) : "vcc");
-}
-
-// two-sided: lanes in [lo, hi)
-__device__ __forceinline__ void sel_lo_rng(unsigned &dst, unsigned src, int lo, int hi, int lane) {
-  unsigned t;
-  asm volatile(
-      "v_subrev_u32 %1, %3, %5\n\t"
-      "v_cmp_gt_u32 vcc, %4, %1\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\ts_nop 0"
-      : "+v"(dst), "=&v"(t) : "v"(src), "s"(lo), "s"(hi > lo ? hi - lo : 0), "v"(lane) : "vcc");
-}
-__device__ __forceinline__ void sel_hi_rng(unsigned &dst, unsigned src, int lo, int hi, int lane) {
-  unsigned t;
-  asm volatile(
-      "v_subrev_u32 %1, %3, %5\n\t"
-      "v_cmp_gt_u32 vcc, %4, %1\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1\n\ts_nop 0"
-      : "+v"(dst), "=&v"(t) : "v"(src), "s"(lo), "s"(hi > lo ? hi - lo : 0), "v"(lane) : "vcc");
-}
-
-// (the same with the range as start + length: the caller has the length in a register already)
-__device__ __forceinline__ void sel_lo_len(unsigned &dst, unsigned src, int lo, int len, int lane) {
-  unsigned t;
-  asm volatile(
-      "v_subrev_u32 %1, %3, %5\n\t"
-      "v_cmp_gt_u32 vcc, %4, %1\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\ts_nop 0"
-      : "+v"(dst), "=&v"(t) : "v"(src), "s"(lo), "s"(len), "v"(lane) : "vcc");
-}
-__device__ __forceinline__ void sel_hi_len(unsigned &dst, unsigned src, int lo, int len, int lane) {
-  unsigned t;
-  asm volatile(
-      "v_subrev_u32 %1, %3, %5\n\t"
-      "v_cmp_gt_u32 vcc, %4, %1\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1\n\ts_nop 0"
-      : "+v"(dst), "=&v"(t) : "v"(src), "s"(lo), "s"(len), "v"(lane) : "vcc");
-}
-
-// (the range [0, bound): one signed compare)
-__device__ __forceinline__ void sel_lo_below(unsigned &dst, unsigned src, int bound, int lane) {
-  asm volatile(
-      "v_cmp_gt_i32 vcc, %2, %3\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\ts_nop 0"
-      : "+v"(dst) : "v"(src), "s"(bound), "v"(lane) : "vcc");
-}
-__device__ __forceinline__ void sel_hi_below(unsigned &dst, unsigned src, int bound, int lane) {
-  asm volatile(
-      "v_cmp_gt_i32 vcc, %2, %3\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1\n\ts_nop 0"
-      : "+v"(dst) : "v"(src), "s"(bound), "v"(lane) : "vcc");
-}
-
-// both halves of one register: lo half where thr_lo <= lane, hi half where thr_hi <= lane
-__device__ __forceinline__ void sel2_ge(unsigned &dst, unsigned src, int thr_lo, int thr_hi, int lane) {
-  asm volatile(
-      "v_cmp_le_i32 vcc, %2, %4\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\t"
-      "v_cmp_le_i32 vcc, %3, %4\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1"
-      : "+v"(dst) : "v"(src), "s"(thr_lo), "s"(thr_hi), "v"(lane) : "vcc");
-}
-__device__ __forceinline__ void sel2_lt(unsigned &dst, unsigned src, int thr_lo, int thr_hi, int lane) {
-  asm volatile(
-      "v_cmp_gt_i32 vcc, %2, %4\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 "
-      "src1_sel:WORD_0\n\t"
-      "v_cmp_gt_i32 vcc, %3, %4\n\t"
-      "v_cndmask_b32_sdwa %0, %0, %1, vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 "
-      "src1_sel:WORD_1"
-      : "+v"(dst) : "v"(src), "s"(thr_lo), "s"(thr_hi), "v"(lane) : "vcc");
-}
-
-__device__ __forceinline__ uint32_t pool_code16(const uint32_t *codes, const uint32_t *nmask, int k,
-                                                uint32_t wild) {
-  const uint32_t c = (codes[k >> 4] >> ((k & 15) * 2)) & 3u;
-  const uint32_t n = (nmask[k >> 5] >> (k & 31)) & 1u;
-  return n ? (0xff00u | wild) : c;
-}
-
-// ---- fresh scores as byte permutes (end of round 6; extz2_pair.hip: SDF_PFRESH has the story) ----------------------------
-// The kernels whose lanes hold TWO ADJACENT target positions per register (wave, stripe, banded stripe): a table of four score
-// bytes per position -- against query base 0..3; an N in the target: the wildcard's score four times --, the row's two query
-// bases as a selector (byte 1 = base of the even position: a byte of the first table; byte 3 = 4 + base of the odd one: a byte
-// of the second; bytes 0, 2 = 0x0c: zero; an N: 0xff, patched afterwards where the sequences hold any N).
-// code: what pool_code16 returns (0..3, N: 0xff00 | wild)
-__device__ __forceinline__ unsigned score_table(const unsigned code, const unsigned mis4, const unsigned delta, const unsigned wild4) {
-  return (code & 0xff00u) ? wild4 : mis4 ^ (delta << (8u * code));
-}
-// an entry of a query window of byte pairs (W[i] = bases of window positions i, i + 1) in selector form
-__device__ __forceinline__ uint16_t qsel_pair(const uint32_t v0, const uint32_t v1) {
-  return (uint16_t)(((v0 & 0xff00u) ? 0xffu : v0) | (((v1 & 0xff00u) ? 0xffu : v1 + 4u) << 8));
-}
-// the two selector bytes of a window entry -> the permute's selector 0x0c, s0, 0x0c, s1
-__device__ __forceinline__ unsigned qsel_spread(const unsigned w16) {
-  return __builtin_amdgcn_perm(0x0c0c0c0cu, w16, 0x01040004u);
-}
-#define SDF_SCORE2(z, k, qs, WITH_N)                                    \
-  {                                                                     \
-    z = __builtin_amdgcn_perm(TB[k], TA[k], (qs));                      \
-    if (WITH_N) {                                                       \
-      unsigned nn_ = pk_ashr15(z);                                      \
-      SDF_OPQ(nn_);                                                     \
-      z = (z_wild & nn_) | (z & ~nn_);                                  \
-    }                                                                   \
-  }
-
-// One anti-diagonal step of the recurrence for packed register k (two cells per lane), in the
-// <<8 int16 domain; appends the four direction flags to the accumulators.
-// Round 5: three of its differences are 32-bit subtracts (v_sub_u32: ~2.3 cycles against ~4.2 for v_pk_sub_i16,
-// profiles/r05_ubench_valu_ops.txt).  They are exact on the packed halves for EVERY cell, the artefact cells of a band's
-// edges included, because they never borrow: the score register only ever holds fresh scores z0 = (score + 2 (q + e)) << 8
-// with q <= z0 >> 8 <= 127 (sdf_api.hip: core32_ok -- other scorings run on the general kernel), z1 = max_i(z0, a) is z0 or a
-// larger non-negative value, zb = max_i(z1, b) likewise, and z3 = min_u(max_u(z1, b), cap) >= min(z1, cap) >= q << 8.  The
-// other sums and differences involve u and v, which ARE negative in those cells: they keep the packed forms.
-#define SDF_CORE(k)                                                     \
-  {                                                                     \
-    const unsigned a_ = pk_add(xt1[k], vt1[k]);                         \
-    const unsigned bb_ = pk_add(Y[k], U[k]);                            \
-    const unsigned z0_ = S[k];                                          \
-    const unsigned z1_ = pk_maxi(z0_, a_);                              \
-    const unsigned fa_ = z1_ - z0_; /* != 0 <=> a > z (signed); no borrow: z1 >= z0 >= 0 */ \
-    const unsigned zb_ = pk_maxi(z1_, bb_);                             \
-    const unsigned fb_ = zb_ - z1_; /* != 0 <=> b > max(z,a); no borrow */ \
-    const unsigned z2_ = pk_maxu(z1_, bb_);                             \
-    const unsigned z3_ = pk_minu(z2_, capv);                            \
-    const unsigned un_ = pk_sub(z3_, vt1[k]);                           \
-    const unsigned vn_ = pk_sub(z3_, U[k]);                             \
-    const unsigned zq_ = z3_ - qv; /* no borrow: z3 >= q << 8 */         \
-    const unsigned a2_ = pk_sub(a_, zq_);                               \
-    const unsigned b2_ = pk_sub(bb_, zq_);                              \
-    const unsigned xn_ = pk_maxi(a2_, 0u);                              \
-    const unsigned yn_ = pk_maxi(b2_, 0u);                              \
-    U[k] = un_;                                                         \
-    V[k] = vn_;                                                         \
-    X[k] = xn_;                                                         \
-    Y[k] = yn_;                                                         \
-    Fa[k] = shl1_or(Fa[k], pk_nonzero(fa_));                            \
-    Fb[k] = shl1_or(Fb[k], pk_nonzero(fb_));                            \
-    Fx[k] = shl1_or(Fx[k], pk_nonzero(xn_));                            \
-    Fy[k] = shl1_or(Fy[k], pk_nonzero(yn_));                            \
-  }
-
 // fresh (score + 2(q+e)) << 8 of the two cells of a lane: two byte permutes (the window entry -> selector, selector -> scores)
-#define SDF_FRESH(z, k, qraw) SDF_SCORE2(z, k, qsel_spread(qraw), has_n)
-
-// entries of the LDS sequence windows: the whole (padded) sequence when it is short, else the window slots plus
-// 1024 entries of slack (see extz2_pair.hip)
-__host__ __device__ inline int wave_tcap(int tlen, int nreg) {
-  const int whole = (tlen + 15) / 16 * 16 + 128 * nreg + 32, win = 128 * nreg + 1024 + 64;
-  return whole < win ? whole : win;
-}
-__host__ __device__ inline int wave_qcap(int qlen, int nreg) {
-  const int whole = qlen + 128 * nreg + 36, win = 128 * nreg + 1024 + 68;
-  return whole < win ? whole : win;
-}
+#define SDF_FRESH(z, k, qraw) SDF_SCORE_PERM(z, k, qsel_spread(qraw), has_n)
 
 // STREAM: the sequences do not fit the LDS windows whole (long tasks); without it the window code compiles out.
 template <int NREG, bool STREAM>
@@ -312,7 +88,7 @@ __global__ __launch_bounds__(64, NREG <= 2 ? 6 : NREG <= 4 ? 4 : NREG <= 6 ? 3 :
       const int e0 = from + i - 32, e1 = e0 + 1;  // QR indices; QR[e] = query[qlen-1-e], 0 outside
       uint32_t v0 = (e0 >= 0 && e0 < qlen) ? pool_code16(qw, qn, qlen - 1 - e0, sc.wild) : 0u;
       uint32_t v1 = (e1 >= 0 && e1 < qlen) ? pool_code16(qw, qn, qlen - 1 - e1, sc.wild) : 0u;
-      W[i] = qsel_pair(v0, v1);  // (selector form: SDF_SCORE2)
+      W[i] = qsel_pair(v0, v1);  // (selector form: SDF_SCORE_PERM)
     }
   };
 
@@ -929,38 +705,17 @@ __global__ __launch_bounds__(64, NREG <= 2 ? 6 : NREG <= 4 ? 4 : NREG <= 6 ? 3 :
 #undef tt0
 #undef we0
 
-template __global__ void extz2_wave_kernel<1, false>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<1, true>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<2, false>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<2, true>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<3, false>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<3, true>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<6, false>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<6, true>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<4, false>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<4, true>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<8, false>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-template __global__ void extz2_wave_kernel<8, true>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK,
-                                                     uint8_t *, sdf_result *);
-
-// the windows hold the sequences whole?
-bool wave_fits_whole(int qlen, int tlen, int nreg) {
-  return wave_tcap(tlen, nreg) == (tlen + 15) / 16 * 16 + 128 * nreg + 32 && wave_qcap(qlen, nreg) == qlen + 128 * nreg + 36;
-}
-
-size_t wave_lds_bytes(int qlen, int tlen, int nreg) {
-  return 2 * (size_t)wave_tcap(tlen, nreg) + 2 * (size_t)wave_qcap(qlen, nreg);
-}
+#define SDF_WAVE_INST(N)                                                                                                  \
+  template __global__ void extz2_wave_kernel<N, false>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, \
+                                                       sdf_result *);                                                      \
+  template __global__ void extz2_wave_kernel<N, true>(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *,  \
+                                                      sdf_result *);
+SDF_WAVE_INST(1)
+SDF_WAVE_INST(2)
+SDF_WAVE_INST(3)
+SDF_WAVE_INST(6)
+SDF_WAVE_INST(4)
+SDF_WAVE_INST(8)
+#undef SDF_WAVE_INST
 
 }  // namespace sdf

@@ -13,7 +13,10 @@
 #include <mutex>
 #include <thread>
 
-#include "sdf_ctx.h"
+#include <hipcub/hipcub.hpp>
+
+#include "sdf_batch.h"
+#include "stripe_sync.h"
 
 using namespace sdf;
 

@@ -1,4 +1,5 @@
-// Context, device / pinned buffers and kernel declarations shared by the pieces of the C-ABI layer
+// Context, device / pinned buffers and the planning threads shared by the pieces of the C-ABI layer; the kernels they launch
+// are declared in sdf_kernels.h, the sizes they reserve come from extz2_geom.h
 // (sdf_plan.hip: batch cutting and chunk planning; sdf_launch.hip: uploads and launches; sdf_api.hip: entry points).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,63 +19,10 @@
 #include <thread>
 #include <vector>
 
-#include "sdf_internal.h"
+#include "extz2_geom.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
-template <int BS, bool GLOBAL, bool PLAIN>
-__global__ void extz2_general_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *,
-                                     sdf_result *, uint8_t *, size_t);
-size_t general_lds_bytes(int qlen, int tlen);
-template <int NREG, bool STREAM>
-__global__ void extz2_wave_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *,
-                                  sdf_result *);
-size_t wave_lds_bytes(int qlen, int tlen, int nreg);
-bool wave_fits_whole(int qlen, int tlen, int nreg);
-template <int NREG, bool STREAM, bool TRACK>
-__global__ void extz2_pair_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *,
-                                  sdf_result *);
-size_t pair_lds_bytes(int qlen, int tlen, int nreg);
-bool pair_fits_whole(int qlen, int tlen, int nreg);
-size_t pair_mixed_lds_bytes(int qmax, int tmax, int nreg);
-constexpr int kMixedMaxNeed = 576;  // widest window of a mixed pair: nine registers of 64 slots (w = 512)
-template <int NREG>
-__global__ void extz2_stripe_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *,
-                                    sdf_result *, int, unsigned long long *, int, unsigned *);
-__global__ void stripe_sync_init_kernel(const PlanTask *, const int32_t *, int, uint8_t *);
-template <int NREG>
-__global__ void extz2_bstripe_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *,
-                                     unsigned long long *, int, unsigned *);
-__global__ void bstripe_init_kernel(const PlanTask *, const int32_t *, int, uint8_t *);
-__global__ void bstripe_finish_kernel(const PlanTask *, const int32_t *, int, int, const uint8_t *, sdf_result *);
-struct LaneRec;
-__global__ void lane_keys_kernel(const LaneRec *, int, uint32_t *, uint32_t *);
-__global__ void lane_sizes_kernel(const LaneRec *, const uint32_t *, int, unsigned long long *, unsigned long long *);
-__global__ void lane_plan_kernel(const LaneRec *, const uint32_t *, int, const unsigned long long *, const unsigned long long *,
-                                 int64_t, int64_t, PlanTask *);
-__global__ void lane_hist_kernel(const LaneRec *, int, uint32_t *);
-__global__ void lane_bins_scan_kernel(const uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, uint32_t *,
-                                      unsigned long long *, unsigned long long *);
-__global__ void lane_bins_top_kernel(uint32_t *, unsigned long long *, unsigned long long *);
-__global__ void lane_place_kernel(const LaneRec *, int, uint32_t *, const uint32_t *, const unsigned long long *,
-                                  const unsigned long long *, const uint32_t *, const unsigned long long *,
-                                  const unsigned long long *, int64_t, int64_t, PlanTask *);
-__global__ void extz2_lane_kernel(const PlanTask *, int, const uint32_t *, ScoreK, uint8_t *, sdf_result *);
-__global__ void extz2_strip_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *);
-template <int C>
-__global__ void extz2_strip_chain_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *,
-                                         unsigned long long *, int, unsigned *);
-__global__ void strip_chain_init_kernel(const PlanTask *, const int32_t *, uint8_t *);
-template <int LAYOUT, int G>
-__global__ void traceback_kernel(const PlanTask *, int, const uint32_t *, const uint8_t *, sdf_result *, uint32_t *);
-__global__ void cigar_scan_blocks_kernel(sdf_result *, int, unsigned long long *);
-__global__ void cigar_scan_parts_kernel(unsigned long long *, int, unsigned long long *);
-__global__ void cigar_scan_add_kernel(sdf_result *, int, const unsigned long long *);
-__global__ void cigar_compact_kernel(const PlanTask *, int, const sdf_result *, const uint32_t *,
-                                     uint32_t *, unsigned long long);
-
-__global__ void reset_results_kernel(sdf_result *res, int n);
-struct PackRec;
-__global__ void pack_chars_kernel(const PackRec *, long long, const char *, uint32_t *);
 // (diagnostics of buffers that have no context to ask: set by every sdf_create from its configuration's debug_timing)
 inline std::atomic<bool> g_debug_timing{false};
 
@@ -224,9 +172,6 @@ struct HostBuf {  // pinned host memory
   bool registered = false;
 };
 
-}  // namespace sdf
-
-namespace sdf {
 struct BatchCut;
 
 // A few parked host threads for the planning of a batch (a thread costs ~0.1 ms to start and join, a planning pass over

@@ -82,58 +82,4 @@ __host__ __device__ inline bool band_of(int r, int qlen, int tlen, int w, Band &
   return lo <= hi;
 }
 
-#ifdef __HIPCC__
-// ---- packed 16-bit helpers of the DP kernels: every state byte of the reference is held as value << 8 in a
-// 16-bit half, so the packed ALU reproduces the reference's wrap-around int8 arithmetic two cells at a time ----
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-
-#define SDF_OPQ(x) asm("" : "+v"(x))  // make a value opaque to instcombine (keeps the packed forms)
-
-__device__ __forceinline__ unsigned pk_add(unsigned a, unsigned b) {
-  return __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b));
-}
-__device__ __forceinline__ unsigned pk_sub(unsigned a, unsigned b) {
-  return __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b));
-}
-__device__ __forceinline__ unsigned pk_maxi(unsigned a, unsigned b) {
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(i16x2, a),
-                                                                __builtin_bit_cast(i16x2, b)));
-}
-__device__ __forceinline__ unsigned pk_maxu(unsigned a, unsigned b) {
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a),
-                                                                __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ unsigned pk_minu(unsigned a, unsigned b) {
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a),
-                                                                __builtin_bit_cast(u16x2, b)));
-}
-// max(a - b, 0) per half: one v_pk_sub_u16 with the clamp bit (unsigned saturation)
-__device__ __forceinline__ unsigned pk_subsat_u(unsigned a, unsigned b) {
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
-// min(x, 1) per half = "x != 0" as 0/1.  Written as the instruction itself: the optimiser would
-// otherwise turn it into per-half compares + selects.
-__device__ __forceinline__ unsigned pk_nonzero_(unsigned a, unsigned one_opaque) {
-  return pk_minu(a, one_opaque);
-}
-#define pk_nonzero(a) pk_nonzero_((a), one2)
-// F <- (F << 1) | bit, as the single instruction it is
-__device__ __forceinline__ unsigned shl1_or(unsigned f, unsigned bit) {
-  return (f << 1) + bit;  // bit 0 of f << 1 is clear: + == |, and it selects as one v_lshl_add_u32
-}
-__device__ __forceinline__ unsigned pk_mad(unsigned a, unsigned b, unsigned c) {
-  return __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2, a) * __builtin_bit_cast(u16x2, b) +
-                                          __builtin_bit_cast(u16x2, c));
-}
-__device__ __forceinline__ unsigned pk_ashr15(unsigned a) {
-  return __builtin_bit_cast(unsigned, __builtin_bit_cast(i16x2, a) >> (i16x2){15, 15});
-}
-__device__ __forceinline__ unsigned pk_shl(unsigned a, unsigned n) {
-  return __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2, a)
-                                          << (u16x2){(unsigned short)n, (unsigned short)n});
-}
-
-#endif  // __HIPCC__
-
 }  // namespace sdf

@@ -1,0 +1,127 @@
+// Every kernel of the library that another file launches, declared once, with the records a kernel takes from the host.
+// Each kernel file includes this header, so a definition is checked against its declaration; the launcher and the entry
+// points (sdf_launch.hip, sdf_api.hip) can only name what is declared here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "sdf_internal.h"
+
+namespace sdf {
+
+// extz2_general.hip
+template <int BS, bool GLOBAL, bool PLAIN>
+__global__ void extz2_general_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *,
+                                     uint8_t *, size_t);
+// extz2_wave.hip
+template <int NREG, bool STREAM>
+__global__ void extz2_wave_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *);
+// extz2_pair.hip
+template <int NREG, bool STREAM, bool TRACK>
+__global__ void extz2_pair_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *);
+template <int NREG>
+__global__ void extz2_pair_mixed_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *,
+                                        sdf_result *);
+// extz2_stripe.hip
+template <int NREG>
+__global__ void extz2_stripe_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *,
+                                    int, unsigned long long *, int, unsigned *);
+__global__ void stripe_sync_init_kernel(const PlanTask *, const int32_t *, int, uint8_t *);
+// extz2_bstripe.hip
+template <int NREG>
+__global__ void extz2_bstripe_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *,
+                                     unsigned long long *, int, unsigned *);
+__global__ void bstripe_init_kernel(const PlanTask *, const int32_t *, int, uint8_t *);
+__global__ void bstripe_finish_kernel(const PlanTask *, const int32_t *, int, int, const uint8_t *, sdf_result *);
+// extz2_lane.hip
+struct LaneRec {      // what the host uploads per task of the batch (16 bytes; invalid: flag = 0xffff)
+  uint32_t q_word, t_word;  // word offsets of the packed sequences in the pool
+  uint32_t out_idx;
+  uint8_t qlen_m1, tlen_m1;  // lengths - 1 (1 .. 256)
+  uint16_t flag;             // SDF_FLAG_SCORE_ONLY | SDF_FLAG_REV_CIGAR
+};
+__global__ void lane_keys_kernel(const LaneRec *, int, uint32_t *, uint32_t *);
+__global__ void lane_sizes_kernel(const LaneRec *, const uint32_t *, int, unsigned long long *, unsigned long long *);
+__global__ void lane_plan_kernel(const LaneRec *, const uint32_t *, int, const unsigned long long *,
+                                 const unsigned long long *, int64_t, int64_t, PlanTask *);
+__global__ void lane_hist_kernel(const LaneRec *, int, uint32_t *);
+__global__ void lane_bins_scan_kernel(const uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, uint32_t *,
+                                      unsigned long long *, unsigned long long *);
+__global__ void lane_bins_top_kernel(uint32_t *, unsigned long long *, unsigned long long *);
+__global__ void lane_place_kernel(const LaneRec *, int, uint32_t *, const uint32_t *, const unsigned long long *,
+                                  const unsigned long long *, const uint32_t *, const unsigned long long *,
+                                  const unsigned long long *, int64_t, int64_t, PlanTask *);
+__global__ void extz2_lane_kernel(const PlanTask *, int, const uint32_t *, ScoreK, uint8_t *, sdf_result *);
+// extz2_strip.hip
+__global__ void extz2_strip_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *, sdf_result *);
+template <int C>
+__global__ void extz2_strip_chain_kernel(const PlanTask *, const int32_t *, const uint32_t *, ScoreK, uint8_t *,
+                                         sdf_result *, unsigned long long *, int, unsigned *);
+__global__ void strip_chain_init_kernel(const PlanTask *, const int32_t *, uint8_t *);
+// traceback.hip
+template <int LAYOUT, int G>
+__global__ void traceback_kernel(const PlanTask *, int, const uint32_t *, const uint8_t *, sdf_result *, uint32_t *);
+__global__ void cigar_scan_blocks_kernel(sdf_result *, int, unsigned long long *);
+__global__ void cigar_scan_parts_kernel(unsigned long long *, int, unsigned long long *);
+__global__ void cigar_scan_add_kernel(sdf_result *, int, const unsigned long long *);
+__global__ void cigar_compact_kernel(const PlanTask *, int, const sdf_result *, const uint32_t *, uint32_t *,
+                                     unsigned long long);
+// sdf_launch.hip
+__global__ void reset_results_kernel(sdf_result *res, int n);
+// seq_pack.hip
+struct PackRec {     // one DP task's two character ranges and where its packed words go (32 bytes)
+  int64_t q_byte;    // first character of the query range in the pool (the first byte in pool order, whatever the strand)
+  int64_t t_byte;
+  int64_t q_word;    // first packed word of the query; the target's words follow the query's
+  int32_t qlen, tlen;  // bit 31 (kPackRc): the side is read reverse-complemented -- base i = rev(pool[byte + len - 1 - i])
+};
+// The two strand bits of a task (SDF_TASK_Q_RC / SDF_TASK_T_RC) travel in the sign bits of the lengths, which are never
+// negative: the record stays 32 bytes.  Only pack_chars_kernel<true> decodes them; a batch without a reversed side is
+// packed by pack_chars_kernel<false>, the kernel as it was.
+constexpr uint32_t kPackRc = 0x80000000u;
+static_assert(sizeof(PackRec) == 32, "PackRec: two records per 64-byte line");
+template <bool REV>
+__global__ void pack_chars_kernel(const PackRec *, long long, const char *, uint32_t *);
+__global__ void fasta_gather_kernel(const char *, char *, uint32_t, uint32_t, uint32_t);
+// anchors.hip
+struct AnchorPairDev {
+  int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool
+  int32_t qlen, rlen;
+  int32_t same_chr, delta;  // near-diagonal filter of self comparisons (:67-69); same_chr: kPairSameChr | kPairRefRc
+  int64_t rk_start, qk_start;  // first global k-mer index of this pair's reference / query
+};
+// AnchorPairDev::same_chr holds two truth values (sdf_anchor_pair::same_chr is one, and stays one)
+constexpr int32_t kPairSameChr = 1;
+constexpr int32_t kPairRefRc = 2;  // the reference range is read reverse-complemented (sdf_anchors_batch_strand: r_rc)
+struct CandOut {
+  int32_t q, r, l, has_u;
+};
+template <bool RC>
+__global__ void ref_keys_kernel(const AnchorPairDev *, int, const char *, int, int, unsigned long long *);
+__global__ void query_lookup_kernel(const AnchorPairDev *, int, const char *, int, int, const unsigned long long *,
+                                    long long, uint32_t *, uint32_t *, uint32_t *, uint32_t *);
+template <bool RC>
+__global__ void candidates_kernel(const AnchorPairDev *, const char *, int, const unsigned long long *, const uint32_t *,
+                                  const uint32_t *, const unsigned long long *, const uint32_t *, long long, long long,
+                                  uint32_t *, CandOut *, int);
+__global__ void anchors_compact_kernel(const uint32_t *, const unsigned long long *, const CandOut *, long long, CandOut *,
+                                       unsigned long long);
+__global__ void anchor_offsets_kernel(const AnchorPairDev *, int, const unsigned long long *, const unsigned long long *,
+                                      long long, unsigned long long, long long, long long *);
+// chain.hip
+__global__ void chain_kernel(const sdf_anchor *, const int64_t *, const int64_t *, int, int, int, int32_t *, int32_t *,
+                             int32_t *, int32_t *, const int32_t *);
+__global__ void chain_wave_kernel(const sdf_anchor *, const int64_t *, const int32_t *, int, int, int32_t *, int32_t *,
+                                  int32_t *);
+__global__ void chain_tree_script_kernel(const int32_t *, int, const int32_t *, int, int32_t *, int, int32_t *, int32_t *);
+// stats_cols.hip
+struct StatsItem {  // a segment of a long alignment
+  sdf_stats_task t;
+  uint32_t task;  // the alignment it belongs to (0xffffffff: nothing to do)
+  uint32_t pad;
+};
+__global__ void stats_columns_kernel(const sdf_stats_task *, int, const char *, const uint32_t *, sdf_stats_cols *,
+                                     StatsItem *, unsigned *, unsigned, unsigned);
+__global__ void stats_segments_kernel(const StatsItem *, const unsigned *, unsigned, const char *, const uint32_t *,
+                                      sdf_stats_cols *);
+
+}  // namespace sdf

@@ -1,6 +1,8 @@
 // Device side of a batch call: uploads a planned chunk, launches its DP kernels and its traceback, and closes the
 // batch (CIGAR scan + compaction, timing).  Planning is in sdf_plan.hip; the entry points are in sdf_api.hip.
-#include "sdf_ctx.h"
+#include <hipcub/hipcub.hpp>
+
+#include "sdf_batch.h"
 
 namespace sdf {
 
@@ -18,45 +20,7 @@ __global__ __launch_bounds__(256) void reset_results_kernel(sdf_result *res, int
   res[k] = o;
 }
 
-struct ChunkEv {
-  hipEvent_t dp0 = nullptr, dpe[16] = {}, tb0 = nullptr, tb1 = nullptr;  // plan uploaded; end of the DP launches per
-                                                                         // stream; traceback (begin, end)
-};
-
-constexpr size_t kClaimSets = 2048;  // stripe launches per call that take their entries through counters (the rest by index)
-
-// Progress of one batch call on the device.
-struct BatchRun {
-  sdf_ctx *ctx = nullptr;
-  hipStream_t st = nullptr;  // the caller's stream
-  ScoreK sk;
-  const uint32_t *d_pool = nullptr;
-  sdf_result *d_out = nullptr;
-  PlanTask *plan = nullptr, *d_plan = nullptr;  // pinned host copy / device copy
-  int32_t *order = nullptr, *d_order = nullptr;
-  uint8_t *d_dir = nullptr;
-  uint8_t *heavy_dir = nullptr;  // the heavy chunks' slice (the workspace as it was when they were launched)
-  size_t claim_sets = 0;         // stripe launches of the call so far (each has eight entry counters in ctx->claim_buf)
-  bool more_chunks = false;      // early start: chunks of ordinary tasks will follow those in cut->chunks
-  uint32_t *d_stage = nullptr;
-  const BatchCut *cut = nullptr;
-  bool want_cigar = false, have_heavy = false;
-  std::vector<ChunkEv> cev;
-  std::vector<size_t> normal_ids;  // chunk indices of the ordinary chunks launched so far
-  double qload[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // estimated DP work queued on each stream during this call
-  size_t evc = 0;
-  hipEvent_t ev_begin = nullptr;
-  bool any_stripe = false;  // a stripe kernel was launched: its give-up list is looked at before the batch closes
-  const sdf_scoring *scoring = nullptr;  // what the caller passed (a re-run of abandoned tasks passes them on)
-  const sdf_task *tasks = nullptr;
-  uint32_t want = 0;
-  hipEvent_t ev_lane = nullptr;  // the lane tasks' DP and traceback have finished
-  hipEvent_t ev_lane0 = nullptr;  // ... are about to start (debug timing)
-  hipStream_t began[24] = {};  // internal streams already ordered behind ev_begin in this call
-  size_t nbegan = 0;
-};
-
-static hipEvent_t next_event(sdf_ctx *ctx, size_t &cursor) {
+hipEvent_t next_event(sdf_ctx *ctx, size_t &cursor) {
   if (cursor == ctx->events.size()) {
     hipEvent_t ev;
     (void)hipEventCreate(&ev);
@@ -66,7 +30,7 @@ static hipEvent_t next_event(sdf_ctx *ctx, size_t &cursor) {
 }
 
 // every stream a batch call may have work on
-static void drain_streams(sdf_ctx *ctx, hipStream_t st) {
+void drain_streams(sdf_ctx *ctx, hipStream_t st) {
   for (hipStream_t q : {st, ctx->stream, ctx->dp_stream[0], ctx->dp_stream[1], ctx->tb_stream, ctx->aux_stream[0],
                         ctx->aux_stream[1], ctx->aux_stream[2], ctx->aux_stream[3], ctx->lane_stream})
     if (q) (void)hipStreamSynchronize(q);
@@ -225,7 +189,7 @@ static void launch_traceback(bool solo, size_t cnt, hipStream_t s, const PlanTas
 // ordinary chunks alternate between the DP streams; every other launch (a class of a few tasks ends in a tail as
 // long as its longest task) goes, longest first, to the stream with the least estimated work queued.  A heavy chunk
 // uploads and traces back on the caller's stream and uses the workspace slice behind the regions.
-static int launch_chunk(BatchRun &run, size_t ci) {
+int launch_chunk(BatchRun &run, size_t ci) {
   sdf_ctx *ctx = run.ctx;
   const BatchCut &cut = *run.cut;
   const ChunkPlan &c = cut.chunks[ci];
@@ -563,7 +527,7 @@ hipError_t create_lane_stream(const sdf_ctx *ctx, hipStream_t *out) {
 // The lane tasks of a batch (extz2_lane.hip), start to finish on a stream of their own next to the chunks: the records the
 // scan wrote -> sort by (class, qlen, tlen) -> CIGAR-slot and flag-region offsets -> plan records behind the host-planned
 // ones -> one DP launch per class present -> traceback.  Nothing here waits for the host.
-static int launch_lane(BatchRun &run, size_t n) {
+int launch_lane(BatchRun &run, size_t n) {
   sdf_ctx *ctx = run.ctx;
   const BatchCut &cut = *run.cut;
   const size_t nl = cut.n_lane;
@@ -698,8 +662,8 @@ static int join_part(BatchRun &run) {
 
 // `head`: the part of the call that was launched first, on another context and stream (null: the call is one part);
 // n / d_out: the whole call's.
-static int finish_batch(BatchRun &run, BatchRun *head, size_t n, sdf_result *d_out, uint32_t *d_cig, size_t cigar_cap,
-                        size_t *cigar_used) {
+int finish_batch(BatchRun &run, BatchRun *head, size_t n, sdf_result *d_out, uint32_t *d_cig, size_t cigar_cap,
+                 size_t *cigar_used) {
   sdf_ctx *ctx = run.ctx;
   hipStream_t st = run.st;
   if (head) {

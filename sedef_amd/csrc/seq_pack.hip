@@ -8,21 +8,9 @@
 // (include/sedef_hip.h: ceil(len/16) words of 2-bit codes, then ceil(len/32) words of N mask).
 #include <hip/hip_runtime.h>
 
-#include "sdf_internal.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
-
-struct PackRec {     // one DP task's two character ranges and where its packed words go (32 bytes)
-  int64_t q_byte;    // first character of the query range in the pool (the first byte in pool order, whatever the strand)
-  int64_t t_byte;
-  int64_t q_word;    // first packed word of the query; the target's words follow the query's
-  int32_t qlen, tlen;  // bit 31 (kPackRc): the side is read reverse-complemented -- base i = rev(pool[byte + len - 1 - i])
-};
-// The two strand bits of a task (SDF_TASK_Q_RC / SDF_TASK_T_RC) travel in the sign bits of the lengths, which are never
-// negative: the record stays 32 bytes.  Only pack_chars_kernel<true> decodes them; a batch without a reversed side is
-// packed by pack_chars_kernel<false>, the kernel as it was.
-constexpr uint32_t kPackRc = 0x80000000u;
-static_assert(sizeof(PackRec) == 32, "PackRec: two records per 64-byte line");
 
 // Sixteen lanes per sequence (a task is two sequences), a lane per group of 32 bases -- two code words and a mask word.
 // SEDEF's tasks are short (708,600 of ~25 bases in a round of the chr1-sized run) with a few of up to 60,000 bases

@@ -14,19 +14,14 @@
 // advances of its runs, STATS_SEG at a time, and leaves one work item per segment -- an alignment of its own: the sequences'
 // ranges the segment's runs consume -- in a list (stats_columns_kernel); a second launch of a fixed number of wavefronts
 // takes the items and adds their counters to the alignment's record (stats_segments_kernel).
-#pragma once
-#include "sdf_internal.h"
+#include <hip/hip_runtime.h>
+
+#include "extz2_geom.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
 
-constexpr int STATS_WAVES = 4;  // alignments per workgroup
 constexpr uint32_t STATS_SEG = 512, STATS_LONG = 1024;  // runs per segment of a long alignment / runs that make one long
-
-struct StatsItem {  // a segment of a long alignment
-  sdf_stats_task t;
-  uint32_t task;  // the alignment it belongs to (0xffffffff: nothing to do)
-  uint32_t pad;
-};
 
 // Prefix sums and sums over the wavefront (all 64 lanes active): an inclusive scan inside each row of sixteen lanes
 // (row_shr 1, 2, 4, 8), the rows' totals passed on (row_bcast 15 into rows 1 and 3, row_bcast 31 into rows 2 and 3) --
@@ -213,7 +208,6 @@ __device__ __forceinline__ int stats_count_alignment(const sdf_stats_task &T, co
 // and ~130 units -- a wavefront of its own spends two thirds of its instructions around the counting.  Same arithmetic as
 // stats_count_alignment; every wave-level step is a row-level one (a DPP row IS sixteen lanes), loop bounds are the
 // maxima over the four groups, and a group that has run out of runs or units idles with ('-', '-') columns it takes back.
-constexpr uint32_t STATS_GROUP_MAX = 32;  // runs of an alignment that shares its wavefront (SDF_STATS_GROUP_MAX; 0: never)
 
 __device__ __forceinline__ int stats_row_scan(int v) {  // inclusive prefix sum inside each row of sixteen lanes
   v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);

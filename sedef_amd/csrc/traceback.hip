@@ -7,14 +7,13 @@
 // traceback_kernel below).
 #include <hip/hip_runtime.h>
 
-#include "sdf_internal.h"
+#include "extz2_dev.h"
+#include "sdf_kernels.h"
 
 namespace sdf {
 
 __device__ __forceinline__ uint32_t code_at(const uint32_t *codes, const uint32_t *nmask, int k) {
-  const uint32_t c = (codes[k >> 4] >> ((k & 15) * 2)) & 3u;
-  const uint32_t n = (nmask[k >> 5] >> (k & 31)) & 1u;
-  return n ? 4u : c;
+  return pool_code<0u>(codes, nmask, k, 4u);
 }
 
 // ---- one cell of the direction matrix ----------------------------------------------------------------------

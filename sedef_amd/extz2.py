@@ -379,6 +379,38 @@ class Extz2Engine:
                                                             cig.ctypes.data, cigar_cap, C.byref(used)))
         return out, cig[:used.value]
 
+    def batch_call(self, form, tasks, pool=None, want=WANT_ALL, cigar_cap=0, guard=0, sentinel=0, fill=0, null_cigar=False,
+                   mat=None, gapo=40, gape=1):
+        """One host-form batch call that reports instead of raising.  form: "batch" / "brief" (the tasks name bytes of `pool`)
+        or "pairs" / "pairs_full" (bytes of the resident pool); `want` is read by "batch" and "pairs_full".  Every byte of the
+        records starts out as `fill`; the CIGAR pool handed over is cigar_cap words long and has `guard` more words behind
+        it, all of them `sentinel` (null_cigar: no pool at all).  Returns (rc, cigar_used, records, the pool's words with the
+        guard, sdf_last_error) -- a caller that sizes its pool by an estimate reads rc == -5 and the need from these."""
+        tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
+        n = len(tasks)
+        sc = _scoring(sedef_mat() if mat is None else mat, gapo, gape)
+        out = np.zeros(n, BRIEF_DTYPE if form in ("brief", "pairs") else RESULT_DTYPE)
+        out.view(np.uint8)[:] = fill
+        cig = np.full(cigar_cap + guard, sentinel, np.uint32)
+        cig_p = None if null_cigar else cig.ctypes.data
+        used = C.c_size_t(0)
+        if form in ("batch", "brief"):
+            pool = np.ascontiguousarray(pool, dtype=np.uint8)
+            head = (self.ctx, C.byref(sc), tasks.ctypes.data, n, pool.ctypes.data, pool.nbytes)
+            if form == "batch":
+                rc = self.lib.sdf_extz2_batch(*head, want, out.ctypes.data, cig_p, cigar_cap, C.byref(used))
+            else:
+                rc = self.lib.sdf_extz2_batch_brief(*head, out.ctypes.data, cig_p, cigar_cap, C.byref(used))
+        elif form == "pairs":
+            rc = self.lib.sdf_extz2_batch_pairs(self.ctx, C.byref(sc), tasks.ctypes.data, n, out.ctypes.data, cig_p, cigar_cap,
+                                                C.byref(used))
+        elif form == "pairs_full":
+            rc = self.lib.sdf_extz2_batch_pairs_full(self.ctx, C.byref(sc), tasks.ctypes.data, n, want, out.ctypes.data, cig_p,
+                                                     cigar_cap, C.byref(used))
+        else:
+            raise ValueError("batch_call: unknown form %r" % (form,))
+        return rc, int(used.value), out, cig, self.lib.sdf_last_error(self.ctx).decode()
+
     def reserve(self, max_tasks, max_bases, workspace_bytes=0, flags=0):
         """sdf_reserve: buffers, pinned staging and pipeline streams sized once (flags: RESERVE_BRIEF | RESERVE_ANCHORS)."""
         self._check(self.lib.sdf_reserve(self.ctx, int(max_tasks), int(max_bases), int(workspace_bytes), int(flags)))
@@ -387,14 +419,17 @@ class Extz2Engine:
         return int(self.lib.sdf_device_bytes(self.ctx))
 
     def align_batch_device(self, tasks, d_pool, d_out, d_cig, cigar_cap, mat=None, gapo=40, gape=1,
-                           want=WANT_ALL, stream=None):
-        """Device-resident form: d_pool/d_out/d_cig are raw HBM addresses (ints)."""
+                           want=WANT_ALL, stream=None, check=True):
+        """Device-resident form: d_pool/d_out/d_cig are raw HBM addresses (ints; d_cig None: no CIGAR pool).  check=False:
+        returns (rc, cigar_used, sdf_last_error) instead of raising -- with rc == -5 cigar_used is the need."""
         tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
         sc = _scoring(sedef_mat() if mat is None else mat, gapo, gape)
         used = C.c_size_t(0)
         rc = self.lib.sdf_extz2_batch_device(self.ctx, C.byref(sc), tasks.ctypes.data, len(tasks),
                                              d_pool, want, d_out, d_cig, cigar_cap, C.byref(used),
                                              stream)
+        if not check:
+            return rc, int(used.value), self.lib.sdf_last_error(self.ctx).decode()
         self._check(rc)
         return used.value
 

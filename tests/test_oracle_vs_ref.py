@@ -1,8 +1,9 @@
 """CPU: fuzz of the oracle against the reference kernel: live where oracle/_ref/libksw2_ref.so is built, else against
 its recorded answers for the same seeded cases (tests/refcalls.py)."""
 import numpy as np
+import pytest
 
-from oracle.binding import Reference, mutate, random_codes, sedef_mat
+from oracle.binding import NEG_INF, Reference, mutate, random_codes, sedef_mat
 from refcalls import ref_calls
 from util import FIELDS
 
@@ -66,3 +67,22 @@ def _fuzz_generic_matrix(oracle, ref):
         kw = dict(w=int(rng.choice([-1, -1, 3, 17, 64])), zdrop=int(rng.choice([-1, 40, 300])), flag=flag,
                   mat=mat if flag & 4 else sedef_mat(), gapo=12, gape=2)
         assert _same(oracle.extz2(q, t, **kw), ref.extz2(q, t, **kw)), kw
+
+
+def test_early_returns_match_the_reference(oracle):
+    """What the reference returns before it does any work (extern/ksw2_extz2_sse.cc:57: a side without a base; :81: a scoring
+    with -min_sc > 2 (q + e)), live against oracle/_ref: the GPU tests of the batch entry points take the expected record of
+    such a task from the oracle (tests/test_gpu_batch_contract.py).  Skips where the reference kernel was not built."""
+    if not Reference.available():
+        pytest.skip("oracle/_ref/libksw2_ref.so not built")
+    ref = Reference()
+    rng = np.random.default_rng(14)
+    reset = dict(score=NEG_INF, mqe=NEG_INF, mte=NEG_INF, max=0, max_q=-1, max_t=-1, mqe_t=-1, mte_q=-1, zdropped=0)
+    cases = [(random_codes(rng, ql), random_codes(rng, tl), kw) for ql, tl in ((0, 5), (5, 0), (0, 0))
+             for kw in (dict(), dict(w=3, zdrop=50, flag=0x40), dict(flag=1))]
+    q = random_codes(rng, 50)
+    cases.append((q, mutate(rng, q)[:50], dict(mat=sedef_mat(1, -20), gapo=4, gape=2)))  # 20 > 2 (4 + 2)
+    for q, t, kw in cases:
+        a, b = oracle.extz2(q, t, **kw), ref.extz2(q, t, **kw)
+        assert _same(a, b), (len(q), len(t), kw)
+        assert all(a[k] == reset[k] for k in FIELDS) and len(a["cigar"]) == 0, (len(q), len(t), kw)

@@ -247,8 +247,9 @@ int sdf_extz2_batch_brief(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *t
  *
  * Resident chromosomes: a caller that serves many batches of one genome uploads each FASTA record once, as the file has
  * it, with sdf_pool_append_fasta, and names (base offset, length, strand) afterwards: SDF_TASK_Q_RC / SDF_TASK_T_RC on the
- * DP tasks, r_rc on the anchor pairs (sdf_anchors_batch_strand).  A forward and a reverse-strand pair on one region share
- * the one resident copy. */
+ * DP tasks, r_rc on the anchor pairs (sdf_anchors_batch_strand), SDF_STATS_A_RC / SDF_STATS_B_RC on the alignments whose
+ * statistics are taken (sdf_stats_columns_pairs).  A forward and a reverse-strand pair on one region share the one
+ * resident copy. */
 char *sdf_pool_host(sdf_ctx *ctx, size_t bytes);
 int sdf_pool_upload(sdf_ctx *ctx, const char *chars, size_t bytes);
 size_t sdf_pool_bytes(const sdf_ctx *ctx); /* characters resident at this moment */
@@ -379,7 +380,7 @@ typedef struct {
   uint64_t a_off, b_off;   /* byte offsets of the two sequences in seq_pool */
   uint32_t a_len, b_len;
   uint64_t cigar_off;      /* first run of the alignment in cigar_pool (in words) */
-  uint32_t n_cigar, reserved;
+  uint32_t n_cigar, reserved; /* sdf_stats_columns_pairs: SDF_STATS_A_RC | SDF_STATS_B_RC; the other calls ignore it */
 } sdf_stats_task;
 
 typedef struct {
@@ -400,6 +401,29 @@ int sdf_stats_columns_batch(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n,
  * overlap). */
 int sdf_stats_columns_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, const char *d_seq_pool,
                              const uint32_t *d_cigar_pool, sdf_stats_cols *d_out, void *stream);
+
+/* Alignments on the RESIDENT pool, by range and strand: a_off / b_off are byte offsets into the characters sdf_pool_upload or
+ * sdf_pool_append_fasta left in HBM (after sdf_pool_append_fasta: *base_off + x), and no character crosses PCIe.  The strand
+ * bits travel in sdf_stats_task::reserved and follow the rule of SDF_TASK_Q_RC / SDF_TASK_T_RC: base i of a reversed side is
+ * rev_dna(pool[off + len - 1 - i]) -- rev_dna: the reference's table (src/common.h:72-87,93), indexed c & 127 as the host does:
+ * the case is kept, everything that is not ACGTacgt becomes upper-case 'N' -- and `off` keeps naming the first byte of the range
+ * in pool order.  The counters are those of sdf_stats_columns_batch on a pool that holds the reverse-complemented bytes.
+ * Only these two calls read `reserved`; sdf_stats_columns_batch / sdf_stats_columns_device never do. */
+#define SDF_STATS_A_RC 0x1 /* side a is the reverse complement of its range */
+#define SDF_STATS_B_RC 0x2 /* side b likewise */
+/* Host form: tasks, runs and results in host memory.  SDF_ERR_INVALID: a sequence range outside sdf_pool_bytes() (an empty
+ * pool holds no non-empty range), a CIGAR range outside cigar_words, or -- after the launch, out[] filled, flags == 1 on the
+ * record -- a CIGAR that does not fit its sequences.  SDF_ERR_UNSUPPORTED: a bit of `reserved` beyond the two above
+ * ("unknown stats task flag"), a side of more than 16 Mb.  All checks but the last precede the first launch.  A call
+ * without a reversed side runs the kernels of sdf_stats_columns_device. */
+int sdf_stats_columns_pairs(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const uint32_t *cigar_pool, size_t cigar_words,
+                            sdf_stats_cols *out);
+/* Device form: tasks, runs and results in HBM, asynchronous on `stream` like sdf_stats_columns_device (NULL: the context's
+ * own stream, synchronised before returning).  Offsets are not checked.  any_rc != 0: some task may carry a strand bit;
+ * any_rc == 0: the bits are not looked at.  The pool's uploads are enqueued on the context's stream: a caller with a
+ * stream of its own calls sdf_pool_sync() between the last upload and this call. */
+int sdf_stats_columns_pairs_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, int any_rc,
+                                   const uint32_t *d_cigar_pool, sdf_stats_cols *d_out, void *stream);
 
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is

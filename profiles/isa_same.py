@@ -3,7 +3,9 @@
 --cuda-device-only -S of sedef_amd/csrc/sdf_unity.hip, once per source tree): the set of function symbols, per function
 the instruction text after dropping comments and renumbering local labels in order of appearance, and per kernel the
 descriptor fields that decide occupancy (VGPRs, SGPRs, accum offset, LDS and scratch bytes).
-usage: isa_same.py parent.s branch.s      (exit status 1 when anything differs)"""
+usage: isa_same.py parent.s branch.s [parent_symbol=branch_symbol ...]      (exit status 1 when anything differs)
+A kernel that became one instantiation of a template has a new mangled name: `old=new` compares the branch's `new` under the
+parent's name `old` (stats_columns_kernel -> stats_columns_kernel<false>, for instance)."""
 import re
 import sys
 
@@ -31,7 +33,8 @@ def parse(path):
                 name, body = None, None
                 continue
             t = t.split(";")[0].split("//")[0].strip()
-            if t and not t.startswith((".p2align", ".loc", ".file", ".cfi")):
+            # (.section / .text: where the function's bytes go -- a template instantiation gets a COMDAT section of its own name)
+            if t and not t.startswith((".p2align", ".loc", ".file", ".cfi", ".section", ".text")):
                 body.append(t)
             continue
         m = re.match(r"\.amdhsa_kernel\s+(\S+)", t)
@@ -56,6 +59,13 @@ def normal(body):
 
 def main():
     (fa, da), (fb, db) = parse(sys.argv[1]), parse(sys.argv[2])
+    for old, new in (a.split("=", 1) for a in sys.argv[3:]):
+        if new not in fb or old in fb:
+            print("alias %s=%s: the branch has no %s, or has both" % (old, new, new))
+            return 1
+        fb[old] = [t.replace(new, old) for t in fb.pop(new)]
+        if new in db:
+            db[old] = db.pop(new)
     bad = 0
     for s in sorted(set(fa) ^ set(fb)):
         print("only in %s: %s" % ("parent" if s in fa else "branch", s))

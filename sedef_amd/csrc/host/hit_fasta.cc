@@ -139,6 +139,23 @@ FastaReference::Span FastaReference::locate(const std::string &seqname, int star
   return sp;
 }
 
+FastaReference::Record FastaReference::record(const std::string &seqname) const {
+  auto it = index_.find(seqname);
+  if (it == index_.end()) throw "Chromosome " + seqname + " does not exist";
+  const FastaIndexEntry &e = it->second;
+  if (e.length < 0 || e.line_blen < 1 || e.line_len < e.line_blen || e.offset < 0 || (size_t)e.offset > size_)
+    throw "Index entry of " + seqname + " is malformed";
+  // length bases and the line ends between them; the last line's own end if the file still holds it
+  const size_t gap = (size_t)(e.line_len - e.line_blen);
+  const size_t least = (size_t)e.length + (e.length ? (size_t)((e.length - 1) / e.line_blen) * gap : 0);
+  if (least > size_ - (size_t)e.offset) throw "Chromosome " + seqname + " ends beyond the FASTA file";
+  Record r;
+  r.entry = &e;
+  r.bytes = (const char *)mm_ + e.offset;
+  r.nbytes = std::min(least + gap, size_ - (size_t)e.offset);
+  return r;
+}
+
 // std::remove of '\n' then '\0' (src/fasta.cc:135-136), a line at a time
 size_t FastaReference::extract(const Span &sp, char *dst) {
   const char *src = sp.src, *const stop = sp.src + sp.bytes;

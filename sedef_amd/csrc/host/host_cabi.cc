@@ -92,10 +92,13 @@ int sdfh_generate_many(const char *ref_path, const char *beds, int kmer, const c
 
 // `sedef stats generate genome.fa final.bed > out` (reference: src/stats_main.cc:339-389); test_cols: the oracle's column
 // walker instead of the device (CPU tests).  stats: hits read, pieces, columns; returns the lines written or -1.
-long sdfh_stats_generate(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,
-                         int min_uppercase, double max_error, test_cols_fn test_cols, int device, long long *stats) {
+// resident != 0, or SDF_STATS_RESIDENT=1 in the environment: StatsParams::resident.
+long sdfh_stats_generate_resident(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,
+                                  int min_uppercase, double max_error, test_cols_fn test_cols, int device, int resident,
+                                  long long *stats) {
   try {
     StatsParams sp;
+    sp.resident = resident != 0 || StageSettings::from_env().stats_resident;
     sp.max_ok_gap = max_ok_gap;
     sp.min_split = min_split;
     sp.min_uppercase = min_uppercase;
@@ -122,6 +125,17 @@ long sdfh_stats_generate(const char *ref_path, const char *bed_path, const char 
     g_err = e.what();
     return -1;
   }
+}
+
+long sdfh_stats_generate(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,
+                         int min_uppercase, double max_error, test_cols_fn test_cols, int device, long long *stats) {
+  return sdfh_stats_generate_resident(ref_path, bed_path, out_path, max_ok_gap, min_split, min_uppercase, max_error, test_cols,
+                                      device, 0, stats);
+}
+
+// stats_piece_range (host/stats.cc; test hook): returns the length, *first the chromosome's first base of the range
+int sdfh_stats_piece_range(int start, int end, int s, int e, int rc, long long *first) {
+  return stats_piece_range(start, end, s, e, rc != 0, first);
 }
 
 // fmt 4.0.1 "{}" of a double, as `stats generate` prints it (test hook)

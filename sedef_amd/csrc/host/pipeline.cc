@@ -961,6 +961,7 @@ StageSettings StageSettings::from_env() {
   s.resident_dp = num("SDF_RESIDENT_DP", 0, 1, 1) != 0;
   s.anchor_parts = (int)num("SDF_ANCHOR_PARTS", 0, 16, 0);
   s.bucket_lanes = (int)num("SDF_BUCKET_LANES", 1, 4, 2);
+  s.stats_resident = num("SDF_STATS_RESIDENT", 0, 1, 0) != 0;
   if (const char *e = getenv("SDF_DEVICES"))
     for (const char *c = e; *c;) {
       char *end = nullptr;

@@ -351,6 +351,14 @@ class FastaReference {
   };
   Span locate(const std::string &seqname, int start, int *end) const;
   static size_t extract(const Span &s, char *dst);
+  // A whole record as the file has it, for sdf_pool_append_fasta (include/sedef_hip.h): its index entry (length, line_blen,
+  // line_len) and the bytes of its sequence lines in the mapped file, with the last line's end where the file has one.
+  struct Record {
+    const FastaIndexEntry *entry = nullptr;
+    const char *bytes = nullptr;
+    size_t nbytes = 0;
+  };
+  Record record(const std::string &seqname) const;
 
  private:
   int fd_ = -1;
@@ -363,11 +371,20 @@ class FastaReference {
 struct StatsParams {  // Globals::Stats (src/globals.cc:36-39), CLI overrides src/stats_main.cc:485-488
   int max_ok_gap = -1, min_split = 1000, min_uppercase = 100;
   double max_scaled_error = 0.5;
+  // SDF_STATS_RESIDENT=1 (read by the entry points, StageSettings::stats_resident): every chromosome the input names is
+  // uploaded once, as the file has it (sdf_pool_append_fasta), and the pieces are counted by base range and strand
+  // (sdf_stats_columns_pairs) -- no character pool is built or uploaded.  Ignored with the `test` hook.
+  bool resident = false;
 };
+// Where the device finds a piece's side in a resident chromosome: the piece covers columns [s, e) of a side that was fetched
+// from [start, end) of its chromosome (end: as get_sequence clamped it) and, with rc, reverse-complemented
+// (reference: src/align_main.cc:317-321 maps such columns back the same way).  *first: the chromosome's first base of the
+// range, in chromosome order whatever the strand; returns its length.
+int stats_piece_range(int start, int end, int s, int e, bool rc, long long *first);
 // TEST HOOK: a column walker with the oracle's signature (oracle/stats_oracle.c: sdfo_stats_columns) instead of the device
 typedef int (*test_cols_fn)(const char *, int, const char *, int, const uint32_t *, int, int32_t *, char *, char *);
 // Reads the BEDPE of `align generate`, writes the table of `stats generate` to `out`; the per-column counters of every
-// piece come from sdf_stats_columns_batch on `device` (or from `test`).  Returns the number of lines written (header
+// piece come from sdf_stats_columns_batch (sp.resident: sdf_stats_columns_pairs) on `device` (or from `test`).  Returns the number of lines written (header
 // excluded); stats[0..2] = hits read, pieces examined, alignment columns walked.
 long stats_generate(const std::string &ref_path, const std::string &bed_path, FILE *out, const StatsParams &sp,
                     test_cols_fn test, int device, long long *stats);
@@ -460,6 +477,7 @@ struct StageSettings {
   bool debug_timing = false; // SDF_DEBUG_TIMING: one line per phase of every super-batch
   int anchor_parts = 0;      // SDF_ANCHOR_PARTS: parts a super-batch's seed anchors are found in, each under the chaining of the one before (0: by its size -- 1, 2 or 4)
   bool resident_dp = true;   // SDF_RESIDENT_DP=0: the DP rounds cut their bases out on the host again instead of naming ranges of the characters the anchors call left in HBM
+  bool stats_resident = false;  // SDF_STATS_RESIDENT=1: `stats generate` counts on resident chromosomes (StatsParams::resident)
   int bucket_lanes = 2;      // SDF_BUCKET_LANES: buckets of a several-bucket run in flight, each on a device context of its own (1: one after the other)
   static StageSettings from_env();
 };

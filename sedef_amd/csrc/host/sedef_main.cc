@@ -202,6 +202,7 @@ int main(int argc, char **argv) {
       a.get({"min-split"}, sp.min_split);
       a.get({"uppercase"}, sp.min_uppercase);
       a.getd({"max-error"}, sp.max_scaled_error);
+      sp.resident = stage_settings().stats_resident;  // (SDF_STATS_RESIDENT=1)
       if (a.pos.size() < 3) throw std::string("Not enough arguments to stats");
       if (a.pos[0] != "generate") throw std::string("Unknown stats command");
       long long st[3] = {0, 0, 0};

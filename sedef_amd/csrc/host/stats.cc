@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <tuple>
 
 #include "../../../include/sedef_hip.h"
@@ -29,6 +30,11 @@ std::string format_double(double x) {
   return buf;
 }
 
+int stats_piece_range(int start, int end, int s, int e, bool rc, long long *first) {
+  *first = rc ? (long long)end - e : (long long)start + s;
+  return e - s;
+}
+
 namespace {
 const int kMinAssemblyGap = 100;   // Globals::Stats::MIN_ASSEMBLY_GAP_SIZE (src/globals.h:101)
 const int kBigOverlap = 100;       // Globals::Stats::BIG_OVERLAP_THRESHOLD (src/globals.h:102)
@@ -38,6 +44,7 @@ struct Piece {
   std::shared_ptr<Sequence> query, ref;
   int query_start, query_end, ref_start, ref_end;
   Alignment aln;
+  size_t src = 0;  // the input line it was cut from (its sequences were fetched from that line's ranges)
 };
 
 // columns [start, end) of hin as a hit of their own.  The hit's coordinates move by the bases BEFORE the trims (the
@@ -183,6 +190,7 @@ long stats_generate(const std::string &ref_path, const std::string &bed_path, FI
   }
   for (Input &x : in) {  // (after the loop above: the strings do not move any more)
     Piece p{x.h.query, x.h.ref, x.h.query_start, x.h.query_end, x.h.ref_start, x.h.ref_end, Alignment(x.fa, x.fb, x.cigar)};
+    p.src = (size_t)(&x - in.data());
     for (auto &q : split_alignment(p, sp))
       if (q.aln.span() >= ap.refine_min_read) pieces.push_back(std::move(q));  // (:229: Chain::Refine::MIN_READ)
   }
@@ -195,20 +203,30 @@ long stats_generate(const std::string &ref_path, const std::string &bed_path, FI
     std::vector<sdf_stats_task> tasks(n);
     std::vector<uint32_t> runs;
     std::string pool;
+    const bool resident = sp.resident && !test;  // (the host's own cuts above still read the fetched strings)
     for (size_t k = 0; k < n; k++) {
       const Alignment &al = pieces[k].aln;
       sdf_stats_task &t = tasks[k];
-      t.a_off = pool.size();
       t.a_len = (uint32_t)(al.end_a - al.start_a);
-      pool.append(al.bases_a(), t.a_len);
-      t.b_off = pool.size();
       t.b_len = (uint32_t)(al.end_b - al.start_b);
-      pool.append(al.bases_b(), t.b_len);
+      t.reserved = 0;
+      if (resident) {  // base ranges of the two chromosomes and strand bits; the chromosomes' pool offsets are added below
+        const Hit &h = in[pieces[k].src].h;
+        long long fa = 0, fb = 0;
+        stats_piece_range(std::max(0, h.query_start), h.query_end, al.start_a, al.end_a, h.query->is_rc, &fa);
+        stats_piece_range(std::max(0, h.ref_start), h.ref_end, al.start_b, al.end_b, h.ref->is_rc, &fb);
+        t.a_off = (uint64_t)fa, t.b_off = (uint64_t)fb;
+        t.reserved = (h.query->is_rc ? SDF_STATS_A_RC : 0u) | (h.ref->is_rc ? SDF_STATS_B_RC : 0u);
+      } else {
+        t.a_off = pool.size();
+        pool.append(al.bases_a(), t.a_len);
+        t.b_off = pool.size();
+        pool.append(al.bases_b(), t.b_len);
+      }
       t.cigar_off = runs.size();
       for (auto &run : al.cigar)
         if (run.second) runs.push_back(((uint32_t)run.second << 4) | (run.first == 'M' ? 0u : run.first == 'D' ? 1u : 2u));
       t.n_cigar = (uint32_t)(runs.size() - t.cigar_off);
-      t.reserved = 0;
       columns += al.span();
     }
     if (test) {
@@ -221,10 +239,44 @@ long stats_generate(const std::string &ref_path, const std::string &bed_path, FI
     } else if (n) {
       sdf_ctx *ctx = sdf_create(device, 0);
       if (!ctx) throw std::string("GPU backend unavailable: ") + sdf_last_error(nullptr);
-      const int rc = sdf_stats_columns_batch(ctx, tasks.data(), n, pool.data(), pool.size(), runs.data(), runs.size(), cols.data());
+      int rc = SDF_OK;
+      const char *call = "sdf_stats_columns_batch";
+      if (resident) {
+        // every chromosome the pieces name, once, straight from the mapped file (the .fai entry is the geometry)
+        std::map<std::string, int64_t> base;
+        for (size_t k = 0; k < n && rc == SDF_OK; k++) {
+          const Hit &h = in[pieces[k].src].h;
+          uint64_t *off[2] = {&tasks[k].a_off, &tasks[k].b_off};
+          const std::string *name[2] = {&h.query->name, &h.ref->name};
+          for (int side = 0; side < 2 && rc == SDF_OK; side++) {
+            auto it = base.find(*name[side]);
+            if (it == base.end()) {
+              FastaReference::Record r;
+              try {
+                r = fr.record(*name[side]);
+              } catch (...) {  // (a name the index does not know: the context goes with the run)
+                sdf_destroy(ctx);
+                throw;
+              }
+              int64_t at = 0;
+              call = "sdf_pool_append_fasta";
+              rc = sdf_pool_append_fasta(ctx, r.bytes, r.nbytes, r.entry->length, r.entry->line_blen, r.entry->line_len,
+                                         base.empty(), &at);
+              it = base.insert({*name[side], at}).first;
+            }
+            *off[side] += (uint64_t)it->second;
+          }
+        }
+        if (rc == SDF_OK) {
+          call = "sdf_stats_columns_pairs";
+          rc = sdf_stats_columns_pairs(ctx, tasks.data(), n, runs.data(), runs.size(), cols.data());
+        }
+      } else {
+        rc = sdf_stats_columns_batch(ctx, tasks.data(), n, pool.data(), pool.size(), runs.data(), runs.size(), cols.data());
+      }
       const std::string err = rc ? sdf_last_error(ctx) : "";
       sdf_destroy(ctx);
-      if (rc) throw std::string("sdf_stats_columns_batch: ") + err;
+      if (rc) throw std::string(call) + ": " + err;
     }
   }
 

@@ -963,7 +963,9 @@ extern "C" int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nby
     size_t free_b = 0, total_b = 0;
     SDF_HIP(hipMemGetInfo(&free_b, &total_b));
     const size_t exact = (grow_pool ? need + 64 : 0) + (grow_raw ? piece_raw + 64 : 0);
-    if (exact > free_b || exact < need) return invalid("the record does not fit the device's free memory beside the resident pool");
+    // (exact < need: the sum wrapped -- only where the pool itself grows; a record that fits the pool's headroom but needs a
+    // larger scratch buffer asks for piece_raw + 64 bytes, which may well be fewer than `need`)
+    if (exact > free_b || (grow_pool && exact < need)) return invalid("the record does not fit the device's free memory beside the resident pool");
     headroom = grow_pool && exact + std::min<size_t>((need + 64) / 2, (size_t)8 << 30) + ((size_t)64 << 20) <= free_b;
   }
   ctx->an_pool.new_call();
@@ -1684,8 +1686,9 @@ extern "C" int sdf_debug_chain_tree_script(sdf_ctx *ctx, const int32_t *pts, int
 }
 
 // ---- per-alignment columns of `stats generate` (reference: src/stats_main.cc:228-270) -------------------
-extern "C" int sdf_stats_columns_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, const char *d_seq_pool,
-                                        const uint32_t *d_cigar_pool, sdf_stats_cols *d_out, void *stream) {
+// the two launches of the stats kernels; rev: some task carries a strand bit (stats_cols.hip: the <true> kernels)
+static int stats_launch(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, const char *d_seq_pool, const uint32_t *d_cigar_pool,
+                        sdf_stats_cols *d_out, void *stream, bool rev) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
   if (n >= ((size_t)1 << 31) || (n && (!d_tasks || !d_out))) {
@@ -1703,14 +1706,27 @@ extern "C" int sdf_stats_columns_device(sdf_ctx *ctx, const sdf_stats_task *d_ta
   SDF_HIP(hipMemsetAsync(d_counter, 0, sizeof(unsigned), st));
   const unsigned group_max = ctx->cfg.stats_group_max >= 0 ? (unsigned)ctx->cfg.stats_group_max : sdf::STATS_GROUP_MAX;
   static_assert(sdf::STATS_WAVES == 4, "a workgroup is the four wavefronts of four consecutive alignments");
-  hipLaunchKernelGGL(sdf::stats_columns_kernel, dim3((unsigned)((n + sdf::STATS_WAVES - 1) / sdf::STATS_WAVES)),
+  hipLaunchKernelGGL(rev ? sdf::stats_columns_kernel<true> : sdf::stats_columns_kernel<false>,
+                     dim3((unsigned)((n + sdf::STATS_WAVES - 1) / sdf::STATS_WAVES)),
                      dim3(64 * sdf::STATS_WAVES), 0, st, d_tasks, (int)n, d_seq_pool, d_cigar_pool, d_out,
                      (sdf::StatsItem *)ctx->st_items.p, d_counter, kItems, group_max);
-  hipLaunchKernelGGL(sdf::stats_segments_kernel, dim3(2048), dim3(64 * sdf::STATS_WAVES), 0, st,
+  hipLaunchKernelGGL(rev ? sdf::stats_segments_kernel<true> : sdf::stats_segments_kernel<false>, dim3(2048), dim3(64 * sdf::STATS_WAVES), 0, st,
                      (const sdf::StatsItem *)ctx->st_items.p, d_counter, kItems, d_seq_pool, d_cigar_pool, d_out);
   SDF_HIP(hipGetLastError());
   if (!stream) SDF_HIP(hipStreamSynchronize(st));
   return SDF_OK;
+}
+
+extern "C" int sdf_stats_columns_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, const char *d_seq_pool,
+                                        const uint32_t *d_cigar_pool, sdf_stats_cols *d_out, void *stream) {
+  return stats_launch(ctx, d_tasks, n, d_seq_pool, d_cigar_pool, d_out, stream, false);
+}
+
+// ... on the resident pool, by range and strand (include/sedef_hip.h)
+extern "C" int sdf_stats_columns_pairs_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, int any_rc,
+                                              const uint32_t *d_cigar_pool, sdf_stats_cols *d_out, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  return stats_launch(ctx, d_tasks, n, (const char *)ctx->an_pool.p, d_cigar_pool, d_out, stream, any_rc != 0);
 }
 
 extern "C" int sdf_stats_columns_batch(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const char *seq_pool,
@@ -1754,6 +1770,57 @@ extern "C" int sdf_stats_columns_batch(sdf_ctx *ctx, const sdf_stats_task *tasks
   SDF_HIP(hipMemcpyAsync(down, ctx->st_out.p, nup * sizeof(sdf_stats_cols), hipMemcpyDeviceToHost, st));
   SDF_HIP(hipStreamSynchronize(st));
   static_assert(sizeof(sdf_stats_cols) == 16 * sizeof(int32_t), "sdf_stats_cols is sixteen counters");
+  for (size_t i = 0; i < n; i++)
+    if (out[i].flags) {
+      ctx->err = "alignment " + std::to_string(i) + ": the CIGAR does not fit its sequences";
+      return SDF_ERR_INVALID;
+    }
+  return SDF_OK;
+}
+
+extern "C" int sdf_stats_columns_pairs(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const uint32_t *cigar_pool,
+                                       size_t cigar_words, sdf_stats_cols *out) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (n >= ((size_t)1 << 31) || (n && (!tasks || !out)) || (!cigar_pool && cigar_words)) {
+    ctx->err = "invalid arguments";
+    return SDF_ERR_INVALID;
+  }
+  const size_t pool_bytes = ctx->pool_bytes;
+  bool any_rc = false;  // (the one scan of the tasks: a call without a reversed side gets the kernels as they were)
+  for (size_t i = 0; i < n; i++) {
+    const sdf_stats_task &t = tasks[i];
+    if (t.reserved & ~(uint32_t)(SDF_STATS_A_RC | SDF_STATS_B_RC)) {
+      ctx->err = "alignment " + std::to_string(i) + ": unknown stats task flag";
+      return SDF_ERR_UNSUPPORTED;
+    }
+    if (t.a_len > (1u << 24) || t.b_len > (1u << 24)) {
+      ctx->err = "stats columns implement sequences up to 16 Mb";
+      return SDF_ERR_UNSUPPORTED;
+    }
+    if (t.a_off > pool_bytes || t.a_len > pool_bytes - t.a_off || t.b_off > pool_bytes || t.b_len > pool_bytes - t.b_off) {
+      ctx->err = "alignment " + std::to_string(i) + ": sequence range outside the resident pool (sdf_pool_upload / sdf_pool_append_fasta)";
+      return SDF_ERR_INVALID;
+    }
+    if (t.cigar_off > cigar_words || t.n_cigar > cigar_words - t.cigar_off || t.n_cigar >= (1u << 31)) {
+      ctx->err = "alignment " + std::to_string(i) + ": CIGAR range outside its pool";
+      return SDF_ERR_INVALID;
+    }
+    any_rc |= t.reserved != 0;
+  }
+  if (n == 0) return SDF_OK;
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;  // (the pool's uploads were enqueued there)
+  SDF_HIP(ctx->st_tasks.reserve(n * sizeof(sdf_stats_task)));
+  SDF_HIP(ctx->st_cig.reserve(cigar_words * 4 + 16));
+  SDF_HIP(ctx->st_out.reserve(n * sizeof(sdf_stats_cols)));
+  SDF_HIP(hipMemcpyAsync(ctx->st_tasks.p, tasks, n * sizeof(sdf_stats_task), hipMemcpyHostToDevice, st));
+  if (cigar_words) SDF_HIP(hipMemcpyAsync(ctx->st_cig.p, cigar_pool, cigar_words * 4, hipMemcpyHostToDevice, st));
+  const int rc = stats_launch(ctx, (const sdf_stats_task *)ctx->st_tasks.p, n, (const char *)ctx->an_pool.p,
+                              (const uint32_t *)ctx->st_cig.p, (sdf_stats_cols *)ctx->st_out.p, st, any_rc);
+  if (rc != SDF_OK) return rc;
+  SDF_HIP(hipMemcpyAsync(out, ctx->st_out.p, n * sizeof(sdf_stats_cols), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
   for (size_t i = 0; i < n; i++)
     if (out[i].flags) {
       ctx->err = "alignment " + std::to_string(i) + ": the CIGAR does not fit its sequences";

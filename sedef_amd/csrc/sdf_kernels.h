@@ -119,8 +119,11 @@ struct StatsItem {  // a segment of a long alignment
   uint32_t task;  // the alignment it belongs to (0xffffffff: nothing to do)
   uint32_t pad;
 };
+// REV: some task of the launch carries SDF_STATS_A_RC / SDF_STATS_B_RC in `reserved`; <false> never reads the word
+template <bool REV>
 __global__ void stats_columns_kernel(const sdf_stats_task *, int, const char *, const uint32_t *, sdf_stats_cols *,
                                      StatsItem *, unsigned *, unsigned, unsigned);
+template <bool REV>
 __global__ void stats_segments_kernel(const StatsItem *, const unsigned *, unsigned, const char *, const uint32_t *,
                                       sdf_stats_cols *);
 

@@ -14,6 +14,11 @@
 // advances of its runs, STATS_SEG at a time, and leaves one work item per segment -- an alignment of its own: the sequences'
 // ranges the segment's runs consume -- in a list (stats_columns_kernel); a second launch of a fixed number of wavefronts
 // takes the items and adds their counters to the alignment's record (stats_segments_kernel).
+//
+// REV (both kernels are templates on it): some task of the launch has a side that is the reverse complement of its range
+// (SDF_STATS_A_RC / SDF_STATS_B_RC in sdf_stats_task::reserved; base i of such a side is rev_dna(pool[off + len - 1 - i])).
+// Only stats_fetch8 reads such a side differently; the <false> kernels never look at `reserved` and are the kernels as they
+// were before the bits existed.
 #include <hip/hip_runtime.h>
 
 #include "extz2_geom.h"
@@ -37,15 +42,48 @@ __device__ __forceinline__ int stats_wave_scan(int v) {  // inclusive prefix sum
 }
 __device__ __forceinline__ int stats_wave_sum(int v) { return __builtin_amdgcn_readlane(stats_wave_scan(v), 63); }
 
+// rev_dna (reference: src/common.h:72-87,93; indexed c & 127) of four characters in one 32-bit word, in the style of
+// count_word below: a flag in bit 7 of every byte.  A <-> T is ^ 0x15, C <-> G is ^ 0x04, the case bit stays; every byte that is
+// not ACGTacgt becomes 'N'.  All bytes of the result are below 0x80.
+__device__ __forceinline__ uint32_t stats_revcomp4(uint32_t x) {
+  constexpr uint32_t O = 0x01010101u, H = 0x80808080u;
+  auto ne = [](uint32_t v, uint32_t c) { return (v ^ (c * O)) + 0x7Fu * O; };  // bit 7: byte != c (bytes below 0x80)
+  x &= 0x7Fu * O;
+  const uint32_t u = x & 0xDFu * O;  // (only 'A' and 'a' become 'A', and so on: bit 5 is the case bit of a letter)
+  const uint32_t at = ~(ne(u, 'A') & ne(u, 'T')) & H, cg = ~(ne(u, 'C') & ne(u, 'G')) & H;
+  const uint32_t flip = (at >> 7) | (at >> 5) | (at >> 3) | (cg >> 5);  // 0x15 / 0x04 in the flagged bytes
+  const uint32_t known = at | cg, keep = known | (known - (known >> 7));  // 0xFF in the bytes that are ACGT of either case
+  return ((x ^ flip) & keep) | (('N' * O) & ~keep);
+}
+
 // Eight consecutive characters of a sequence, as many of them as the sequence still holds (the rest unspecified):
 // one unaligned 8-byte load, taken from the last eight bytes of the sequence when fewer remain.
+// rc (REV only; per lane): the sequence is the reverse complement of its range.  Its characters pos .. pos + 7 are the eight
+// pool bytes that END at slen - pos, last byte first: the same one load, two byte permutes and stats_revcomp4 on either half.
+// When fewer than eight remain the load takes the FIRST eight bytes of the range -- no load leaves [s, s + slen) -- and, once
+// reversed, the characters wanted are its high ones: the shift of the forward side.
 __device__ __forceinline__ uint64_t stats_ld8(const char *p) {
   uint64_t v;
   __builtin_memcpy(&v, p, 8);
   return v;
 }
-__device__ __forceinline__ uint64_t stats_fetch8(const char *s, int pos, int slen, bool wide) {
+template <bool REV>
+__device__ __forceinline__ uint64_t stats_fetch8(const char *s, int pos, int slen, bool wide, bool rc) {
   const int avail = slen - pos;
+  if (REV && rc) {
+    bool whole = avail >= 8;
+    uint64_t v = 0;
+    if (wide) {
+      v = stats_ld8(s + (whole ? avail - 8 : 0));
+      v = (uint64_t)__builtin_amdgcn_perm(0u, (uint32_t)(v >> 32), 0x00010203u) |
+          (uint64_t)__builtin_amdgcn_perm(0u, (uint32_t)v, 0x00010203u) << 32;
+    } else {
+      for (int i = 0; i < avail && i < 8; i++) v |= (uint64_t)(unsigned char)s[avail - 1 - i] << (8 * i);
+      whole = true;
+    }
+    v = (uint64_t)stats_revcomp4((uint32_t)v) | (uint64_t)stats_revcomp4((uint32_t)(v >> 32)) << 32;
+    return whole ? v : v >> (8 * (8 - avail));
+  }
   if (wide) {  // wave-uniform: the sequence holds eight bytes
     const bool whole = avail >= 8;
     const uint64_t v = stats_ld8(s + (whole ? pos : slen - 8));
@@ -59,6 +97,7 @@ __device__ __forceinline__ uint64_t stats_fetch8(const char *s, int pos, int sle
 constexpr uint64_t STATS_DASHES = 0x2D2D2D2D2D2D2D2DULL;
 
 // the counters of one alignment (or segment), summed over the wavefront: v[0..11], and whether its CIGAR fits
+template <bool REV>
 __device__ __forceinline__ int stats_count_alignment(const sdf_stats_task &T, const char *__restrict__ pool,
                                                      const uint32_t *__restrict__ cigars, int *unit, int *sa, int *sb, int *sl,
                                                      const int lane, int (&v)[12]) {
@@ -66,6 +105,9 @@ __device__ __forceinline__ int stats_count_alignment(const sdf_stats_task &T, co
   const uint32_t *cg = cigars + T.cigar_off;
   const int n_cigar = (int)T.n_cigar, a_len = (int)T.a_len, b_len = (int)T.b_len;
   const bool wide_a = a_len >= 8, wide_b = b_len >= 8;
+  // (one task per wavefront: its strand bits are wave-uniform)
+  const uint32_t strand = REV ? (uint32_t)__builtin_amdgcn_readfirstlane((int)T.reserved) : 0u;
+  const bool rc_a = (strand & SDF_STATS_A_RC) != 0, rc_b = (strand & SDF_STATS_B_RC) != 0;
 
   // mismatchB = alnB - matchB, transversionsB = mismatchB - transitionsB, mismatches = alnB - matches: derived at the end
   int indel_a = 0, indel_b = 0, aln_b = 0, match_b = 0, ts = 0, up_a = 0, up_b = 0, up_m = 0;
@@ -85,8 +127,8 @@ __device__ __forceinline__ int stats_count_alignment(const sdf_stats_task &T, co
     const int d = 8 * (u - unit[j]), pa = sa[j], pb = sb[j];
     const int left = sl[j] - d;
     cnt = valid ? (left < 8 ? left : 8) : 0;
-    wa = pa >= 0 ? stats_fetch8(a, pa + d, a_len, wide_a) : STATS_DASHES;
-    wb = pb >= 0 ? stats_fetch8(b, pb + d, b_len, wide_b) : STATS_DASHES;
+    wa = pa >= 0 ? stats_fetch8<REV>(a, pa + d, a_len, wide_a, rc_a) : STATS_DASHES;
+    wb = pb >= 0 ? stats_fetch8<REV>(b, pb + d, b_len, wide_b, rc_b) : STATS_DASHES;
     const uint64_t keep = cnt >= 8 ? ~0ULL : (1ULL << (8 * cnt)) - 1ULL;
     wa = (wa & keep) | (STATS_DASHES & ~keep);
     wb = (wb & keep) | (STATS_DASHES & ~keep);
@@ -229,6 +271,8 @@ __device__ __forceinline__ int stats_wave_max(int v) {
 }
 
 // T: the task of this lane's group (n_cigar = 0, a_len = b_len = 0 for a group without one).  v: the group's sums.
+// (REV: every group has its own task and so its own strand bits -- the choice in stats_fetch8 is per lane here)
+template <bool REV>
 __device__ __forceinline__ int stats_count_groups(const sdf_stats_task &T, const char *__restrict__ pool,
                                                   const uint32_t *__restrict__ cigars, int *unit, int *sa, int *sb, int *sl,
                                                   const int lane, int (&v)[12]) {
@@ -237,6 +281,7 @@ __device__ __forceinline__ int stats_count_groups(const sdf_stats_task &T, const
   const uint32_t *cg = cigars + T.cigar_off;
   const int n_cigar = (int)T.n_cigar, a_len = (int)T.a_len, b_len = (int)T.b_len;
   const bool wide_a = a_len >= 8, wide_b = b_len >= 8;
+  const bool rc_a = REV && (T.reserved & SDF_STATS_A_RC) != 0, rc_b = REV && (T.reserved & SDF_STATS_B_RC) != 0;
   int indel_a = 0, indel_b = 0, aln_b = 0, match_b = 0, ts = 0, up_a = 0, up_b = 0, up_m = 0;
   int matches = 0, gaps = 0, gap_bases = 0;
   int ia = 0, ib = 0, bad = 0;  // uniform inside a group
@@ -334,8 +379,8 @@ __device__ __forceinline__ int stats_count_groups(const sdf_stats_task &T, const
         const int d = 8 * (u - unit[j]), pa = sa[j], pb = sb[j];
         const int left = sl[j] - d;
         cnt = left < 8 ? left : 8;
-        if (pa >= 0) wa = stats_fetch8(a, pa + d, a_len, wide_a);
-        if (pb >= 0) wb = stats_fetch8(b, pb + d, b_len, wide_b);
+        if (pa >= 0) wa = stats_fetch8<REV>(a, pa + d, a_len, wide_a, rc_a);
+        if (pb >= 0) wb = stats_fetch8<REV>(b, pb + d, b_len, wide_b, rc_b);
         const uint64_t keep = cnt >= 8 ? ~0ULL : (1ULL << (8 * cnt)) - 1ULL;
         wa = (wa & keep) | (STATS_DASHES & ~keep);
         wb = (wb & keep) | (STATS_DASHES & ~keep);
@@ -364,6 +409,9 @@ __device__ __forceinline__ sdf_stats_cols stats_record(const int (&v)[12], const
 // One wavefront per alignment.  items / counter / cap: the list for the segments of long alignments (items == nullptr:
 // every alignment is counted by its own wavefront).
 // one alignment by a whole wavefront (the long ones: into segments for the second launch)
+// REV: a segment that consumes [ia, ia + da) of a reversed side lies at the range's bytes [len - ia - da, len - ia), and its
+// item carries the task's strand bits; whether the CIGAR fits does not depend on the strand.
+template <bool REV>
 __device__ __forceinline__ void stats_one_task(const int task, const sdf_stats_task *__restrict__ tasks, const char *__restrict__ pool,
                                                const uint32_t *__restrict__ cigars, sdf_stats_cols *__restrict__ out,
                                                StatsItem *__restrict__ items, unsigned *__restrict__ counter, unsigned cap,
@@ -402,6 +450,11 @@ __device__ __forceinline__ void stats_one_task(const int task, const sdf_stats_t
           it.t.a_off = T.a_off + ia, it.t.b_off = T.b_off + ib;
           it.t.a_len = (uint32_t)da, it.t.b_len = (uint32_t)db;
           it.t.cigar_off = T.cigar_off + k0, it.t.n_cigar = nk, it.t.reserved = 0;
+          if (REV && !bad) {  // (bad: the item is never counted, and the ranges below need ia + da <= a_len, ib + db <= b_len)
+            if (T.reserved & SDF_STATS_A_RC) it.t.a_off = T.a_off + (T.a_len - ia - (uint64_t)da);
+            if (T.reserved & SDF_STATS_B_RC) it.t.b_off = T.b_off + (T.b_len - ib - (uint64_t)db);
+            it.t.reserved = T.reserved & (SDF_STATS_A_RC | SDF_STATS_B_RC);
+          }
           it.task = bad ? 0xffffffffu : (uint32_t)task;  // (nothing after a segment that does not fit is counted)
           it.pad = 0;
           items[first + sg] = it;
@@ -418,13 +471,14 @@ __device__ __forceinline__ void stats_one_task(const int task, const sdf_stats_t
     for (unsigned sg = lane; first < cap && sg < cap - first; sg += 64) items[first + sg].task = 0xffffffffu;
   }
   int v[12];
-  const int bad = stats_count_alignment(T, pool, cigars, s_unit_w, s_a_w, s_b_w, s_len_w, lane, v);
+  const int bad = stats_count_alignment<REV>(T, pool, cigars, s_unit_w, s_a_w, s_b_w, s_len_w, lane, v);
   if (lane == 0) out[task] = stats_record(v, bad);
 }
 
 // One wavefront per alignment -- except that four consecutive SHORT alignments (at most `group_max` runs each: a chunk or two
 // of sixteen) are taken side by side by one wavefront, in its four rows of sixteen lanes.  items / counter / cap: the list
 // for the segments of long alignments (items == nullptr: every alignment is counted whole).
+template <bool REV>
 __global__ __launch_bounds__(64 * STATS_WAVES, 6) void stats_columns_kernel(const sdf_stats_task *__restrict__ tasks, int n,
                                                                          const char *__restrict__ pool,
                                                                          const uint32_t *__restrict__ cigars,
@@ -449,14 +503,15 @@ __global__ __launch_bounds__(64 * STATS_WAVES, 6) void stats_columns_kernel(cons
   if (group_max && !__any(T.n_cigar > group_max)) {
     if (task != task0) return;
     int v[12];
-    const int bad = stats_count_groups(T, pool, cigars, s_unit[wv], s_a[wv], s_b[wv], s_len[wv], lane, v);
+    const int bad = stats_count_groups<REV>(T, pool, cigars, s_unit[wv], s_a[wv], s_b[wv], s_len[wv], lane, v);
     if ((lane & 15) == 0 && mine < n) out[mine] = stats_record(v, bad);
     return;
   }
-  stats_one_task(task, tasks, pool, cigars, out, items, counter, cap, s_unit[wv], s_a[wv], s_b[wv], s_len[wv], lane);
+  stats_one_task<REV>(task, tasks, pool, cigars, out, items, counter, cap, s_unit[wv], s_a[wv], s_b[wv], s_len[wv], lane);
 }
 
 // The segments of the long alignments: wavefront g of the grid takes items g, g + G, ... and adds their counters up.
+template <bool REV>
 __global__ __launch_bounds__(64 * STATS_WAVES, 6) void stats_segments_kernel(const StatsItem *__restrict__ items,
                                                                           const unsigned *__restrict__ counter, unsigned cap,
                                                                           const char *__restrict__ pool,
@@ -469,7 +524,7 @@ __global__ __launch_bounds__(64 * STATS_WAVES, 6) void stats_segments_kernel(con
     const StatsItem it = items[i];
     if (it.task == 0xffffffffu) continue;  // (wave-uniform)
     int v[12];
-    const int bad = stats_count_alignment(it.t, pool, cigars, s_unit[wv], s_a[wv], s_b[wv], s_len[wv], lane, v);
+    const int bad = stats_count_alignment<REV>(it.t, pool, cigars, s_unit[wv], s_a[wv], s_b[wv], s_len[wv], lane, v);
     const sdf_stats_cols R = stats_record(v, bad);
     const int32_t *src = reinterpret_cast<const int32_t *>(&R);
     int32_t *dst = reinterpret_cast<int32_t *>(&out[it.task]);
@@ -477,5 +532,14 @@ __global__ __launch_bounds__(64 * STATS_WAVES, 6) void stats_segments_kernel(con
     if (lane == 15 && bad) atomicOr(dst + 15, 1);
   }
 }
+
+template __global__ void stats_columns_kernel<false>(const sdf_stats_task *, int, const char *, const uint32_t *, sdf_stats_cols *,
+                                                     StatsItem *, unsigned *, unsigned, unsigned);
+template __global__ void stats_columns_kernel<true>(const sdf_stats_task *, int, const char *, const uint32_t *, sdf_stats_cols *,
+                                                    StatsItem *, unsigned *, unsigned, unsigned);
+template __global__ void stats_segments_kernel<false>(const StatsItem *, const unsigned *, unsigned, const char *, const uint32_t *,
+                                                      sdf_stats_cols *);
+template __global__ void stats_segments_kernel<true>(const StatsItem *, const unsigned *, unsigned, const char *, const uint32_t *,
+                                                     sdf_stats_cols *);
 
 }  // namespace sdf

@@ -37,6 +37,9 @@ STATS_COLS_DTYPE = np.dtype([(f, "<i4") for f in (
     "indel_a", "indel_b", "aln_b", "match_b", "mismatch_b", "transitions_b", "transversions_b", "uppercase_a",
     "uppercase_b", "uppercase_matches", "matches", "mismatches", "gaps", "gap_bases", "span", "flags")])
 assert STATS_TASK_DTYPE.itemsize == 40 and STATS_COLS_DTYPE.itemsize == 64
+# strand bits of a stats task on the resident pool (include/sedef_hip.h: SDF_STATS_A_RC / SDF_STATS_B_RC; in `reserved`,
+# stats_columns_pairs only)
+STATS_A_RC, STATS_B_RC = 0x1, 0x2
 
 
 class SdfError(RuntimeError):
@@ -131,6 +134,11 @@ def load_library():
     L.sdf_stats_columns_device.restype = C.c_int
     L.sdf_stats_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]
+    L.sdf_stats_columns_pairs.restype = C.c_int
+    L.sdf_stats_columns_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdf_stats_columns_pairs_device.restype = C.c_int
+    L.sdf_stats_columns_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -546,6 +554,33 @@ class Extz2Engine:
     def stats_columns_device(self, d_tasks, n, d_pool, d_cigar, d_out, stream=None):
         """The same over device pointers (ints); asynchronous on `stream` when one is given."""
         self._check(self.lib.sdf_stats_columns_device(self.ctx, d_tasks, n, d_pool, d_cigar, d_out, stream))
+
+    def stats_columns_pairs(self, tasks, cigar, a_rc=None, b_rc=None, out=None):
+        """sdf_stats_columns_pairs: a_off / b_off of the tasks (STATS_TASK_DTYPE) are byte offsets into the resident character
+        pool (pool_upload / pool_append_fasta), cigar the uint32 runs the tasks' cigar_off / n_cigar name.  a_rc / b_rc: per
+        task (or one for all), that side is the reverse complement of its range (STATS_A_RC / STATS_B_RC are or-ed into
+        `reserved`).  out: a STATS_COLS_DTYPE array to fill (it holds the records also when the call raises for a CIGAR
+        that does not fit).  Returns the STATS_COLS_DTYPE array."""
+        tasks = np.ascontiguousarray(tasks, dtype=STATS_TASK_DTYPE)
+        if a_rc is not None or b_rc is not None:
+            tasks = tasks.copy()
+            for side, bit in ((a_rc, STATS_A_RC), (b_rc, STATS_B_RC)):
+                if side is not None:
+                    tasks["reserved"] |= np.where(np.broadcast_to(np.asarray(side, bool), tasks.shape), bit, 0).astype(np.uint32)
+        cig = np.ascontiguousarray(cigar, dtype=np.uint32)
+        n = len(tasks)
+        if out is None:
+            out = np.zeros(n, STATS_COLS_DTYPE)
+        assert out.dtype == STATS_COLS_DTYPE and len(out) == n and out.flags.c_contiguous
+        self._check(self.lib.sdf_stats_columns_pairs(self.ctx, tasks.ctypes.data if n else None, n,
+                                                     cig.ctypes.data if len(cig) else None, len(cig),
+                                                     out.ctypes.data if n else None))
+        return out
+
+    def stats_columns_pairs_device(self, d_tasks, n, any_rc, d_cigar, d_out, stream=None):
+        """The same over device pointers (ints) of tasks, runs and records; asynchronous on `stream` when one is given
+        (pool_sync() first: the pool's uploads run on the context's stream).  any_rc: some task may carry a strand bit."""
+        self._check(self.lib.sdf_stats_columns_pairs_device(self.ctx, d_tasks, n, int(bool(any_rc)), d_cigar, d_out, stream))
 
     def last_ms(self, which):
         return float(self.lib.sdf_last_ms(self.ctx, which))

@@ -195,18 +195,31 @@ def merge(bed_lines, merge_dist=250):
 
 
 def stats_generate(ref_path, bed_path, out_path, max_ok_gap=-1, min_split=1000, uppercase=100, max_error=0.5,
-                   test_cols=None, device=0):
+                   test_cols=None, device=0, resident=False):
     """`sedef stats generate` (reference: src/stats_main.cc:339-389): the table of the final calls.  test_cols: a column
-    walker with the oracle's signature (oracle/stats_oracle.c) instead of the device.  Returns (lines, hits, pieces, columns)."""
+    walker with the oracle's signature (oracle/stats_oracle.c) instead of the device.  resident=True (or SDF_STATS_RESIDENT=1
+    in the environment): the chromosomes are uploaded once, as the file has them, and the pieces are counted by base range
+    and strand (sdf_stats_columns_pairs); ignored with test_cols.  Returns (lines, hits, pieces, columns)."""
     lib = load_host()
     st = (C.c_longlong * 3)()
-    lib.sdfh_stats_generate.restype = C.c_long
-    lib.sdfh_stats_generate.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
-                                        C.c_int, C.c_void_p]
-    n = lib.sdfh_stats_generate(ref_path.encode(), bed_path.encode(), out_path.encode(), max_ok_gap, min_split, uppercase,
-                                max_error, test_cols, device, st)
+    lib.sdfh_stats_generate_resident.restype = C.c_long
+    lib.sdfh_stats_generate_resident.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                 C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    n = lib.sdfh_stats_generate_resident(ref_path.encode(), bed_path.encode(), out_path.encode(), max_ok_gap, min_split,
+                                         uppercase, max_error, test_cols, device, int(bool(resident)), st)
     _err(lib, min(n, 0))
     return (int(n),) + tuple(int(x) for x in st)
+
+
+def stats_piece_range(start, end, s, e, rc):
+    """stats_piece_range (csrc/host/stats.cc): columns [s, e) of a side fetched from [start, end) of its chromosome and, with
+    rc, reverse-complemented -> (first base of the range in the chromosome, length)."""
+    lib = load_host()
+    first = C.c_longlong(0)
+    lib.sdfh_stats_piece_range.restype = C.c_int
+    lib.sdfh_stats_piece_range.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]
+    n = lib.sdfh_stats_piece_range(int(start), int(end), int(s), int(e), int(bool(rc)), C.byref(first))
+    return int(first.value), int(n)
 
 
 def format_double(x):

@@ -183,8 +183,12 @@ int sdf_reserve(sdf_ctx *ctx, size_t max_tasks, size_t max_bases, size_t workspa
  * last call (index xcd << 9 | se << 6 | cu << 2 | simd) and the counters are cleared; the first call (out may be NULL) switches
  * the counting on for the process. */
 int sdf_debug_placement(sdf_ctx *ctx, uint32_t *out);
-/* Device bytes the context holds at this moment (buffers in use, outgrown ones not yet freed). */
+/* Device bytes the context holds at this moment: every device buffer of it and of the contexts it owns (buffers in use,
+ * outgrown ones not yet freed). */
 size_t sdf_device_bytes(const sdf_ctx *ctx);
+/* Debug: device bytes all contexts of the process hold in their buffers at this moment -- what their allocations obtained
+ * minus what they gave back.  The sum of sdf_device_bytes over the live contexts; what it was before, once they are gone. */
+size_t sdf_debug_live_device_bytes(void);
 const char *sdf_last_error(const sdf_ctx *ctx);
 
 /* ---- packed sequence format --------------------------------------------------------------

@@ -1,10 +1,8 @@
-// The C ABI (include/sedef_hip.h): context, packing helpers and the batch entry points.
+// The C ABI (include/sedef_hip.h): packing helpers and the batch entry points (the context itself: sdf_context.hip).
 // Replaces the call site of ksw_extz2_sse in align_helper (reference: src/align.cc:39-68) with a
 // batched device path.  No CPU fallback exists here: every DP cell is computed by a gfx950 kernel.
 // Planning lives in sdf_plan.hip, uploads and launches in sdf_launch.hip (same translation unit, see sdf_unity.hip).
 #include <hip/hip_runtime.h>
-
-#include <sched.h>
 
 #include <atomic>
 #include <cstring>
@@ -19,206 +17,6 @@
 #include "stripe_sync.h"
 
 using namespace sdf;
-
-namespace {
-std::string g_err;  // error of the last failed sdf_create
-}  // namespace
-
-extern "C" int sdf_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-extern "C" const char *sdf_last_error(const sdf_ctx *ctx) {
-  return ctx ? ctx->err.c_str() : g_err.c_str();
-}
-
-namespace {
-std::atomic<int> g_live_contexts{0};
-// CPUs this process may really use: the affinity mask capped by the cgroup's CPU quota
-int usable_cpus() {
-  int n = (int)std::thread::hardware_concurrency();
-  cpu_set_t set;
-  if (sched_getaffinity(0, sizeof(set), &set) == 0) n = std::min(n > 0 ? n : CPU_COUNT(&set), CPU_COUNT(&set));
-  if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {  // cgroup v2: "<quota> <period>" or "max <period>"
-    char q[32];
-    long period = 0;
-    if (fscanf(f, "%31s %ld", q, &period) == 2 && strcmp(q, "max") != 0 && period > 0)
-      n = std::min(n, (int)((atol(q) + period / 2) / period));
-    fclose(f);
-  }
-  return std::max(n, 1);
-}
-}  // namespace
-
-extern "C" const sdf_config *sdf_get_config(const sdf_ctx *ctx) { return ctx ? &ctx->cfg : nullptr; }
-
-extern "C" sdf_ctx *sdf_create(int device, size_t workspace_bytes) { return sdf_create_cfg(device, workspace_bytes, nullptr); }
-
-extern "C" sdf_ctx *sdf_create_cfg(int device, size_t workspace_bytes, const sdf_config *cfg_in) {
-  sdf_config cfg;
-  if (cfg_in) {
-    if (cfg_in->size != sizeof(sdf_config)) {
-      g_err = "sdf_create_cfg: the configuration was not initialised by sdf_config_default / sdf_config_from_env (size field)";
-      return nullptr;
-    }
-    cfg = *cfg_in;
-  } else {
-    char why[256];
-    if (sdf_config_from_env(&cfg, why, sizeof why) != SDF_OK) {  // (a typo in an SDF_* variable is an error, not a silent default)
-      g_err = std::string("environment: ") + why;
-      return nullptr;
-    }
-  }
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0) {
-    g_err = "no HIP device available (this library has no CPU fallback)";
-    return nullptr;
-  }
-  if (device < 0 || device >= n) {
-    g_err = "device ordinal out of range";
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_err = "hipSetDevice failed";
-    return nullptr;
-  }
-  const auto t_create = std::chrono::steady_clock::now();
-  sdf_ctx *ctx = new sdf_ctx();
-  ctx->device = device;
-  ctx->cfg = cfg;
-  ctx->pipeline_ok = cfg.pipeline != 0;
-  if (cfg.debug_timing) g_debug_timing.store(true, std::memory_order_relaxed);
-  if (cfg.debug_plan) {
-    std::string dump(sdf_config_dump(&cfg, nullptr, 0), '\0');
-    sdf_config_dump(&cfg, &dump[0], dump.size());
-    fprintf(stderr, "[sdf_create device %d: configuration]\n%s", device, dump.c_str());
-  }
-  if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-    g_err = "hipStreamCreate failed";
-    delete ctx;
-    return nullptr;
-  }
-  auto lap = [&](const char *what) {
-    if (cfg.debug_timing)
-      fprintf(stderr, "[sdf_create %s at %.1f ms]\n", what,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count());
-  };
-  lap("first stream");
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  lap("mem info");
-  // (0: half of the free HBM -- the workspace is allocated by NEED, region by region (cut_batch), so a large budget costs a
-  // small batch nothing, and a batch of long banded tasks -- BASELINE configs[4] at 100,000 tasks: 131 GB of flags -- is not cut
-  // into more, smaller chunks because of a constructor default: 64 GiB until round 4, 252 ms against 201 at 128 GiB)
-  size_t budget = workspace_bytes ? workspace_bytes : free_b ? free_b / 2 : (size_t)64 << 30;
-  if (cfg.workspace_gib > 0) budget = (size_t)(cfg.workspace_gib * 1073741824.0);  // (overrides the caller's figure: experiments with the stage driver)
-  if (free_b && budget > free_b / 2) budget = free_b / 2;
-  ctx->ws_budget = budget;
-  // Every kernel that takes dynamic LDS may have up to 160 KiB of it.  The first five, the general kernel's LDS-resident
-  // instantiations, decide what the planner may ask for: max_dyn_lds is raised only when all of them accept it.
-  const int want_lds = 160 * 1024;
-#define SDF_K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
-  const void *const dyn_lds_kernels[] = {
-      SDF_K(extz2_general_kernel<64, false, false>), SDF_K(extz2_general_kernel<256, false, false>),
-      SDF_K(extz2_general_kernel<1024, false, false>), SDF_K(extz2_general_kernel<1024, false, true>),
-      SDF_K(extz2_general_kernel<256, false, true>),
-      SDF_K(extz2_wave_kernel<1, false>), SDF_K(extz2_wave_kernel<1, true>), SDF_K(extz2_wave_kernel<2, false>),
-      SDF_K(extz2_wave_kernel<2, true>), SDF_K(extz2_wave_kernel<3, false>), SDF_K(extz2_wave_kernel<3, true>),
-      SDF_K(extz2_wave_kernel<6, false>), SDF_K(extz2_wave_kernel<6, true>), SDF_K(extz2_wave_kernel<4, false>),
-      SDF_K(extz2_wave_kernel<4, true>), SDF_K(extz2_wave_kernel<8, false>), SDF_K(extz2_wave_kernel<8, true>),
-      SDF_K(extz2_pair_kernel<1, false, false>), SDF_K(extz2_pair_kernel<1, true, false>),
-      SDF_K(extz2_pair_kernel<2, false, false>), SDF_K(extz2_pair_kernel<2, true, false>),
-      SDF_K(extz2_pair_kernel<3, false, false>), SDF_K(extz2_pair_kernel<3, true, false>),
-      SDF_K(extz2_pair_kernel<4, false, false>), SDF_K(extz2_pair_kernel<4, true, false>),
-      SDF_K(extz2_pair_kernel<6, false, false>), SDF_K(extz2_pair_kernel<6, true, false>),
-      SDF_K(extz2_pair_kernel<8, false, false>), SDF_K(extz2_pair_kernel<8, true, false>),
-      SDF_K(extz2_pair_kernel<3, true, true>), SDF_K(extz2_pair_kernel<6, true, true>),
-      SDF_K(extz2_pair_mixed_kernel<2>), SDF_K(extz2_pair_mixed_kernel<3>), SDF_K(extz2_pair_mixed_kernel<4>),
-      SDF_K(extz2_pair_mixed_kernel<5>), SDF_K(extz2_pair_mixed_kernel<6>), SDF_K(extz2_pair_mixed_kernel<8>),
-      SDF_K(extz2_pair_mixed_kernel<9>),
-      SDF_K(extz2_stripe_kernel<1>), SDF_K(extz2_stripe_kernel<2>), SDF_K(extz2_stripe_kernel<4>),
-      SDF_K(extz2_bstripe_kernel<1>), SDF_K(extz2_bstripe_kernel<2>), SDF_K(extz2_bstripe_kernel<4>),
-      SDF_K(extz2_strip_kernel), SDF_K(extz2_lane_kernel)};
-#undef SDF_K
-  bool general_ok = true;
-  for (size_t i = 0; i < sizeof(dyn_lds_kernels) / sizeof(dyn_lds_kernels[0]); ++i) {
-    const bool ok = hipFuncSetAttribute(dyn_lds_kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, want_lds) == hipSuccess;
-    if (i < 5) general_ok = general_ok && ok;
-  }
-  if (general_ok) ctx->max_dyn_lds = want_lds;
-  (void)hipGetLastError();
-  // (per context, hence per device: a process-wide once-flag would leave a second GPU's copy of the kernel at 64 KiB)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sdf::chain_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            std::max(ctx->max_dyn_lds, 65536));
-  (void)hipGetLastError();
-  lap("attributes");
-  if (hipStreamCreateWithFlags(&ctx->dp_stream[0], hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->dp_stream[1], hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->tb_stream, hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->pipeline_ok = false;
-  }
-  // (three streams of our own: the runtime multiplexes streams onto GPU_MAX_HW_QUEUES -- default 4 -- hardware
-  // queues, and two of ours landing on one queue serialises what the pipeline wants side by side; with the
-  // caller's stream that makes four)
-  g_live_contexts.fetch_add(1);
-  if (cfg.debug_timing)
-    fprintf(stderr, "[sdf_create device %d: %.1f ms]\n", device,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count());
-  return ctx;
-}
-
-void mark_internal_context(sdf_ctx *c) {
-  if (!c || c->is_part) return;
-  c->is_part = true;
-  g_live_contexts.fetch_sub(1);
-}
-
-extern "C" void sdf_destroy(sdf_ctx *ctx) {
-  if (!ctx) return;
-  if (!ctx->is_part) g_live_contexts.fetch_sub(1);
-  (void)hipSetDevice(ctx->device);
-  for (hipStream_t q : {ctx->stream, ctx->dp_stream[0], ctx->dp_stream[1], ctx->tb_stream, ctx->aux_stream[0],
-                        ctx->aux_stream[1], ctx->aux_stream[2], ctx->aux_stream[3]})
-    if (q) (void)hipStreamSynchronize(q);
-  for (hipStream_t q : ctx->wide_stream)
-    if (q) (void)hipStreamSynchronize(q);
-  for (auto ev : ctx->events) (void)hipEventDestroy(ev);
-  for (DevBuf *b : {&ctx->an_pool, &ctx->an_pairs, &ctx->an_keys, &ctx->an_keys2, &ctx->an_q, &ctx->an_off, &ctx->an_flag,
-                    &ctx->an_pos, &ctx->an_cand, &ctx->an_out, &ctx->an_tmp, &ctx->an_outoff, &ctx->ch_an, &ctx->ch_off,
-                    &ctx->ch_wsoff, &ctx->ch_work, &ctx->ch_path, &ctx->ch_bounds, &ctx->ch_nb, &ctx->ch_which, &ctx->st_tasks, &ctx->st_pool,
-                    &ctx->st_cig, &ctx->st_out})
-    b->release();
-  for (DevBuf *b : {&ctx->dir_ws, &ctx->stage_ws, &ctx->plan_buf, &ctx->order_buf, &ctx->misc_buf, &ctx->gstate_buf,
-                    &ctx->h_pool, &ctx->h_out, &ctx->h_brief, &ctx->h_cig, &ctx->rr_out, &ctx->rr_cig, &ctx->rr_map, &ctx->ln_recs,
-                    &ctx->ln_keys, &ctx->ln_vals, &ctx->ln_sizes, &ctx->ln_tmp})
-    b->release();
-  if (ctx->lane_stream) (void)hipStreamDestroy(ctx->lane_stream);
-  ctx->host_lane.release();
-  ctx->host_an.release();
-  ctx->host_chars.release();
-  ctx->pk_recs.release();
-  ctx->fa_raw.release();
-  if (ctx->rerun_ctx) sdf_destroy(ctx->rerun_ctx);
-  if (ctx->part_ctx) sdf_destroy(ctx->part_ctx);
-  if (ctx->part_ev) (void)hipEventDestroy(ctx->part_ev);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  for (hipStream_t s : {ctx->dp_stream[0], ctx->dp_stream[1], ctx->tb_stream, ctx->aux_stream[0], ctx->aux_stream[1],
-                        ctx->aux_stream[2], ctx->aux_stream[3]})
-    if (s) (void)hipStreamDestroy(s);
-  for (hipStream_t s : ctx->wide_stream)
-    if (s) (void)hipStreamDestroy(s);
-  if (!ctx->pool_shared) delete ctx->pool;
-  delete ctx->cut;
-  ctx->host_plan.release();
-  ctx->host_order.release();
-  ctx->host_pool.release();
-  ctx->host_out.release();
-  delete ctx;
-}
 
 extern "C" size_t sdf_packed_words(int32_t len) {
   if (len <= 0) return 0;
@@ -284,16 +82,6 @@ extern "C" int64_t sdf_band_cells(int32_t qlen, int32_t tlen, int32_t w) {
   }
   return cells;
 }
-
-extern "C" float sdf_last_ms(const sdf_ctx *ctx, int which) {
-  if (!ctx || which < 0 || which > 6) return 0.f;
-  return ctx->ms[which];
-}
-
-extern "C" int sdf_last_launches(const sdf_ctx *ctx) { return ctx ? ctx->launches : 0; }
-extern "C" long long sdf_last_paired(const sdf_ctx *ctx) { return ctx ? ctx->paired : 0; }
-extern "C" long long sdf_last_reran(const sdf_ctx *ctx) { return ctx ? ctx->reran : 0; }
-extern "C" long long sdf_last_lane_tasks(const sdf_ctx *ctx) { return ctx ? ctx->lane_tasks : 0; }
 
 namespace {
 
@@ -413,11 +201,9 @@ static int batch_part(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks
   ctx->launches = 0;
   ctx->paired = 0;
   // (nothing of this context's earlier calls is in flight: what they outgrew is idle now -- sdf_ctx.h: DevBuf)
-  for (DevBuf *b : {&ctx->dir_ws, &ctx->stage_ws, &ctx->plan_buf, &ctx->order_buf, &ctx->gstate_buf, &ctx->h_pool, &ctx->h_out,
-                    &ctx->h_brief, &ctx->h_cig, &ctx->ln_recs, &ctx->ln_keys, &ctx->ln_vals, &ctx->ln_sizes, &ctx->ln_tmp})
-    b->new_call();
+  for_each_device_buffer(ctx, [](DevBuf &b) { b.new_call(); }, BufGroup::BatchCall);
   const auto host_t0 = std::chrono::steady_clock::now();
-  auto host_ms = [&] { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - host_t0).count(); };
+  auto host_ms = [&] { return (float)ms_since(host_t0); };
   run.ctx = ctx;
   run.st = st;
   run.d_pool = d_pool;
@@ -609,7 +395,7 @@ extern "C" int sdf_extz2_batch_device(sdf_ctx *ctx, const sdf_scoring *sc, const
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
   const auto host_t0 = std::chrono::steady_clock::now();
-  auto host_ms = [&] { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - host_t0).count(); };
+  auto host_ms = [&] { return (float)ms_since(host_t0); };
   if (cigar_used) *cigar_used = 0;
   if (n == 0) return SDF_OK;
   if (!tasks || !d_out || n > 0x7fffffffu) {
@@ -858,11 +644,8 @@ static int batch_host_tail(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *
   }
   if (dbg_t) {
     const auto dbg3 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-      return std::chrono::duration<double, std::milli>(b - a).count();
-    };
     fprintf(stderr, "[%s n=%zu words=%zu cap=%zu used=%zu] pack %.1f ms, h2d+device %.1f ms (plan %.1f, dp %.1f, tb %.1f), d2h %.1f ms%s\n",
-            what, n, words, cigar_cap, used, ms(dbg0, dbg1), ms(dbg1, dbg2), ctx->ms[4], ctx->ms[0], ctx->ms[1], ms(dbg2, dbg3),
+            what, n, words, cigar_cap, used, ms_between(dbg0, dbg1), ms_between(dbg1, dbg2), ctx->ms[4], ctx->ms[0], ctx->ms[1], ms_between(dbg2, dbg3),
             ctx->reran ? (", " + std::to_string(ctx->reran) + " tasks given up by a stripe wait and run again").c_str() : "");
   }
   return SDF_OK;
@@ -900,7 +683,7 @@ extern "C" char *sdf_pool_host(sdf_ctx *ctx, size_t bytes) {
   if (!ctx->pool_bytes) (void)ctx->an_pool.reserve(bytes + 64);
   if (ctx->cfg.debug_timing && ctx->host_chars.cap != had)
     fprintf(stderr, "[sdf_pool_host %zu MiB %s in %.1f ms]\n", ctx->host_chars.cap >> 20, ctx->host_chars.registered ? "registered huge pages" : "hipHostMalloc",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            ms_since(t0));
   return (char *)ctx->host_chars.p;
 }
 
@@ -968,8 +751,7 @@ extern "C" int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nby
     if (exact > free_b || (grow_pool && exact < need)) return invalid("the record does not fit the device's free memory beside the resident pool");
     headroom = grow_pool && exact + std::min<size_t>((need + 64) / 2, (size_t)8 << 30) + ((size_t)64 << 20) <= free_b;
   }
-  ctx->an_pool.new_call();
-  ctx->fa_raw.new_call();
+  for_each_device_buffer(ctx, [](DevBuf &b) { b.new_call(); }, BufGroup::Pool);
   if (grow_pool) {  // (the bases resident move to the larger buffer; the outgrown one is retired, not freed: DevBuf)
     const void *old = ctx->an_pool.p;
     ctx->pool_bytes = 0;  // (nothing is resident until the move has been enqueued: a failure below leaves an empty pool)
@@ -993,8 +775,7 @@ extern "C" int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nby
   SDF_HIP(hipGetLastError());
   if (ctx->cfg.debug_timing) {
     SDF_HIP(hipStreamSynchronize(ctx->stream));
-    fprintf(stderr, "[sdf_pool_append_fasta %zu bytes -> %lld bases at %zu] %.2f ms\n", nbytes, (long long)n_bases, at,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fprintf(stderr, "[sdf_pool_append_fasta %zu bytes -> %lld bases at %zu] %.2f ms\n", nbytes, (long long)n_bases, at, ms_since(t0));
   }
   ctx->pool_bytes = need;
   *base_off = (int64_t)at;
@@ -1087,7 +868,7 @@ static int batch_pairs(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *task
     if (block_rc & kStrandBits) any_rc.store(true, std::memory_order_relaxed);
   });
   const auto dbg1 = std::chrono::steady_clock::now();
-  for (DevBuf *b : {&ctx->pk_recs}) b->new_call();
+  for_each_device_buffer(ctx, [](DevBuf &b) { b.new_call(); }, BufGroup::Pairs);
   SDF_HIP(ctx->h_pool.reserve(std::max<size_t>(words, 1) * 4));
   SDF_HIP(ctx->pk_recs.reserve(n * sizeof(PackRec)));
   SDF_HIP(hipMemcpyAsync(ctx->pk_recs.p, recs, n * sizeof(PackRec), hipMemcpyHostToDevice, ctx->stream));
@@ -1123,118 +904,6 @@ extern "C" int sdf_extz2_batch_pairs_full(sdf_ctx *ctx, const sdf_scoring *sc, c
   return batch_pairs(ctx, sc, tasks, n, want, out, nullptr, cigar_pool, cigar_cap, cigar_used);
 }
 
-// Buffers sized once (include/sedef_hip.h).  The bounds per task are the planner's: a launch-order entry per task and
-// stripe / block of columns, a CIGAR staging slot of qlen + tlen + 2 words.
-extern "C" int sdf_reserve(sdf_ctx *ctx, size_t max_tasks, size_t max_bases, size_t workspace_bytes, uint32_t flags) {
-  if (!ctx) return SDF_ERR_INVALID;
-  ctx->err.clear();
-  SDF_HIP(hipSetDevice(ctx->device));
-  const auto rt0 = std::chrono::steady_clock::now();
-  auto lap = [&, last = rt0](const char *what) mutable {  // (SDF_DEBUG_TIMING: the sections that took more than 20 ms)
-    const auto t = std::chrono::steady_clock::now();
-    const double ms = std::chrono::duration<double, std::milli>(t - last).count();
-    if (ctx->cfg.debug_timing && ms > 20) fprintf(stderr, "[sdf_reserve: %s %.1f ms]\n", what, ms);
-    last = t;
-  };
-  const size_t n = std::max<size_t>(max_tasks, 1);
-  const size_t words = max_bases / 16 + max_bases / 32 + 4 * n + 16;  // (packed sequences: two roundings per sequence)
-  const size_t cig_words = max_bases + 2 * n + 16;
-  const size_t nord = 3 * n + max_bases / 16 + 1024;
-  // pinned staging (registered huge pages unless sdf_config.pin_register says otherwise: sdf_ctx.h, HostBuf::reserve_huge)
-  const bool reg_small = ctx->cfg.pin_register >= 1, reg_big = ctx->cfg.pin_register >= 2;
-  SDF_HIP(ctx->host_pool.reserve_pinned(reg_small, std::max(words * 4, n * sizeof(sdf::PackRec))));  // (packed sequences, or a record per task of sdf_extz2_batch_pairs)
-  SDF_HIP(ctx->pk_recs.reserve_exact(n * sizeof(sdf::PackRec)));
-  SDF_HIP(ctx->host_plan.reserve_pinned(reg_small, n * sizeof(PlanTask)));
-  SDF_HIP(ctx->host_order.reserve_pinned(reg_small, nord * sizeof(int32_t)));
-  SDF_HIP(ctx->host_lane.reserve_pinned(reg_small, n * sizeof(LaneRec)));
-  // (results + CIGAR words: a quarter of the CIGAR bound -- the stage's rounds fill a tenth of it)
-  SDF_HIP(ctx->host_out.reserve_pinned(reg_small, n * ((flags & SDF_RESERVE_BRIEF) ? sizeof(sdf_result_brief) : sizeof(sdf_result)) +
-                                      cig_words / 4 * 4 + 64));
-  if (ctx->host_tasks.size() < n) ctx->host_tasks.resize(n);
-  lap("pinned staging");
-  // device
-  SDF_HIP(ctx->h_pool.reserve_exact(words * 4));
-  SDF_HIP(ctx->h_out.reserve_exact(n * sizeof(sdf_result)));
-  SDF_HIP(ctx->h_brief.reserve_exact(n * sizeof(sdf_result_brief)));
-  SDF_HIP(ctx->h_cig.reserve_exact(cig_words * 4));
-  SDF_HIP(ctx->stage_ws.reserve_exact(cig_words * 4));
-  SDF_HIP(ctx->plan_buf.reserve_exact(2 * n * sizeof(PlanTask)));  // (host-planned records, the lane tasks' behind them)
-  SDF_HIP(ctx->order_buf.reserve_exact(nord * sizeof(int32_t)));
-  SDF_HIP(ctx->misc_buf.reserve_exact(SDF_MISC_PARTS * 8 + ((n + 1023) / 1024 + 1) * 8));
-  SDF_HIP(ctx->claim_buf.reserve_exact(kClaimSets * 8 * sizeof(unsigned)));
-  SDF_HIP(ctx->ln_recs.reserve_exact(n * sizeof(LaneRec)));
-  SDF_HIP(ctx->ln_keys.reserve_exact(n * 8));
-  SDF_HIP(ctx->ln_vals.reserve_exact(n * 8));
-  SDF_HIP(ctx->ln_sizes.reserve_exact(n * 32 + 64));
-  SDF_HIP(ctx->ln_bins.reserve_exact((size_t)kLaneBins * (4 + 4 + 4 + 8 + 8) + (size_t)(kLaneBins / kLaneScanBlock) * 24 + 256));
-  lap("device buffers");
-  {  // (the library sort / scan of the lane tasks' planning: sdf_launch.hip, launch_lane)
-    size_t t_sort = 0, t_scan = 0;
-    SDF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                               (uint32_t *)nullptr, (int)n, 0, 20, ctx->stream));
-    SDF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)n,
-                                             ctx->stream));
-    SDF_HIP(ctx->ln_tmp.reserve_exact(std::max(t_sort, t_scan) + 256));
-  }
-  // the streams the pipeline would create the first time it wants them (a stream is a hardware queue: 7-15 ms each to set
-  // up -- the stage's first two rounds spent 35 ms on five of them)
-  lap("sort / scan scratch");
-  if (flags & SDF_RESERVE_FEW_STREAMS) ctx->aux_limit = 0;
-  if (ctx->pipeline_ok) {
-    for (hipStream_t *q : {&ctx->lane_stream, &ctx->aux_stream[0], &ctx->aux_stream[1], &ctx->aux_stream[2], &ctx->aux_stream[3]}) {
-      if (q != &ctx->lane_stream && (size_t)(q - &ctx->aux_stream[0]) >= ctx->aux_limit) continue;
-      if (!*q && (q == &ctx->lane_stream ? create_lane_stream(ctx, q) : hipStreamCreateWithFlags(q, hipStreamNonBlocking)) != hipSuccess) {
-        (void)hipGetLastError();
-        *q = nullptr;
-      }
-    }
-  }
-  lap("pipeline streams");
-  if (workspace_bytes) {
-    const size_t ws = std::min(workspace_bytes, ctx->ws_budget);
-    if (ctx->dir_ws.reserve_exact(ws) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->err = "cannot allocate the direction-matrix workspace";
-      return SDF_ERR_NOMEM;
-    }
-  }
-  lap("direction-flag workspace");
-  if (flags & SDF_RESERVE_ANCHORS) SDF_HIP(ctx->host_an.reserve_pinned(reg_big, (size_t)48 << 20));
-  lap("pinned anchors staging");
-  if (flags & SDF_RESERVE_ANCHORS) {  // two copies of a short sequence: a handful of anchors through every kernel of the path
-    char seq[192];
-    uint32_t x = 12345u;
-    for (int i = 0; i < 96; ++i) {
-      x = x * 1664525u + 1013904223u;
-      seq[i] = seq[96 + i] = "ACGT"[x >> 30];
-    }
-    sdf_anchor_pair pr;
-    memset(&pr, 0, sizeof(pr));
-    pr.q_off = 0;
-    pr.r_off = 96;
-    pr.qlen = pr.rlen = 96;
-    sdf_anchor out[256];
-    int64_t off[2];
-    size_t used = 0;
-    (void)sdf_anchors_batch(ctx, &pr, 1, seq, sizeof(seq), 11, out, 256, off, &used);
-    ctx->err.clear();
-  }
-  lap("anchors warm-up call");
-  {  // the stream's first asynchronous copy in each direction costs its caller ~8 ms (the runtime sets its copy path up): here,
-     // not in front of a super-batch's upload and its anchors' way back (profiles/r06_stage_timeline.txt)
-    const size_t probe = std::min<size_t>({(size_t)1 << 20, ctx->host_pool.cap, ctx->h_pool.cap, ctx->host_out.cap, ctx->h_out.cap});
-    if (probe) {
-      SDF_HIP(hipMemcpyAsync(ctx->h_pool.p, ctx->host_pool.p, probe, hipMemcpyHostToDevice, ctx->stream));
-      // (device to host: a copy of the size the rounds' results have -- a small one does not take the path a 17 MB one takes)
-      const size_t back = std::min<size_t>({(size_t)32 << 20, ctx->host_out.cap, ctx->h_out.cap});
-      SDF_HIP(hipMemcpyAsync(ctx->host_out.p, ctx->h_out.p, back, hipMemcpyDeviceToHost, ctx->stream));
-      SDF_HIP(hipStreamSynchronize(ctx->stream));
-    }
-  }
-  lap("first asynchronous copies");
-  return SDF_OK;
-}
-
 // Debug: wavefronts started per (XCD, shader engine, CU, SIMD) since the last call, 4096 counters indexed
 // xcd << 9 | se << 6 | cu << 2 | simd (the chained strips note theirs: how evenly the dispatcher spreads a launch).
 extern "C" int sdf_debug_placement(sdf_ctx *ctx, uint32_t *out) {
@@ -1254,33 +923,12 @@ extern "C" int sdf_debug_placement(sdf_ctx *ctx, uint32_t *out) {
   return SDF_OK;
 }
 
-extern "C" size_t sdf_device_bytes(const sdf_ctx *ctx) {
-  if (!ctx) return 0;
-  size_t sum = 0;
-  for (const DevBuf *b : {&ctx->dir_ws, &ctx->stage_ws, &ctx->plan_buf, &ctx->order_buf, &ctx->misc_buf, &ctx->gstate_buf, &ctx->claim_buf,
-                          &ctx->h_pool, &ctx->h_out, &ctx->h_brief, &ctx->h_cig, &ctx->rr_out, &ctx->rr_cig, &ctx->rr_map, &ctx->ln_recs,
-                          &ctx->ln_keys, &ctx->ln_vals, &ctx->ln_sizes, &ctx->ln_tmp, &ctx->pk_recs,
-                          // the anchors / chaining / stats entry points
-                          &ctx->an_pool, &ctx->fa_raw, &ctx->an_pairs, &ctx->an_keys, &ctx->an_keys2, &ctx->an_q, &ctx->an_off, &ctx->an_flag, &ctx->an_pos,
-                          &ctx->an_cand, &ctx->an_out, &ctx->an_tmp, &ctx->an_outoff, &ctx->ch_an, &ctx->ch_off, &ctx->ch_wsoff, &ctx->ch_work,
-                          &ctx->ch_path, &ctx->ch_bounds, &ctx->ch_nb, &ctx->ch_which, &ctx->st_tasks, &ctx->st_pool, &ctx->st_cig, &ctx->st_out})
-    sum += b->held_bytes();
-  if (ctx->part_ctx) sum += sdf_device_bytes(ctx->part_ctx);
-  if (ctx->rerun_ctx) sum += sdf_device_bytes(ctx->rerun_ctx);
-  return sum;
-}
 
 // ---- seed anchors (reference: src/chain.cc:24-101) ---------------------------------------------------
 static int anchors_range(sdf_ctx *ctx, const sdf_anchor_pair *pairs, const uint8_t *r_rc, size_t n, const char *d_pool, int kmer,
                          int pos_bits, sdf_anchor *out, size_t out_cap, int64_t *out_off, size_t *out_used, hipStream_t st) {
   using namespace sdf;
-  const auto lt0 = std::chrono::steady_clock::now();
-  auto lap = [&, last = lt0](const char *what) mutable {  // (SDF_DEBUG_TIMING: host milliseconds of the call's sections)
-    if (!ctx->cfg.debug_timing) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[anchors_range: %s %.2f ms]\n", what, std::chrono::duration<double, std::milli>(t - last).count());
-    last = t;
-  };
+  Lap lap{ctx->cfg.debug_timing != 0, "[anchors_range: %s %.2f ms]\n"};  // (host milliseconds of the call's sections)
   int pair_bits = 1;
   while (((size_t)1 << pair_bits) <= n) ++pair_bits;  // (strictly more than n - 1 needs: the all-ones pair field is the invalid keys' alone)
   const int key_bits = std::min(64, pair_bits + 2 * kmer + pos_bits);  // (the sort looks at the bits in use only)
@@ -1495,8 +1143,7 @@ extern "C" int sdf_anchors_batch_strand(sdf_ctx *ctx, const sdf_anchor_pair *pai
   *out_used = used_total;
   if (dbg_t)
     fprintf(stderr, "[sdf_anchors_batch n=%zu pool=%zu anchors=%zu] upload %.1f ms, rest %.1f ms\n", n, pool_bytes, *out_used,
-            std::chrono::duration<double, std::milli>(dbg1 - dbg0).count(),
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg1).count());
+            ms_between(dbg0, dbg1), ms_since(dbg1));
   return rc;
 }
 
@@ -1729,45 +1376,55 @@ extern "C" int sdf_stats_columns_pairs_device(sdf_ctx *ctx, const sdf_stats_task
   return stats_launch(ctx, d_tasks, n, (const char *)ctx->an_pool.p, d_cigar_pool, d_out, stream, any_rc != 0);
 }
 
-extern "C" int sdf_stats_columns_batch(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const char *seq_pool,
-                                       size_t pool_bytes, const uint32_t *cigar_pool, size_t cigar_words,
-                                       sdf_stats_cols *out) {
+// The host forms: tasks and runs from the host, records back.  resident: the tasks name ranges of the resident pool and may
+// carry a strand bit per side in `reserved` (else: of seq_pool, uploaded here behind the checks -- nothing leaves the
+// caller's memory for a call that is refused -- and `reserved` is not looked at).
+static int stats_host(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, bool resident, const char *seq_pool, size_t pool_bytes,
+                      const uint32_t *cigar_pool, size_t cigar_words, sdf_stats_cols *out) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
-  if (n >= ((size_t)1 << 31) || (n && (!tasks || !out)) || (!seq_pool && pool_bytes) || (!cigar_pool && cigar_words)) {
+  if (n >= ((size_t)1 << 31) || (n && (!tasks || !out)) || (!seq_pool && !resident && pool_bytes) || (!cigar_pool && cigar_words)) {
     ctx->err = "invalid arguments";
     return SDF_ERR_INVALID;
   }
+  const uint32_t rc_bits = resident ? SDF_STATS_A_RC | SDF_STATS_B_RC : 0;
+  bool any_rc = false;  // (the one scan of the tasks: a call without a reversed side gets the kernels as they were)
   for (size_t i = 0; i < n; i++) {
     const sdf_stats_task &t = tasks[i];
+    if (resident && (t.reserved & ~rc_bits)) {
+      ctx->err = "alignment " + std::to_string(i) + ": unknown stats task flag";
+      return SDF_ERR_UNSUPPORTED;
+    }
     if (t.a_len > (1u << 24) || t.b_len > (1u << 24)) {
       ctx->err = "stats columns implement sequences up to 16 Mb";
       return SDF_ERR_UNSUPPORTED;
     }
-    if (t.a_off > pool_bytes || t.a_len > pool_bytes - t.a_off || t.b_off > pool_bytes || t.b_len > pool_bytes - t.b_off ||
-        t.cigar_off > cigar_words || t.n_cigar > cigar_words - t.cigar_off || t.n_cigar >= (1u << 31)) {
-      ctx->err = "alignment " + std::to_string(i) + ": sequence or CIGAR range outside its pool";
+    if (t.a_off > pool_bytes || t.a_len > pool_bytes - t.a_off || t.b_off > pool_bytes || t.b_len > pool_bytes - t.b_off) {
+      ctx->err = "alignment " + std::to_string(i) + (resident ? ": sequence range outside the resident pool (sdf_pool_upload / sdf_pool_append_fasta)"
+                                                               : ": sequence or CIGAR range outside its pool");
       return SDF_ERR_INVALID;
     }
+    if (t.cigar_off > cigar_words || t.n_cigar > cigar_words - t.cigar_off || t.n_cigar >= (1u << 31)) {
+      ctx->err = "alignment " + std::to_string(i) + (resident ? ": CIGAR range outside its pool" : ": sequence or CIGAR range outside its pool");
+      return SDF_ERR_INVALID;
+    }
+    any_rc |= resident && t.reserved != 0;
   }
   if (n == 0) return SDF_OK;
   SDF_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  // (long alignments are cut into segments on the device: stats_cols.hip)
-  const sdf_stats_task *up = tasks;
-  const size_t nup = n;
-  sdf_stats_cols *down = out;
-  SDF_HIP(ctx->st_tasks.reserve(nup * sizeof(sdf_stats_task)));
-  SDF_HIP(ctx->st_pool.reserve(pool_bytes + 16));
+  hipStream_t st = ctx->stream;  // (the pool's uploads were enqueued there)
+  SDF_HIP(ctx->st_tasks.reserve(n * sizeof(sdf_stats_task)));
+  if (!resident) SDF_HIP(ctx->st_pool.reserve(pool_bytes + 16));
   SDF_HIP(ctx->st_cig.reserve(cigar_words * 4 + 16));
-  SDF_HIP(ctx->st_out.reserve(nup * sizeof(sdf_stats_cols)));
-  SDF_HIP(hipMemcpyAsync(ctx->st_tasks.p, up, nup * sizeof(sdf_stats_task), hipMemcpyHostToDevice, st));
-  if (pool_bytes) SDF_HIP(hipMemcpyAsync(ctx->st_pool.p, seq_pool, pool_bytes, hipMemcpyHostToDevice, st));
+  SDF_HIP(ctx->st_out.reserve(n * sizeof(sdf_stats_cols)));
+  SDF_HIP(hipMemcpyAsync(ctx->st_tasks.p, tasks, n * sizeof(sdf_stats_task), hipMemcpyHostToDevice, st));
+  if (!resident && pool_bytes) SDF_HIP(hipMemcpyAsync(ctx->st_pool.p, seq_pool, pool_bytes, hipMemcpyHostToDevice, st));
   if (cigar_words) SDF_HIP(hipMemcpyAsync(ctx->st_cig.p, cigar_pool, cigar_words * 4, hipMemcpyHostToDevice, st));
-  const int rc = sdf_stats_columns_device(ctx, (const sdf_stats_task *)ctx->st_tasks.p, nup, (const char *)ctx->st_pool.p,
-                                          (const uint32_t *)ctx->st_cig.p, (sdf_stats_cols *)ctx->st_out.p, st);
+  // (long alignments are cut into segments on the device: stats_cols.hip)
+  const int rc = stats_launch(ctx, (const sdf_stats_task *)ctx->st_tasks.p, n, (const char *)(resident ? ctx->an_pool.p : ctx->st_pool.p),
+                              (const uint32_t *)ctx->st_cig.p, (sdf_stats_cols *)ctx->st_out.p, st, any_rc);
   if (rc != SDF_OK) return rc;
-  SDF_HIP(hipMemcpyAsync(down, ctx->st_out.p, nup * sizeof(sdf_stats_cols), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipMemcpyAsync(out, ctx->st_out.p, n * sizeof(sdf_stats_cols), hipMemcpyDeviceToHost, st));
   SDF_HIP(hipStreamSynchronize(st));
   static_assert(sizeof(sdf_stats_cols) == 16 * sizeof(int32_t), "sdf_stats_cols is sixteen counters");
   for (size_t i = 0; i < n; i++)
@@ -1778,55 +1435,15 @@ extern "C" int sdf_stats_columns_batch(sdf_ctx *ctx, const sdf_stats_task *tasks
   return SDF_OK;
 }
 
+extern "C" int sdf_stats_columns_batch(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const char *seq_pool,
+                                       size_t pool_bytes, const uint32_t *cigar_pool, size_t cigar_words,
+                                       sdf_stats_cols *out) {
+  return stats_host(ctx, tasks, n, false, seq_pool, pool_bytes, cigar_pool, cigar_words, out);
+}
+
 extern "C" int sdf_stats_columns_pairs(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const uint32_t *cigar_pool,
                                        size_t cigar_words, sdf_stats_cols *out) {
-  if (!ctx) return SDF_ERR_INVALID;
-  ctx->err.clear();
-  if (n >= ((size_t)1 << 31) || (n && (!tasks || !out)) || (!cigar_pool && cigar_words)) {
-    ctx->err = "invalid arguments";
-    return SDF_ERR_INVALID;
-  }
-  const size_t pool_bytes = ctx->pool_bytes;
-  bool any_rc = false;  // (the one scan of the tasks: a call without a reversed side gets the kernels as they were)
-  for (size_t i = 0; i < n; i++) {
-    const sdf_stats_task &t = tasks[i];
-    if (t.reserved & ~(uint32_t)(SDF_STATS_A_RC | SDF_STATS_B_RC)) {
-      ctx->err = "alignment " + std::to_string(i) + ": unknown stats task flag";
-      return SDF_ERR_UNSUPPORTED;
-    }
-    if (t.a_len > (1u << 24) || t.b_len > (1u << 24)) {
-      ctx->err = "stats columns implement sequences up to 16 Mb";
-      return SDF_ERR_UNSUPPORTED;
-    }
-    if (t.a_off > pool_bytes || t.a_len > pool_bytes - t.a_off || t.b_off > pool_bytes || t.b_len > pool_bytes - t.b_off) {
-      ctx->err = "alignment " + std::to_string(i) + ": sequence range outside the resident pool (sdf_pool_upload / sdf_pool_append_fasta)";
-      return SDF_ERR_INVALID;
-    }
-    if (t.cigar_off > cigar_words || t.n_cigar > cigar_words - t.cigar_off || t.n_cigar >= (1u << 31)) {
-      ctx->err = "alignment " + std::to_string(i) + ": CIGAR range outside its pool";
-      return SDF_ERR_INVALID;
-    }
-    any_rc |= t.reserved != 0;
-  }
-  if (n == 0) return SDF_OK;
-  SDF_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;  // (the pool's uploads were enqueued there)
-  SDF_HIP(ctx->st_tasks.reserve(n * sizeof(sdf_stats_task)));
-  SDF_HIP(ctx->st_cig.reserve(cigar_words * 4 + 16));
-  SDF_HIP(ctx->st_out.reserve(n * sizeof(sdf_stats_cols)));
-  SDF_HIP(hipMemcpyAsync(ctx->st_tasks.p, tasks, n * sizeof(sdf_stats_task), hipMemcpyHostToDevice, st));
-  if (cigar_words) SDF_HIP(hipMemcpyAsync(ctx->st_cig.p, cigar_pool, cigar_words * 4, hipMemcpyHostToDevice, st));
-  const int rc = stats_launch(ctx, (const sdf_stats_task *)ctx->st_tasks.p, n, (const char *)ctx->an_pool.p,
-                              (const uint32_t *)ctx->st_cig.p, (sdf_stats_cols *)ctx->st_out.p, st, any_rc);
-  if (rc != SDF_OK) return rc;
-  SDF_HIP(hipMemcpyAsync(out, ctx->st_out.p, n * sizeof(sdf_stats_cols), hipMemcpyDeviceToHost, st));
-  SDF_HIP(hipStreamSynchronize(st));
-  for (size_t i = 0; i < n; i++)
-    if (out[i].flags) {
-      ctx->err = "alignment " + std::to_string(i) + ": the CIGAR does not fit its sequences";
-      return SDF_ERR_INVALID;
-    }
-  return SDF_OK;
+  return stats_host(ctx, tasks, n, true, nullptr, ctx ? ctx->pool_bytes : 0, cigar_pool, cigar_words, out);
 }
 
 // ---- one-task drop-in with the reference's exact signature (extern/ksw2.h:50) -----------------
@@ -1956,7 +1573,7 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
   }
   if (dcfg.debug_plan)
     fprintf(stderr, "[sdf] debug plan: cut %.2f ms (%zu tasks, %d threads, %zu chunks started early)\n",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count(), n, nthreads, cut.n_early);
+            ms_since(tc0), n, nthreads, cut.n_early);
   const size_t np = std::max<size_t>(cut.ntask_total, 1);
   if (cut.n_early && np > plan.size()) return SDF_ERR_INVALID;  // (the upper bound of the plan records holds)
   if (!cut.n_early) plan.resize(np);

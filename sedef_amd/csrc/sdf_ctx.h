@@ -1,6 +1,7 @@
 // Context, device / pinned buffers and the planning threads shared by the pieces of the C-ABI layer; the kernels they launch
 // are declared in sdf_kernels.h, the sizes they reserve come from extz2_geom.h
-// (sdf_plan.hip: batch cutting and chunk planning; sdf_launch.hip: uploads and launches; sdf_api.hip: entry points).
+// (sdf_context.hip: a context's lifecycle; sdf_plan.hip: batch cutting and chunk planning; sdf_launch.hip: uploads and
+// launches; sdf_api.hip: entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
@@ -26,14 +27,37 @@ namespace sdf {
 // (diagnostics of buffers that have no context to ask: set by every sdf_create from its configuration's debug_timing)
 inline std::atomic<bool> g_debug_timing{false};
 
+using Clock = std::chrono::steady_clock;
+inline double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+inline double ms_since(Clock::time_point t0) { return ms_between(t0, Clock::now()); }
+
+// The sections of a set-up or a call on stderr (SDF_DEBUG_TIMING).  fmt takes a section's name and its milliseconds;
+// over_ms: only the sections that took longer.
+struct Lap {
+  bool on;
+  const char *fmt;
+  double over_ms = -1;
+  Clock::time_point t0 = Clock::now(), last = t0;
+  void operator()(const char *what) {  // since the section before
+    const auto t = Clock::now();
+    if (on && ms_between(last, t) > over_ms) fprintf(stderr, fmt, what, ms_between(last, t));
+    last = t;
+  }
+  void at(const char *what) const {  // since the start
+    if (on) fprintf(stderr, fmt, what, ms_since(t0));
+  }
+};
+
 struct DevBuf {
+  // bytes obtained by the hipMalloc calls below minus bytes given back by the hipFree calls (sdf_debug_live_device_bytes)
+  static inline std::atomic<long long> live_bytes{0};
   void *p = nullptr;
   size_t cap = 0;
   // `limit`: no headroom beyond this many bytes (the direction-flag workspace: the context's budget)
   hipError_t reserve(size_t bytes, size_t limit = ~(size_t)0) {
     if (bytes <= cap) return hipSuccess;
     const bool dbg_t = g_debug_timing.load(std::memory_order_relaxed);
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     const size_t old = cap;
     // hipFree waits for the whole DEVICE -- the other lanes' batches included: 100-170 ms measured in a stage run, where
     // the allocation itself takes 0.2 ms -- so an outgrown buffer is only retired here: work of THIS call may still use it.
@@ -53,6 +77,7 @@ struct DevBuf {
     if (e != hipSuccess) {  // short of memory: give the retired buffers back first, then without headroom
       (void)hipGetLastError();
       for (void *q : retired) (void)hipFree(q);
+      live_bytes -= (long long)retired_bytes;
       retired.clear();
       retired_bytes = 0;
       e = hipMalloc(&p, want);
@@ -62,10 +87,8 @@ struct DevBuf {
         e = hipMalloc(&p, want);
       }
     }
-    if (e == hipSuccess) cap = want;
-    if (dbg_t && want >= (64u << 20))
-      fprintf(stderr, "[DevBuf %zu -> %zu MiB in %.1f ms]\n", old >> 20, want >> 20,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (e == hipSuccess) live_bytes += (long long)(cap = want);
+    if (dbg_t && want >= (64u << 20)) fprintf(stderr, "[DevBuf %zu -> %zu MiB in %.1f ms]\n", old >> 20, want >> 20, ms_since(t0));
     return e;
   }
   // without headroom (sdf_reserve: the caller's bound IS the headroom)
@@ -81,12 +104,14 @@ struct DevBuf {
   }
   void release_stale() {
     for (void *q : stale) (void)hipFree(q);
+    live_bytes -= (long long)stale_bytes;
     stale.clear();
     stale_bytes = 0;
   }
   void release() {
     if (p) (void)hipFree(p);
     for (void *q : retired) (void)hipFree(q);
+    live_bytes -= (long long)(cap + retired_bytes);
     retired.clear();
     retired_bytes = 0;
     release_stale();
@@ -258,6 +283,45 @@ class WorkerPool {
 using sdf::DevBuf;
 using sdf::HostBuf;
 
+// Every device buffer of a context, one X(name, group) each: the members of sdf_ctx, and what sdf_destroy releases and
+// sdf_device_bytes sums.  `group`: the calls at whose start the buffer is renewed (DevBuf::new_call: what it outgrew in
+// earlier calls is idle and may be freed) -- BatchCall: batch_part; Pairs: batch_pairs; Pool: sdf_pool_append_fasta
+// (sdf_pool_upload: an_pool alone); None: never, what such a buffer outgrows stays until the context goes.
+enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
+#define SDF_DEVICE_BUFFERS(X)                                                                                        \
+  X(dir_ws, BatchCall)   /* direction flags of the chunks in flight: the context's workspace */                       \
+  X(stage_ws, BatchCall) /* CIGAR staging slots */                                                                    \
+  X(plan_buf, BatchCall)                                                                                              \
+  X(order_buf, BatchCall)                                                                                             \
+  X(misc_buf, None)                                                                                                   \
+  X(gstate_buf, BatchCall)                                                                                            \
+  X(an_pool, Pool) /* the resident characters (pool_bytes of them) */                                                 \
+  X(an_pairs, None) X(an_keys, None) X(an_keys2, None) X(an_q, None) X(an_off, None) X(an_flag, None) /* anchors calls */ \
+  X(an_pos, None) X(an_cand, None) X(an_out, None) X(an_tmp, None) X(an_outoff, None)                                 \
+  X(ch_an, None) X(ch_off, None) X(ch_wsoff, None) X(ch_work, None) /* sdf_chain_batch */                             \
+  X(ch_path, None) X(ch_bounds, None) X(ch_nb, None) X(ch_which, None)                                                \
+  X(st_tasks, None) X(st_pool, None) X(st_cig, None) X(st_out, None) /* sdf_stats_columns_batch */                    \
+  X(claim_buf, None)   /* stripe launches: eight entry counters each (stripe_claim), zeroed per call */               \
+  X(st_items, None)    /* sdf_stats_columns_device: segments of long alignments + their counter */                    \
+  X(h_pool, BatchCall) X(h_out, BatchCall) X(h_cig, BatchCall) /* device buffers of the host-buffer entry point */    \
+  X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
+  X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \
+  X(fa_raw, Pool) /* a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta) */           \
+  /* lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch */ \
+  X(ln_recs, BatchCall) X(ln_keys, BatchCall) X(ln_vals, BatchCall) X(ln_sizes, BatchCall) X(ln_tmp, BatchCall)       \
+  X(ln_bins, None) /* ... second form of the lane planning: per-key counts, ranks, prefixes (lane_hist_kernel and on) */ \
+  /* outputs of rerun_ctx, and the (record, staging slot) map of the merge */                                         \
+  X(rr_out, None) X(rr_cig, None) X(rr_map, None)
+// ... and every pinned host buffer
+#define SDF_HOST_BUFFERS(X)                                                                                          \
+  X(host_plan) /* pinned staging of the plan (two) */                                                                 \
+  X(host_order)                                                                                                       \
+  X(host_pool) /* pinned staging of the host-buffer entry point: packed sequences; results + CIGARs */                \
+  X(host_out)                                                                                                         \
+  X(host_lane)  /* the lane kernel's records */                                                                       \
+  X(host_chars) /* pinned staging of a super-batch's FASTA characters (sdf_pool_host) */                              \
+  X(host_an) /* pinned staging of the anchors call's output (sdf_reserve with SDF_RESERVE_ANCHORS; a pageable copy runs at ~3 GB/s) */
+
 struct sdf_ctx {
   sdf_config cfg;  // the context's settings, fixed when it is made (sdf_config.hip): every setting is read from here
   int device = 0;
@@ -267,27 +331,15 @@ struct sdf_ctx {
   hipStream_t wide_stream[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // chunks of several mixed-pair launches (sdf_launch.hip)
   size_t aux_limit = 4;  // extra pipeline streams this context may create (sdf_reserve with SDF_RESERVE_FEW_STREAMS: 0)
   hipStream_t aux_stream[4] = {nullptr, nullptr, nullptr, nullptr};    // more room for launches that end in a tail
-  DevBuf dir_ws, stage_ws, plan_buf, order_buf, misc_buf, gstate_buf;
-  HostBuf host_plan, host_order;  // pinned staging of the plan
-  HostBuf host_pool, host_out;    // pinned staging of the host-buffer entry point (packed sequences; results + CIGARs)
-  DevBuf an_pool, an_pairs, an_keys, an_keys2, an_q, an_off, an_flag, an_pos, an_cand, an_out, an_tmp, an_outoff;
-  DevBuf ch_an, ch_off, ch_wsoff, ch_work, ch_path, ch_bounds, ch_nb, ch_which;
-  DevBuf st_tasks, st_pool, st_cig, st_out;  // sdf_stats_columns_batch
-  DevBuf claim_buf;                          // stripe launches: eight entry counters each (stripe_claim), zeroed per call
-  DevBuf st_items;                           // sdf_stats_columns_device: segments of long alignments + their counter
-  DevBuf h_pool, h_out, h_cig;  // device buffers of the host-buffer entry point
-  DevBuf h_brief;               // ... 16-byte result records (sdf_extz2_batch_brief)
-  std::vector<sdf_task> host_tasks;  // ... the task array with word offsets
-  // lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch
-  HostBuf host_lane;
-  HostBuf host_chars;      // pinned staging of a super-batch's FASTA characters (sdf_pool_host)
-  size_t pool_bytes = 0;   // characters resident in an_pool (sdf_pool_upload / sdf_anchors_batch): what sdf_extz2_batch_pairs may name
-  DevBuf pk_recs;          // ... one PackRec per task of such a call (seq_pack.hip)
-  DevBuf fa_raw;           // a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta)
-  HostBuf host_an;  // pinned staging of the anchors call's output (sdf_reserve with SDF_RESERVE_ANCHORS; a pageable copy runs at ~3 GB/s)
-  DevBuf ln_recs, ln_keys, ln_vals, ln_sizes, ln_tmp;
-  DevBuf ln_bins;  // ... second form of the lane planning: per-key counts, ranks, prefixes (extz2_lane.hip: lane_hist_kernel and on)
   hipStream_t lane_stream = nullptr;
+#define X(name, group) DevBuf name;
+  SDF_DEVICE_BUFFERS(X)
+#undef X
+#define X(name) HostBuf name;
+  SDF_HOST_BUFFERS(X)
+#undef X
+  std::vector<sdf_task> host_tasks;  // the task array of the host-buffer entry point with word offsets
+  size_t pool_bytes = 0;   // characters resident in an_pool (sdf_pool_upload / sdf_anchors_batch): what sdf_extz2_batch_pairs may name
   long long lane_tasks = 0;   // tasks of the last batch call the lane kernel took
   sdf::WorkerPool *pool = nullptr;  // planning threads, started with the first batch large enough to use them
   sdf::BatchCut *cut = nullptr;  // chunk list and planning scratch of the last batch call (sdf_plan.hip)
@@ -303,13 +355,38 @@ struct sdf_ctx {
   hipEvent_t part_ev = nullptr;
   bool is_part = false, pool_shared = false;
   sdf_ctx *rerun_ctx = nullptr;   // context without stripe kernels for the tasks they gave up (created when first needed)
-  DevBuf rr_out, rr_cig, rr_map;  // its outputs, and the (record, staging slot) map of the merge
   long long reran = 0;            // tasks of the last batch call that were re-run after a stripe gave up
 };
 
+// f(DevBuf &) for every device buffer of a context, or for those of one group; f(HostBuf &) for every pinned one
+template <class Ctx, class F>
+inline void for_each_device_buffer(Ctx *ctx, F &&f, BufGroup only = BufGroup::Any) {
+#define X(name, group) if (only == BufGroup::Any || only == BufGroup::group) f(ctx->name);
+  SDF_DEVICE_BUFFERS(X)
+#undef X
+}
+template <class F>
+inline void for_each_host_buffer(sdf_ctx *ctx, F &&f) {
+#define X(name) f(ctx->name);
+  SDF_HOST_BUFFERS(X)
+#undef X
+}
+// f(hipStream_t &) for every stream of a context, created or not: the one place that lists them
+template <class F>
+inline void for_each_stream(sdf_ctx *ctx, F &&f) {
+  f(ctx->stream);
+  for (hipStream_t &q : ctx->dp_stream) f(q);
+  f(ctx->tb_stream);
+  for (hipStream_t &q : ctx->aux_stream) f(q);
+  for (hipStream_t &q : ctx->wide_stream) f(q);
+  f(ctx->lane_stream);
+}
+
 // a context another context owns (the first part of a split batch, the re-run of abandoned stripe tasks): not another
-// user of the process's CPUs (defined in sdf_api.hip)
+// user of the process's CPUs (sdf_context.hip, like the two below)
 void mark_internal_context(sdf_ctx *c);
+extern std::atomic<int> g_live_contexts;  // contexts of this process that callers made
+int usable_cpus();                        // CPUs this process may really use: the affinity mask capped by the cgroup's CPU quota
 
 #define SDF_HIP(call)                                                                          \
   do {                                                                                         \

@@ -31,11 +31,8 @@ hipEvent_t next_event(sdf_ctx *ctx, size_t &cursor) {
 
 // every stream a batch call may have work on
 void drain_streams(sdf_ctx *ctx, hipStream_t st) {
-  for (hipStream_t q : {st, ctx->stream, ctx->dp_stream[0], ctx->dp_stream[1], ctx->tb_stream, ctx->aux_stream[0],
-                        ctx->aux_stream[1], ctx->aux_stream[2], ctx->aux_stream[3], ctx->lane_stream})
-    if (q) (void)hipStreamSynchronize(q);
-  for (hipStream_t q : ctx->wide_stream)
-    if (q) (void)hipStreamSynchronize(q);
+  if (st) (void)hipStreamSynchronize(st);
+  for_each_stream(ctx, [](hipStream_t q) { if (q) (void)hipStreamSynchronize(q); });
   (void)hipGetLastError();
 }
 

@@ -118,6 +118,8 @@ def load_library():
     L.sdf_reserve.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32]
     L.sdf_device_bytes.restype = C.c_size_t
     L.sdf_device_bytes.argtypes = [C.c_void_p]
+    L.sdf_debug_live_device_bytes.restype = C.c_size_t
+    L.sdf_debug_live_device_bytes.argtypes = []
     L.sdf_extz2_batch_device.restype = C.c_int
     L.sdf_extz2_batch_device.argtypes = [C.c_void_p, C.POINTER(_Scoring), C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -163,6 +165,11 @@ def pack_codes(codes):
     if len(codes):
         load_library().sdf_pack_codes(codes.ctypes.data, len(codes), out.ctypes.data)
     return out
+
+
+def live_device_bytes():
+    """sdf_debug_live_device_bytes: device bytes the buffers of all contexts of this process hold at this moment."""
+    return int(load_library().sdf_debug_live_device_bytes())
 
 
 def band_cells(qlen, tlen, w):

@@ -282,6 +282,36 @@ int sdf_extz2_batch_pairs_full(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_ta
 int sdf_extz2_batch_pairs_view(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks, size_t n,
                                const sdf_result_brief **out, const uint32_t **cigar_pool, size_t *cigar_used);
 
+/* ---- character classes of ranges of the resident pool ----------------------------------------------------------------
+ * How many bytes of pool[off, off + len), as they lie in HBM, are ACGT, acgt, 'N' or 'n', and anything else; the four counts
+ * add up to len.  The class of a byte is decided on the WHOLE byte: one of 128 or more is `other` (the stage driver's own
+ * scan, PairJob in host/pipeline.cc, indexes its table by the unsigned char -- unlike rev_dna and align_dna, which look at
+ * c & 127).  The counts are strand-free: rev_dna maps every class onto itself or onto 'N' (A <-> T and C <-> G keep their
+ * case, N and n become N, everything else becomes N), so `other == 0` holds for a range exactly when it holds for its
+ * reverse complement, and a pair of the stage driver is "plain" -- nothing but ACGTNacgtn -- exactly when other == 0 on both
+ * of its ranges.
+ * SDF_ERR_INVALID, before any launch: a range outside sdf_pool_bytes() (an empty pool holds no non-empty range), len < 0,
+ * n != 0 without ranges or out.  SDF_ERR_UNSUPPORTED: reserved != 0.  len == 0 is legal (all counts zero), and so is
+ * n == 0 with NULL pointers.  Enqueued on the context's stream, behind the pool's uploads; returns with out[0, n) filled. */
+typedef struct { int64_t off; int32_t len; int32_t reserved; /* must be 0 */ } sdf_pool_range;
+typedef struct { int32_t upper_acgt, lower_acgt, n_any /* 'N' or 'n' */, other; } sdf_range_classes;
+int sdf_pool_range_classes(sdf_ctx *ctx, const sdf_pool_range *ranges, size_t n, sdf_range_classes *out);
+
+/* ---- one resident pool read by several contexts of a device ---------------------------------------------------------
+ * dst reads src's resident pool: dst's pool is replaced by a VIEW of src's (same device; SDF_ERR_INVALID otherwise, or when
+ * src == dst, or when src is itself a view, or when dst's own pool has views).  sdf_pool_bytes(dst) == sdf_pool_bytes(src) at
+ * the time of the call.  The view holds no memory: sdf_device_bytes(dst) does not count it and sdf_destroy(dst) does not free
+ * it.  Before the call returns, dst's streams wait for everything src has enqueued on its own: the uploads.
+ *   on dst   sdf_pool_upload, sdf_pool_append_fasta(reset != 0) and an anchors call with a host seq_pool drop the view and give
+ *            dst a pool of its own again; sdf_pool_append_fasta(reset == 0) answers SDF_ERR_INVALID while dst holds a view.
+ *   on src   the owner must not grow or replace its pool while views exist -- a pool that grows moves: sdf_pool_upload,
+ *            sdf_pool_append_fasta and an anchors call with a host seq_pool answer SDF_ERR_INVALID ("pool is shared") with the
+ *            pool as it was, until every view has been destroyed or has a pool of its own; sdf_pool_host leaves the pool alone.
+ * The owner must outlive its views.  sdf_destroy(owner) with live views is the caller's error: the views are left with an
+ * EMPTY pool, so their later calls that name a range answer SDF_ERR_INVALID instead of reading freed memory.
+ * Not thread-safe against calls in flight on either context: share where the contexts are set up. */
+int sdf_pool_share(sdf_ctx *dst, const sdf_ctx *src);
+
 /* Device-resident form: d_packed_pool, d_out and d_cigar_pool are HBM pointers on ctx's device;
  * tasks (host) carry word offsets into d_packed_pool.  Work is enqueued on `stream`
  * (a hipStream_t, NULL = the context's own stream) and the call returns after the stream has

@@ -65,11 +65,12 @@ int sdfh_generate(const char *ref_path, const char *bed_path, int kmer, const ch
 
 // several buckets, one provider (host/pipeline.cc: generate_many): `beds` = bucket paths separated by newlines; every
 // bucket's lines go to `<bucket><out_suffix>`.  stats: per bucket {lines, hits} (2 x buckets entries).
-int sdfh_generate_many(const char *ref_path, const char *beds, int kmer, const char *out_suffix, const char *log_dir,
-                       test_dp_fn test_dp, int device, long long *stats) {
+// `totals`: behind them the four totals of the process (stage_totals).  resident: StageSettings::stage_resident for this
+// run -- the lanes' providers are then set up side by side, as the CLI does, and the chromosomes loaded before the stage.
+static int generate_many_impl(const char *ref_path, const char *beds, int kmer, const char *out_suffix, const char *log_dir,
+                              test_dp_fn test_dp, int device, bool resident, bool totals, long long *stats) {
   try {
     Params p;
-    auto dp = provider(test_dp, device);
     std::vector<std::string> list;
     for (const char *c = beds; *c;) {
       const char *e = strchr(c, '\n');
@@ -78,8 +79,23 @@ int sdfh_generate_many(const char *ref_path, const char *beds, int kmer, const c
       if (!e) break;
       c = e + 1;
     }
-    const auto sts = generate_many(ref_path, expand_buckets(list), kmer, p, *dp, out_suffix, log_dir ? log_dir : "", stderr);
+    const std::vector<std::string> buckets = expand_buckets(list);
+    std::unique_ptr<DpProvider> dp;
+    stage_totals_reset();
+    if (resident && !test_dp) {  // (the CPU path keeps no chromosomes anywhere: the hook ignores the mode)
+      StageSettings s = StageSettings::from_env();
+      s.stage_resident = true;
+      set_stage_settings(s);
+      const StageHint hint = stage_hint_many(buckets);
+      dp = make_gpu_providers(device, hint.lanes, hint.devices, hint.max_batch_bytes);
+      load_stage_genome(*dp, ref_path, buckets, kmer, hint.max_batch_bytes, stderr);
+    } else {
+      dp = provider(test_dp, device);
+      if (!test_dp) load_stage_genome(*dp, ref_path, buckets, kmer, stage_hint_many(buckets).max_batch_bytes, stderr);
+    }
+    const auto sts = generate_many(ref_path, buckets, kmer, p, *dp, out_suffix, log_dir ? log_dir : "", stderr);
     for (size_t k = 0; stats && k < sts.size(); k++) stats[2 * k] = sts[k].lines, stats[2 * k + 1] = sts[k].total_written;
+    if (stats && totals) stage_totals(stats + 2 * sts.size());
     return (int)sts.size();
   } catch (std::string &s) {
     g_err = s;
@@ -88,6 +104,25 @@ int sdfh_generate_many(const char *ref_path, const char *beds, int kmer, const c
     g_err = e.what();
     return -1;
   }
+}
+int sdfh_generate_many(const char *ref_path, const char *beds, int kmer, const char *out_suffix, const char *log_dir,
+                       test_dp_fn test_dp, int device, long long *stats) {
+  return generate_many_impl(ref_path, beds, kmer, out_suffix, log_dir, test_dp, device, false, false, stats);
+}
+// ... on chromosomes that stay resident in HBM (resident != 0, or SDF_STAGE_RESIDENT=1 in the environment; resident == 0
+// without the variable: sdfh_generate_many).  stats: 2 x buckets entries, then FASTA records uploaded, characters uploaded
+// to a device pool, super-batches run, super-batches that named resident ranges.
+int sdfh_generate_many_resident(const char *ref_path, const char *beds, int kmer, const char *out_suffix, const char *log_dir,
+                                test_dp_fn test_dp, int device, int resident, long long *stats) {
+  return generate_many_impl(ref_path, beds, kmer, out_suffix, log_dir, test_dp, device,
+                            resident != 0 || StageSettings::from_env().stage_resident, true, stats);
+}
+// resident_range (host/pipeline.cc; test hook): 0 and *off, or -1 when the request is not inside the host's copy
+int sdfh_resident_range(long long base, long long start, long long seq_len, long long s, long long len, int rc, long long *off) {
+  int64_t o = 0;
+  if (!resident_range(base, start, seq_len, s, len, rc != 0, &o)) return -1;
+  *off = o;
+  return 0;
 }
 
 // `sedef stats generate genome.fa final.bed > out` (reference: src/stats_main.cc:339-389); test_cols: the oracle's column

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <map>
 #include <memory>
 #include <fstream>
 #include <atomic>
@@ -26,6 +27,22 @@
 namespace sdfh {
 
 void set_alignment_scoring(const Params &p);
+
+namespace {
+struct StageTotals {
+  std::atomic<long long> records{0}, chars{0}, batches{0}, batches_resident{0};
+} g_totals;
+}  // namespace
+void stage_totals_reset() { g_totals.records = g_totals.chars = g_totals.batches = g_totals.batches_resident = 0; }
+void stage_totals(long long out[4]) {
+  out[0] = g_totals.records, out[1] = g_totals.chars, out[2] = g_totals.batches, out[3] = g_totals.batches_resident;
+}
+
+bool resident_range(int64_t base, int64_t start, int64_t seq_len, int64_t s, int64_t len, bool rc, int64_t *off) {
+  if (s < 0 || len < 0 || seq_len < 0 || s > seq_len || len > seq_len - s) return false;
+  *off = rc ? base + start + seq_len - s - len : base + start + s;
+  return true;
+}
 static void parallel_for(int n, const std::function<void(int)> &body);  // all host cores (defined below)
 
 // ======================================================================================================
@@ -179,6 +196,8 @@ class GpuProvider : public DpProvider {
         if (spares_[i]) return std::unique_ptr<DpProvider>(spares_[i].release());
       }
     }
+    // (a pool is shared where the contexts are set up, include/sedef_hip.h: a context made now could not read the genome)
+    if (genome_) throw std::string("no spare device context reads the resident chromosomes");
     return std::unique_ptr<DpProvider>(new GpuProvider(want, 0, std::vector<int>(), 0, 3));
   }
   void give_back(std::unique_ptr<DpProvider> p) override {
@@ -276,9 +295,12 @@ class GpuProvider : public DpProvider {
         const ResidentReq &r = reqs[k];
         raw.first_task[k] = at;
         const size_t lim = (size_t)std::min(r.qlen, r.tlen);
-        for (size_t sp = 0; sp < lim; sp += step)
-          tasks[at++] = make_task(r.q_off + (int64_t)sp, r.t_off + (int64_t)sp, (int)std::min<size_t>(step, (size_t)r.qlen - sp),
-                                  (int)std::min<size_t>(step, (size_t)r.tlen - sp));
+        for (size_t sp = 0; sp < lim; sp += step) {
+          const int ql = (int)std::min<size_t>(step, (size_t)r.qlen - sp), tl = (int)std::min<size_t>(step, (size_t)r.tlen - sp);
+          // (a reversed target is read from the END of its range: chunk sp holds its bases [sp, sp + tl))
+          const int64_t to = (r.flag & SDF_TASK_T_RC) ? r.t_off + r.tlen - (int64_t)sp - tl : r.t_off + (int64_t)sp;
+          tasks[at++] = make_task(r.q_off + (int64_t)sp, to, ql, tl, r.flag);
+        }
       }
     });
     call_batch(tasks.get(), nt, nullptr, p, raw, tp0);
@@ -286,7 +308,7 @@ class GpuProvider : public DpProvider {
   }
 
  private:
-  static sdf_task make_task(int64_t q_off, int64_t t_off, int qlen, int tlen) {
+  static sdf_task make_task(int64_t q_off, int64_t t_off, int qlen, int tlen, int flag = 0) {
     sdf_task t;
     memset(&t, 0, sizeof(t));
     t.q_off = q_off;
@@ -295,7 +317,7 @@ class GpuProvider : public DpProvider {
     t.tlen = tlen;
     t.w = -1;      // src/align.cc:86
     t.zdrop = -1;  // src/align.cc:54
-    t.flag = 0;
+    t.flag = flag;
     return t;
   }
   // one device batch call and its results as Raw: `pool` holds the tasks' codes (offsets are bytes of it), or is NULL when the
@@ -351,7 +373,7 @@ class GpuProvider : public DpProvider {
 
  public:
   char *pool_host(size_t bytes) override {
-    if (!stage_settings().gpu_anchors) return nullptr;
+    if (!stage_settings().gpu_anchors || genome_) return nullptr;
     ready();
     uploaded_ = 0;
     pool_ = sdf_pool_host(ctx_, bytes + 64);
@@ -361,8 +383,8 @@ class GpuProvider : public DpProvider {
 
   void pool_ready(size_t bytes) override {
     uploaded_ = 0;
-    if (!pool_ || !stage_settings().gpu_anchors || bytes > pool_cap_) return;
-    if (sdf_pool_upload(ctx_, pool_, bytes) == SDF_OK) uploaded_ = bytes;
+    if (!pool_ || !stage_settings().gpu_anchors || bytes > pool_cap_ || genome_) return;
+    if (sdf_pool_upload(ctx_, pool_, bytes) == SDF_OK) uploaded_ = bytes, g_totals.chars += (long long)bytes;
   }
 
   // what the device kernels do not cover goes to the host's generate_anchors -- said once, not silently
@@ -410,6 +432,7 @@ class GpuProvider : public DpProvider {
     if (!stage_settings().gpu_anchors || jobs.empty()) return false;
     ready();  // (a reserve still running on its thread uses the context: its warm-up call, its pinning next to this upload)
     if (kmer > 15) return host_instead("GPU anchors implement k-mer sizes up to 15");
+    if (genome_) return anchors_genome(jobs, kmer, false, 0, out);
     std::vector<sdf_anchor_pair> pairs;
     size_t total = 0;
     bool in_pool = false;
@@ -434,6 +457,7 @@ class GpuProvider : public DpProvider {
     if (!sent) {
       if (sdf_pool_upload(ctx_, pool, total) != SDF_OK) return host_instead(sdf_last_error(ctx_));
       uploaded_ = total;
+      g_totals.chars += (long long)total;
     }
     if (stage_settings().debug_timing)
       fprintf(stderr, "[anchors: %zu pairs, pool %zu bytes %s, upload enqueued in %.1f ms]\n", jobs.size(), total,
@@ -458,6 +482,7 @@ class GpuProvider : public DpProvider {
   }
 
   bool anchors_more(const std::vector<AnchorJob> &jobs, int kmer, size_t keep, AnchorBatch &out) override {
+    if (genome_) return stage_settings().gpu_anchors && !jobs.empty() && kmer <= 15 && anchors_genome(jobs, kmer, true, keep, out);
     if (!stage_settings().gpu_anchors || jobs.empty() || kmer > 15 || !pool_ || !uploaded_) return false;
     std::vector<sdf_anchor_pair> pairs;
     size_t total = 0;
@@ -474,7 +499,114 @@ class GpuProvider : public DpProvider {
     return true;
   }
 
+  // ---- resident chromosomes ----
+  struct Genome {
+    std::map<std::string, int64_t> base;  // record name -> pool offset of its base 0
+  };
+  bool has_genome() const override { return genome_ != nullptr; }
+  bool chromosome_base(const std::string &name, int64_t *base_off) const override {
+    if (!genome_) return false;
+    const auto it = genome_->base.find(name);
+    if (it == genome_->base.end()) return false;
+    *base_off = it->second;
+    return true;
+  }
+  bool load_genome(const FastaReference &fr, const std::vector<std::string> &names, size_t max_batch_bytes,
+                   std::string &why) override {
+    // every context first: its buffers sized and its warm-up calls -- which leave a small pool of their own -- over
+    std::vector<GpuProvider *> all{this};
+    for (auto &t : spare_threads_)
+      if (t.joinable()) t.join();
+    for (auto &e : spares_)
+      if (e) all.push_back(e.get());
+    for (GpuProvider *g : all) {
+      g->ready();
+      if (!g->prepared_) {
+        g->prepared_ = true;
+        g->reserve(std::max<size_t>(max_batch_bytes, 1));
+      }
+      if (g->device_ != device_) {
+        why = "the lanes are on several devices";
+        return false;
+      }
+    }
+    auto genome = std::make_shared<Genome>();
+    long long chars = 0;
+    for (const std::string &name : names) {
+      const FastaReference::Record r = fr.record(name);
+      int64_t at = 0;
+      // (straight from the mapped file: no staged buffer is reused, one sdf_pool_sync below covers every record)
+      const int rc = sdf_pool_append_fasta(ctx_, r.bytes, r.nbytes, r.entry->length, r.entry->line_blen, r.entry->line_len,
+                                           genome->base.empty(), &at);
+      if (rc != SDF_OK) {
+        why = name + ": " + sdf_last_error(ctx_);
+        return false;  // (what was appended so far goes with the next upload: it replaces the pool)
+      }
+      genome->base[name] = at;
+      chars += r.entry->length;
+    }
+    if (genome->base.empty()) {
+      why = "the buckets name no chromosome";
+      return false;
+    }
+    if (sdf_pool_sync(ctx_) != SDF_OK) {
+      why = sdf_last_error(ctx_);
+      return false;
+    }
+    for (size_t i = 1; i < all.size(); i++)
+      if (sdf_pool_share(all[i]->ctx_, ctx_) != SDF_OK) {
+        why = sdf_last_error(all[i]->ctx_);
+        // (all or nothing: the views made so far get a pool of their own again, so that the owner may replace its own)
+        for (size_t j = 1; j < i; j++) (void)sdf_pool_upload(all[j]->ctx_, "N", 1);
+        return false;
+      }
+    for (GpuProvider *g : all) g->genome_ = genome;
+    g_totals.records += (long long)genome->base.size();
+    g_totals.chars += chars;
+    return true;
+  }
+  void plain_ranges(const int64_t *off, const int32_t *len, size_t n, char *plain) override {
+    ready();
+    std::vector<sdf_pool_range> ranges(n);
+    for (size_t i = 0; i < n; i++) ranges[i] = {off[i], len[i], 0};
+    std::vector<sdf_range_classes> cls(n);
+    if (sdf_pool_range_classes(ctx_, ranges.data(), n, cls.data()) != SDF_OK)
+      throw std::string("character classes of the resident pool failed: ") + sdf_last_error(ctx_);
+    for (size_t i = 0; i < n; i++) plain[i] = cls[i].other == 0;
+  }
+
  private:
+  // the seed anchors of jobs that name ranges of the resident chromosomes: nothing is copied or uploaded
+  bool anchors_genome(const std::vector<AnchorJob> &jobs, int kmer, bool more, size_t keep, AnchorBatch &out) {
+    const size_t n = jobs.size();
+    std::vector<sdf_anchor_pair> pairs(n);
+    std::vector<uint8_t> strand(n);
+    for (size_t k = 0; k < n; k++) {
+      if (jobs[k].q_off < 0 || jobs[k].r_off < 0) throw std::string("internal: an anchor job without its resident ranges");
+      if (jobs[k].query.size() >= (1u << 31) || jobs[k].ref.size() >= (1u << 31))
+        return host_instead("GPU anchors implement sequences shorter than 2 Gb");
+      pairs[k] = {jobs[k].q_off, jobs[k].r_off, (int32_t)jobs[k].query.size(), (int32_t)jobs[k].ref.size(), jobs[k].same_chr,
+                  jobs[k].delta};
+      strand[k] = jobs[k].r_rc;
+    }
+    out.off.assign(n + 1, 0);
+    out.buf.reset();
+    size_t used = 0;
+    const sdf_anchor *found = nullptr;
+    const size_t pool_bytes = sdf_pool_bytes(ctx_);
+    const int rc = more ? sdf_anchors_batch_more_strand(ctx_, pairs.data(), strand.data(), n, pool_bytes, kmer, keep, &found,
+                                                        out.off.data(), &used)
+                        : sdf_anchors_batch_view_strand(ctx_, pairs.data(), strand.data(), n, nullptr, pool_bytes, kmer, &found,
+                                                        out.off.data(), &used);
+    if (more && rc != SDF_OK) return false;  // (no room behind the kept anchors: the caller's ordinary call)
+    if (rc == SDF_ERR_UNSUPPORTED || rc == SDF_ERR_NOMEM) return host_instead(sdf_last_error(ctx_));
+    if (rc != SDF_OK) throw std::string("GPU anchors failed: ") + sdf_last_error(ctx_);
+    out.view = (const Anchor *)found;
+    resident_ = true;  // (load_stage_genome: never with SDF_RESIDENT_DP=0)
+    describe_out(pairs, out);
+    return true;
+  }
+  std::shared_ptr<const Genome> genome_;  // the chromosomes in this context's pool (its own, or a view of the first lane's)
   sdf_ctx *ctx_;
   int device_;
   size_t ws_;
@@ -646,8 +778,9 @@ struct PairJob::PathState {
   Hit result;
 };
 
-PairJob::PairJob(SeqView query, SeqView ref, const Hit &orig, const Params &p)
+PairJob::PairJob(SeqView query, SeqView ref, const Hit &orig, const Params &p, bool scan)
     : query_(query), ref_(ref), orig_(orig), p_(p) {
+  if (!scan) return;
   auto plain = [](SeqView s) {
     static const struct Tab {
       bool ok[256];
@@ -962,6 +1095,7 @@ StageSettings StageSettings::from_env() {
   s.anchor_parts = (int)num("SDF_ANCHOR_PARTS", 0, 16, 0);
   s.bucket_lanes = (int)num("SDF_BUCKET_LANES", 1, 4, 2);
   s.stats_resident = num("SDF_STATS_RESIDENT", 0, 1, 0) != 0;
+  s.stage_resident = num("SDF_STAGE_RESIDENT", 0, 1, 0) != 0;
   if (const char *e = getenv("SDF_DEVICES"))
     for (const char *c = e; *c;) {
       char *end = nullptr;
@@ -1204,6 +1338,9 @@ struct SuperBatch {
   std::vector<Item> items = std::vector<Item>((size_t)n);
   std::vector<size_t> slot;  // pair k's query at pool + slot[2k], its reference at pool + slot[2k + 1]
   bool provider_pool = false;
+  // resident chromosomes: the pairs name ranges of the pool the lane's provider reads (q_base / r_base: the first pool byte
+  // of each pair's two ranges, in pool order), the host's copies below serve the host's own reads only
+  const bool genome = lane.dp->has_genome();
   std::vector<DpProvider::AnchorBatch> seeds;  // (live until the jobs have taken their copies: their first advance)
   std::vector<int64_t> q_base = std::vector<int64_t>((size_t)n, 0), r_base = q_base;  // resident: the pairs in the device pool
   bool resident = false;
@@ -1227,7 +1364,7 @@ struct SuperBatch {
       slot[2 * k + 2] = slot[2 * k + 1] + span[2 * k + 1].bytes;
     }
     const size_t bytes = slot[2 * (size_t)n];
-    char *pool = dp.pool_host(bytes + 1);
+    char *pool = genome ? nullptr : dp.pool_host(bytes + 1);
     provider_pool = pool != nullptr;
     if (!pool) {
       if (lane.own_pool_cap < bytes + 1) {
@@ -1242,10 +1379,31 @@ struct SuperBatch {
       it.fa = SeqView(qa, FastaReference::extract(span[2 * k], qa));
       it.fb = SeqView(ra, FastaReference::extract(span[2 * k + 1], ra));
       if (it.h.ref->is_rc) rc_inplace(ra, it.fb.size());
-      it.job.reset(new PairJob(it.fa, it.fb, it.h, run.p));
+      it.job.reset(new PairJob(it.fa, it.fb, it.h, run.p, !genome));
     });
+    ++g_totals.batches;
+    if (genome) {
+      // Nothing is uploaded: the pairs' ranges of the resident chromosomes, and ONE device call that says which pairs hold
+      // nothing but ACGTNacgtn (PairJob's own scan of every character otherwise).
+      std::vector<int64_t> off(2 * (size_t)n);
+      std::vector<int32_t> len(2 * (size_t)n);
+      std::vector<char> plain(2 * (size_t)n);
+      for (int k = 0; k < n; k++) {
+        const Hit &h = items[k].h;
+        int64_t qb = 0, rb = 0;
+        if (!dp.chromosome_base(h.query->name, &qb) || !dp.chromosome_base(h.ref->name, &rb))
+          throw std::string("internal: a pair on a chromosome that is not resident");
+        off[2 * k] = q_base[k] = qb + std::max(0, h.query_start);
+        off[2 * k + 1] = r_base[k] = rb + std::max(0, h.ref_start);
+        len[2 * k] = (int32_t)items[k].fa.size();
+        len[2 * k + 1] = (int32_t)items[k].fb.size();
+      }
+      dp.plain_ranges(off.data(), len.data(), off.size(), plain.data());
+      for (int k = 0; k < n; k++) items[k].job->set_exact(plain[2 * k] && plain[2 * k + 1]);
+      ++g_totals.batches_resident;
+    }
     a.t_fetch += since(tf);
-    dp.pool_ready(bytes);  // (the whole pool to the device, asynchronously)
+    if (!genome) dp.pool_ready(bytes);  // (the whole pool to the device, asynchronously)
     run.mark(base, "sequences fetched");
   }
 
@@ -1254,10 +1412,11 @@ struct SuperBatch {
   // that copies them replaces its pool with every call).
   std::vector<int> part_cuts() const {
     const size_t total = slot[2 * (size_t)n];
+    const bool on_device = provider_pool || genome;  // (resident chromosomes: no call replaces the pool)
     int parts = 1;
-    if (provider_pool && n >= 64 && total >= ((size_t)16 << 20)) parts = 2;  // (small super-batches: one call)
-    if (provider_pool && n >= 256 && total >= ((size_t)64 << 20)) parts = 4;
-    if (stage_settings().anchor_parts > 0 && provider_pool) parts = std::min(stage_settings().anchor_parts, std::max(n / 16, 1));
+    if (on_device && n >= 64 && total >= ((size_t)16 << 20)) parts = 2;  // (small super-batches: one call)
+    if (on_device && n >= 256 && total >= ((size_t)64 << 20)) parts = 4;
+    if (stage_settings().anchor_parts > 0 && on_device) parts = std::min(stage_settings().anchor_parts, std::max(n / 16, 1));
     std::vector<int> cut((size_t)parts + 1, n);
     cut[0] = 0;
     for (int i = 1, k = 0; i < parts; i++) {
@@ -1293,13 +1452,14 @@ struct SuperBatch {
       const Hit &h = items[k].h;
       aj[k] = {items[k].fa, items[k].fb, h.query->name == h.ref->name && h.query->is_rc == h.ref->is_rc,
                h.ref_start - h.query_start};
+      if (genome) aj[k].q_off = q_base[k], aj[k].r_off = r_base[k], aj[k].r_rc = h.ref->is_rc;
     }
     const std::vector<int> cut = part_cuts();
     const int parts = (int)cut.size() - 1;
     seeds.resize(parts);
     auto part_jobs = [&](int i) { return std::vector<DpProvider::AnchorJob>(aj.begin() + cut[i], aj.begin() + cut[i + 1]); };
     auto take_bases = [&](int i) {
-      for (int k = cut[i]; k < cut[i + 1]; k++) {
+      for (int k = cut[i]; k < cut[i + 1] && !genome; k++) {
         q_base[k] = resident ? seeds[i].q_base[k - cut[i]] : 0;
         r_base[k] = resident ? seeds[i].r_base[k - cut[i]] : 0;
       }
@@ -1391,9 +1551,13 @@ struct SuperBatch {
         size_t at = first[k];
         if (resident) {
           const char *qa = it.fa.data(), *ra = it.fb.data();
+          const bool rc = genome && it.h.ref->is_rc;  // (the host's copy of the reference is reverse-complemented)
           for (const DpRequest &r : it.pending) {
-            if (r.q < qa || r.q + r.qlen > qa + it.fa.size() || r.t < ra || r.t + r.tlen > ra + it.fb.size()) outside.store(true);
-            rbatch[at++] = {q_base[k] + (r.q - qa), r_base[k] + (r.t - ra), r.qlen, r.tlen};
+            int64_t qo = 0, to = 0;
+            if (!resident_range(q_base[k], 0, (int64_t)it.fa.size(), r.q - qa, r.qlen, false, &qo) ||
+                !resident_range(r_base[k], 0, (int64_t)it.fb.size(), r.t - ra, r.tlen, rc, &to))
+              outside.store(true);
+            rbatch[at++] = {qo, to, r.qlen, r.tlen, rc ? SDF_TASK_T_RC : 0};
           }
         } else {
           for (const DpRequest &r : it.pending) batch[at++] = r;
@@ -1557,6 +1721,11 @@ GenerateStats generate_alignments(const std::string &ref_path, const std::string
       lane.dp = lane.own.get();
       run.mark(-2 - l, "lane's device context ready");
       if (!lane.dp) return;
+      if (lane.dp->has_genome() != dp0.has_genome()) {  // (it could not read the resident chromosomes: one lane fewer)
+        dp0.give_back(std::move(lane.own));
+        lane.dp = nullptr;
+        return;
+      }
       zero_counters(*lane.dp);
       lane.dp->prepare((size_t)max_batch_bytes);
     }
@@ -1657,6 +1826,43 @@ StageHint stage_hint_many(const std::vector<std::string> &beds, int super_batch)
   if (all.lanes <= 1 && beds.size() >= 2 && stage_settings().bucket_lanes > 1)
     all.lanes = (int)std::min<size_t>((size_t)stage_settings().bucket_lanes, beds.size());
   return all;
+}
+
+bool load_stage_genome(DpProvider &dp, const std::string &ref_path, const std::vector<std::string> &beds, int kmer,
+                       size_t max_batch_bytes, FILE *log) {
+  const StageSettings &st = stage_settings();
+  if (!st.stage_resident) return false;
+  std::string why;
+  if (kmer > 15) why = "k-mer sizes above 15 find their seed anchors on the host";
+  else if (!st.resident_dp) why = "SDF_RESIDENT_DP=0";
+  else if (!st.gpu_anchors) why = "SDF_GPU_ANCHORS=0";
+  else if (st.devices.size() > 1) why = "the lanes are on several devices";
+  bool ok = false;
+  if (why.empty()) {
+    // the chromosomes the seed pairs name: columns 1 and 4 of every line (src/hit.cc: Hit::from_bed), in order of appearance
+    std::vector<std::string> names;
+    std::set<std::string> seen;
+    for (const std::string &bed : beds) {
+      std::ifstream fin(bed.c_str());
+      std::string line;
+      while (std::getline(fin, line)) {
+        size_t at = 0;
+        for (int col = 0; col < 4 && at <= line.size(); col++) {
+          const size_t e = std::min(line.find('\t', at), line.size());
+          if ((col == 0 || col == 3) && e > at && seen.insert(line.substr(at, e - at)).second) names.push_back(line.substr(at, e - at));
+          at = e + 1;
+        }
+      }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    FastaReference fr(ref_path);
+    ok = dp.load_genome(fr, names, max_batch_bytes, why);
+    if (ok && st.debug_timing)
+      fprintf(log, "[resident chromosomes: %zu records loaded and shared in %.1f ms]\n", names.size(),
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+  if (!ok) fprintf(log, "[sedef_amd] SDF_STAGE_RESIDENT=1 ignored, every bucket runs on uploaded super-batches: %s\n", why.c_str());
+  return ok;
 }
 
 // One bucket of generate_many: its lines to `<bed><out_suffix>`, its log to `<log_dir>/<basename>.log` with a log directory,

@@ -120,6 +120,7 @@ struct DpRequest {
 };
 
 // Runs a batch of align_helper-equivalent requests.
+class FastaReference;
 class DpProvider {
  public:
   virtual ~DpProvider() {}
@@ -149,6 +150,7 @@ class DpProvider {
   struct ResidentReq {
     int64_t q_off, t_off;
     int32_t qlen, tlen;
+    int32_t flag = 0;  // SDF_TASK_T_RC: the target is the reverse complement of its range (resident chromosomes)
   };
   virtual bool run_resident(const std::vector<ResidentReq> &, const Params &, Raw &) { return false; }
   // Optional: another provider of the same kind (own device context) for a second lane of the stage driver.
@@ -167,6 +169,10 @@ class DpProvider {
     SeqView query, ref;
     bool same_chr;
     int delta;
+    // resident chromosomes (load_genome): where the two ranges lie in the device pool, in pool order whatever the strand;
+    // `ref` is then the host's reverse-complemented copy of a range the device reads with r_rc.  -1: not named.
+    int64_t q_off = -1, r_off = -1;
+    bool r_rc = false;
   };
   // Optional: a host buffer of `bytes` the provider would like the super-batch's sequences fetched INTO (pinned memory it
   // uploads from: AnchorJob views inside it are not copied again).  Valid until the provider's next pool_host() call.
@@ -189,6 +195,22 @@ class DpProvider {
   virtual bool anchors_more(const std::vector<AnchorJob> &, int /*kmer*/, size_t /*keep*/, AnchorBatch &) { return false; }
   // Optional: the first `bytes` of the pool_host() buffer are complete (the provider may send them to the device now).
   virtual void pool_ready(size_t /*bytes*/) {}
+  // Optional, resident chromosomes (SDF_STAGE_RESIDENT=1): every record of `names` is uploaded ONCE, as the file has it, to
+  // this provider's device pool, and every provider clone() hands out reads that pool too.  Called where the providers are
+  // set up, before any other call; `max_batch_bytes` as prepare() takes it.  false, with `why` filled: nothing is resident
+  // and the providers work as if the call had not been made.  While a genome is loaded pool_host() returns NULL, anchors()
+  // takes jobs that name pool ranges (AnchorJob::q_off) and clone() hands out only providers that read the pool.
+  virtual bool load_genome(const FastaReference & /*fr*/, const std::vector<std::string> & /*names*/, size_t /*max_batch_bytes*/,
+                           std::string &why) {
+    why = "the provider keeps no chromosomes resident";
+    return false;
+  }
+  virtual bool has_genome() const { return false; }
+  virtual bool chromosome_base(const std::string & /*name*/, int64_t * /*base_off*/) const { return false; }
+  // Optional: plain[i] = 1 when pool bytes [off[i], off[i] + len[i]) hold nothing but ACGTNacgtn (one device call)
+  virtual void plain_ranges(const int64_t * /*off*/, const int32_t * /*len*/, size_t /*n*/, char * /*plain*/) {
+    throw std::string("internal: no resident pool to classify");
+  }
   int64_t tasks = 0, cells = 0;  // statistics
   double t_pack = 0, t_call = 0, t_unpack = 0;  // wall seconds: request packing and device call (run), unpacking (run_cigars)
 };
@@ -411,7 +433,10 @@ int rangemax_script(const int *pts, int n, const int *ops, int nops, int *out, i
 // ---- per-pair job: fast_align (src/chain.cc:203-268) + refine_chains (src/refine.cc:23-193), staged ----
 class PairJob {
  public:
-  PairJob(SeqView query, SeqView ref, const Hit &orig, const Params &p);  // (views: the sequences outlive the job)
+  // (views: the sequences outlive the job)  scan = false: the caller knows from elsewhere whether the pair is plain ACGTN
+  // and says so with set_exact() before the first advance()
+  PairJob(SeqView query, SeqView ref, const Hit &orig, const Params &p, bool scan = true);
+  void set_exact(bool exact) { exact_ = exact; }
   // Advances as far as possible.  Returns the DP requests it is waiting for (empty => finished).
   // Call again with the results of the previous return value, in the same order.
   std::vector<DpRequest> advance(const std::vector<Cigar> &results);
@@ -478,6 +503,7 @@ struct StageSettings {
   int anchor_parts = 0;      // SDF_ANCHOR_PARTS: parts a super-batch's seed anchors are found in, each under the chaining of the one before (0: by its size -- 1, 2 or 4)
   bool resident_dp = true;   // SDF_RESIDENT_DP=0: the DP rounds cut their bases out on the host again instead of naming ranges of the characters the anchors call left in HBM
   bool stats_resident = false;  // SDF_STATS_RESIDENT=1: `stats generate` counts on resident chromosomes (StatsParams::resident)
+  bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
   int bucket_lanes = 2;      // SDF_BUCKET_LANES: buckets of a several-bucket run in flight, each on a device context of its own (1: one after the other)
   static StageSettings from_env();
 };
@@ -504,5 +530,22 @@ StageHint stage_hint_many(const std::vector<std::string> &beds, int super_batch 
 std::vector<GenerateStats> generate_many(const std::string &ref_path, const std::vector<std::string> &beds, int kmer_size,
                                          const Params &p, DpProvider &dp, const std::string &out_suffix,
                                          const std::string &log_dir, FILE *log, int super_batch = 8192);
+
+// ---- the stage on resident chromosomes (StageSettings::stage_resident) ----------------------------------------------
+// Where a DP request finds its bases in a resident chromosome: the request covers bytes [s, s + len) of the host's copy of a
+// sequence that was fetched from [start, start + seq_len) of a record whose base 0 is pool byte `base` and, with rc,
+// reverse-complemented.  *off: the first pool byte of the range in pool order, [base + start + s, + len) forward,
+// [base + start + seq_len - s - len, + len) read with the strand bit when rc.  false: the request is not inside the copy.
+bool resident_range(int64_t base, int64_t start, int64_t seq_len, int64_t s, int64_t len, bool rc, int64_t *off);
+// The loader: with StageSettings::stage_resident, every chromosome the seed BEDs `beds` name goes to `dp`'s device pool once
+// (DpProvider::load_genome) -- called where the providers are set up, before the stage clock.  false: the process runs every
+// bucket the ordinary way, which is said on `log` in one line when the setting asked for resident chromosomes (k-mers
+// above 15, SDF_RESIDENT_DP=0, SDF_GPU_ANCHORS=0, several devices, a record that does not fit).
+bool load_stage_genome(DpProvider &dp, const std::string &ref_path, const std::vector<std::string> &beds, int kmer,
+                       size_t max_batch_bytes, FILE *log);
+// Totals of the process since stage_totals_reset(): FASTA records uploaded, characters uploaded to a device pool,
+// super-batches run, super-batches that named resident ranges.
+void stage_totals_reset();
+void stage_totals(long long out[4]);
 
 }  // namespace sdfh

@@ -118,6 +118,8 @@ int main(int argc, char **argv) {
               "sedef align generate -k [kmer] [--log-dir dir] [genome.fa] [bucket ... | bucket directory]\n"
               "  several buckets in one process: bucket b's BEDPE goes to b.aligned.bed, its log to dir/b.log\n"
               "  params: -k/--kmer, --match, --mismatch, --gap-open, --gap-extend (default 5, -4, -40, -1)\n"
+              "  SDF_STAGE_RESIDENT=1 in the environment: every chromosome the buckets name is uploaded once per process and\n"
+              "  the super-batches name ranges of it (same output; off by default)\n"
               "sedef align bucket -n [count] [bed_directory(/)] [buckets/] [genome.fa]\n"
               "  bucket BEDs into [count] files for the alignment stage (--extend-ratio, --max-extend, --merge-dist)\n"
               "sedef stats generate [genome.fa] [final.bed]\n"
@@ -164,6 +166,8 @@ int main(int argc, char **argv) {
           set_stage_settings(s);
         }
         auto dp = make_gpu_providers(dv, hint.lanes, hint.devices, hint.max_batch_bytes);
+        // (SDF_STAGE_RESIDENT=1: the chromosomes the buckets name go to the device once, here, before the stage clock)
+        load_stage_genome(*dp, a.pos[1], buckets, k, hint.max_batch_bytes, stderr);
         const auto t1 = std::chrono::steady_clock::now();
         if (many) {
           const auto sts = generate_many(a.pos[1], buckets, k, p, *dp, suffix, log_dir, stderr);

@@ -680,7 +680,8 @@ extern "C" char *sdf_pool_host(sdf_ctx *ctx, size_t bytes) {
   }
   // (its place in HBM with it: a first upload of 180 MB waited 8 ms for this -- but only while nothing is resident: a grown
   // buffer starts empty, and the records sdf_pool_append_fasta left must stay where they are)
-  if (!ctx->pool_bytes) (void)ctx->an_pool.reserve(bytes + 64);
+  // (... and a pool that is shared, either way, is not touched at all: sdf_pool_share)
+  if (!ctx->pool_bytes && !ctx->an_pool.borrowed && ctx->views.empty()) (void)ctx->an_pool.reserve(bytes + 64);
   if (ctx->cfg.debug_timing && ctx->host_chars.cap != had)
     fprintf(stderr, "[sdf_pool_host %zu MiB %s in %.1f ms]\n", ctx->host_chars.cap >> 20, ctx->host_chars.registered ? "registered huge pages" : "hipHostMalloc",
             ms_since(t0));
@@ -690,11 +691,12 @@ extern "C" char *sdf_pool_host(sdf_ctx *ctx, size_t bytes) {
 extern "C" int sdf_pool_upload(sdf_ctx *ctx, const char *chars, size_t bytes) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
-  ctx->pool_bytes = 0;
-  if (!chars && bytes) {
+  if (!chars && bytes) {  // (before anything changes: a view stays a view)
     ctx->err = "invalid arguments";
     return SDF_ERR_INVALID;
   }
+  if (pool_writable(ctx) != SDF_OK) return SDF_ERR_INVALID;  // (an owner with views keeps its pool as it is)
+  ctx->pool_bytes = 0;
   SDF_HIP(hipSetDevice(ctx->device));
   ctx->an_pool.new_call();
   SDF_HIP(ctx->an_pool.reserve(bytes + 64));
@@ -733,6 +735,7 @@ extern "C" int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nby
   // n_bases bases and the line ends between them, with or without the last line's own
   const size_t least = (size_t)n_bases + (n_bases ? (size_t)((n_bases - 1) / line_bases) * gap : 0);
   if (nbytes < least || nbytes > least + gap) return invalid("nbytes does not fit n_bases bases in lines of this geometry");
+  if (pool_writable(ctx, /*keep_view=*/reset == 0) != SDF_OK) return SDF_ERR_INVALID;
   const size_t at = reset ? 0 : ctx->pool_bytes, need = at + (size_t)n_bases;
   SDF_HIP(hipSetDevice(ctx->device));
   // pieces of whole lines, 64 MiB or so each (the gather's indices within a piece are 32-bit)
@@ -902,6 +905,63 @@ extern "C" int sdf_extz2_batch_pairs(sdf_ctx *ctx, const sdf_scoring *sc, const 
 extern "C" int sdf_extz2_batch_pairs_full(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want,
                                           sdf_result *out, uint32_t *cigar_pool, size_t cigar_cap, size_t *cigar_used) {
   return batch_pairs(ctx, sc, tasks, n, want, out, nullptr, cigar_pool, cigar_cap, cigar_used);
+}
+
+// Character classes of ranges of the resident pool (include/sedef_hip.h; seq_pack.hip: pool_classes_kernel)
+extern "C" int sdf_pool_range_classes(sdf_ctx *ctx, const sdf_pool_range *ranges, size_t n, sdf_range_classes *out) {
+  using sdf::ClassRange;
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (n == 0) return SDF_OK;
+  if (!ranges || !out || n > 0x3fffffffu) {
+    ctx->err = "invalid arguments";
+    return SDF_ERR_INVALID;
+  }
+  SDF_HIP(hipSetDevice(ctx->device));
+  // the device's records in the pinned staging, the counts behind them
+  SDF_HIP(ctx->host_cls.reserve(n * (sizeof(ClassRange) + sizeof(sdf_range_classes))));
+  ClassRange *recs = (ClassRange *)ctx->host_cls.p;
+  sdf_range_classes *back = (sdf_range_classes *)(recs + n);
+  const size_t pool_bytes = ctx->pool_bytes;
+  long long n_seg = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const sdf_pool_range &r = ranges[i];
+    if (r.reserved != 0) {
+      ctx->err = "sdf_pool_range_classes: reserved must be 0";
+      return SDF_ERR_UNSUPPORTED;
+    }
+    if (r.len < 0 || r.off < 0 || (size_t)r.off > pool_bytes || (size_t)r.len > pool_bytes - (size_t)r.off) {
+      ctx->err = "sdf_pool_range_classes: range outside the resident pool";
+      return SDF_ERR_INVALID;
+    }
+    recs[i] = ClassRange{r.off, r.len, (int32_t)n_seg};
+    n_seg += (r.len + sdf::kClassSegBytes - 1) / sdf::kClassSegBytes;
+    if (n_seg > 0x7fffff00ll) {
+      ctx->err = "sdf_pool_range_classes: more than 2^31 segments in one call";
+      return SDF_ERR_UNSUPPORTED;
+    }
+  }
+  if (n_seg == 0) {
+    memset(out, 0, n * sizeof(sdf_range_classes));
+    return SDF_OK;
+  }
+  if (((uintptr_t)ctx->an_pool.p & 15) != 0) {  // (the kernel reads aligned slots: those of the first range start at the base)
+    ctx->err = "sdf_pool_range_classes: the pool's base is not 16-byte aligned";
+    return SDF_ERR_INVALID;
+  }
+  for_each_device_buffer(ctx, [](DevBuf &b) { b.new_call(); }, BufGroup::Pairs);
+  SDF_HIP(ctx->cl_ranges.reserve(n * sizeof(ClassRange)));
+  SDF_HIP(ctx->cl_out.reserve(n * sizeof(sdf_range_classes)));
+  SDF_HIP(hipMemcpyAsync(ctx->cl_ranges.p, recs, n * sizeof(ClassRange), hipMemcpyHostToDevice, ctx->stream));
+  SDF_HIP(hipMemsetAsync(ctx->cl_out.p, 0, n * sizeof(sdf_range_classes), ctx->stream));
+  hipLaunchKernelGGL(sdf::pool_classes_kernel, dim3((unsigned)((n_seg + 15) / 16)), dim3(256), 0, ctx->stream,
+                     (const ClassRange *)ctx->cl_ranges.p, (int)n, n_seg, (const char *)ctx->an_pool.p,
+                     (sdf_range_classes *)ctx->cl_out.p);
+  SDF_HIP(hipGetLastError());
+  SDF_HIP(hipMemcpyAsync(back, ctx->cl_out.p, n * sizeof(sdf_range_classes), hipMemcpyDeviceToHost, ctx->stream));
+  SDF_HIP(hipStreamSynchronize(ctx->stream));
+  memcpy(out, back, n * sizeof(sdf_range_classes));
+  return SDF_OK;
 }
 
 // Debug: wavefronts started per (XCD, shader engine, CU, SIMD) since the last call, 4096 counters indexed
@@ -1090,6 +1150,7 @@ extern "C" int sdf_anchors_batch_strand(sdf_ctx *ctx, const sdf_anchor_pair *pai
   const bool dbg_t = ctx->cfg.debug_timing != 0;
   const auto dbg0 = std::chrono::steady_clock::now();
   if (!resident) {  // (the pool stays where it is after the call: sdf_extz2_batch_pairs may name ranges of it)
+    if (pool_writable(ctx) != SDF_OK) return SDF_ERR_INVALID;
     ctx->pool_bytes = 0;
     SDF_HIP(ctx->an_pool.reserve(pool_bytes + 64));
     SDF_HIP(hipMemcpyAsync(ctx->an_pool.p, seq_pool, pool_bytes, hipMemcpyHostToDevice, ctx->stream));

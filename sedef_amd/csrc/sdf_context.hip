@@ -157,11 +157,79 @@ void mark_internal_context(sdf_ctx *c) {
   g_live_contexts.fetch_sub(1);
 }
 
+// ---- one resident pool read by several contexts of a device (include/sedef_hip.h: sdf_pool_share) ----
+static std::mutex g_share_mu;  // every context's view_of / views
+
+// (g_share_mu held) the view gives its owner's pool back: an empty pool of its own
+static void drop_view_locked(sdf_ctx *v) {
+  if (sdf_ctx *owner = v->view_of) {
+    auto &l = owner->views;
+    l.erase(std::remove(l.begin(), l.end(), v), l.end());
+    v->view_of = nullptr;
+  }
+  v->an_pool.drop_borrow();
+  v->pool_bytes = 0;
+}
+
+int pool_writable(sdf_ctx *ctx, bool keep_view) {
+  std::lock_guard<std::mutex> g(g_share_mu);
+  if (!ctx->views.empty()) {
+    ctx->err = "pool is shared: other contexts hold views of it (sdf_pool_share)";
+    return SDF_ERR_INVALID;
+  }
+  if (ctx->an_pool.borrowed) {
+    if (keep_view) {
+      ctx->err = "pool is shared: this context holds a view of another context's pool and cannot add to it";
+      return SDF_ERR_INVALID;
+    }
+    drop_view_locked(ctx);
+  }
+  return SDF_OK;
+}
+
+extern "C" int sdf_pool_share(sdf_ctx *dst, const sdf_ctx *src_c) {
+  sdf_ctx *src = const_cast<sdf_ctx *>(src_c);  // (the owner's list of views and a marker on its stream)
+  if (!dst) return SDF_ERR_INVALID;
+  sdf_ctx *ctx = dst;
+  ctx->err.clear();
+  std::lock_guard<std::mutex> g(g_share_mu);
+  auto invalid = [&](const char *why) {
+    ctx->err = std::string("sdf_pool_share: ") + why;
+    return SDF_ERR_INVALID;
+  };
+  if (!src || src == dst) return invalid("the source is the destination, or none");
+  if (src->device != dst->device) return invalid("the two contexts are on different devices");
+  if (src->an_pool.borrowed) return invalid("the source is itself a view");
+  if (!dst->views.empty()) return invalid("pool is shared: other contexts hold views of the destination's pool");
+  SDF_HIP(hipSetDevice(dst->device));
+  // dst's streams see what the owner has enqueued so far: its uploads
+  hipEvent_t ev = nullptr;
+  SDF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, src->stream);
+  for_each_stream(dst, [&](hipStream_t q) {
+    if (q && e == hipSuccess) e = hipStreamWaitEvent(q, ev, 0);
+  });
+  (void)hipEventDestroy(ev);  // (released once it has completed)
+  SDF_HIP(e);
+  drop_view_locked(dst);  // (a view of another owner, if it held one)
+  dst->an_pool.borrow(src->an_pool.p, src->an_pool.cap);
+  dst->pool_bytes = src->pool_bytes;
+  dst->view_of = src;
+  src->views.push_back(dst);
+  return SDF_OK;
+}
+
 extern "C" void sdf_destroy(sdf_ctx *ctx) {
   if (!ctx) return;
   if (!ctx->is_part) g_live_contexts.fetch_sub(1);
   (void)hipSetDevice(ctx->device);
   for_each_stream(ctx, [](hipStream_t q) { if (q) (void)hipStreamSynchronize(q); });
+  {  // a view leaves its owner's list; an owner's views (the caller's error: the owner outlives its views) are left with an
+     // empty pool, so that their later calls answer SDF_ERR_INVALID instead of reading freed memory
+    std::lock_guard<std::mutex> g(g_share_mu);
+    drop_view_locked(ctx);
+    while (!ctx->views.empty()) drop_view_locked(ctx->views.back());
+  }
   for (auto ev : ctx->events) (void)hipEventDestroy(ev);
   for_each_device_buffer(ctx, [](DevBuf &b) { b.release(); });
   for_each_host_buffer(ctx, [](HostBuf &b) { b.release(); });

@@ -53,9 +53,26 @@ struct DevBuf {
   static inline std::atomic<long long> live_bytes{0};
   void *p = nullptr;
   size_t cap = 0;
+  // BORROWED: p / cap name memory another DevBuf holds (sdf_pool_share: a view of the owner's resident pool).  Such a buffer
+  // counts no bytes, frees nothing and is never retired; whoever wants memory of its own here calls drop_borrow() first
+  // (reserve() does, when it has to grow).
+  bool borrowed = false;
+  void borrow(void *ptr, size_t bytes) {
+    release();
+    p = ptr;
+    cap = bytes;
+    borrowed = true;
+  }
+  void drop_borrow() {
+    if (!borrowed) return;
+    p = nullptr;
+    cap = 0;
+    borrowed = false;
+  }
   // `limit`: no headroom beyond this many bytes (the direction-flag workspace: the context's budget)
   hipError_t reserve(size_t bytes, size_t limit = ~(size_t)0) {
     if (bytes <= cap) return hipSuccess;
+    drop_borrow();
     const bool dbg_t = g_debug_timing.load(std::memory_order_relaxed);
     const auto t0 = Clock::now();
     const size_t old = cap;
@@ -109,6 +126,7 @@ struct DevBuf {
     stale_bytes = 0;
   }
   void release() {
+    drop_borrow();
     if (p) (void)hipFree(p);
     for (void *q : retired) (void)hipFree(q);
     live_bytes -= (long long)(cap + retired_bytes);
@@ -118,7 +136,7 @@ struct DevBuf {
     p = nullptr;
     cap = 0;
   }
-  size_t held_bytes() const { return cap + retired_bytes + stale_bytes; }
+  size_t held_bytes() const { return (borrowed ? 0 : cap) + retired_bytes + stale_bytes; }
   std::vector<void *> retired, stale;
   size_t retired_bytes = 0, stale_bytes = 0;
 };
@@ -285,7 +303,7 @@ using sdf::HostBuf;
 
 // Every device buffer of a context, one X(name, group) each: the members of sdf_ctx, and what sdf_destroy releases and
 // sdf_device_bytes sums.  `group`: the calls at whose start the buffer is renewed (DevBuf::new_call: what it outgrew in
-// earlier calls is idle and may be freed) -- BatchCall: batch_part; Pairs: batch_pairs; Pool: sdf_pool_append_fasta
+// earlier calls is idle and may be freed) -- BatchCall: batch_part; Pairs: batch_pairs, sdf_pool_range_classes; Pool: sdf_pool_append_fasta
 // (sdf_pool_upload: an_pool alone); None: never, what such a buffer outgrows stays until the context goes.
 enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
 #define SDF_DEVICE_BUFFERS(X)                                                                                        \
@@ -306,6 +324,7 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(h_pool, BatchCall) X(h_out, BatchCall) X(h_cig, BatchCall) /* device buffers of the host-buffer entry point */    \
   X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \
+  X(cl_ranges, Pairs) X(cl_out, Pairs) /* sdf_pool_range_classes: a ClassRange and a record of four counts per range */ \
   X(fa_raw, Pool) /* a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta) */           \
   /* lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch */ \
   X(ln_recs, BatchCall) X(ln_keys, BatchCall) X(ln_vals, BatchCall) X(ln_sizes, BatchCall) X(ln_tmp, BatchCall)       \
@@ -320,6 +339,7 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(host_out)                                                                                                         \
   X(host_lane)  /* the lane kernel's records */                                                                       \
   X(host_chars) /* pinned staging of a super-batch's FASTA characters (sdf_pool_host) */                              \
+  X(host_cls) /* sdf_pool_range_classes: the ranges' records on their way up, the counts on their way back */          \
   X(host_an) /* pinned staging of the anchors call's output (sdf_reserve with SDF_RESERVE_ANCHORS; a pageable copy runs at ~3 GB/s) */
 
 struct sdf_ctx {
@@ -354,6 +374,11 @@ struct sdf_ctx {
   sdf_ctx *part_ctx = nullptr;    // second context of this device: the first part of a very large batch (sdf_api.hip)
   hipEvent_t part_ev = nullptr;
   bool is_part = false, pool_shared = false;
+  // sdf_pool_share (sdf_context.hip): a VIEW borrows its owner's an_pool and names the owner here; the owner lists its views.
+  // Both sides are touched under one process-wide lock, by sdf_pool_share, by whatever gives a view a pool of its own again
+  // (pool_writable) and by sdf_destroy.
+  sdf_ctx *view_of = nullptr;
+  std::vector<sdf_ctx *> views;
   sdf_ctx *rerun_ctx = nullptr;   // context without stripe kernels for the tasks they gave up (created when first needed)
   long long reran = 0;            // tasks of the last batch call that were re-run after a stripe gave up
 };
@@ -385,6 +410,10 @@ inline void for_each_stream(sdf_ctx *ctx, F &&f) {
 // a context another context owns (the first part of a split batch, the re-run of abandoned stripe tasks): not another
 // user of the process's CPUs (sdf_context.hip, like the two below)
 void mark_internal_context(sdf_ctx *c);
+// In front of everything that replaces or grows a context's resident pool.  SDF_ERR_INVALID ("pool is shared"): other
+// contexts view this one's pool, or -- keep_view -- this context holds a view and the caller wants to add to it.  Otherwise
+// SDF_OK, and a context that held a view holds none any more: an empty pool of its own.
+int pool_writable(sdf_ctx *ctx, bool keep_view = false);
 extern std::atomic<int> g_live_contexts;  // contexts of this process that callers made
 int usable_cpus();                        // CPUs this process may really use: the affinity mask capped by the cgroup's CPU quota
 

@@ -82,6 +82,14 @@ static_assert(sizeof(PackRec) == 32, "PackRec: two records per 64-byte line");
 template <bool REV>
 __global__ void pack_chars_kernel(const PackRec *, long long, const char *, uint32_t *);
 __global__ void fasta_gather_kernel(const char *, char *, uint32_t, uint32_t, uint32_t);
+struct ClassRange {  // one range of sdf_pool_range_classes (16 bytes)
+  int64_t off;       // first byte of the range in the pool
+  int32_t len;
+  int32_t seg0;      // segments of the ranges before this one: the launch's group g counts segment g - seg0 of its range
+};
+constexpr int kClassSegBytes = 16384;  // bytes of a range that one group of sixteen lanes counts
+static_assert(sizeof(ClassRange) == 16 && sizeof(sdf_range_classes) == 16, "four records per 64-byte line");
+__global__ void pool_classes_kernel(const ClassRange *, int, long long, const char *, sdf_range_classes *);
 // anchors.hip
 struct AnchorPairDev {
   int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool

@@ -107,4 +107,82 @@ __global__ void __launch_bounds__(256) fasta_gather_kernel(const char *__restric
   }
 }
 
+// ---- character classes of ranges of the resident pool (include/sedef_hip.h: sdf_pool_range_classes) ----
+// What the stage driver's PairJob asks of every pair: does it hold anything but ACGTNacgtn?  Its table is indexed by the whole
+// unsigned char, so a byte of 128 or more is `other` here too -- NOT the class of c & 127, which is what rev_dna and align_dna
+// look at.  Four counts per range: ACGT, acgt, N or n, everything else.
+//
+// A range is cut into segments of kClassSegBytes; a group of sixteen lanes takes one segment and reads the 16-byte ALIGNED slots
+// of the pool that hold it, a slot per lane and step: 256 contiguous bytes a step, one vector load a lane.  The bytes of the
+// first and the last slot that lie outside the segment are masked, not skipped: no load leaves the slots of the range, and those
+// lie inside the pool's allocation (its base is aligned, and it ends 64 bytes or more behind the last character).  Bytes are
+// classified four at a time, a flag in bit 7 of each byte of a 32-bit word as in stats_cols.hip.  The group's sums go to the
+// range's record with relaxed agent-scope additions, as the lane planner counts its bins; the host zeroes the records in front
+// of the launch.
+__device__ __forceinline__ void classes_word(uint32_t x, uint32_t valid, int &up, int &lo, int &nn, int &ot) {
+  constexpr uint32_t O = 0x01010101u, H = 0x80808080u;
+  auto eq = [](uint32_t v, uint32_t c) { return ~((v ^ (c * O)) + 0x7Fu * O) & H; };  // bit 7: byte == c (bytes below 0x80)
+  const uint32_t ok = valid & ~x;           // bit 7: a byte of the segment that is below 128
+  const uint32_t u = x & (0x5Fu * O);       // bit 7 and the case bit dropped: only 'A' and 'a' become 'A', and so on
+  const uint32_t acgt = (eq(u, 'A') | eq(u, 'C') | eq(u, 'G') | eq(u, 'T')) & ok;
+  const uint32_t n = eq(u, 'N') & ok;
+  const uint32_t lower = x << 2;            // the case bit in bit 7
+  up += __popc(acgt & ~lower);
+  lo += __popc(acgt & lower);
+  nn += __popc(n);
+  ot += __popc(valid & ~(acgt | n));
+}
+
+__global__ void __launch_bounds__(256) pool_classes_kernel(const ClassRange *__restrict__ ranges, int n_ranges, long long n_seg,
+                                                           const char *__restrict__ pool, sdf_range_classes *__restrict__ out) {
+  const int sub = threadIdx.x & 15;
+  const long long g = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (g >= n_seg) return;  // (the whole group)
+  // the range of segment g: the last one whose seg0 is at most g (ranges without a byte have no segment and share the seg0 of
+  // the range behind them)
+  int a = 0, b = n_ranges;
+  while (b - a > 1) {
+    const int mid = (a + b) >> 1;
+    if ((long long)ranges[mid].seg0 <= g) a = mid; else b = mid;
+  }
+  const ClassRange r = ranges[a];
+  const long long first = r.off + (g - r.seg0) * (long long)kClassSegBytes;            // the segment: pool bytes [first, last)
+  const long long last = min(first + (long long)kClassSegBytes, r.off + (long long)r.len);
+  // slots by ADDRESS.  Precondition, checked by the host call: the pool's base is 16-byte aligned, so the slot of the first
+  // byte, lo_a & ~15, does not begin below the base; the last slot ends inside the slack behind every pool allocation
+  const uintptr_t base = (uintptr_t)pool, lo_a = base + (uintptr_t)first, hi_a = base + (uintptr_t)last;
+  int up = 0, lo = 0, nn = 0, ot = 0;
+  for (uintptr_t s = (lo_a & ~(uintptr_t)15) + 16u * (unsigned)sub; s < hi_a; s += 256) {
+    const u32x4 v = *(const u32x4 *)s;
+    if (s >= lo_a && s + 16 <= hi_a) {
+      classes_word(v.x, 0x80808080u, up, lo, nn, ot);
+      classes_word(v.y, 0x80808080u, up, lo, nn, ot);
+      classes_word(v.z, 0x80808080u, up, lo, nn, ot);
+      classes_word(v.w, 0x80808080u, up, lo, nn, ot);
+    } else {  // the ragged first or last slot (both, in a short range): bit j of m -- byte j of the slot belongs to the segment
+      const int j0 = s < lo_a ? (int)(lo_a - s) : 0, j1 = s + 16 > hi_a ? (int)(hi_a - s) : 16;
+      const uint32_t m = ((1u << j1) - 1u) & ~((1u << j0) - 1u);
+      // (four bits -> bit 7 of four bytes: bit i of the nibble lands on bit 8 i of the product, and on nothing else that is kept)
+      auto spread = [](uint32_t nib) { return ((nib * 0x00204081u) & 0x01010101u) << 7; };
+      classes_word(v.x, spread(m & 15u), up, lo, nn, ot);
+      classes_word(v.y, spread((m >> 4) & 15u), up, lo, nn, ot);
+      classes_word(v.z, spread((m >> 8) & 15u), up, lo, nn, ot);
+      classes_word(v.w, spread((m >> 12) & 15u), up, lo, nn, ot);
+    }
+  }
+  for (int d = 8; d; d >>= 1) {
+    up += __shfl_xor(up, d, 16);
+    lo += __shfl_xor(lo, d, 16);
+    nn += __shfl_xor(nn, d, 16);
+    ot += __shfl_xor(ot, d, 16);
+  }
+  if (sub == 0) {
+    sdf_range_classes *o = out + a;
+    if (up) (void)__hip_atomic_fetch_add(&o->upper_acgt, up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lo) (void)__hip_atomic_fetch_add(&o->lower_acgt, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (nn) (void)__hip_atomic_fetch_add(&o->n_any, nn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ot) (void)__hip_atomic_fetch_add(&o->other, ot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 }  // namespace sdf

@@ -27,6 +27,8 @@ ANCHOR_PAIR_DTYPE = np.dtype([("q_off", "<i8"), ("r_off", "<i8"), ("qlen", "<i4"
                               ("same_chr", "<i4"), ("delta", "<i4")])
 ANCHOR_DTYPE = np.dtype([("q", "<i4"), ("r", "<i4"), ("l", "<i4"), ("has_u", "<i4")])
 BRIEF_DTYPE = np.dtype([("cigar_off", "<i8"), ("n_cigar", "<i4"), ("matches", "<i4")])  # sdf_result_brief
+POOL_RANGE_DTYPE = np.dtype([("off", "<i8"), ("len", "<i4"), ("reserved", "<i4")])  # sdf_pool_range
+RANGE_CLASSES_DTYPE = np.dtype([(f, "<i4") for f in ("upper_acgt", "lower_acgt", "n_any", "other")])  # sdf_range_classes
 RESERVE_BRIEF, RESERVE_ANCHORS = 1, 2
 assert BRIEF_DTYPE.itemsize == 16
 assert TASK_DTYPE.itemsize == 40 and RESULT_DTYPE.itemsize == 64 and ANCHOR_PAIR_DTYPE.itemsize == 32
@@ -105,6 +107,10 @@ def load_library():
                                         C.POINTER(C.c_int64)]
     L.sdf_pool_sync.restype = C.c_int
     L.sdf_pool_sync.argtypes = [C.c_void_p]
+    L.sdf_pool_range_classes.restype = C.c_int
+    L.sdf_pool_range_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdf_pool_share.restype = C.c_int
+    L.sdf_pool_share.argtypes = [C.c_void_p, C.c_void_p]
     L.sdf_anchors_batch_strand.restype = C.c_int
     L.sdf_anchors_batch_strand.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int,
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
@@ -357,6 +363,29 @@ class Extz2Engine:
 
     def pool_bytes(self):
         return int(self.lib.sdf_pool_bytes(self.ctx))
+
+    def pool_range_classes(self, ranges, check=True):
+        """sdf_pool_range_classes: the character classes of ranges of the resident pool.  ranges: a POOL_RANGE_DTYPE array, or
+        (off, len) pairs.  Returns a RANGE_CLASSES_DTYPE array (upper_acgt, lower_acgt, n_any, other), one record per range;
+        check=False: (rc, that array, sdf_last_error) instead of raising."""
+        if not (isinstance(ranges, np.ndarray) and ranges.dtype == POOL_RANGE_DTYPE):
+            pairs = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+            ranges = np.zeros(len(pairs), POOL_RANGE_DTYPE)
+            ranges["off"], ranges["len"] = pairs[:, 0], pairs[:, 1]
+        ranges = np.ascontiguousarray(ranges)
+        n = len(ranges)
+        out = np.zeros(n, RANGE_CLASSES_DTYPE)
+        rc = self.lib.sdf_pool_range_classes(self.ctx, ranges.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        if not check:
+            return rc, out, self.lib.sdf_last_error(self.ctx).decode()
+        self._check(rc)
+        return out
+
+    def pool_share(self, owner):
+        """sdf_pool_share: this context reads `owner`'s resident pool from now on (a view: no memory of its own).  The owner
+        outlives the view and leaves its pool alone meanwhile."""
+        self._check(self.lib.sdf_pool_share(self.ctx, owner.ctx))
+        return self.pool_bytes()
 
     def align_batch_pairs(self, tasks, mat=None, gapo=40, gape=1, want=None, cigar_cap=None, q_rc=None, t_rc=None, view=False):
         """sdf_extz2_batch_pairs (want=None: 16-byte records) / sdf_extz2_batch_pairs_full: q_off / t_off of the tasks are byte

@@ -95,6 +95,21 @@ def generate_many(ref_path, beds, kmer, out_suffix=".aligned.bed", log_dir=None,
     return [(int(stats[2 * k]), int(stats[2 * k + 1])) for k in range(n)]
 
 
+def generate_many_resident(ref_path, beds, kmer, out_suffix=".aligned.bed", log_dir=None, test_dp=None, device=0, resident=True):
+    """generate_many on chromosomes that stay resident in HBM (sdfh_generate_many_resident; resident=False: generate_many).
+    Returns ([(lines, hits)] per bucket, (FASTA records uploaded, characters uploaded to a device pool, super-batches run,
+    super-batches that named resident ranges))."""
+    lib = load_host()
+    nb = sum(len(os.listdir(b)) if os.path.isdir(b) else 1 for b in beds)
+    stats = (C.c_longlong * (2 * max(nb, 1) + 4))()
+    lib.sdfh_generate_many_resident.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int,
+                                                C.c_int, C.c_void_p]
+    n = lib.sdfh_generate_many_resident(ref_path.encode(), "\n".join(beds).encode(), kmer, out_suffix.encode(),
+                                        log_dir.encode() if log_dir else None, test_dp, device, int(bool(resident)), stats)
+    _err(lib, min(n, 0))
+    return [(int(stats[2 * k]), int(stats[2 * k + 1])) for k in range(n)], tuple(int(stats[2 * n + i]) for i in range(4))
+
+
 _buf = None
 
 

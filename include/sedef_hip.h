@@ -347,6 +347,9 @@ long long sdf_last_reran(const sdf_ctx *ctx);
  * least 8,192 of them, under a scoring with match + 2 (gap open + gap extend) <= 127.  They are sorted and planned on the
  * device; the host only marks them. */
 long long sdf_last_lane_tasks(const sdf_ctx *ctx);
+/* Pairs of the context's last sdf_chain_batch per launch class: out[0..5] the LDS classes of the wavefront kernel
+ * (smallest first), out[6] the thread-per-pair kernel, out[7] the LDS cap in bytes of class 5 on this device. */
+int sdf_last_chain_classes(const sdf_ctx *ctx, int64_t out[8]);
 
 /* ---- seed anchors on the GPU (next row of the scope table) -----------------------------------
  * Replaces generate_anchors (reference: src/chain.cc:24-101) for a batch of candidate pairs: maximal exact
@@ -398,7 +401,8 @@ int sdf_anchors_batch_more_strand(sdf_ctx *ctx, const sdf_anchor_pair *pairs, co
  *   path[off[i] + k]                    k-th path element of pair i (index within the pair), k < off[i+1]-off[i]
  *   bounds[2 * (off[i] + i + b) + 0/1]  b-th boundary of pair i, b < nbound[i]
  * path holds off[n] entries, bounds 2 * (off[n] + n), nbound n.  max_chain_gap / match_chain_score are the
- * reference's MAX_CHAIN_GAP / MATCH_CHAIN_SCORE (src/common.h). */
+ * reference's MAX_CHAIN_GAP / MATCH_CHAIN_SCORE (src/common.h).  Coordinates and scores are `int` and are ordered as
+ * `int`, as in the reference: negative ones sort before the others, whichever kernel takes the pair. */
 int sdf_chain_batch(sdf_ctx *ctx, const sdf_anchor *anchors, const int64_t *off, size_t n, int max_chain_gap,
                     int match_chain_score, int32_t *path, int32_t *bounds, int32_t *nbound);
 

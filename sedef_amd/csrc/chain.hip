@@ -341,6 +341,14 @@ __global__ __launch_bounds__(64) void chain_kernel(const sdf_anchor *__restrict_
 // (a node's point range follows from its index alone).  LDS per pair: 64 m + 16 nodes bytes (m anchors -- their records
 // included --, nodes = 2 * 2^ceil(log2 m) <= 4 m); pairs beyond the launch's LDS go to the thread-per-pair kernel.
 
+// The sorts' keys: (value, anchor) in one 64-bit word compared UNSIGNED.  The value is an int -- a coordinate or a chain score,
+// either may be negative -- and must order as the reference's pair<int, int> does: its sign bit is flipped on the way in
+// and on the way out (the thread-per-pair kernel, the host and the reference compare ints).
+__device__ __forceinline__ unsigned long long chain_key(int v, int i) {
+  return ((unsigned long long)((unsigned)v ^ 0x80000000u) << 32) | (unsigned)i;
+}
+__device__ __forceinline__ int chain_key_value(unsigned long long k) { return (int)((unsigned)(k >> 32) ^ 0x80000000u); }
+
 // ascending sort of a[0 .. n) in LDS by the workgroup's single wavefront (normalised bitonic network: the first step of a
 // merge pairs i with its mirror image in the block, the others i with i + j; a partner at or beyond n is a virtual +inf)
 __device__ __forceinline__ void chain_sort_u64(unsigned long long *a, const int n, const int lane) {
@@ -401,9 +409,9 @@ __global__ __launch_bounds__(64) void chain_wave_kernel(const sdf_anchor *__rest
   for (int i = lane; i < m; i += 64) {
     const sdf_anchor a = A[i];
     L[i] = a;
-    kx[2 * i] = ((unsigned long long)(unsigned)a.q << 32) | (unsigned)i;            // start event (x, anchor)
-    kx[2 * i + 1] = ((unsigned long long)(unsigned)(a.q + a.l) << 32) | (unsigned)i;  // end event
-    ky[i] = ((unsigned long long)(unsigned)(a.r + a.l - 1) << 32) | (unsigned)i;
+    kx[2 * i] = chain_key(a.q, i);            // start event (x, anchor)
+    kx[2 * i + 1] = chain_key(a.q + a.l, i);  // end event
+    ky[i] = chain_key(a.r + a.l - 1, i);
     max_q = max(max_q, a.q + a.l);
     max_r = max(max_r, a.r + a.l);
     dpv[i] = 0;
@@ -419,7 +427,7 @@ __global__ __launch_bounds__(64) void chain_wave_kernel(const sdf_anchor *__rest
   // the points in their sorted order, then (ky is dead) prev / used
   for (int i = lane; i < m; i += 64) {
     const unsigned long long kv = ky[i];
-    ys[i] = Pt{P2{(int)(kv >> 32), (int)(kv & 0xffffffffu)}, TREE_MIN, (int)(kv & 0xffffffffu)};
+    ys[i] = Pt{P2{chain_key_value(kv), (int)(kv & 0xffffffffu)}, TREE_MIN, (int)(kv & 0xffffffffu)};
   }
   __syncthreads();
   for (int i = lane; i < m; i += 64) prev[i] = -1, used[i] = 0;
@@ -455,14 +463,14 @@ __global__ __launch_bounds__(64) void chain_wave_kernel(const sdf_anchor *__rest
     int deactivate_bound = 0;
     for (int xi = 0; xi < 2 * m; ++xi) {
       const unsigned long long ev = kx[xi];
-      const int i = (int)(ev & 0xffffffffu), x = (int)(ev >> 32);
+      const int i = (int)(ev & 0xffffffffu), x = chain_key_value(ev);
       const sdf_anchor a = L[i];
       if (x == a.q) {  // start point
         while (deactivate_bound < xi) {
           const unsigned long long dv = kx[deactivate_bound];
           const int t = (int)(dv & 0xffffffffu);
           const sdf_anchor at = L[t];
-          if ((int)(dv >> 32) == at.q + at.l) {  // an end point
+          if (chain_key_value(dv) == at.q + at.l) {  // an end point
             if (a.q - (at.q + at.l) <= max_chain_gap) break;
             tr.deactivate(P2{at.r + at.l - 1, t});
           }
@@ -490,7 +498,7 @@ __global__ __launch_bounds__(64) void chain_wave_kernel(const sdf_anchor *__rest
   }
   __syncthreads();
   // sort(dp, greater) on (score, anchor): ascending on the complemented key
-  for (int i = lane; i < m; i += 64) kx[i] = ~(((unsigned long long)(unsigned)dpv[i] << 32) | (unsigned)i);
+  for (int i = lane; i < m; i += 64) kx[i] = ~chain_key(dpv[i], i);
   __syncthreads();
   chain_sort_u64(kx, m, lane);
   if (lane == 0) {

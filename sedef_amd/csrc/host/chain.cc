@@ -94,10 +94,11 @@ inline int64_t key_of(int coord, int idx) { return (int64_t)coord * ((int64_t)1 
 // Sorts keys of the form key_of(coord, idx) whose idx ascend in the input (so a STABLE sort by coord alone is the sort by
 // the whole key): counting passes over 11-bit digits of the coordinate -- two for sequences below 4 Mb -- instead of a
 // comparison sort; the three sorts of a pair's anchors were a third of chain_anchors.  Short inputs and negative
-// coordinates keep std::sort.
-void sort_by_coord(std::vector<int64_t> &v, std::vector<int64_t> &tmp, int64_t max_coord) {
+// coordinates keep std::sort: the digits below are those of a non-negative number, so the caller names the smallest
+// coordinate too (a set with ONE negative coordinate -- or negative chain scores -- is ordered as `int`, like the reference's).
+void sort_by_coord(std::vector<int64_t> &v, std::vector<int64_t> &tmp, int64_t min_coord, int64_t max_coord) {
   const size_t n = v.size();
-  if (n < 96 || max_coord < 0 || max_coord >= ((int64_t)1 << 31)) {
+  if (n < 96 || min_coord < 0 || max_coord >= ((int64_t)1 << 31)) {
     std::sort(v.begin(), v.end());
     return;
   }
@@ -282,6 +283,7 @@ std::pair<std::vector<int>, std::vector<std::pair<int, bool>>> chain_anchors(std
   // lists as it goes (an unsorted input sorts its starts too).
   std::vector<int64_t> starts((size_t)n), ends((size_t)n), sorted_r((size_t)n);
   int far_q = 0, far_r = 0;
+  int near_q = INT_MAX, near_r = INT_MAX;  // smallest query start / reference end: what sort_by_coord may assume of its keys
   bool starts_sorted = true;
   for (int i = 0; i < n; i++) {
     const Anchor &a = anchors[i];
@@ -291,11 +293,13 @@ std::pair<std::vector<int>, std::vector<std::pair<int, bool>>> chain_anchors(std
     starts_sorted = starts_sorted && (i == 0 || anchors[i - 1].q <= a.q);
     far_q = std::max(far_q, a.q + a.l);
     far_r = std::max(far_r, a.r + a.l);
+    near_q = std::min(near_q, std::min(a.q, a.q + a.l));
+    near_r = std::min(near_r, a.r + a.l - 1);
   }
   std::vector<int64_t> scratch;
-  if (!starts_sorted) sort_by_coord(starts, scratch, far_q);
-  sort_by_coord(ends, scratch, far_q);
-  sort_by_coord(sorted_r, scratch, far_r);
+  if (!starts_sorted) sort_by_coord(starts, scratch, near_q, far_q);
+  sort_by_coord(ends, scratch, near_q, far_q);
+  sort_by_coord(sorted_r, scratch, near_r, far_r);
   std::vector<int> point_of((size_t)n);  // anchor -> its point of the tree (the rank of its reference end)
   for (int p = 0; p < n; p++) point_of[(size_t)(uint32_t)sorted_r[(size_t)p]] = p;
   RangeMax tree(std::move(sorted_r));
@@ -336,12 +340,13 @@ std::pair<std::vector<int>, std::vector<std::pair<int, bool>>> chain_anchors(std
   // chains, best first (ties: the later anchor first), each from its last anchor backwards until it meets an anchor
   // an earlier chain took (src/chain.cc:179-197)
   std::vector<int64_t> order((size_t)n);  // (score, anchor) in one word: sorted as numbers
-  int best_max = 0;
+  int best_min = 0, best_max = 0;
   for (int i = 0; i < n; i++) {
     order[(size_t)i] = key_of(best[i], i);
+    best_min = std::min(best_min, best[i]);
     best_max = std::max(best_max, best[i]);
   }
-  sort_by_coord(order, scratch, best_max);  // (ascending, ties by ascending anchor: read backwards)
+  sort_by_coord(order, scratch, best_min, best_max);  // (ascending, ties by ascending anchor: read backwards)
   std::reverse(order.begin(), order.end());
   path.reserve((size_t)n);
   std::vector<char> taken(n, 0);

@@ -1276,6 +1276,7 @@ extern "C" int sdf_chain_batch(sdf_ctx *ctx, const sdf_anchor *anchors, const in
     ctx->err = "invalid arguments";
     return SDF_ERR_INVALID;
   }
+  std::fill(ctx->chain_classes, ctx->chain_classes + 7, (int64_t)0);  // (sdf_last_chain_classes: this call's; [7] stays)
   if (n == 0) return SDF_OK;
   // Round 4: a pair whose arrays fit the LDS of a workgroup is swept by ONE WAVEFRONT with everything in LDS
   // (chain_wave_kernel: launch classes by LDS size, the pairs of most anchors first); the others keep the thread-per-pair
@@ -1285,7 +1286,7 @@ extern "C" int sdf_chain_batch(sdf_ctx *ctx, const sdf_anchor *anchors, const in
   // sweeps an anchor in ~14 us where a thread chasing nodes in HBM takes ~85 -- the launch is its largest pair --, but two
   // such workgroups fit a CU: 8,192 pairs of ~700 anchors take 150 ms that way against 59 ms with every pair in flight on
   // the thread-per-pair kernel; profiles/r04_chain_bench.txt)
-  const size_t caps[6] = {2048, 4096, 8192, 16384, 32768, (size_t)std::max(ctx->max_dyn_lds, 65536)};
+  const size_t caps[6] = {2048, 4096, 8192, 16384, 32768, (size_t)ctx->chain_classes[7]};
   std::vector<int32_t> cls[7];  // [6]: thread-per-pair
   std::vector<int64_t> ws_off(n + 1);
   int64_t words = 0;
@@ -1321,6 +1322,7 @@ extern "C" int sdf_chain_batch(sdf_ctx *ctx, const sdf_anchor *anchors, const in
     cls[5].clear();
   }
   ws_off[n] = words;
+  for (int c = 0; c < 7; ++c) ctx->chain_classes[c] = (int64_t)cls[c].size();
   std::vector<int32_t> which;
   size_t cls_first[7];
   for (int c = 0; c < 7; ++c) {

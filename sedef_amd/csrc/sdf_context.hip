@@ -133,8 +133,11 @@ extern "C" sdf_ctx *sdf_create_cfg(int device, size_t workspace_bytes, const sdf
   if (general_ok) ctx->max_dyn_lds = want_lds;
   (void)hipGetLastError();
   // (per context, hence per device: a process-wide once-flag would leave a second GPU's copy of the kernel at 64 KiB)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sdf::chain_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            std::max(ctx->max_dyn_lds, 65536));
+  // (refused: the kernel keeps the 64 KiB every kernel has, and sdf_chain_batch's largest LDS class ends there)
+  const int chain_lds = std::max(ctx->max_dyn_lds, 65536);
+  const bool chain_lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&sdf::chain_wave_kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds) == hipSuccess;
+  ctx->chain_classes[7] = chain_lds_ok ? chain_lds : 65536;
   (void)hipGetLastError();
   lap.at("attributes");
   if (hipStreamCreateWithFlags(&ctx->dp_stream[0], hipStreamNonBlocking) != hipSuccess ||
@@ -251,6 +254,11 @@ extern "C" int sdf_last_launches(const sdf_ctx *ctx) { return ctx ? ctx->launche
 extern "C" long long sdf_last_paired(const sdf_ctx *ctx) { return ctx ? ctx->paired : 0; }
 extern "C" long long sdf_last_reran(const sdf_ctx *ctx) { return ctx ? ctx->reran : 0; }
 extern "C" long long sdf_last_lane_tasks(const sdf_ctx *ctx) { return ctx ? ctx->lane_tasks : 0; }
+extern "C" int sdf_last_chain_classes(const sdf_ctx *ctx, int64_t out[8]) {
+  if (!ctx || !out) return SDF_ERR_INVALID;
+  std::copy(ctx->chain_classes, ctx->chain_classes + 8, out);
+  return SDF_OK;
+}
 
 // Buffers sized once (include/sedef_hip.h).  The bounds per task are the planner's: a launch-order entry per task and
 // stripe / block of columns, a CIGAR staging slot of qlen + tlen + 2 words.

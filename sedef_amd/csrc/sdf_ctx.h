@@ -361,6 +361,9 @@ struct sdf_ctx {
   std::vector<sdf_task> host_tasks;  // the task array of the host-buffer entry point with word offsets
   size_t pool_bytes = 0;   // characters resident in an_pool (sdf_pool_upload / sdf_anchors_batch): what sdf_extz2_batch_pairs may name
   long long lane_tasks = 0;   // tasks of the last batch call the lane kernel took
+  // sdf_last_chain_classes: pairs of the last sdf_chain_batch per launch class -- [0..5] the LDS classes of chain_wave_kernel,
+  // [6] chain_kernel --, [7] the LDS cap of class 5 in bytes (fixed in sdf_create: what the kernel was granted there)
+  int64_t chain_classes[8] = {0, 0, 0, 0, 0, 0, 0, 64 * 1024};
   sdf::WorkerPool *pool = nullptr;  // planning threads, started with the first batch large enough to use them
   sdf::BatchCut *cut = nullptr;  // chunk list and planning scratch of the last batch call (sdf_plan.hip)
   std::vector<hipEvent_t> events;

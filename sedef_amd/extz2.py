@@ -157,6 +157,8 @@ def load_library():
     L.sdf_last_reran.argtypes = [C.c_void_p]
     L.sdf_last_lane_tasks.restype = C.c_longlong
     L.sdf_last_lane_tasks.argtypes = [C.c_void_p]
+    L.sdf_last_chain_classes.restype = C.c_int
+    L.sdf_last_chain_classes.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -631,6 +633,13 @@ class Extz2Engine:
     def last_lane_tasks(self):
         """Tasks of the last batch that ran one per lane (extz2_lane.hip: small full-band tasks of a large batch)."""
         return int(self.lib.sdf_last_lane_tasks(self.ctx))
+
+    def last_chain_classes(self):
+        """Pairs of the last chain_batch per launch class: [0..5] the LDS classes of the wavefront kernel, [6] the
+        thread-per-pair kernel; [7] the LDS cap of class 5 in bytes (include/sedef_hip.h: sdf_last_chain_classes)."""
+        out = np.zeros(8, np.int64)
+        self._check(self.lib.sdf_last_chain_classes(self.ctx, out.ctypes.data))
+        return [int(x) for x in out]
 
     def last_reran(self):
         """Tasks of the last batch that a stripe kernel gave up and the call ran again on another kernel."""

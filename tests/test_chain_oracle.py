@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import bruteforce
+import chaingen
 import hostgen
 from refcalls import ref_calls
 
@@ -150,6 +151,41 @@ def test_host_chains_equal_oracle(oracle, host):
             assert np.array_equal(path, res["path"]) and np.array_equal(bounds, res["bounds"]), (len(a), gap, score)
             n += 1
     assert n >= 120
+
+
+# ---- the host's chain_anchors at every size: 1 to 6,000 anchors (sort_by_coord: std::sort below 96 keys, counting passes
+# from there on), on the generators and inputs of the GPU tests (tests/test_gpu_chain_paths.py, tests/chaingen.py)
+@pytest.fixture(scope="module")
+def sized_cases(oracle, host):
+    rng = np.random.default_rng(61)
+    real = chaingen.RealAnchors(host, rng)
+    sizes = set(chaingen.edge_sizes(160 * 1024)) | set(chaingen.edge_sizes(64 * 1024)) | {95, 96, 97, 3000, 6000}
+    return chaingen.cases_of(rng, real, sorted(sizes), accept=chaingen.has_chain_of_three(oracle))
+
+
+def test_host_chains_equal_oracle_at_every_size(oracle, host, sized_cases):
+    assert max(len(a) for a in sized_cases) == 6000 and min(len(a) for a in sized_cases) == 0
+    for gap, score in chaingen.SETTINGS:
+        res = [oracle.chain_anchors(a, gap, score) for a in sized_cases]
+        chaingen.check_inputs(sized_cases, res, 160 * 1024)
+        bad = [len(a) for a, r in zip(sized_cases, res) if not chaingen.same(host.chain_raw(a, gap, score), r)]
+        assert not bad, (gap, score, bad)
+
+
+@pytest.mark.parametrize("variant", ["a", "b", "b1", "c"])
+def test_host_chains_order_keys_as_int(oracle, host, sized_cases, variant):
+    """Negative coordinates, negative scores, coordinates near 10^9 (chaingen.signed_variants): the reference compares
+    pair<int, int> and int, and so does the oracle; the host packs (value, anchor) into one signed 64-bit key."""
+    cases, gap, score = chaingen.signed_variants(sized_cases)[variant]
+    if variant == "a":
+        assert chaingen.mixed_signs(cases) >= 10
+    res = [oracle.chain_anchors(a, gap, score) for a in cases]
+    if variant == "b":
+        assert all(int(r["dp"].max()) < 0 for a, r in zip(cases, res) if len(a))
+    if variant == "b1":
+        assert sum(int(r["dp"].min()) < 0 <= int(r["dp"].max()) for a, r in zip(cases, res) if len(a)) >= 10
+    bad = [len(a) for a, r in zip(cases, res) if not chaingen.same(host.chain_raw(a, gap, score), r)]
+    assert not bad, (variant, bad)
 
 
 @pytest.mark.gpu

@@ -462,7 +462,8 @@ def _chain_cases(host):
 
 @pytest.mark.gpu
 def test_gpu_chains_equal_host_chains(host):
-    """sdf_chain_batch (one GPU thread per pair) returns chain_anchors' path and boundaries exactly."""
+    """sdf_chain_batch (one wavefront per pair, everything in LDS, at these sizes; tests/test_gpu_chain_paths.py runs the
+    thread-per-pair kernel) returns chain_anchors' path and boundaries exactly."""
     import sedef_amd
     eng = sedef_amd.Extz2Engine(0)
     cases = _chain_cases(host)

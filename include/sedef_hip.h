@@ -148,7 +148,7 @@ typedef struct sdf_config {
   int64_t pin_register;
   double workspace_gib;
   /* other entry points */
-  int64_t chain_threads_only, stats_items, stats_group_max;
+  int64_t chain_threads_only, stats_items, stats_group_max, fetch_stage_bytes;
   /* diagnostics on stderr */
   int64_t debug_plan, debug_timing, debug_classes, debug_plan_early;
 } sdf_config;
@@ -296,6 +296,52 @@ int sdf_extz2_batch_pairs_view(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_ta
 typedef struct { int64_t off; int32_t len; int32_t reserved; /* must be 0 */ } sdf_pool_range;
 typedef struct { int32_t upper_acgt, lower_acgt, n_any /* 'N' or 'n' */, other; } sdf_range_classes;
 int sdf_pool_range_classes(sdf_ctx *ctx, const sdf_pool_range *ranges, size_t n, sdf_range_classes *out);
+
+/* ---- reading ranges of the resident pool back, by strand ---------------------------------------------------------------
+ * The characters of pool[off, off + len) as they lie in HBM, or their reverse complement (SDF_FETCH_RC), written to
+ * dst[dst_off, dst_off + len):
+ *   forward    dst[dst_off + j] = pool[off + j]                          byte for byte, bytes of 128 and above included
+ *   reversed   dst[dst_off + j] = rev_dna(pool[off + len - 1 - j])      the reference's table, indexed c & 127
+ *              (src/common.h:72-87,93: what rc() applies): A <-> T and C <-> G keep their case, every other byte becomes 'N'.
+ * No byte of dst outside the ranges' destinations is written; source ranges may overlap and repeat.  Destination ranges that
+ * overlap one another are the caller's error: they are NOT checked, and which range's bytes such a place ends up with is
+ * unspecified.  (seq_pack.hip: pool_fetch_kernel.)
+ *
+ * Host form.  dst is any host memory of dst_bytes bytes.  Everything is validated before any launch; a refused call leaves
+ * dst untouched and sdf_last_error() names the first offending range ("range <index>: ...").
+ *   SDF_ERR_INVALID      off < 0, len < 0, off + len > sdf_pool_bytes(ctx) (an empty pool holds no non-empty range), dst_off < 0,
+ *                        dst_off + len > dst_bytes, r == NULL with n > 0, dst == NULL with a byte to write
+ *   SDF_ERR_UNSUPPORTED  a flags bit other than SDF_FETCH_RC
+ * n == 0, or lengths that are all 0, is SDF_OK without a launch.  The bytes cross PCIe through a pinned staging buffer of the
+ * context, in pieces of at most sdf_config.fetch_stage_bytes when there are more; the call is enqueued on the context's stream,
+ * behind the pool's uploads (on a view made by sdf_pool_share: behind the owner's, as for every reader of a view), and returns
+ * when dst is complete.
+ *
+ * Device form.  Records and destination in HBM, nothing copied to the host: enqueued on `stream` (NULL: the context's own, and
+ * the call then returns after it has drained; a caller's stream is not waited for -- after sdf_pool_sync() when the pool was
+ * uploaded on the context's stream, as for sdf_stats_columns_pairs_device).  The kernel cuts ranges into segments of
+ * SDF_FETCH_SEG_BYTES destination bytes, a group of sixteen lanes each, and finds a segment's range by its record's seg0 -- the
+ * segments of the records before it.  sdf_pool_fetch_plan() makes those records from ranges, on the host, without a context:
+ * recs[i] describes r[i] (recs may be NULL: validation and counts only), *any_rc is whether a range carries SDF_FETCH_RC,
+ * *n_seg the segments of all of them, *bytes the sum of the lengths; the checks and codes are the host form's (pool_bytes /
+ * dst_bytes: the bounds to check against), and *bad receives the index of the first offending range.  The device form
+ * checks what it can see -- a resident pool, its alignment, n, n_seg -- and trusts the records: any_rc == 0 with a record
+ * whose rc is set copies that range forward. */
+#define SDF_FETCH_RC 0x1
+#define SDF_FETCH_SEG_BYTES 16384
+typedef struct { int64_t off; int32_t len; int32_t flags; int64_t dst_off; } sdf_pool_fetch;
+typedef struct {
+  int64_t src_off; /* first byte of the range in the pool, in pool order, whatever the strand */
+  int64_t dst_off;
+  int32_t len;
+  int32_t rc;      /* != 0: reversed */
+  int64_t seg0;    /* sum of ceil(len / SDF_FETCH_SEG_BYTES) over the records before this one */
+} sdf_pool_fetch_rec;
+int sdf_pool_fetch_ranges(sdf_ctx *ctx, const sdf_pool_fetch *r, size_t n, char *dst, size_t dst_bytes);
+int sdf_pool_fetch_plan(const sdf_pool_fetch *r, size_t n, size_t pool_bytes, size_t dst_bytes, sdf_pool_fetch_rec *recs,
+                        int *any_rc, long long *n_seg, size_t *bytes, size_t *bad);
+int sdf_pool_fetch_ranges_device(sdf_ctx *ctx, const sdf_pool_fetch_rec *d_recs /* HBM */, size_t n, int any_rc, long long n_seg,
+                                 char *d_dst, void *stream);
 
 /* ---- one resident pool read by several contexts of a device ---------------------------------------------------------
  * dst reads src's resident pool: dst's pool is replaced by a VIEW of src's (same device; SDF_ERR_INVALID otherwise, or when

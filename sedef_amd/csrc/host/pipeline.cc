@@ -574,6 +574,15 @@ class GpuProvider : public DpProvider {
       throw std::string("character classes of the resident pool failed: ") + sdf_last_error(ctx_);
     for (size_t i = 0; i < n; i++) plain[i] = cls[i].other == 0;
   }
+  bool fetch_ranges(const int64_t *off, const int32_t *len, const char *rc, const size_t *dst_off, size_t n, char *dst,
+                    size_t dst_bytes, std::string &why) override {
+    ready();
+    std::vector<sdf_pool_fetch> r(n);
+    for (size_t i = 0; i < n; i++) r[i] = {off[i], len[i], rc[i] ? SDF_FETCH_RC : 0, (int64_t)dst_off[i]};
+    if (sdf_pool_fetch_ranges(ctx_, r.data(), n, dst, dst_bytes) == SDF_OK) return true;
+    why = sdf_last_error(ctx_);
+    return false;
+  }
 
  private:
   // the seed anchors of jobs that name ranges of the resident chromosomes: nothing is copied or uploaded
@@ -1096,6 +1105,7 @@ StageSettings StageSettings::from_env() {
   s.bucket_lanes = (int)num("SDF_BUCKET_LANES", 1, 4, 2);
   s.stats_resident = num("SDF_STATS_RESIDENT", 0, 1, 0) != 0;
   s.stage_resident = num("SDF_STAGE_RESIDENT", 0, 1, 0) != 0;
+  s.fetch_device = num("SDF_STAGE_FETCH_DEVICE", 0, 1, 0) != 0;
   if (const char *e = getenv("SDF_DEVICES"))
     for (const char *c = e; *c;) {
       char *end = nullptr;
@@ -1281,10 +1291,11 @@ double since(Clock::time_point a) { return std::chrono::duration<double>(Clock::
 struct Acc {  // wall seconds of the phases of one lane of the driver
   double dp_secs = 0, anchor_secs = 0, t_fetch = 0, t_adv = 0, t_longest = 0, t_sum = 0, t_collect = 0, t_out = 0;
   int rounds = 0;
+  int batches = 0, fetched_device = 0;  // super-batches, and those whose sequences came back from the device pool (SDF_STAGE_FETCH_DEVICE)
   Acc &operator+=(const Acc &o) {
     dp_secs += o.dp_secs, anchor_secs += o.anchor_secs, t_fetch += o.t_fetch, t_adv += o.t_adv;
     t_longest += o.t_longest, t_sum += o.t_sum, t_collect += o.t_collect, t_out += o.t_out;
-    rounds += o.rounds;
+    rounds += o.rounds, batches += o.batches, fetched_device += o.fetched_device;
     return *this;
   }
 };
@@ -1354,33 +1365,82 @@ struct SuperBatch {
     // has one: the anchors call uploads from there without another copy, and the DP rounds name ranges of it -- a slot per
     // sequence as long as the bytes its range spans in the file (line ends included: the bound known before the copy).
     std::vector<FastaReference::Span> span(2 * (size_t)n);
-    slot.assign(2 * (size_t)n + 1, 0);
     for (int k = 0; k < n; k++) {
       Item &it = items[k];
       it.h = run.schedule[base + k];
       span[2 * k] = run.fr->locate(it.h.query->name, it.h.query_start, &it.h.query_end);
       span[2 * k + 1] = run.fr->locate(it.h.ref->name, it.h.ref_start, &it.h.ref_end);
-      slot[2 * k + 1] = slot[2 * k] + span[2 * k].bytes;
-      slot[2 * k + 2] = slot[2 * k + 1] + span[2 * k + 1].bytes;
     }
-    const size_t bytes = slot[2 * (size_t)n];
-    char *pool = genome ? nullptr : dp.pool_host(bytes + 1);
-    provider_pool = pool != nullptr;
-    if (!pool) {
-      if (lane.own_pool_cap < bytes + 1) {
-        lane.own_pool_cap = bytes + 1 + bytes / 8;
-        lane.own_pool.reset(new char[lane.own_pool_cap]);
+    char *pool = nullptr;
+    size_t bytes = 0;
+    auto lay_out = [&](const std::vector<size_t> &need) {  // a slot of need[i] bytes per sequence, in the pool
+      slot.assign(2 * (size_t)n + 1, 0);
+      for (size_t i = 0; i < 2 * (size_t)n; i++) slot[i + 1] = slot[i] + need[i];
+      bytes = slot[2 * (size_t)n];
+      pool = genome ? nullptr : dp.pool_host(bytes + 1);
+      provider_pool = pool != nullptr;
+      if (!pool) {
+        if (lane.own_pool_cap < bytes + 1) {
+          lane.own_pool_cap = bytes + 1 + bytes / 8;
+          lane.own_pool.reset(new char[lane.own_pool_cap]);
+        }
+        pool = lane.own_pool.get();
       }
-      pool = lane.own_pool.get();
+    };
+    std::vector<size_t> need(2 * (size_t)n);
+    ++a.batches;
+    bool fetched = false;
+    if (genome && stage_settings().fetch_device) {
+      // Resident chromosomes hold these bases already: ONE device call of 2n ranges -- the query forward, the reference
+      // reverse-complemented on its way where the hit says so -- writes them into slots as long as the bases (locate() has
+      // clamped the ends).  A call that fails is said in one line, and this super-batch cuts its sequences out of the file.
+      std::vector<int64_t> off(2 * (size_t)n);
+      std::vector<int32_t> len(2 * (size_t)n);
+      std::vector<char> rc(2 * (size_t)n, 0);
+      std::string why;
+      for (int k = 0; k < n && why.empty(); k++) {
+        const Hit &h = items[k].h;
+        int64_t qb = 0, rb = 0;
+        if (!dp.chromosome_base(h.query->name, &qb) || !dp.chromosome_base(h.ref->name, &rb)) {
+          why = "a pair on a chromosome that is not resident";
+          break;
+        }
+        off[2 * k] = qb + std::max(0, h.query_start);
+        off[2 * k + 1] = rb + std::max(0, h.ref_start);
+        len[2 * k] = span[2 * k].bytes ? std::max(0, h.query_end - std::max(0, h.query_start)) : 0;
+        len[2 * k + 1] = span[2 * k + 1].bytes ? std::max(0, h.ref_end - std::max(0, h.ref_start)) : 0;
+        rc[2 * k + 1] = h.ref->is_rc;
+        need[2 * k] = (size_t)len[2 * k], need[2 * k + 1] = (size_t)len[2 * k + 1];
+      }
+      if (why.empty()) {
+        lay_out(need);
+        fetched = dp.fetch_ranges(off.data(), len.data(), rc.data(), slot.data(), off.size(), pool, bytes, why);
+      }
+      if (fetched) {
+        ++a.fetched_device;
+        parallel_for(n, [&](int k) {
+          Item &it = items[k];
+          it.fa = SeqView(pool + slot[2 * k], need[2 * k]);
+          it.fb = SeqView(pool + slot[2 * k + 1], need[2 * k + 1]);
+          it.job.reset(new PairJob(it.fa, it.fb, it.h, run.p, !genome));
+        });
+      } else {
+        fprintf(stderr, "[sedef_amd] SDF_STAGE_FETCH_DEVICE=1: super-batch at pair %d cuts its sequences out of the FASTA file: %s\n",
+                base, why.c_str());
+      }
     }
-    parallel_for(n, [&](int k) {
-      Item &it = items[k];
-      char *qa = pool + slot[2 * k], *ra = pool + slot[2 * k + 1];
-      it.fa = SeqView(qa, FastaReference::extract(span[2 * k], qa));
-      it.fb = SeqView(ra, FastaReference::extract(span[2 * k + 1], ra));
-      if (it.h.ref->is_rc) rc_inplace(ra, it.fb.size());
-      it.job.reset(new PairJob(it.fa, it.fb, it.h, run.p, !genome));
-    });
+    if (!fetched) {
+      for (size_t i = 0; i < 2 * (size_t)n; i++) need[i] = span[i].bytes;
+      lay_out(need);
+      parallel_for(n, [&](int k) {
+        Item &it = items[k];
+        char *qa = pool + slot[2 * k], *ra = pool + slot[2 * k + 1];
+        it.fa = SeqView(qa, FastaReference::extract(span[2 * k], qa));
+        it.fb = SeqView(ra, FastaReference::extract(span[2 * k + 1], ra));
+        if (it.h.ref->is_rc) rc_inplace(ra, it.fb.size());
+        it.job.reset(new PairJob(it.fa, it.fb, it.h, run.p, !genome));
+      });
+    }
     ++g_totals.batches;
     if (genome) {
       // Nothing is uploaded: the pairs' ranges of the resident chromosomes, and ONE device call that says which pairs hold
@@ -1777,6 +1837,9 @@ GenerateStats generate_alignments(const std::string &ref_path, const std::string
                "%.2fs, all jobs %.2fs thread time), request collection %.2fs, output %.2fs; DP provider: request "
                "packing %.2fs, device call %.2fs, CIGAR unpacking %.2fs]\n",
           a.t_fetch, a.t_adv, a.t_longest, a.t_sum, a.t_collect, a.t_out, t_pack, t_call, t_unpack);
+  if (stage_settings().fetch_device && dp0.has_genome())  // (the marker that the device fetch ran, and how often it did not)
+    fprintf(log, "  [sequence fetch: %d of %d super-batches read their sequences back from the device pool (SDF_STAGE_FETCH_DEVICE=1)]\n",
+            a.fetched_device, a.batches);
   // (the extra lanes' providers go back to the one they came from: the next bucket of this process takes them again, and the
   // first provider gives all their device contexts back side by side when it goes)
   for (Lane &l : lanes)

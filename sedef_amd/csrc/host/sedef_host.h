@@ -211,6 +211,13 @@ class DpProvider {
   virtual void plain_ranges(const int64_t * /*off*/, const int32_t * /*len*/, size_t /*n*/, char * /*plain*/) {
     throw std::string("internal: no resident pool to classify");
   }
+  // Optional, resident chromosomes: dst[dst_off[i], dst_off[i] + len[i]) = pool bytes [off[i], off[i] + len[i]), reverse-
+  // complemented where rc[i] (one device call: sdf_pool_fetch_ranges).  false, with `why` filled: dst holds nothing usable.
+  virtual bool fetch_ranges(const int64_t * /*off*/, const int32_t * /*len*/, const char * /*rc*/, const size_t * /*dst_off*/,
+                            size_t /*n*/, char * /*dst*/, size_t /*dst_bytes*/, std::string &why) {
+    why = "the provider keeps no chromosomes resident";
+    return false;
+  }
   int64_t tasks = 0, cells = 0;  // statistics
   double t_pack = 0, t_call = 0, t_unpack = 0;  // wall seconds: request packing and device call (run), unpacking (run_cigars)
 };
@@ -504,6 +511,7 @@ struct StageSettings {
   bool resident_dp = true;   // SDF_RESIDENT_DP=0: the DP rounds cut their bases out on the host again instead of naming ranges of the characters the anchors call left in HBM
   bool stats_resident = false;  // SDF_STATS_RESIDENT=1: `stats generate` counts on resident chromosomes (StatsParams::resident)
   bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
+  bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise
   int bucket_lanes = 2;      // SDF_BUCKET_LANES: buckets of a several-bucket run in flight, each on a device context of its own (1: one after the other)
   static StageSettings from_env();
 };

@@ -120,6 +120,8 @@ int main(int argc, char **argv) {
               "  params: -k/--kmer, --match, --mismatch, --gap-open, --gap-extend (default 5, -4, -40, -1)\n"
               "  SDF_STAGE_RESIDENT=1 in the environment: every chromosome the buckets name is uploaded once per process and\n"
               "  the super-batches name ranges of it (same output; off by default)\n"
+              "  SDF_STAGE_FETCH_DEVICE=1 (default 0; only with SDF_STAGE_RESIDENT=1): a super-batch reads its sequences back from\n"
+              "  the resident chromosomes in one device call instead of cutting them out of the FASTA file (same output)\n"
               "sedef align bucket -n [count] [bed_directory(/)] [buckets/] [genome.fa]\n"
               "  bucket BEDs into [count] files for the alignment stage (--extend-ratio, --max-extend, --merge-dist)\n"
               "sedef stats generate [genome.fa] [final.bed]\n"

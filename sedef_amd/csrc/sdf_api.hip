@@ -964,6 +964,169 @@ extern "C" int sdf_pool_range_classes(sdf_ctx *ctx, const sdf_pool_range *ranges
   return SDF_OK;
 }
 
+// ---- ranges of the resident pool read back, by strand (include/sedef_hip.h; seq_pack.hip: pool_fetch_kernel) ----
+// The checks of one range, and its record.  `why` gets the reason of a refusal.
+static int fetch_check(const sdf_pool_fetch &r, size_t pool_bytes, size_t dst_bytes, const char **why) {
+  if (r.flags & ~SDF_FETCH_RC) {
+    *why = "unknown flag";
+    return SDF_ERR_UNSUPPORTED;
+  }
+  if (r.off < 0 || r.len < 0 || (size_t)r.off > pool_bytes || (size_t)r.len > pool_bytes - (size_t)r.off) {
+    *why = "outside the resident pool";
+    return SDF_ERR_INVALID;
+  }
+  if (r.dst_off < 0 || (size_t)r.dst_off > dst_bytes || (size_t)r.len > dst_bytes - (size_t)r.dst_off) {
+    *why = "destination outside dst";
+    return SDF_ERR_INVALID;
+  }
+  return SDF_OK;
+}
+
+extern "C" int sdf_pool_fetch_plan(const sdf_pool_fetch *r, size_t n, size_t pool_bytes, size_t dst_bytes, sdf_pool_fetch_rec *recs,
+                                   int *any_rc, long long *n_seg, size_t *bytes, size_t *bad) {
+  int rc_any = 0;
+  long long seg = 0;
+  size_t sum = 0;
+  int ret = SDF_OK;
+  if (bad) *bad = 0;
+  if ((!r && n) || n > 0x3fffffffu) ret = SDF_ERR_INVALID;
+  for (size_t i = 0; i < n && ret == SDF_OK; ++i) {
+    const char *why = nullptr;
+    ret = fetch_check(r[i], pool_bytes, dst_bytes, &why);
+    if (ret == SDF_OK && seg + (r[i].len + sdf::kFetchSegBytes - 1) / sdf::kFetchSegBytes > 0x7fffff00ll) ret = SDF_ERR_UNSUPPORTED;
+    if (ret != SDF_OK) {
+      if (bad) *bad = i;
+      break;
+    }
+    if (recs) recs[i] = sdf_pool_fetch_rec{r[i].off, r[i].dst_off, r[i].len, (r[i].flags & SDF_FETCH_RC) ? 1 : 0, (int64_t)seg};
+    seg += (r[i].len + sdf::kFetchSegBytes - 1) / sdf::kFetchSegBytes;
+    sum += (size_t)r[i].len;
+    rc_any |= r[i].flags & SDF_FETCH_RC;
+  }
+  if (any_rc) *any_rc = ret == SDF_OK && rc_any;
+  if (n_seg) *n_seg = ret == SDF_OK ? seg : 0;
+  if (bytes) *bytes = ret == SDF_OK ? sum : 0;
+  return ret;
+}
+
+// what both forms ask of the pool before the kernel may read aligned slots of it
+static int fetch_pool_ok(sdf_ctx *ctx, const char *who) {
+  if (ctx->pool_bytes == 0 || !ctx->an_pool.p) {
+    ctx->err = std::string(who) + ": no resident pool";
+    return SDF_ERR_INVALID;
+  }
+  // (the slots of the first range start at the base; those of the last end inside the 64 bytes behind every pool allocation)
+  if (((uintptr_t)ctx->an_pool.p & 15) != 0 || ctx->an_pool.cap < ctx->pool_bytes + 16) {
+    ctx->err = std::string(who) + ": the pool's base is not 16-byte aligned, or nothing is allocated behind its last character";
+    return SDF_ERR_INVALID;
+  }
+  return SDF_OK;
+}
+
+static void fetch_launch(const sdf::FetchRec *d_recs, int n, long long n_seg, bool rev, const char *d_pool, char *d_dst, hipStream_t st) {
+  hipLaunchKernelGGL(rev ? sdf::pool_fetch_kernel<true> : sdf::pool_fetch_kernel<false>, dim3((unsigned)((n_seg + 15) / 16)), dim3(256),
+                     0, st, d_recs, n, n_seg, d_pool, d_dst);
+}
+
+extern "C" int sdf_pool_fetch_ranges_device(sdf_ctx *ctx, const sdf_pool_fetch_rec *d_recs, size_t n, int any_rc, long long n_seg,
+                                            char *d_dst, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (n == 0 || n_seg == 0) return SDF_OK;
+  if (!d_recs || !d_dst || n > 0x3fffffffu || n_seg < 0 || n_seg > 0x7fffff00ll) {
+    ctx->err = "sdf_pool_fetch_ranges_device: invalid arguments";
+    return SDF_ERR_INVALID;
+  }
+  if (int rc = fetch_pool_ok(ctx, "sdf_pool_fetch_ranges_device")) return rc;
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  fetch_launch(d_recs, (int)n, n_seg, any_rc != 0, (const char *)ctx->an_pool.p, d_dst, st);
+  SDF_HIP(hipGetLastError());
+  if (!stream) SDF_HIP(hipStreamSynchronize(st));
+  return SDF_OK;
+}
+
+// The host form: the output crosses PCIe through the context's pinned staging, a piece of at most fetch_stage_bytes at a time.
+// A piece's device buffer mirrors the caller's dst modulo 16: ranges whose destinations follow one another without a gap lie
+// back to back in it (the stage driver's slots: one copy out of the staging per piece), any other range begins at the next
+// place that is congruent to its dst_off -- so the kernel's stores are aligned where the caller's destination is.  A range
+// that does not fit the rest of a piece is cut: the sub-range [a, a + take) of a reversed range's output reads the source
+// bytes [off + len - a - take, off + len - a).
+extern "C" int sdf_pool_fetch_ranges(sdf_ctx *ctx, const sdf_pool_fetch *r, size_t n, char *dst, size_t dst_bytes) {
+  using sdf::FetchRec;
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (n == 0) return SDF_OK;
+  if (!r || n > 0x3fffffffu) {
+    ctx->err = "sdf_pool_fetch_ranges: invalid arguments";
+    return SDF_ERR_INVALID;
+  }
+  const size_t pool_bytes = ctx->pool_bytes;
+  size_t total = 0, first_byte = 0;  // (first_byte: the first range that has one)
+  bool any_rc = false;
+  for (size_t i = 0; i < n; ++i) {
+    const char *why = nullptr;
+    if (int rc = fetch_check(r[i], pool_bytes, dst_bytes, &why)) {
+      ctx->err = "sdf_pool_fetch_ranges: range " + std::to_string(i) + ": " + why;
+      return rc;
+    }
+    if (total == 0) first_byte = i;
+    total += (size_t)r[i].len;
+    any_rc |= (r[i].flags & SDF_FETCH_RC) != 0;
+  }
+  if (total == 0) return SDF_OK;
+  if (!dst) {
+    ctx->err = "sdf_pool_fetch_ranges: range " + std::to_string(first_byte) + ": a byte to write and no dst";
+    return SDF_ERR_INVALID;
+  }
+  if (int rc = fetch_pool_ok(ctx, "sdf_pool_fetch_ranges")) return rc;
+  SDF_HIP(hipSetDevice(ctx->device));
+  // (a range costs its bytes and up to 30 of padding; records: one per range of a piece and one per cut)
+  const size_t cap = std::min<size_t>((size_t)ctx->cfg.fetch_stage_bytes, total + 32 * n + 4095) & ~(size_t)4095;
+  const size_t max_recs = std::min<size_t>(n + 1, (size_t)1 << 18);
+  SDF_HIP(ctx->host_fetch.reserve_exact(cap + max_recs * sizeof(FetchRec)));
+  SDF_HIP(ctx->pf_out.reserve_exact(cap + 64));
+  SDF_HIP(ctx->pf_recs.reserve_exact(max_recs * sizeof(FetchRec)));
+  char *back = (char *)ctx->host_fetch.p;
+  FetchRec *recs = (FetchRec *)(back + cap);
+  struct Run { size_t dst_off, at, len; };
+  std::vector<Run> runs;
+  size_t i = 0, a = 0;  // the next byte to fetch: byte a of range i's output
+  while (i < n) {
+    size_t p = 0, nrec = 0;
+    long long n_seg = 0;
+    runs.clear();
+    while (i < n && nrec < max_recs) {
+      const size_t len = (size_t)r[i].len;
+      if (a >= len) {
+        ++i, a = 0;
+        continue;
+      }
+      const size_t d = (size_t)r[i].dst_off + a;
+      const bool follows = !runs.empty() && runs.back().dst_off + runs.back().len == d;
+      const size_t at = follows ? p : ((p + 15) & ~(size_t)15) + (d & 15);
+      if (at >= cap) break;
+      const size_t take = std::min(len - a, cap - at);
+      if (take < len - a && take < 4096 && nrec) break;  // (no slivers at the end of a piece)
+      const bool rc = (r[i].flags & SDF_FETCH_RC) != 0;
+      recs[nrec++] = FetchRec{r[i].off + (int64_t)(rc ? len - a - take : a), (int64_t)at, (int32_t)take, rc ? 1 : 0, (int64_t)n_seg};
+      n_seg += (long long)((take + sdf::kFetchSegBytes - 1) / sdf::kFetchSegBytes);
+      if (follows) runs.back().len += take;
+      else runs.push_back(Run{d, at, take});
+      p = at + take;
+      a += take;
+    }
+    if (nrec == 0) continue;  // (only empty ranges were left)
+    SDF_HIP(hipMemcpyAsync(ctx->pf_recs.p, recs, nrec * sizeof(FetchRec), hipMemcpyHostToDevice, ctx->stream));
+    fetch_launch((const FetchRec *)ctx->pf_recs.p, (int)nrec, n_seg, any_rc, (const char *)ctx->an_pool.p, (char *)ctx->pf_out.p, ctx->stream);
+    SDF_HIP(hipGetLastError());
+    SDF_HIP(hipMemcpyAsync(back, ctx->pf_out.p, p, hipMemcpyDeviceToHost, ctx->stream));
+    SDF_HIP(hipStreamSynchronize(ctx->stream));
+    for (const Run &q : runs) memcpy(dst + q.dst_off, back + q.at, q.len);
+  }
+  return SDF_OK;
+}
+
 // Debug: wavefronts started per (XCD, shader engine, CU, SIMD) since the last call, 4096 counters indexed
 // xcd << 9 | se << 6 | cu << 2 | simd (the chained strips note theirs: how evenly the dispatcher spreads a launch).
 extern "C" int sdf_debug_placement(sdf_ctx *ctx, uint32_t *out) {

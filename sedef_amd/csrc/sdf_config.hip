@@ -61,6 +61,7 @@ static const ConfigField kConfigFields[] = {
     SDF_CF("SDF_CHAIN_THREADS", chain_threads_only, 0, 0, 1, "sdf_chain_batch: 1: every pair on the thread-per-pair kernel"),
     SDF_CF("SDF_STATS_ITEMS", stats_items, 1 << 18, 1, 1e9, "sdf_stats_columns: capacity of the long alignments' segment list"),
     SDF_CF("SDF_STATS_GROUP_MAX", stats_group_max, -1, -1, 1e6, "sdf_stats_columns: runs above which an alignment gets a wavefront of its own; -1: default"),
+    SDF_CF("SDF_FETCH_STAGE_BYTES", fetch_stage_bytes, 64 << 20, 4096, 1 << 30, "sdf_pool_fetch_ranges: bytes of output per piece (the pinned staging and its device buffer)"),
     // ---- what the library says on stderr ----
     SDF_CF("SDF_DEBUG_PLAN", debug_plan, 0, 0, 1, "1: the cut, the plan and this configuration"),
     SDF_CF("SDF_DEBUG_TIMING", debug_timing, 0, 0, 1, "1: milliseconds of the phases of the entry points"),

@@ -325,6 +325,7 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \
   X(cl_ranges, Pairs) X(cl_out, Pairs) /* sdf_pool_range_classes: a ClassRange and a record of four counts per range */ \
+  X(pf_recs, None) X(pf_out, None) /* sdf_pool_fetch_ranges: a piece's FetchRec records and its output bytes (fetch_stage_bytes) */ \
   X(fa_raw, Pool) /* a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta) */           \
   /* lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch */ \
   X(ln_recs, BatchCall) X(ln_keys, BatchCall) X(ln_vals, BatchCall) X(ln_sizes, BatchCall) X(ln_tmp, BatchCall)       \
@@ -340,6 +341,7 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(host_lane)  /* the lane kernel's records */                                                                       \
   X(host_chars) /* pinned staging of a super-batch's FASTA characters (sdf_pool_host) */                              \
   X(host_cls) /* sdf_pool_range_classes: the ranges' records on their way up, the counts on their way back */          \
+  X(host_fetch) /* sdf_pool_fetch_ranges: a piece's output on its way back, its records behind it on their way up */  \
   X(host_an) /* pinned staging of the anchors call's output (sdf_reserve with SDF_RESERVE_ANCHORS; a pageable copy runs at ~3 GB/s) */
 
 struct sdf_ctx {

@@ -90,6 +90,14 @@ struct ClassRange {  // one range of sdf_pool_range_classes (16 bytes)
 constexpr int kClassSegBytes = 16384;  // bytes of a range that one group of sixteen lanes counts
 static_assert(sizeof(ClassRange) == 16 && sizeof(sdf_range_classes) == 16, "four records per 64-byte line");
 __global__ void pool_classes_kernel(const ClassRange *, int, long long, const char *, sdf_range_classes *);
+// one range of sdf_pool_fetch_ranges (include/sedef_hip.h: sdf_pool_fetch_rec, 32 bytes): len bytes from pool + src_off to
+// dst + dst_off, reversed and complemented when rc; seg0 as ClassRange has it
+using FetchRec = sdf_pool_fetch_rec;
+constexpr int kFetchSegBytes = SDF_FETCH_SEG_BYTES;  // destination bytes of a range that one group of sixteen lanes writes
+static_assert(sizeof(FetchRec) == 32, "FetchRec: two records per 64-byte line");
+// REV: some record of the launch has rc set; <false> never reads the word and is the plain copy
+template <bool REV>
+__global__ void pool_fetch_kernel(const FetchRec *, int, long long, const char *, char *);
 // anchors.hip
 struct AnchorPairDev {
   int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool

@@ -185,4 +185,100 @@ __global__ void __launch_bounds__(256) pool_classes_kernel(const ClassRange *__r
   }
 }
 
+// ---- ranges of the resident pool read back, by strand (include/sedef_hip.h: sdf_pool_fetch_ranges) ----
+// dst[dst_off + j] = pool[src_off + j], or rev_dna(pool[src_off + len - 1 - j]) for a reversed range: what the stage driver's
+// fetch() does per pair with FastaReference::extract and rc_inplace.  Cut like the counting above: a range's DESTINATION bytes in
+// segments of kFetchSegBytes, a group of sixteen lanes per segment.  Source and destination are misaligned independently, so a
+// lane works in 16-byte units aligned at the destination: the unit's sixteen source bytes start at any address s, lie in the
+// two ALIGNED 16-byte slots of the pool at s & ~15 and behind it, and are cut out of their eight words with word selects and
+// funnel shifts; a reversed unit takes the sixteen bytes that END where the forward one would begin to mirror, byte-swaps
+// the words in reversed order and maps them four at a time.  Per lane and step: two 16-byte vector loads (the second is the
+// first of the lane's neighbour -- same cache line or the next, seven times in eight -- and is not issued at all where source
+// and destination are aligned alike), one 16-byte vector store; the sixteen lanes of a group write 256 contiguous bytes a step.
+// A slot is loaded only if it is one of the slots of the record's range (those lie inside the pool's allocation: its base is
+// aligned, and it ends 64 bytes or more behind the last character); a slot outside reads as zero, and its bytes are never
+// among those stored.  The ragged first and last unit of a segment are written byte by byte: a neighbouring range, or the
+// neighbouring segment of this one, may own the rest of the unit.  One pass, nothing reused: bound by HBM.
+
+// rev_dna (reference: src/common.h:72-87,93; indexed c & 127) of four characters in one 32-bit word: stats_cols.hip's
+// stats_revcomp4, kept as a copy so that the stats kernels' file stays as it is.  A <-> T is ^ 0x15, C <-> G is ^ 0x04, the
+// case bit stays; every byte that is not ACGTacgt becomes 'N'.
+__host__ __device__ __forceinline__ uint32_t fetch_revcomp4(uint32_t x) {
+  constexpr uint32_t O = 0x01010101u, H = 0x80808080u;
+  auto ne = [](uint32_t v, uint32_t c) { return (v ^ (c * O)) + 0x7Fu * O; };  // bit 7: byte != c (bytes below 0x80)
+  x &= 0x7Fu * O;
+  const uint32_t u = x & 0xDFu * O;
+  const uint32_t at = ~(ne(u, 'A') & ne(u, 'T')) & H, cg = ~(ne(u, 'C') & ne(u, 'G')) & H;
+  const uint32_t flip = (at >> 7) | (at >> 5) | (at >> 3) | (cg >> 5);
+  const uint32_t known = at | cg, keep = known | (known - (known >> 7));
+  return ((x ^ flip) & keep) | (('N' * O) & ~keep);
+}
+
+// (addresses are computed as integers: on the device the accesses are told that they go to global memory, or they would be
+// flat ones)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SDF_FETCH_GLOBAL __attribute__((address_space(1)))
+#else
+#define SDF_FETCH_GLOBAL
+#endif
+// What lane `sub` of the group of segment g does.  Plain C++ for host and device: pool_fetch_kernel is this per lane, and a
+// host program can walk the same code over every (g, sub) under a sanitizer.
+template <bool REV>
+__host__ __device__ __forceinline__ void pool_fetch_lane(const FetchRec *__restrict__ recs, int n_ranges, long long g, int sub,
+                                                         const char *__restrict__ pool, char *__restrict__ dst) {
+  int a = 0, b = n_ranges;  // the range of segment g: the last one whose seg0 is at most g (pool_classes_kernel)
+  while (b - a > 1) {
+    const int mid = (a + b) >> 1;
+    if ((long long)recs[mid].seg0 <= g) a = mid; else b = mid;
+  }
+  const FetchRec r = recs[a];
+  const long long j0 = (g - (long long)r.seg0) * (long long)kFetchSegBytes;  // the segment: bytes [j0, j1) of the range's output
+  const long long j1 = j0 + (long long)kFetchSegBytes < (long long)r.len ? j0 + (long long)kFetchSegBytes : (long long)r.len;
+  if (j0 < 0 || j0 >= j1) return;  // (records and n_seg that do not belong together: nothing is touched)
+  const uintptr_t d_base = (uintptr_t)dst + (uintptr_t)r.dst_off, d_lo = d_base + (uintptr_t)j0, d_hi = d_base + (uintptr_t)j1;
+  const uintptr_t s_lo = (uintptr_t)pool + (uintptr_t)r.src_off, s_hi = s_lo + (uintptr_t)r.len;  // the RANGE's source bytes
+  const uintptr_t slot_lo = s_lo & ~(uintptr_t)15, slot_hi = (s_hi + 15) & ~(uintptr_t)15;        // ... and its slots
+  const bool rc = REV && r.rc != 0;
+  for (uintptr_t u = (d_lo & ~(uintptr_t)15) + 16u * (unsigned)sub; u < d_hi; u += 256) {
+    // destination byte u + i comes from source byte s + i (forward), s + 15 - i (reversed); u may lie up to 15 bytes below
+    // d_base, and s as far outside [s_lo, s_hi): modulo 2^64, and only the slots of the range are read
+    const uintptr_t s = rc ? s_hi - 16 - (u - d_base) : s_lo + (u - d_base);
+    const uintptr_t sa = s & ~(uintptr_t)15;
+    const unsigned sh = (unsigned)(s & 15);
+    u32x4 lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
+    if (sa >= slot_lo && sa < slot_hi) lo = *(const SDF_FETCH_GLOBAL u32x4 *)sa;
+    if (sh != 0 && sa + 16 >= slot_lo && sa + 16 < slot_hi) hi = *(const SDF_FETCH_GLOBAL u32x4 *)(sa + 16);
+    // words sh / 4 .. sh / 4 + 4 of the eight, then the bytes from sh % 4 on
+    uint32_t w0 = lo.x, w1 = lo.y, w2 = lo.z, w3 = lo.w, w4 = hi.x, w5 = hi.y;
+    if (sh & 8) w0 = w2, w1 = w3, w2 = w4, w3 = w5, w4 = hi.z, w5 = hi.w;
+    if (sh & 4) w0 = w1, w1 = w2, w2 = w3, w3 = w4, w4 = w5;
+    const unsigned bs = (sh & 3) * 8;
+    auto funnel = [bs](uint32_t l, uint32_t h) { return (uint32_t)((((uint64_t)h << 32) | l) >> bs); };
+    uint32_t o0 = funnel(w0, w1), o1 = funnel(w1, w2), o2 = funnel(w2, w3), o3 = funnel(w3, w4);
+    if (rc) {
+      const uint32_t t0 = fetch_revcomp4(__builtin_bswap32(o3)), t1 = fetch_revcomp4(__builtin_bswap32(o2));
+      const uint32_t t2 = fetch_revcomp4(__builtin_bswap32(o1)), t3 = fetch_revcomp4(__builtin_bswap32(o0));
+      o0 = t0, o1 = t1, o2 = t2, o3 = t3;
+    }
+    if (u >= d_lo && u + 16 <= d_hi) {
+      *(SDF_FETCH_GLOBAL u32x4 *)u = u32x4{o0, o1, o2, o3};
+    } else {  // the ragged first or last unit of the segment (both, in a short range): bytes [i0, i1) of it are this segment's
+      const int i0 = u < d_lo ? (int)(d_lo - u) : 0, i1 = u + 16 > d_hi ? (int)(d_hi - u) : 16;
+      const uint32_t o[4] = {o0, o1, o2, o3};
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (i >= i0 && i < i1) ((SDF_FETCH_GLOBAL unsigned char *)u)[i] = (unsigned char)(o[i >> 2] >> (8 * (i & 3)));
+    }
+  }
+}
+
+template <bool REV>
+__global__ void __launch_bounds__(256) pool_fetch_kernel(const FetchRec *__restrict__ recs, int n_ranges, long long n_seg,
+                                                         const char *__restrict__ pool, char *__restrict__ dst) {
+  const long long g = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (g >= n_seg) return;  // (the whole group)
+  pool_fetch_lane<REV>(recs, n_ranges, g, threadIdx.x & 15, pool, dst);
+}
+#undef SDF_FETCH_GLOBAL
+
 }  // namespace sdf

@@ -29,6 +29,11 @@ ANCHOR_DTYPE = np.dtype([("q", "<i4"), ("r", "<i4"), ("l", "<i4"), ("has_u", "<i
 BRIEF_DTYPE = np.dtype([("cigar_off", "<i8"), ("n_cigar", "<i4"), ("matches", "<i4")])  # sdf_result_brief
 POOL_RANGE_DTYPE = np.dtype([("off", "<i8"), ("len", "<i4"), ("reserved", "<i4")])  # sdf_pool_range
 RANGE_CLASSES_DTYPE = np.dtype([(f, "<i4") for f in ("upper_acgt", "lower_acgt", "n_any", "other")])  # sdf_range_classes
+# include/sedef_hip.h: sdf_pool_fetch / sdf_pool_fetch_rec (pool_fetch; FETCH_RC in `flags`)
+POOL_FETCH_DTYPE = np.dtype([("off", "<i8"), ("len", "<i4"), ("flags", "<i4"), ("dst_off", "<i8")])
+POOL_FETCH_REC_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("rc", "<i4"), ("seg0", "<i8")])
+FETCH_RC, FETCH_SEG_BYTES = 0x1, 16384
+assert POOL_FETCH_DTYPE.itemsize == 24 and POOL_FETCH_REC_DTYPE.itemsize == 32
 RESERVE_BRIEF, RESERVE_ANCHORS = 1, 2
 assert BRIEF_DTYPE.itemsize == 16
 assert TASK_DTYPE.itemsize == 40 and RESULT_DTYPE.itemsize == 64 and ANCHOR_PAIR_DTYPE.itemsize == 32
@@ -109,6 +114,13 @@ def load_library():
     L.sdf_pool_sync.argtypes = [C.c_void_p]
     L.sdf_pool_range_classes.restype = C.c_int
     L.sdf_pool_range_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdf_pool_fetch_ranges.restype = C.c_int
+    L.sdf_pool_fetch_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.sdf_pool_fetch_plan.restype = C.c_int
+    L.sdf_pool_fetch_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_longlong), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.sdf_pool_fetch_ranges_device.restype = C.c_int
+    L.sdf_pool_fetch_ranges_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     L.sdf_pool_share.restype = C.c_int
     L.sdf_pool_share.argtypes = [C.c_void_p, C.c_void_p]
     L.sdf_anchors_batch_strand.restype = C.c_int
@@ -382,6 +394,56 @@ class Extz2Engine:
             return rc, out, self.lib.sdf_last_error(self.ctx).decode()
         self._check(rc)
         return out
+
+    def pool_fetch_raw(self, ranges, rc=None):
+        """sdf_pool_fetch_ranges: the characters of ranges of the resident pool, reverse-complemented where asked, packed back
+        to back.  ranges: (off, len) pairs, rc: one truth value for all or one per range -- or a POOL_FETCH_DTYPE array, whose
+        flags and dst_off are used as they are (rc must be None).  Returns (bytes as one numpy.uint8 array, offsets): range i
+        is out[offsets[i]:offsets[i + 1]] for pairs; for a POOL_FETCH_DTYPE array `offsets` is its dst_off and the array is as
+        long as the furthest destination."""
+        if isinstance(ranges, np.ndarray) and ranges.dtype == POOL_FETCH_DTYPE:
+            assert rc is None
+            recs = np.ascontiguousarray(ranges)
+            offsets = recs["dst_off"].astype(np.int64)
+            size = int((offsets + recs["len"]).max()) if len(recs) else 0
+        else:
+            pairs = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+            recs = np.zeros(len(pairs), POOL_FETCH_DTYPE)
+            recs["off"], recs["len"] = pairs[:, 0], pairs[:, 1]
+            if rc is not None:
+                recs["flags"] = np.where(np.broadcast_to(np.asarray(rc, dtype=bool), len(pairs)), FETCH_RC, 0)
+            offsets = np.zeros(len(pairs) + 1, np.int64)
+            np.cumsum(np.maximum(pairs[:, 1], 0), out=offsets[1:])
+            recs["dst_off"] = offsets[:-1]
+            size = int(offsets[-1])
+        out = np.zeros(size, np.uint8)
+        n = len(recs)
+        self._check(self.lib.sdf_pool_fetch_ranges(self.ctx, recs.ctypes.data if n else None, n, out.ctypes.data if size else None,
+                                                   size))
+        return out, offsets
+
+    def pool_fetch(self, ranges, rc=None):
+        """The same as a list of bytes objects, one per (off, len) range."""
+        out, offsets = self.pool_fetch_raw(np.asarray(ranges, dtype=np.int64).reshape(-1, 2), rc)
+        return [out[int(a):int(b)].tobytes() for a, b in zip(offsets[:-1], offsets[1:])]
+
+    def pool_fetch_plan(self, ranges, pool_bytes=None, dst_bytes=None):
+        """sdf_pool_fetch_plan: the device form's records of a POOL_FETCH_DTYPE array.  Returns (rc, POOL_FETCH_REC_DTYPE array,
+        any_rc, n_seg, bytes, index of the first offending range); pool_bytes / dst_bytes default to the resident pool's size
+        and to no bound."""
+        recs = np.ascontiguousarray(ranges, dtype=POOL_FETCH_DTYPE)
+        n = len(recs)
+        out = np.zeros(n, POOL_FETCH_REC_DTYPE)
+        any_rc, n_seg, nbytes, bad = C.c_int(0), C.c_longlong(0), C.c_size_t(0), C.c_size_t(0)
+        rc = self.lib.sdf_pool_fetch_plan(recs.ctypes.data if n else None, n, self.pool_bytes() if pool_bytes is None else pool_bytes,
+                                          (1 << 62) if dst_bytes is None else dst_bytes, out.ctypes.data if n else None,
+                                          C.byref(any_rc), C.byref(n_seg), C.byref(nbytes), C.byref(bad))
+        return rc, out, int(any_rc.value), int(n_seg.value), int(nbytes.value), int(bad.value)
+
+    def pool_fetch_device(self, d_recs, n, any_rc, n_seg, d_dst, stream=None):
+        """sdf_pool_fetch_ranges_device: records (POOL_FETCH_REC_DTYPE, as pool_fetch_plan makes them) and destination in HBM,
+        given as device pointers."""
+        self._check(self.lib.sdf_pool_fetch_ranges_device(self.ctx, d_recs, n, int(bool(any_rc)), n_seg, d_dst, stream))
 
     def pool_share(self, owner):
         """sdf_pool_share: this context reads `owner`'s resident pool from now on (a view: no memory of its own).  The owner

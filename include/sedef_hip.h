@@ -396,6 +396,12 @@ long long sdf_last_lane_tasks(const sdf_ctx *ctx);
 /* Pairs of the context's last sdf_chain_batch per launch class: out[0..5] the LDS classes of the wavefront kernel
  * (smallest first), out[6] the thread-per-pair kernel, out[7] the LDS cap in bytes of class 5 on this device. */
 int sdf_last_chain_classes(const sdf_ctx *ctx, int64_t out[8]);
+/* Traceback launches of the context's last batch call per instantiation: out[2 * layout + (G == 16)] counts the launches of
+ * the walk over direction-flag layout `layout` (0 general kernel, 1 wave, 2 pair, 3 full-band stripes, 4 banded stripes,
+ * 5 lane, 6 strips and chained strips) with groups of G = 64 (one task per wavefront) or G = 16 lanes (four tasks per
+ * wavefront).  Counted on the host where the kernels are launched, the parts of a split call and a re-run of abandoned
+ * stripe tasks included; all zero after a call that asked for no CIGAR. */
+int sdf_last_traceback_classes(const sdf_ctx *ctx, int64_t out[14]);
 
 /* ---- seed anchors on the GPU (next row of the scope table) -----------------------------------
  * Replaces generate_anchors (reference: src/chain.cc:24-101) for a batch of candidate pairs: maximal exact

@@ -200,6 +200,7 @@ static int batch_part(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_task *tasks
   for (float &m : ctx->ms) m = 0.f;
   ctx->launches = 0;
   ctx->paired = 0;
+  std::fill(ctx->tb_classes, ctx->tb_classes + 14, (int64_t)0);
   // (nothing of this context's earlier calls is in flight: what they outgrew is idle now -- sdf_ctx.h: DevBuf)
   for_each_device_buffer(ctx, [](DevBuf &b) { b.new_call(); }, BufGroup::BatchCall);
   const auto host_t0 = std::chrono::steady_clock::now();
@@ -491,6 +492,7 @@ extern "C" int sdf_extz2_batch_device(sdf_ctx *ctx, const sdf_scoring *sc, const
     ctx->paired += head->ctx->paired;
     ctx->lane_tasks += head->ctx->lane_tasks;
     ctx->reran += head->ctx->reran;
+    for (int c = 0; c < 14; ++c) ctx->tb_classes[c] += head->ctx->tb_classes[c];
     ctx->ms[4] = head->ctx->ms[4];  // host time before the call's first launch
   }
   ctx->ms[5] = host_ms();

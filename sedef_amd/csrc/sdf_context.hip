@@ -259,6 +259,11 @@ extern "C" int sdf_last_chain_classes(const sdf_ctx *ctx, int64_t out[8]) {
   std::copy(ctx->chain_classes, ctx->chain_classes + 8, out);
   return SDF_OK;
 }
+extern "C" int sdf_last_traceback_classes(const sdf_ctx *ctx, int64_t out[14]) {
+  if (!ctx || !out) return SDF_ERR_INVALID;
+  std::copy(ctx->tb_classes, ctx->tb_classes + 14, out);
+  return SDF_OK;
+}
 
 // Buffers sized once (include/sedef_hip.h).  The bounds per task are the planner's: a launch-order entry per task and
 // stripe / block of columns, a CIGAR staging slot of qlen + tlen + 2 words.

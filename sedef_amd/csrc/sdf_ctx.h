@@ -366,6 +366,9 @@ struct sdf_ctx {
   // sdf_last_chain_classes: pairs of the last sdf_chain_batch per launch class -- [0..5] the LDS classes of chain_wave_kernel,
   // [6] chain_kernel --, [7] the LDS cap of class 5 in bytes (fixed in sdf_create: what the kernel was granted there)
   int64_t chain_classes[8] = {0, 0, 0, 0, 0, 0, 0, 64 * 1024};
+  // sdf_last_traceback_classes: launches of traceback_kernel<layout, G> in the last batch call, [2 * layout + (G == 16)];
+  // counted on the host where they are launched (sdf_launch.hip), zeroed when a batch call starts
+  int64_t tb_classes[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   sdf::WorkerPool *pool = nullptr;  // planning threads, started with the first batch large enough to use them
   sdf::BatchCut *cut = nullptr;  // chunk list and planning scratch of the last batch call (sdf_plan.hip)
   std::vector<hipEvent_t> events;

@@ -169,8 +169,9 @@ static bool launch_dp(const Launch &L, hipStream_t sdp, const PlanTask *lp, cons
 }
 
 template <int LAYOUT>
-static void launch_traceback(bool solo, size_t cnt, hipStream_t s, const PlanTask *lp, const uint32_t *d_pool,
+static void launch_traceback(sdf_ctx *ctx, bool solo, size_t cnt, hipStream_t s, const PlanTask *lp, const uint32_t *d_pool,
                              const uint8_t *dir_reg, sdf_result *d_out, uint32_t *d_stage) {
+  ++ctx->tb_classes[2 * LAYOUT + (solo ? 0 : 1)];  // (sdf_last_traceback_classes)
   // few tasks: a wavefront per walk (runs of up to 64 cells per round), else four walks per wavefront (16 cells;
   // 8 and 32 cells per walk were measured within noise of 16 on the headline batch)
   if (solo)
@@ -394,12 +395,12 @@ int launch_chunk(BatchRun &run, size_t ci) {
       return s2;
     };
     const PlanTask *lp = run.d_plan + pb;
-    if (layouts & 64u) launch_traceback<6>(tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
-    if (layouts & 16u) launch_traceback<4>(tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
-    if (layouts & 8u) launch_traceback<3>(tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
-    if (layouts & 4u) launch_traceback<2>(tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
-    if (layouts & 2u) launch_traceback<1>(tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
-    if (layouts & 1u) launch_traceback<0>(tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
+    if (layouts & 64u) launch_traceback<6>(ctx, tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
+    if (layouts & 16u) launch_traceback<4>(ctx, tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
+    if (layouts & 8u) launch_traceback<3>(ctx, tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
+    if (layouts & 4u) launch_traceback<2>(ctx, tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
+    if (layouts & 2u) launch_traceback<1>(ctx, tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
+    if (layouts & 1u) launch_traceback<0>(ctx, tb_solo, cnt, tb_on(), lp, run.d_pool, dir_reg, run.d_out, run.d_stage);
     if (side_by_side)
       for (int j = 1; j < used_tb && j < 3; ++j) {
         if (tbs[j] == stb) continue;
@@ -508,6 +509,7 @@ static int rerun_abandoned(BatchRun &run, unsigned long long count) {
   SDF_HIP(hipMemsetAsync(d_gave, 0, sizeof(unsigned long long), st));
   SDF_HIP(hipStreamSynchronize(st));  // (`map` is pageable host memory)
   ctx->reran = (long long)count;
+  for (int c = 0; c < 14; ++c) ctx->tb_classes[c] += ctx->rerun_ctx->tb_classes[c];
   return SDF_OK;
 }
 
@@ -577,7 +579,7 @@ int launch_lane(BatchRun &run, size_t n) {
       pos += cnt;
     }
     if (run.want_cigar)
-      launch_traceback<5>(false, nl, sl, lp, run.d_pool, run.d_dir, run.d_out, run.d_stage);
+      launch_traceback<5>(ctx, false, nl, sl, lp, run.d_pool, run.d_dir, run.d_out, run.d_stage);
     run.ev_lane = next_event(ctx, run.evc);
     SDF_HIP(hipEventRecord(run.ev_lane, sl));
     SDF_HIP(hipGetLastError());
@@ -628,7 +630,7 @@ int launch_lane(BatchRun &run, size_t n) {
     pos += cnt;
   }
   if (run.want_cigar)
-    launch_traceback<5>(false, nl, sl, lp, run.d_pool, run.d_dir, run.d_out, run.d_stage);
+    launch_traceback<5>(ctx, false, nl, sl, lp, run.d_pool, run.d_dir, run.d_out, run.d_stage);
   run.ev_lane = next_event(ctx, run.evc);
   SDF_HIP(hipEventRecord(run.ev_lane, sl));
   SDF_HIP(hipGetLastError());

@@ -171,6 +171,8 @@ def load_library():
     L.sdf_last_lane_tasks.argtypes = [C.c_void_p]
     L.sdf_last_chain_classes.restype = C.c_int
     L.sdf_last_chain_classes.argtypes = [C.c_void_p, C.c_void_p]
+    L.sdf_last_traceback_classes.restype = C.c_int
+    L.sdf_last_traceback_classes.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -701,6 +703,13 @@ class Extz2Engine:
         thread-per-pair kernel; [7] the LDS cap of class 5 in bytes (include/sedef_hip.h: sdf_last_chain_classes)."""
         out = np.zeros(8, np.int64)
         self._check(self.lib.sdf_last_chain_classes(self.ctx, out.ctypes.data))
+        return [int(x) for x in out]
+
+    def last_traceback_classes(self):
+        """Traceback launches of the last batch call per instantiation: [2 * layout + (G == 16)] for the direction-flag
+        layouts 0..6 and groups of G = 64 or 16 lanes (include/sedef_hip.h: sdf_last_traceback_classes)."""
+        out = np.zeros(14, np.int64)
+        self._check(self.lib.sdf_last_traceback_classes(self.ctx, out.ctypes.data))
         return [int(x) for x in out]
 
     def last_reran(self):

@@ -268,6 +268,14 @@ __device__ __forceinline__ void pair_body(
     }
   };
 
+  // x, v of slots 0..15 read as 0 from here on.  Selects, not a branch on the lane: a lane-dependent branch inside the
+  // wave-uniform one makes the compiler hold `low16` and `zero_low` as lane masks and treat every branch on them as
+  // divergent -- the row flavours then run "one after the other" and each copies the whole state in and out.
+  auto zero_slots_0_15 = [&]() {
+    const bool low = lane < 16;
+    X[0] = low ? 0u : X[0];
+    V[0] = low ? 0u : V[0];
+  };
   int32_t carry_h = SDF_NEG_INF;  // TRACK: H of target position base - 1 (left the window at the last re-base)
   // TRACK: H of every in-band cell after row r's recurrence (reference :222-258), and the running best per lane
   auto track_row = [&](const int r, const int lo0, const int hi0) {
@@ -316,10 +324,7 @@ __device__ __forceinline__ void pair_body(
     const bool ref_rebased = lo != prev_lo && prev_lo >= 0;
     if (ref_rebased && off_lo == 16) drop_row = r;
     if (off_lo == 16 && !ref_rebased && !zero_low) {
-      if (lane < 16) {
-        X[0] = 0u;
-        V[0] = 0u;
-      }
+      zero_slots_0_15();
       zero_low = true;
     }
     // ---- boundary cell t = r: y = 0, u = gap open (reference :122) ----
@@ -426,6 +431,7 @@ __device__ __forceinline__ void pair_body(
     constexpr bool SCALARH = decltype(scalarh_c)::value;
     constexpr bool STEADY = decltype(steady_c)::value;
     constexpr int KT = NREG - 1;
+    if (rb >= re) return;  // (a flavour that is not this segment's: see lean_rows)
     if (SCALARH) fold_h();
     // (the row's query codes are read at its start: a fetch one row ahead costs four register copies a row and three
     // registers, and with four or five wavefronts on the SIMD the LDS latency is covered anyway)
@@ -564,9 +570,30 @@ __device__ __forceinline__ void pair_body(
       track_row(r, lo0, hi0);
     }
   };
-  auto lean_rows = [&](auto low16_c, auto scalarh_c, auto steady_c, const int rb, const int re) {
-    if (has_n) lean_rows_n(low16_c, scalarh_c, steady_c, std::true_type{}, rb, re);
-    else lean_rows_n(low16_c, scalarh_c, steady_c, std::false_type{}, rb, re);
+  // Rows [rb, re) by the flavour (low16, scalarh, steady, has_n) names.  NOT an if / else over the twelve instances: the
+  // kernel's branches on lanes make the compiler lay such a chain out as "if (f1) A; if (f2) B; ...", where B still reads the
+  // state from before A -- so A could not update the thirty state registers in place and copied them in and out, at every
+  // segment (1,211 static v_mov, ~15 executed per row of the headline batch).  Instead EVERY instance runs, one after the
+  // other on the same registers, over a range that is empty for all but the segment's own; the ranges pass through an
+  // empty asm so that the compiler cannot turn the sequence back into the chain.  Scalar work per SEGMENT, none per row.
+  auto lean_rows = [&](const bool low16, const bool scalarh, const bool steady, const int rb, const int re) {
+    const int nrows = re - rb;
+    auto upto = [rb, nrows](const bool mine) {
+      int e = __builtin_amdgcn_readfirstlane(rb + (mine ? nrows : 0));
+      asm("" : "+s"(e));
+      return e;
+    };
+    const int e_steady = upto(!scalarh && steady), e_scalarh = upto(scalarh), e_plain = upto(!scalarh && !steady);
+    auto group = [&](auto scalarh_c, auto steady_c, const int e) {
+      if (rb >= e) return;
+      lean_rows_n(std::false_type{}, scalarh_c, steady_c, std::false_type{}, rb, upto(!low16 && !has_n));
+      lean_rows_n(std::true_type{}, scalarh_c, steady_c, std::false_type{}, rb, upto(low16 && !has_n));
+      lean_rows_n(std::false_type{}, scalarh_c, steady_c, std::true_type{}, rb, upto(!low16 && has_n));
+      lean_rows_n(std::true_type{}, scalarh_c, steady_c, std::true_type{}, rb, upto(low16 && has_n));
+    };
+    group(std::false_type{}, std::true_type{}, e_steady);
+    group(std::true_type{}, std::false_type{}, e_scalarh);
+    group(std::false_type{}, std::false_type{}, e_plain);
   };
   // U,V,X,Y of the cells t in [t_from, t_to] back to "never computed" (both bounds block aligned)
   auto zero_cells = [&](const int t_from, const int t_to) {
@@ -766,10 +793,7 @@ __device__ __forceinline__ void pair_body(
             low16 = true;
           }
         } else if (low16 && !zero_low) {
-          if (lane < 16) {
-            X[0] = 0u;
-            V[0] = 0u;
-          }
+          zero_slots_0_15();
           zero_low = true;
         }
         // rows until the reference window changes again (closed forms of the band geometry)
@@ -795,17 +819,7 @@ __device__ __forceinline__ void pair_body(
             if (rx > r && rx < stop) stop = rx;
           }
         }
-        const bool scalarh = hi0 == tlen - 1;
-        if (scalarh) {
-          if (low16) lean_rows(std::true_type{}, std::true_type{}, std::false_type{}, r, stop);
-          else lean_rows(std::false_type{}, std::true_type{}, std::false_type{}, r, stop);
-        } else if (steady) {
-          if (low16) lean_rows(std::true_type{}, std::false_type{}, std::true_type{}, r, stop);
-          else lean_rows(std::false_type{}, std::false_type{}, std::true_type{}, r, stop);
-        } else {
-          if (low16) lean_rows(std::true_type{}, std::false_type{}, std::false_type{}, r, stop);
-          else lean_rows(std::false_type{}, std::false_type{}, std::false_type{}, r, stop);
-        }
+        lean_rows(low16, hi0 == tlen - 1, steady, r, stop);
         {  // the top register of the window now holds scratch values above the window
           const int top = base + 64 * (((win_hi - base) >> 6) + 1) - 1;
           if (top > dirty_hi) dirty_hi = top;

@@ -379,7 +379,7 @@ int64_t sdf_band_cells(int32_t qlen, int32_t tlen, int32_t w);
  * 6 is the sum of the chunks' DP intervals.  SDF_PIPELINE=0 in the environment of sdf_create() keeps a batch
  * in one chunk on one stream. */
 float sdf_last_ms(const sdf_ctx *ctx, int which);
-/* Number of DP kernel launches in the last batch call and algorithmic bytes they moved. */
+/* Number of DP kernel launches in the last batch call and algorithmic bytes they moved (sdf_stats_cuts_pairs adds its own). */
 int sdf_last_launches(const sdf_ctx *ctx);
 /* Number of tasks of the last batch call that ran two per wavefront: tasks with the same (qlen, tlen, w, flag)
  * share the reference's band schedule (extern/ksw2_extz2_sse.cc:101-115) and are packed side by side. */
@@ -514,6 +514,59 @@ int sdf_stats_columns_pairs(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n,
  * stream of its own calls sdf_pool_sync() between the last upload and this call. */
 int sdf_stats_columns_pairs_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, int any_rc,
                                    const uint32_t *d_cigar_pool, sdf_stats_cols *d_out, void *stream);
+
+/* ---- the cuts of `stats generate` on the RESIDENT pool: match counter, assembly-gap cuts, trims ----------------------
+ * What the host does to every input alignment before the column counters (reference: Alignment(fa, fb, cigar),
+ * src/align.cc:90-105; split_alignment, src/stats_main.cc:163-211; subhit with trim_back / trim_front, src/stats_main.cc:33-84,
+ * src/align.cc:343-456), for the tasks sdf_stats_columns_pairs takes: ranges of the resident pool, strand bits in `reserved`,
+ * runs `len << 4 | op`.  All in COLUMN space: column i of side a is '-' inside an I run, of side b inside a D run.
+ *   matches   Two characters match when they are equal ignoring case and are not N (sdf_stats_cols::matches).
+ *   events    A column is N for a side when toupper(c) == 'N': on a forward side the bytes 'N' and 'n'; on a reversed side the
+ *             character is rev_dna(pool byte), so every byte that is not ACGTacgt (indexed c & 127) is N; '-' is not N.  A
+ *             maximal N run [s, e) of one side is an event at e when e - s >= 100 and a non-N column follows it (e < span; a
+ *             run that reaches the last column is no event).  Events are ordered by e; at equal e, side a's comes first.
+ *   pieces    With begin = 0 before the first event, every event emits the piece [begin, s) if s > begin, then sets begin = e;
+ *             after the last event the final piece is [begin, span).  An alignment without an event is ONE piece [0, span),
+ *             and that piece is NOT trimmed.
+ *   trims     Every piece of an alignment that has an event goes through trim_back, then trim_front on the result.  A pair
+ *             column scores `match` or `mismatch`; a gap column `gap_extend`, plus `gap_open` when it is the first column of
+ *             the scan or its neighbour towards the scan's origin is not a gap in the same sequence (a piece that starts
+ *             inside a gap run pays gap_open at its first column).  trim_back keeps the best prefix: score >= best, from
+ *             best = 0, ties to the longer prefix; no prefix reaches 0: the piece becomes empty.  trim_front keeps the best
+ *             suffix of what trim_back kept, ties to the longer suffix.  The reference's "nothing found" marker there is the
+ *             number of a-bases of the piece, not its column count: a best suffix that starts at that column of the piece
+ *             empties the piece, and so it does here.
+ * Per piece one record: the untrimmed columns [begin, end), the trimmed columns [t_begin, t_end) (t_begin == t_end: emptied)
+ * and the matches inside the trimmed range.  Everything else (bases before and inside a range, run slices, gaps, gap bases,
+ * mismatches) follows from the CIGAR.  pieces[first[i] .. first[i + 1]) are alignment i's, in column order; first has n + 1
+ * entries, in TASK order.  Scores: |match|, |mismatch| <= 63 and |gap_open| + |gap_extend| <= 63 (sums in 32 bits over 2^25
+ * columns; SDF_ERR_UNSUPPORTED beyond).  One wavefront per alignment, whatever its number of runs. */
+typedef struct {
+  int32_t begin, end;     /* the piece as it was cut, in the alignment's columns */
+  int32_t t_begin, t_end; /* ... after the trims */
+  int32_t matches;        /* match columns of [t_begin, t_end) */
+  int32_t flags;          /* 1: the CIGAR does not fit the sequences (the alignment's ONE record; ranges 0) */
+  int32_t reserved[2];
+} sdf_stats_piece;
+/* Host form.  pieces_cap: capacity of `pieces` in records.  SDF_ERR_CIGAR_OVERFLOW when the batch needs more: *pieces_used
+ * holds the need, first[] is filled, and nothing is written to `pieces`; else *pieces_used = first[n].  SDF_ERR_INVALID: a
+ * sequence range outside sdf_pool_bytes(), a CIGAR range outside cigar_words, or -- after the launches, everything filled,
+ * flags == 1 on the alignment's record -- a CIGAR that does not fit its sequences.  SDF_ERR_UNSUPPORTED: a bit of `reserved`
+ * beyond SDF_STATS_A_RC | SDF_STATS_B_RC, a side of more than 16 Mb, scores out of range.  All checks but the CIGAR misfit
+ * precede the first launch; n == 0 is SDF_OK without one (first[0] = 0).  sdf_last_launches() grows by the call's launches
+ * (two for the count, one more for the records), and not at all for a call that is refused. */
+int sdf_stats_cuts_pairs(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const uint32_t *cigar_pool, size_t cigar_words,
+                         int match, int mismatch, int gap_open, int gap_extend, uint64_t *first, sdf_stats_piece *pieces,
+                         size_t pieces_cap, size_t *pieces_used);
+/* Device form: tasks, runs, d_first (n + 1 entries) and d_pieces in HBM, asynchronous on `stream` (NULL: the context's own
+ * stream, synchronised before returning -- then *pieces_used, if given, holds d_first[n] and the call answers
+ * SDF_ERR_CIGAR_OVERFLOW when that exceeds pieces_cap).  An alignment whose pieces do not all lie below pieces_cap writes
+ * none, so no record is written past the capacity; with a stream of its own the caller compares d_first[n] with pieces_cap
+ * itself.  Offsets are not checked; any_rc and the pool's uploads as for sdf_stats_columns_pairs_device.  The counts of the
+ * call live in the context: calls on one context do not overlap. */
+int sdf_stats_cuts_pairs_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, int any_rc, const uint32_t *d_cigar_pool,
+                                int match, int mismatch, int gap_open, int gap_extend, uint64_t *d_first,
+                                sdf_stats_piece *d_pieces, size_t pieces_cap, size_t *pieces_used, void *stream);
 
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is

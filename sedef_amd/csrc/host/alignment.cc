@@ -221,6 +221,21 @@ Alignment::Alignment(const std::string &fa, const std::string &fb, const std::st
   recount(count_matches(seq_a, seq_b, cigar));
 }
 
+// (a CIGAR string over sequences of known lengths, its match counter given: no character is read -- a / b may be null)
+Alignment::Alignment(const char *a, int a_len, const char *b, int b_len, const std::string &cigar_str, int matches)
+    : end_a(a_len), end_b(b_len), seq_a(a), seq_b(b), len_a(a_len), len_b(b_len) {
+  int num = 0;
+  for (char ch : cigar_str) {
+    if (isdigit((unsigned char)ch)) num = 10 * num + (ch - '0');
+    else if (ch == ';') continue;
+    else {
+      cigar.push_back({ch, num});
+      num = 0;
+    }
+  }
+  recount(matches);
+}
+
 Alignment::Alignment(SeqView qstr, SeqView rstr, const std::vector<Anchor> &guide, const std::vector<int> &guide_idx,
                      DpSession &dp)
     : seq_a(qstr.data()), seq_b(rstr.data()), len_a((int)qstr.size()), len_b((int)rstr.size()) {
@@ -429,6 +444,11 @@ void Alignment::trim_back() {
 
 // ---- a range of columns (reference: subhit, src/stats_main.cc:33-84, up to the trims) ------------------------
 Alignment Alignment::slice_columns(int start, int end, int &sa, int &la, int &sb, int &lb) const {
+  return slice_columns(start, end, -1, sa, la, sb, lb);
+}
+
+// ... with the match columns of the range given (matches >= 0): nothing is counted, no character is read
+Alignment Alignment::slice_columns(int start, int end, int matches, int &sa, int &la, int &sb, int &lb) const {
   Alignment out;
   out.seq_a = seq_a;
   out.seq_b = seq_b;
@@ -456,7 +476,7 @@ Alignment Alignment::slice_columns(int start, int end, int &sa, int &la, int &sb
   out.start_b = start_b + sb;
   out.end_b = out.start_b + lb;
   out.normalise();
-  out.recount(count_matches(seq_a + out.start_a, seq_b + out.start_b, out.cigar));
+  out.recount(matches >= 0 ? matches : count_matches(seq_a + out.start_a, seq_b + out.start_b, out.cigar));
   return out;
 }
 

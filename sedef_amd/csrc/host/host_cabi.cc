@@ -128,12 +128,13 @@ int sdfh_resident_range(long long base, long long start, long long seq_len, long
 // `sedef stats generate genome.fa final.bed > out` (reference: src/stats_main.cc:339-389); test_cols: the oracle's column
 // walker instead of the device (CPU tests).  stats: hits read, pieces, columns; returns the lines written or -1.
 // resident != 0, or SDF_STATS_RESIDENT=1 in the environment: StatsParams::resident.
-long sdfh_stats_generate_resident(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,
-                                  int min_uppercase, double max_error, test_cols_fn test_cols, int device, int resident,
-                                  long long *stats) {
+static long stats_generate_impl(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,
+                                int min_uppercase, double max_error, test_cols_fn test_cols, test_cuts_fn test_cuts, int device,
+                                int resident, int cuts, long long *stats) {
   try {
     StatsParams sp;
     sp.resident = resident != 0 || StageSettings::from_env().stats_resident;
+    sp.cuts_device = cuts != 0;
     sp.max_ok_gap = max_ok_gap;
     sp.min_split = min_split;
     sp.min_uppercase = min_uppercase;
@@ -150,7 +151,7 @@ long sdfh_stats_generate_resident(const char *ref_path, const char *bed_path, co
     out.path = out_path;
     out.f = fopen(out_path, "w");
     if (!out.f) throw std::string("Cannot open output ") + out_path;
-    const long lines = stats_generate(ref_path, bed_path, out.f, sp, test_cols, device, stats);
+    const long lines = stats_generate(ref_path, bed_path, out.f, sp, test_cols, device, stats, test_cuts);
     out.done = true;
     return lines;
   } catch (std::string &s) {
@@ -160,6 +161,23 @@ long sdfh_stats_generate_resident(const char *ref_path, const char *bed_path, co
     g_err = e.what();
     return -1;
   }
+}
+
+long sdfh_stats_generate_resident(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,
+                                  int min_uppercase, double max_error, test_cols_fn test_cols, int device, int resident,
+                                  long long *stats) {
+  return stats_generate_impl(ref_path, bed_path, out_path, max_ok_gap, min_split, min_uppercase, max_error, test_cols, nullptr, device,
+                             resident, 0, stats);
+}
+
+// ... with the cuts and trims on the device too (cuts != 0, or SDF_STATS_CUTS_DEVICE=1 in the environment:
+// StatsParams::cuts_device; only together with resident chromosomes and without max_ok_gap).  test_cuts: a CPU stand-in for
+// sdf_stats_cuts_pairs (sedef_host.h: test_cuts_fn) -- the new host path then runs without a device, with test_cols for the columns.
+long sdfh_stats_generate_cuts(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,
+                              int min_uppercase, double max_error, test_cols_fn test_cols, int device, int resident, int cuts,
+                              test_cuts_fn test_cuts, long long *stats) {
+  return stats_generate_impl(ref_path, bed_path, out_path, max_ok_gap, min_split, min_uppercase, max_error, test_cols, test_cuts,
+                             device, resident, cuts != 0 || StageSettings::from_env().stats_cuts_device, stats);
 }
 
 long sdfh_stats_generate(const char *ref_path, const char *bed_path, const char *out_path, int max_ok_gap, int min_split,

@@ -1104,6 +1104,7 @@ StageSettings StageSettings::from_env() {
   s.anchor_parts = (int)num("SDF_ANCHOR_PARTS", 0, 16, 0);
   s.bucket_lanes = (int)num("SDF_BUCKET_LANES", 1, 4, 2);
   s.stats_resident = num("SDF_STATS_RESIDENT", 0, 1, 0) != 0;
+  s.stats_cuts_device = num("SDF_STATS_CUTS_DEVICE", 0, 1, 0) != 0;
   s.stage_resident = num("SDF_STAGE_RESIDENT", 0, 1, 0) != 0;
   s.fetch_device = num("SDF_STAGE_FETCH_DEVICE", 0, 1, 0) != 0;
   if (const char *e = getenv("SDF_DEVICES"))

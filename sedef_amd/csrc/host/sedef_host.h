@@ -292,6 +292,9 @@ class Alignment {
   Alignment(const std::string &fa, const std::string &fb, DpSession &dp);
   // a given CIGAR string over two whole strings (src/align.cc:90-105)
   Alignment(const std::string &fa, const std::string &fb, const std::string &cigar);
+  // a given CIGAR string and its match counter over sequences of known lengths; a / b may be null where no operation that
+  // compares bases follows (`stats generate` with the cuts on the device)
+  Alignment(const char *a, int a_len, const char *b, int b_len, const std::string &cigar, int matches);
   // guide of refined chains + side extension (src/align.cc:107-197)
   Alignment(SeqView qstr, SeqView rstr, const std::vector<Hit> &guide, int side, DpSession &dp);
   // chain of seed anchors (src/align.cc:199-270)
@@ -306,6 +309,8 @@ class Alignment {
   // cigar_from_alignment does (src/align.cc:480-501), counters recounted; sa / sb = bases of a / b in the columns before
   // `start`, la / lb = in the kept ones (src/stats_main.cc:33-56: subhit's own counting)
   Alignment slice_columns(int start, int end, int &sa, int &la, int &sb, int &lb) const;
+  // ... with the range's match columns given instead of counted (matches >= 0)
+  Alignment slice_columns(int start, int end, int matches, int &sa, int &la, int &sb, int &lb) const;
   // every column in order: f(column, character of a or '-', character of b or '-')
   template <typename F>
   void for_each_column(F f) const {
@@ -404,6 +409,11 @@ struct StatsParams {  // Globals::Stats (src/globals.cc:36-39), CLI overrides sr
   // uploaded once, as the file has it (sdf_pool_append_fasta), and the pieces are counted by base range and strand
   // (sdf_stats_columns_pairs) -- no character pool is built or uploaded.  Ignored with the `test` hook.
   bool resident = false;
+  // SDF_STATS_CUTS_DEVICE=1 (StageSettings::stats_cuts_device), only together with `resident` and without --max-ok-gap (whose
+  // recursion trims on the host; said in one line on stderr): the match counter, the cuts at assembly gaps and the trims of
+  // every input alignment come from ONE sdf_stats_cuts_pairs call on the resident chromosomes -- no sequence is fetched or
+  // reverse-complemented, no column is walked on the host; the pieces are built from the records and the CIGAR alone.
+  bool cuts_device = false;
 };
 // Where the device finds a piece's side in a resident chromosome: the piece covers columns [s, e) of a side that was fetched
 // from [start, end) of its chromosome (end: as get_sequence clamped it) and, with rc, reverse-complemented
@@ -412,11 +422,16 @@ struct StatsParams {  // Globals::Stats (src/globals.cc:36-39), CLI overrides sr
 int stats_piece_range(int start, int end, int s, int e, bool rc, long long *first);
 // TEST HOOK: a column walker with the oracle's signature (oracle/stats_oracle.c: sdfo_stats_columns) instead of the device
 typedef int (*test_cols_fn)(const char *, int, const char *, int, const uint32_t *, int, int32_t *, char *, char *);
+// TEST HOOK: a CPU stand-in for sdf_stats_cuts_pairs on ONE alignment -- a, a_len, b, b_len (the fetched strings, a reversed
+// side reverse-complemented), runs, n_runs, scores {match, mismatch, gap_open, gap_extend}, records out (eight int32 each, the
+// fields of sdf_stats_piece), their capacity; returns the number of pieces.  With it the path of StatsParams::cuts_device runs
+// without a device (and needs the `test` hook for the columns).
+typedef long (*test_cuts_fn)(const char *, int, const char *, int, const uint32_t *, int, const int *, int32_t *, long);
 // Reads the BEDPE of `align generate`, writes the table of `stats generate` to `out`; the per-column counters of every
 // piece come from sdf_stats_columns_batch (sp.resident: sdf_stats_columns_pairs) on `device` (or from `test`).  Returns the number of lines written (header
 // excluded); stats[0..2] = hits read, pieces examined, alignment columns walked.
 long stats_generate(const std::string &ref_path, const std::string &bed_path, FILE *out, const StatsParams &sp,
-                    test_cols_fn test, int device, long long *stats);
+                    test_cols_fn test, int device, long long *stats, test_cuts_fn test_cuts = nullptr);
 std::string format_double(double x);  // fmt 4.0.1 "{}" of a double, as the reference prints columns 22-25 and 35
 
 // ---- utilities (reference: src/util.cc:33-48, src/common.h:56-99) ----------------------------------
@@ -510,6 +525,7 @@ struct StageSettings {
   int anchor_parts = 0;      // SDF_ANCHOR_PARTS: parts a super-batch's seed anchors are found in, each under the chaining of the one before (0: by its size -- 1, 2 or 4)
   bool resident_dp = true;   // SDF_RESIDENT_DP=0: the DP rounds cut their bases out on the host again instead of naming ranges of the characters the anchors call left in HBM
   bool stats_resident = false;  // SDF_STATS_RESIDENT=1: `stats generate` counts on resident chromosomes (StatsParams::resident)
+  bool stats_cuts_device = false;  // SDF_STATS_CUTS_DEVICE=1: with stats_resident, the cuts and trims of `stats generate` run on the device too (StatsParams::cuts_device)
   bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
   bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise
   int bucket_lanes = 2;      // SDF_BUCKET_LANES: buckets of a several-bucket run in flight, each on a device context of its own (1: one after the other)

@@ -126,6 +126,8 @@ int main(int argc, char **argv) {
               "  bucket BEDs into [count] files for the alignment stage (--extend-ratio, --max-extend, --merge-dist)\n"
               "sedef stats generate [genome.fa] [final.bed]\n"
               "  the per-alignment table of the final calls (--max-ok-gap, --min-split, --uppercase, --max-error)\n"
+              "  SDF_STATS_CUTS_DEVICE=1 (default 0; only with SDF_STATS_RESIDENT=1 and without --max-ok-gap): the match counter,\n"
+              "  the cuts at assembly gaps and the trims run on the resident chromosomes too (same output)\n"
               "Other SEDEF stages (search, stats diff, translate) are not part of this build.\n");
       return 0;
     } else if (command == "align") {
@@ -209,6 +211,7 @@ int main(int argc, char **argv) {
       a.get({"uppercase"}, sp.min_uppercase);
       a.getd({"max-error"}, sp.max_scaled_error);
       sp.resident = stage_settings().stats_resident;  // (SDF_STATS_RESIDENT=1)
+      sp.cuts_device = stage_settings().stats_cuts_device;  // (SDF_STATS_CUTS_DEVICE=1)
       if (a.pos.size() < 3) throw std::string("Not enough arguments to stats");
       if (a.pos[0] != "generate") throw std::string("Unknown stats command");
       long long st[3] = {0, 0, 0};

@@ -5,6 +5,8 @@
 // (stats_cols.hip) -- the device reads the characters and the runs, nothing is expanded -- and this file does the text
 // around it: BEDPE parsing, the query / reference swap, the order, the cuts at assembly gaps and large gaps
 // (split_alignment / gap_split / subhit), the four floating-point columns, the filters and the formatting.
+// With StatsParams::cuts_device the match counter, the cuts at assembly gaps and the trims come from ONE sdf_stats_cuts_pairs
+// call on the resident chromosomes (stats_cuts.hip) and the pieces are built from its records and the CIGAR alone.
 //
 // Parity: src/stats_main.cc includes boost/dynamic_bitset.hpp and cannot be compiled here -- this file is a restatement,
 // parity unpinned, except for what it shares with pinned pieces: Alignment(fa, fb, cigar), trim_front / trim_back,
@@ -12,6 +14,7 @@
 // double is printf's %g: tests/test_stats_generate.py against the reference's vendored fmt) and the column counters
 // (tests/test_stats_columns.py).
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -143,6 +146,34 @@ std::vector<Piece> split_alignment(const Piece &h, const StatsParams &sp) {
   return out;
 }
 
+// The run's device context and the chromosomes resident in it: every chromosome goes up once, straight from the mapped file
+// (the .fai entry is the geometry), whichever call names it first.
+struct Device {
+  sdf_ctx *ctx = nullptr;
+  std::map<std::string, int64_t> base;  // chromosome -> its first byte in the pool
+  ~Device() {
+    if (ctx) sdf_destroy(ctx);
+  }
+  void open(int device) {
+    if (ctx) return;
+    ctx = sdf_create(device, 0);
+    if (!ctx) throw std::string("GPU backend unavailable: ") + sdf_last_error(nullptr);
+  }
+  [[noreturn]] void fail(const char *call) { throw std::string(call) + ": " + sdf_last_error(ctx); }
+  int64_t chromosome(const FastaReference &fr, const std::string &name) {
+    auto it = base.find(name);
+    if (it != base.end()) return it->second;
+    const FastaReference::Record r = fr.record(name);  // (a name the index does not know throws: the context goes with the run)
+    int64_t at = 0;
+    if (sdf_pool_append_fasta(ctx, r.bytes, r.nbytes, r.entry->length, r.entry->line_blen, r.entry->line_len, base.empty(), &at) != SDF_OK)
+      fail("sdf_pool_append_fasta");
+    base.insert({name, at});
+    return at;
+  }
+};
+
+uint32_t run_word(char op, int len) { return ((uint32_t)len << 4) | (op == 'M' ? 0u : op == 'D' ? 1u : op == 'I' ? 2u : 3u); }
+
 struct Input {  // one BEDPE line after the swap of src/stats_main.cc:346-358
   Hit h;
   std::string cigar;
@@ -151,7 +182,7 @@ struct Input {  // one BEDPE line after the swap of src/stats_main.cc:346-358
 }  // namespace
 
 long stats_generate(const std::string &ref_path, const std::string &bed_path, FILE *out, const StatsParams &sp,
-                    test_cols_fn test, int device, long long *stats) {
+                    test_cols_fn test, int device, long long *stats, test_cuts_fn test_cuts) {
   FastaReference fr(ref_path);
   std::ifstream fin(bed_path.c_str());
   if (!fin.is_open()) throw std::string("BED file ") + bed_path + " does not exist";
@@ -180,19 +211,131 @@ long stats_generate(const std::string &ref_path, const std::string &bed_path, FI
   std::vector<Piece> pieces;
   Params ap;
   set_alignment_scoring(ap);  // (the trims score with Globals::Align, defaults in `stats`)
+  // SDF_STATS_CUTS_DEVICE=1: match counter, cuts and trims from one sdf_stats_cuts_pairs call (or the hook's stand-in)
+  const bool want_cuts = test_cuts || (sp.cuts_device && sp.resident && !test);
+  const bool cuts = want_cuts && sp.max_ok_gap <= -1;
+  if (want_cuts && !cuts)
+    fprintf(stderr, "[sedef_amd] SDF_STATS_CUTS_DEVICE=1 ignored: --max-ok-gap cuts again and trims on the host, the cuts stay there\n");
+  if (test_cuts && !test) throw std::string("the cuts hook needs the columns hook");
+  Device dev;
+  const bool fetch = !cuts || test_cuts;  // (the hook's stand-in and the columns hook read strings)
   for (Input &x : in) {
     Hit &hs = x.h;
-    x.fa = fr.get_sequence(hs.query->name, hs.query_start, &hs.query_end);
-    x.fb = fr.get_sequence(hs.ref->name, hs.ref_start, &hs.ref_end);
-    if (hs.query->is_rc) x.fa = rc(x.fa);
-    if (hs.ref->is_rc) x.fb = rc(x.fb);
+    if (fetch) {
+      x.fa = fr.get_sequence(hs.query->name, hs.query_start, &hs.query_end);
+      x.fb = fr.get_sequence(hs.ref->name, hs.ref_start, &hs.ref_end);
+      if (hs.query->is_rc) x.fa = rc(x.fa);
+      if (hs.ref->is_rc) x.fb = rc(x.fb);
+    } else {  // get_sequence's clamp of the ends, from the .fai length
+      hs.query_end = std::min(hs.query_end, fr.record(hs.query->name).entry->length);
+      hs.ref_end = std::min(hs.ref_end, fr.record(hs.ref->name).entry->length);
+    }
     if (x.cigar.empty()) throw std::string("BED line without a CIGAR in column 13");
   }
-  for (Input &x : in) {  // (after the loop above: the strings do not move any more)
-    Piece p{x.h.query, x.h.ref, x.h.query_start, x.h.query_end, x.h.ref_start, x.h.ref_end, Alignment(x.fa, x.fb, x.cigar)};
-    p.src = (size_t)(&x - in.data());
-    for (auto &q : split_alignment(p, sp))
-      if (q.aln.span() >= ap.refine_min_read) pieces.push_back(std::move(q));  // (:229: Chain::Refine::MIN_READ)
+  if (!cuts) {
+    for (Input &x : in) {  // (after the loop above: the strings do not move any more)
+      Piece p{x.h.query, x.h.ref, x.h.query_start, x.h.query_end, x.h.ref_start, x.h.ref_end, Alignment(x.fa, x.fb, x.cigar)};
+      p.src = (size_t)(&x - in.data());
+      for (auto &q : split_alignment(p, sp))
+        if (q.aln.span() >= ap.refine_min_read) pieces.push_back(std::move(q));  // (:229: Chain::Refine::MIN_READ)
+    }
+  } else {
+    // ---- one task per input line: the two fetched ranges, in chromosome order whatever the strand ----
+    const size_t ni = in.size();
+    std::vector<sdf_stats_task> tasks(ni);
+    std::vector<uint32_t> runs;
+    for (size_t i = 0; i < ni; i++) {
+      const Hit &h = in[i].h;
+      sdf_stats_task &t = tasks[i];
+      t.a_off = (uint64_t)std::max(0, h.query_start), t.b_off = (uint64_t)std::max(0, h.ref_start);
+      t.a_len = (uint32_t)std::max(0, h.query_end - std::max(0, h.query_start));
+      t.b_len = (uint32_t)std::max(0, h.ref_end - std::max(0, h.ref_start));
+      t.reserved = (h.query->is_rc ? SDF_STATS_A_RC : 0u) | (h.ref->is_rc ? SDF_STATS_B_RC : 0u);
+      t.cigar_off = runs.size();
+      int num = 0;
+      for (char ch : in[i].cigar) {  // (Alignment's own parse; zero-length runs hold no column)
+        if (isdigit((unsigned char)ch)) num = 10 * num + (ch - '0');
+        else if (ch == ';') continue;
+        else {
+          if (num) runs.push_back(run_word(ch, num));
+          num = 0;
+        }
+      }
+      t.n_cigar = (uint32_t)(runs.size() - t.cigar_off);
+    }
+    const int scores[4] = {ap.match, ap.mismatch, ap.gap_open, ap.gap_extend};
+    std::vector<uint64_t> first(ni + 1, 0);
+    std::vector<sdf_stats_piece> recs;
+    if (test_cuts) {
+      for (size_t i = 0; i < ni; i++) {
+        const sdf_stats_task &t = tasks[i];
+        std::vector<sdf_stats_piece> one(4);
+        for (;;) {
+          static_assert(sizeof(sdf_stats_piece) == 8 * sizeof(int32_t), "a record is eight int32 for the hook");
+          const long need = test_cuts(in[i].fa.data(), (int)in[i].fa.size(), in[i].fb.data(), (int)in[i].fb.size(),
+                                      runs.data() + t.cigar_off, (int)t.n_cigar, scores, (int32_t *)one.data(), (long)one.size());
+          if (need < 0) throw std::string("the cuts hook failed");
+          if ((size_t)need <= one.size()) {
+            one.resize((size_t)need);
+            break;
+          }
+          one.resize((size_t)need);
+        }
+        recs.insert(recs.end(), one.begin(), one.end());
+        first[i + 1] = recs.size();
+      }
+    } else if (ni) {
+      dev.open(device);
+      for (size_t i = 0; i < ni; i++) {
+        tasks[i].a_off += (uint64_t)dev.chromosome(fr, in[i].h.query->name);
+        tasks[i].b_off += (uint64_t)dev.chromosome(fr, in[i].h.ref->name);
+      }
+      recs.resize(ni + 64);  // (an alignment without an assembly gap is one piece)
+      size_t used = 0;
+      int rc = sdf_stats_cuts_pairs(dev.ctx, tasks.data(), ni, runs.data(), runs.size(), scores[0], scores[1], scores[2], scores[3],
+                                    first.data(), recs.data(), recs.size(), &used);
+      if (rc == SDF_ERR_CIGAR_OVERFLOW) {
+        recs.resize(used);
+        rc = sdf_stats_cuts_pairs(dev.ctx, tasks.data(), ni, runs.data(), runs.size(), scores[0], scores[1], scores[2], scores[3],
+                                  first.data(), recs.data(), recs.size(), &used);
+      }
+      if (rc != SDF_OK) dev.fail("sdf_stats_cuts_pairs");
+      recs.resize(used);
+    }
+    // ---- the pieces, from the records and the CIGAR alone (subhit's coordinates: the bases BEFORE the trims) ----
+    for (size_t i = 0; i < ni; i++) {
+      const Input &x = in[i];
+      const Hit &h = x.h;
+      const sdf_stats_piece *r = recs.data() + first[i];
+      const size_t np = (size_t)(first[i + 1] - first[i]);
+      if (np == 0) throw std::string("internal: an alignment without a piece record");
+      if (r[0].flags) throw std::string("the CIGAR of a BED line does not fit its sequences");
+      const bool untouched = np == 1 && r[0].begin == 0;  // (no event: an event moves `begin` past an N run)
+      const Alignment whole(fetch ? x.fa.data() : nullptr, (int)tasks[i].a_len, fetch ? x.fb.data() : nullptr, (int)tasks[i].b_len,
+                            x.cigar, untouched ? r[0].matches : 0);
+      Piece p{h.query, h.ref, h.query_start, h.query_end, h.ref_start, h.ref_end, whole};
+      p.src = i;
+      if (untouched) {
+        if (whole.span() >= ap.refine_min_read) pieces.push_back(std::move(p));
+        continue;
+      }
+      for (size_t k = 0; k < np; k++) {
+        Piece q = p;
+        int sa, la, sb, lb, ta, tla, tb, tlb;
+        whole.slice_columns(r[k].begin, r[k].end, 0, sa, la, sb, lb);
+        q.aln = whole.slice_columns(r[k].t_begin, r[k].t_end, r[k].matches, ta, tla, tb, tlb);  // (emptied: no column)
+        q.query_start += sa;
+        q.query_end = q.query_start + la;
+        if (q.ref->is_rc) {
+          q.ref_start = q.ref_end - (lb + sb);
+          q.ref_end = q.ref_end - sb;
+        } else {
+          q.ref_start += sb;
+          q.ref_end = q.ref_start + lb;
+        }
+        if (q.aln.span() >= ap.refine_min_read) pieces.push_back(std::move(q));
+      }
+    }
   }
 
   // ---- the column counters of all pieces: one device call ----
@@ -237,46 +380,19 @@ long stats_generate(const std::string &ref_path, const std::string &bed_path, FI
         memcpy(&cols[k], o, sizeof(sdf_stats_cols));
       }
     } else if (n) {
-      sdf_ctx *ctx = sdf_create(device, 0);
-      if (!ctx) throw std::string("GPU backend unavailable: ") + sdf_last_error(nullptr);
-      int rc = SDF_OK;
-      const char *call = "sdf_stats_columns_batch";
+      dev.open(device);
       if (resident) {
-        // every chromosome the pieces name, once, straight from the mapped file (the .fai entry is the geometry)
-        std::map<std::string, int64_t> base;
-        for (size_t k = 0; k < n && rc == SDF_OK; k++) {
+        for (size_t k = 0; k < n; k++) {
           const Hit &h = in[pieces[k].src].h;
-          uint64_t *off[2] = {&tasks[k].a_off, &tasks[k].b_off};
-          const std::string *name[2] = {&h.query->name, &h.ref->name};
-          for (int side = 0; side < 2 && rc == SDF_OK; side++) {
-            auto it = base.find(*name[side]);
-            if (it == base.end()) {
-              FastaReference::Record r;
-              try {
-                r = fr.record(*name[side]);
-              } catch (...) {  // (a name the index does not know: the context goes with the run)
-                sdf_destroy(ctx);
-                throw;
-              }
-              int64_t at = 0;
-              call = "sdf_pool_append_fasta";
-              rc = sdf_pool_append_fasta(ctx, r.bytes, r.nbytes, r.entry->length, r.entry->line_blen, r.entry->line_len,
-                                         base.empty(), &at);
-              it = base.insert({*name[side], at}).first;
-            }
-            *off[side] += (uint64_t)it->second;
-          }
+          tasks[k].a_off += (uint64_t)dev.chromosome(fr, h.query->name);
+          tasks[k].b_off += (uint64_t)dev.chromosome(fr, h.ref->name);
         }
-        if (rc == SDF_OK) {
-          call = "sdf_stats_columns_pairs";
-          rc = sdf_stats_columns_pairs(ctx, tasks.data(), n, runs.data(), runs.size(), cols.data());
-        }
-      } else {
-        rc = sdf_stats_columns_batch(ctx, tasks.data(), n, pool.data(), pool.size(), runs.data(), runs.size(), cols.data());
+        if (sdf_stats_columns_pairs(dev.ctx, tasks.data(), n, runs.data(), runs.size(), cols.data()) != SDF_OK)
+          dev.fail("sdf_stats_columns_pairs");
+      } else if (sdf_stats_columns_batch(dev.ctx, tasks.data(), n, pool.data(), pool.size(), runs.data(), runs.size(), cols.data()) !=
+                 SDF_OK) {
+        dev.fail("sdf_stats_columns_batch");
       }
-      const std::string err = rc ? sdf_last_error(ctx) : "";
-      sdf_destroy(ctx);
-      if (rc) throw std::string(call) + ": " + err;
     }
   }
 

@@ -1674,6 +1674,145 @@ extern "C" int sdf_stats_columns_pairs(sdf_ctx *ctx, const sdf_stats_task *tasks
   return stats_host(ctx, tasks, n, true, nullptr, ctx ? ctx->pool_bytes : 0, cigar_pool, cigar_words, out);
 }
 
+// ---- the cuts of `stats generate` on the resident pool (stats_cuts.hip; include/sedef_hip.h) -------------------
+static int cuts_scores(sdf_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, sdf::CutsScores &sc) {
+  if (std::abs(match) > 63 || std::abs(mismatch) > 63 || std::abs(gap_open) > 63 || std::abs(gap_extend) > 63 ||
+      std::abs(gap_open) + std::abs(gap_extend) > 63) {
+    ctx->err = "stats cuts implement |match|, |mismatch| <= 63 and |gap_open| + |gap_extend| <= 63";
+    return SDF_ERR_UNSUPPORTED;
+  }
+  sc = sdf::CutsScores{match, mismatch, gap_open, gap_extend};
+  return SDF_OK;
+}
+
+// launches 1 and 2: the alignments' count words and first[]
+static int cuts_count(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, bool rev, const uint32_t *d_cigar_pool, uint64_t *d_first,
+                      hipStream_t st) {
+  SDF_HIP(ctx->sc_counts.reserve(n * 12 + 64));
+  uint32_t *d_counts = (uint32_t *)ctx->sc_counts.p;
+  int32_t *d_whole = (int32_t *)(d_counts + n);
+  const dim3 grid((unsigned)((n + sdf::STATS_WAVES - 1) / sdf::STATS_WAVES)), block(64 * sdf::STATS_WAVES);
+  hipLaunchKernelGGL(rev ? sdf::stats_cuts_count_kernel<true> : sdf::stats_cuts_count_kernel<false>, grid, block, 0, st, d_tasks, (int)n,
+                     (const char *)ctx->an_pool.p, d_cigar_pool, d_counts, d_whole);
+  hipLaunchKernelGGL(sdf::stats_cuts_scan_kernel, dim3(1), dim3(1024), 0, st, d_counts, (int)n, d_first);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += 2;
+  return SDF_OK;
+}
+// launch 3: the records (after cuts_count on the same stream)
+static int cuts_emit(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, bool rev, const uint32_t *d_cigar_pool, const sdf::CutsScores &sc,
+                     const uint64_t *d_first, sdf_stats_piece *d_pieces, size_t cap, hipStream_t st) {
+  const uint32_t *d_counts = (const uint32_t *)ctx->sc_counts.p;
+  const int32_t *d_whole = (const int32_t *)(d_counts + n);
+  const dim3 grid((unsigned)((n + sdf::STATS_WAVES - 1) / sdf::STATS_WAVES)), block(64 * sdf::STATS_WAVES);
+  hipLaunchKernelGGL(rev ? sdf::stats_cuts_emit_kernel<true> : sdf::stats_cuts_emit_kernel<false>, grid, block, 0, st, d_tasks, (int)n,
+                     (const char *)ctx->an_pool.p, d_cigar_pool, sc, d_counts, d_whole, d_first, d_pieces, (uint64_t)cap);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += 1;
+  return SDF_OK;
+}
+
+extern "C" int sdf_stats_cuts_pairs_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, size_t n, int any_rc, const uint32_t *d_cigar_pool,
+                                           int match, int mismatch, int gap_open, int gap_extend, uint64_t *d_first,
+                                           sdf_stats_piece *d_pieces, size_t pieces_cap, size_t *pieces_used, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (n >= ((size_t)1 << 31) || !d_first || (n && !d_tasks) || (pieces_cap && !d_pieces)) {
+    ctx->err = "invalid arguments";
+    return SDF_ERR_INVALID;
+  }
+  sdf::CutsScores sc;
+  if (int rc = cuts_scores(ctx, match, mismatch, gap_open, gap_extend, sc)) return rc;
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (n == 0) {
+    SDF_HIP(hipMemsetAsync(d_first, 0, sizeof(uint64_t), st));
+    if (!stream) SDF_HIP(hipStreamSynchronize(st));
+    if (pieces_used) *pieces_used = 0;
+    return SDF_OK;
+  }
+  if (int rc = cuts_count(ctx, d_tasks, n, any_rc != 0, d_cigar_pool, d_first, st)) return rc;
+  if (int rc = cuts_emit(ctx, d_tasks, n, any_rc != 0, d_cigar_pool, sc, d_first, d_pieces, pieces_cap, st)) return rc;
+  if (stream) return SDF_OK;
+  uint64_t need = 0;
+  SDF_HIP(hipMemcpyAsync(&need, d_first + n, sizeof need, hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  if (pieces_used) *pieces_used = (size_t)need;
+  if (need > pieces_cap) {
+    ctx->err = "the batch cuts into " + std::to_string(need) + " pieces, more than pieces_cap";
+    return SDF_ERR_CIGAR_OVERFLOW;
+  }
+  return SDF_OK;
+}
+
+extern "C" int sdf_stats_cuts_pairs(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n, const uint32_t *cigar_pool, size_t cigar_words,
+                                    int match, int mismatch, int gap_open, int gap_extend, uint64_t *first, sdf_stats_piece *pieces,
+                                    size_t pieces_cap, size_t *pieces_used) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (n >= ((size_t)1 << 31) || !first || !pieces_used || (n && !tasks) || (pieces_cap && !pieces) || (!cigar_pool && cigar_words)) {
+    ctx->err = "invalid arguments";
+    return SDF_ERR_INVALID;
+  }
+  sdf::CutsScores sc;
+  if (int rc = cuts_scores(ctx, match, mismatch, gap_open, gap_extend, sc)) return rc;
+  const size_t pool_bytes = ctx->pool_bytes;
+  bool any_rc = false;
+  for (size_t i = 0; i < n; i++) {  // (the checks of sdf_stats_columns_pairs)
+    const sdf_stats_task &t = tasks[i];
+    if (t.reserved & ~(uint32_t)(SDF_STATS_A_RC | SDF_STATS_B_RC)) {
+      ctx->err = "alignment " + std::to_string(i) + ": unknown stats task flag";
+      return SDF_ERR_UNSUPPORTED;
+    }
+    if (t.a_len > (1u << 24) || t.b_len > (1u << 24)) {
+      ctx->err = "stats cuts implement sequences up to 16 Mb";
+      return SDF_ERR_UNSUPPORTED;
+    }
+    if (t.a_off > pool_bytes || t.a_len > pool_bytes - t.a_off || t.b_off > pool_bytes || t.b_len > pool_bytes - t.b_off) {
+      ctx->err = "alignment " + std::to_string(i) + ": sequence range outside the resident pool (sdf_pool_upload / sdf_pool_append_fasta)";
+      return SDF_ERR_INVALID;
+    }
+    if (t.cigar_off > cigar_words || t.n_cigar > cigar_words - t.cigar_off || t.n_cigar >= (1u << 31)) {
+      ctx->err = "alignment " + std::to_string(i) + ": CIGAR range outside its pool";
+      return SDF_ERR_INVALID;
+    }
+    any_rc |= t.reserved != 0;
+  }
+  *pieces_used = 0;
+  first[0] = 0;
+  if (n == 0) return SDF_OK;
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;  // (the pool's uploads were enqueued there)
+  SDF_HIP(ctx->sc_tasks.reserve(n * sizeof(sdf_stats_task)));
+  SDF_HIP(ctx->sc_cig.reserve(cigar_words * 4 + 16));
+  SDF_HIP(ctx->sc_first.reserve((n + 1) * sizeof(uint64_t)));
+  const sdf_stats_task *d_tasks = (const sdf_stats_task *)ctx->sc_tasks.p;
+  const uint32_t *d_cig = (const uint32_t *)ctx->sc_cig.p;
+  uint64_t *d_first = (uint64_t *)ctx->sc_first.p;
+  SDF_HIP(hipMemcpyAsync(ctx->sc_tasks.p, tasks, n * sizeof(sdf_stats_task), hipMemcpyHostToDevice, st));
+  if (cigar_words) SDF_HIP(hipMemcpyAsync(ctx->sc_cig.p, cigar_pool, cigar_words * 4, hipMemcpyHostToDevice, st));
+  if (int rc = cuts_count(ctx, d_tasks, n, any_rc, d_cig, d_first, st)) return rc;
+  SDF_HIP(hipMemcpyAsync(first, d_first, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  const uint64_t need = first[n];
+  *pieces_used = (size_t)need;
+  if (need > pieces_cap) {
+    ctx->err = "the batch cuts into " + std::to_string(need) + " pieces, more than pieces_cap";
+    return SDF_ERR_CIGAR_OVERFLOW;
+  }
+  SDF_HIP(ctx->sc_out.reserve((size_t)need * sizeof(sdf_stats_piece)));
+  if (int rc = cuts_emit(ctx, d_tasks, n, any_rc, d_cig, sc, d_first, (sdf_stats_piece *)ctx->sc_out.p, (size_t)need, st)) return rc;
+  SDF_HIP(hipMemcpyAsync(pieces, ctx->sc_out.p, (size_t)need * sizeof(sdf_stats_piece), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  static_assert(sizeof(sdf_stats_piece) == 32, "sdf_stats_piece: two records per 64-byte line");
+  for (size_t i = 0; i < n; i++)
+    if (pieces[first[i]].flags) {
+      ctx->err = "alignment " + std::to_string(i) + ": the CIGAR does not fit its sequences";
+      return SDF_ERR_INVALID;
+    }
+  return SDF_OK;
+}
+
 // ---- one-task drop-in with the reference's exact signature (extern/ksw2.h:50) -----------------
 namespace {
 std::mutex g_mu;

@@ -321,6 +321,8 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(st_tasks, None) X(st_pool, None) X(st_cig, None) X(st_out, None) /* sdf_stats_columns_batch */                    \
   X(claim_buf, None)   /* stripe launches: eight entry counters each (stripe_claim), zeroed per call */               \
   X(st_items, None)    /* sdf_stats_columns_device: segments of long alignments + their counter */                    \
+  X(sc_counts, None) /* sdf_stats_cuts_pairs_device: per alignment the count word and {matches, span} */              \
+  X(sc_tasks, None) X(sc_cig, None) X(sc_first, None) X(sc_out, None) /* sdf_stats_cuts_pairs: the host form's copies */ \
   X(h_pool, BatchCall) X(h_out, BatchCall) X(h_cig, BatchCall) /* device buffers of the host-buffer entry point */    \
   X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \

@@ -142,5 +142,17 @@ __global__ void stats_columns_kernel(const sdf_stats_task *, int, const char *, 
 template <bool REV>
 __global__ void stats_segments_kernel(const StatsItem *, const unsigned *, unsigned, const char *, const uint32_t *,
                                       sdf_stats_cols *);
+// stats_cuts.hip
+struct CutsScores {  // the trims' column scores (host: Params::match and on)
+  int match, mismatch, gap_open, gap_extend;
+};
+// an alignment's word of the count launch: pieces, and two flags
+constexpr uint32_t kCutsEvents = 0x80000000u, kCutsBad = 0x40000000u, kCutsCount = 0x3fffffffu;
+template <bool REV>
+__global__ void stats_cuts_count_kernel(const sdf_stats_task *, int, const char *, const uint32_t *, uint32_t *, int32_t *);
+__global__ void stats_cuts_scan_kernel(const uint32_t *, int, uint64_t *);
+template <bool REV>
+__global__ void stats_cuts_emit_kernel(const sdf_stats_task *, int, const char *, const uint32_t *, CutsScores, const uint32_t *,
+                                       const int32_t *, const uint64_t *, sdf_stats_piece *, uint64_t);
 
 }  // namespace sdf

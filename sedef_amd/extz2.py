@@ -44,6 +44,10 @@ STATS_COLS_DTYPE = np.dtype([(f, "<i4") for f in (
     "indel_a", "indel_b", "aln_b", "match_b", "mismatch_b", "transitions_b", "transversions_b", "uppercase_a",
     "uppercase_b", "uppercase_matches", "matches", "mismatches", "gaps", "gap_bases", "span", "flags")])
 assert STATS_TASK_DTYPE.itemsize == 40 and STATS_COLS_DTYPE.itemsize == 64
+# sdf_stats_piece (sdf_stats_cuts_pairs): a cut piece in the alignment's columns, before and after the trims
+STATS_PIECE_DTYPE = np.dtype([("begin", "<i4"), ("end", "<i4"), ("t_begin", "<i4"), ("t_end", "<i4"), ("matches", "<i4"),
+                              ("flags", "<i4"), ("reserved", "<i4", (2,))])
+assert STATS_PIECE_DTYPE.itemsize == 32
 # strand bits of a stats task on the resident pool (include/sedef_hip.h: SDF_STATS_A_RC / SDF_STATS_B_RC; in `reserved`,
 # stats_columns_pairs only)
 STATS_A_RC, STATS_B_RC = 0x1, 0x2
@@ -156,6 +160,12 @@ def load_library():
                                            C.c_void_p]
     L.sdf_stats_columns_pairs.restype = C.c_int
     L.sdf_stats_columns_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdf_stats_cuts_pairs.restype = C.c_int
+    L.sdf_stats_cuts_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sdf_stats_cuts_pairs_device.restype = C.c_int
+    L.sdf_stats_cuts_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     L.sdf_stats_columns_pairs_device.restype = C.c_int
     L.sdf_stats_columns_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
@@ -683,6 +693,53 @@ class Extz2Engine:
         """The same over device pointers (ints) of tasks, runs and records; asynchronous on `stream` when one is given
         (pool_sync() first: the pool's uploads run on the context's stream).  any_rc: some task may carry a strand bit."""
         self._check(self.lib.sdf_stats_columns_pairs_device(self.ctx, d_tasks, n, int(bool(any_rc)), d_cigar, d_out, stream))
+
+    def stats_cuts_pairs_raw(self, tasks, cigar, scores=(5, -4, -40, -1), cap=None, pieces=None):
+        """sdf_stats_cuts_pairs as it is: returns (rc, first, pieces, used).  tasks as stats_columns_pairs takes them (strand
+        bits in `reserved`), scores (match, mismatch, gap_open, gap_extend) of the trims, cap: capacity in pieces (default:
+        len(pieces), or what the batch needs, found by a first call), pieces: a STATS_PIECE_DTYPE array to fill."""
+        tasks = np.ascontiguousarray(tasks, dtype=STATS_TASK_DTYPE)
+        cig = np.ascontiguousarray(cigar, dtype=np.uint32)
+        n = len(tasks)
+        first = np.zeros(n + 1, np.uint64)
+        used = C.c_size_t(0)
+
+        def call(buf, c):
+            return self.lib.sdf_stats_cuts_pairs(self.ctx, tasks.ctypes.data if n else None, n, cig.ctypes.data if len(cig) else None,
+                                                 len(cig), *[int(x) for x in scores], first.ctypes.data,
+                                                 buf.ctypes.data if len(buf) else None, c, C.byref(used))
+        if pieces is None:
+            if cap is None:
+                rc = call(np.zeros(0, STATS_PIECE_DTYPE), 0)
+                if rc not in (0, -5):  # (SDF_ERR_CIGAR_OVERFLOW: *pieces_used holds the need)
+                    return rc, first, np.zeros(0, STATS_PIECE_DTYPE), int(used.value)
+                cap = int(used.value)
+            pieces = np.zeros(cap, STATS_PIECE_DTYPE)
+        assert pieces.dtype == STATS_PIECE_DTYPE and pieces.flags.c_contiguous
+        rc = call(pieces, len(pieces) if cap is None else cap)
+        return rc, first, pieces, int(used.value)
+
+    def stats_cuts_pairs(self, tasks, cigar, a_rc=None, b_rc=None, scores=(5, -4, -40, -1)):
+        """sdf_stats_cuts_pairs: per alignment of the resident pool (tasks, cigar, a_rc / b_rc as stats_columns_pairs takes
+        them) the pieces `stats generate` cuts at assembly gaps, before and after trim_back / trim_front, and the matches
+        inside.  Returns (first, pieces): pieces[first[i]:first[i + 1]] (STATS_PIECE_DTYPE) are alignment i's, in column order."""
+        tasks = np.ascontiguousarray(tasks, dtype=STATS_TASK_DTYPE)
+        if a_rc is not None or b_rc is not None:
+            tasks = tasks.copy()
+            for side, bit in ((a_rc, STATS_A_RC), (b_rc, STATS_B_RC)):
+                if side is not None:
+                    tasks["reserved"] |= np.where(np.broadcast_to(np.asarray(side, bool), tasks.shape), bit, 0).astype(np.uint32)
+        rc, first, pieces, used = self.stats_cuts_pairs_raw(tasks, cigar, scores)
+        self._check(rc)
+        return first.astype(np.int64), pieces[:used]
+
+    def stats_cuts_pairs_device(self, d_tasks, n, any_rc, d_cigar, d_first, d_pieces, cap, scores=(5, -4, -40, -1), stream=None):
+        """The same over device pointers (ints) of tasks, runs, first (n + 1 uint64) and records; asynchronous on `stream` when
+        one is given (pool_sync() first), else returns the pieces the batch needs (raises when they exceed cap)."""
+        used = C.c_size_t(0)
+        self._check(self.lib.sdf_stats_cuts_pairs_device(self.ctx, d_tasks, n, int(bool(any_rc)), d_cigar, *[int(x) for x in scores],
+                                                         d_first, d_pieces, cap, C.byref(used), stream))
+        return int(used.value)
 
     def last_ms(self, which):
         return float(self.lib.sdf_last_ms(self.ctx, which))

@@ -226,6 +226,29 @@ def stats_generate(ref_path, bed_path, out_path, max_ok_gap=-1, min_split=1000, 
     return (int(n),) + tuple(int(x) for x in st)
 
 
+# a CPU stand-in for sdf_stats_cuts_pairs on one alignment (csrc/host/sedef_host.h: test_cuts_fn)
+CUTS_HOOK = C.CFUNCTYPE(C.c_long, C.POINTER(C.c_char), C.c_int, C.POINTER(C.c_char), C.c_int, C.POINTER(C.c_uint32), C.c_int,
+                        C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_long)
+
+
+def stats_generate_cuts(ref_path, bed_path, out_path, max_ok_gap=-1, min_split=1000, uppercase=100, max_error=0.5,
+                        test_cols=None, device=0, resident=True, cuts=True, test_cuts=None):
+    """stats_generate with the match counter, the cuts at assembly gaps and the trims on the resident chromosomes too
+    (sdfh_stats_generate_cuts; cuts=True or SDF_STATS_CUTS_DEVICE=1, only with resident chromosomes and without max_ok_gap).
+    test_cuts: a CUTS_HOOK stand-in for the device call -- the path then runs without a device, with test_cols for the
+    columns.  Returns (lines, hits, pieces, columns)."""
+    lib = load_host()
+    st = (C.c_longlong * 3)()
+    lib.sdfh_stats_generate_cuts.restype = C.c_long
+    lib.sdfh_stats_generate_cuts.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
+    n = lib.sdfh_stats_generate_cuts(ref_path.encode(), bed_path.encode(), out_path.encode(), max_ok_gap, min_split, uppercase,
+                                     max_error, test_cols, device, int(bool(resident)), int(bool(cuts)),
+                                     C.cast(test_cuts, C.c_void_p) if test_cuts is not None else None, st)
+    _err(lib, min(n, 0))
+    return (int(n),) + tuple(int(x) for x in st)
+
+
 def stats_piece_range(start, end, s, e, rc):
     """stats_piece_range (csrc/host/stats.cc): columns [s, e) of a side fetched from [start, end) of its chromosome and, with
     rc, reverse-complemented -> (first base of the range in the chromosome, length)."""

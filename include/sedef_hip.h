@@ -568,6 +568,62 @@ int sdf_stats_cuts_pairs_device(sdf_ctx *ctx, const sdf_stats_task *d_tasks, siz
                                 int match, int mismatch, int gap_open, int gap_extend, uint64_t *d_first,
                                 sdf_stats_piece *d_pieces, size_t pieces_cap, size_t *pieces_used, void *stream);
 
+/* ---- winnowed minimizers of ranges of the resident pool, and the index over them (minimizers.hip) --------------------------
+ * What `sedef search -k 12 -w 16` rests on: get_minimizers and Index::Index of the reference (src/hash.cc:53-141), for many
+ * ranges in one call.  The sequence s of a range is pool[off, off + len) as it lies, or -- SDF_MINIM_RC -- its reverse complement
+ * by rev_dna (s[i] = rev_dna(pool[off + len - 1 - i]): every byte that is not ACGTacgt becomes 'N'; loc counts in s, as for the
+ * reference's Sequence(..., is_rc)).  Characters are taken & 127 on either strand.  With k-mer starts j = 0 .. len - k:
+ *   hash     the 2-bit codes of s[j, j + k), first character most significant: A/a 0, C/c 1, G/g 2, T/t 3, anything else 0
+ *   status   2 when one of the k characters is N or n, else 0 when one is an uppercase letter, else 1 -- or 0 with
+ *            separate_lowercase == 0
+ *   root     start j is a root when no y in [max(0, j - w), j) has (status, hash)(y) < (status, hash)(j); equal keys do not
+ *            suppress each other, start 0 is always one
+ *   records  the largest root <= w, then every root > w, in ascending loc; none when the range has w starts or fewer.
+ * That is the reference's deque loop, whose second loop tests the back and pops the front, in closed form
+ * (tests/minim_model.py holds the loop as written).  out[first[i], first[i + 1]) are range i's records, `range` = i.
+ * Limits: k 1..15 (the reference's mask is undefined at 16), w 1..SDF_MINIM_MAX_W (a wavefront keeps the keys of a block of
+ * SDF_MINIM_BLOCK starts and of the w before them in LDS, and looks back w deep per start).
+ *
+ * Host form.  Every check precedes the first launch, and a refused call launches nothing (sdf_last_launches() as it was):
+ *   SDF_ERR_INVALID      off < 0, len < 0, off + len > sdf_pool_bytes(ctx), w < 1, r / first / used == NULL with n > 0,
+ *                        out == NULL with cap > 0
+ *   SDF_ERR_UNSUPPORTED  k outside 1..15, w > SDF_MINIM_MAX_W, a flags bit other than SDF_MINIM_RC
+ * n == 0 is SDF_OK without a launch.  SDF_ERR_CIGAR_OVERFLOW when the ranges have more than cap records: *used holds the need,
+ * first[] is filled and nothing is written to out; else *used = first[n].  Six launches: blocks per range and their scan, records
+ * per block and their scan, first[], the records (five when cap is short).  Works on a view (sdf_pool_share) like every reader
+ * of the pool; enqueued on the context's stream behind the pool's uploads, returns with everything filled. */
+#define SDF_MINIM_RC 0x1
+#define SDF_MINIM_BLOCK 1024  /* k-mer starts of one range that one wavefront takes (sdf_minimizer_block()) */
+#define SDF_MINIM_MAX_W 1000
+typedef struct { int64_t off; int32_t len; int32_t flags; } sdf_minim_range;
+typedef struct { uint32_t hash; int32_t loc; int32_t status; int32_t range; } sdf_minimizer; /* 16 bytes */
+int sdf_minimizer_block(void); /* SDF_MINIM_BLOCK as the library was built */
+int sdf_pool_minimizers(sdf_ctx *ctx, const sdf_minim_range *r, size_t n, int k, int w, int separate_lowercase,
+                        uint64_t *first /* n + 1 */, sdf_minimizer *out, size_t cap, size_t *used);
+/* Device form: ranges, d_first (n + 1 entries) and d_out in HBM.  k, w and n are checked as above; the ranges are not, but a
+ * range that does not lie in the pool or carries an unknown flag has no records instead of being read.  any_rc == 0 with a range
+ * that carries SDF_MINIM_RC reads that range forward.  The call waits ONCE on the host, for the ranges' block count (eight
+ * bytes), before it enqueues the other launches on `stream` (NULL: the context's own, synchronised before returning -- then
+ * *used, if given, holds d_first[n] and the call answers SDF_ERR_CIGAR_OVERFLOW when that exceeds cap).  No record is written
+ * at or behind d_out[cap]; with a stream of its own the caller compares d_first[n] with cap itself.  The pool's uploads as for
+ * sdf_stats_columns_pairs_device (sdf_pool_sync() first).  The counts of the call live in the context: calls on one context
+ * do not overlap. */
+int sdf_pool_minimizers_device(sdf_ctx *ctx, const sdf_minim_range *d_ranges, size_t n, int any_rc, int k, int w,
+                               int separate_lowercase, uint64_t *d_first, sdf_minimizer *d_out, size_t cap, size_t *used,
+                               void *stream);
+/* The index of every range (Index::Index): the range's records grouped by (status, hash) -- sorted[first[i], first[i + 1]) are
+ * range i's in ascending (status, hash, loc) order, so a group is a run of equal (status, hash) with ascending locs --,
+ * n_groups[i] the number of groups and threshold[i] the reference's cutoff: with ignore = int(records * 0.001 / 100.0) (the
+ * reference's doubles), the distinct group sizes are walked from the largest down, the groups of each size added up, and while
+ * the sum is <= ignore the threshold becomes that size; it starts at 2147483648 and stays there for fewer than 100,000 records.
+ * Checks, overflow protocol (cap, *used) and first[] as for sdf_pool_minimizers; n_groups and threshold (n entries each) must
+ * be given.  At most 2^31 - 1 records in one call (SDF_ERR_UNSUPPORTED beyond).  One radix sort of range | status | hash
+ * keys (stable: the records come in loc order), one more of the group sizes.  There is NO device form of the index: the call
+ * reads the number of records and of groups back to size its sorts. */
+int sdf_pool_minimizer_index(sdf_ctx *ctx, const sdf_minim_range *r, size_t n, int k, int w, int separate_lowercase,
+                             uint64_t *first /* n + 1 */, sdf_minimizer *sorted, size_t cap, size_t *used,
+                             uint32_t *n_groups /* n */, uint32_t *threshold /* n */);
+
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is
  * sharded over the GPUs of a node with no data-path collective; after the DP an RCCL all-gatherv over xGMI gives every GPU

@@ -323,6 +323,10 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(st_items, None)    /* sdf_stats_columns_device: segments of long alignments + their counter */                    \
   X(sc_counts, None) /* sdf_stats_cuts_pairs_device: per alignment the count word and {matches, span} */              \
   X(sc_tasks, None) X(sc_cig, None) X(sc_first, None) X(sc_out, None) /* sdf_stats_cuts_pairs: the host form's copies */ \
+  X(mz_plan, None) X(mz_counts, None) /* sdf_pool_minimizers_device: blocks per range / records per block, and their scans */ \
+  X(mz_ranges, None) X(mz_first, None) X(mz_out, None) /* sdf_pool_minimizers: the host form's copies */               \
+  X(mz_keys, None) X(mz_vals, None) X(mz_groups, None) X(mz_tmp, None) /* sdf_pool_minimizer_index: sort keys (in, out), */ \
+  X(mz_sorted, None) X(mz_res, None) /* ... places (in, out), heads / ranks / starts, sort scratch, sorted records, results */ \
   X(h_pool, BatchCall) X(h_out, BatchCall) X(h_cig, BatchCall) /* device buffers of the host-buffer entry point */    \
   X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \

@@ -154,5 +154,25 @@ __global__ void stats_cuts_scan_kernel(const uint32_t *, int, uint64_t *);
 template <bool REV>
 __global__ void stats_cuts_emit_kernel(const sdf_stats_task *, int, const char *, const uint32_t *, CutsScores, const uint32_t *,
                                        const int32_t *, const uint64_t *, sdf_stats_piece *, uint64_t);
+// minimizers.hip
+constexpr int MINIM_BLOCK = SDF_MINIM_BLOCK;  // k-mer starts of one range that one wavefront takes
+constexpr int MINIM_MAX_W = SDF_MINIM_MAX_W;  // (a wavefront's LDS holds the keys of MINIM_BLOCK + MINIM_MAX_W starts; MINIM_BLOCK > MINIM_MAX_W:
+                                              // the block at start 0 sees every root <= w)
+static_assert(MINIM_BLOCK > MINIM_MAX_W && MINIM_BLOCK % 64 == 0, "minimizers.hip: the first block holds the starts 0 .. w");
+static_assert(sizeof(sdf_minim_range) == 16 && sizeof(sdf_minimizer) == 16, "four records per 64-byte line");
+__global__ void minim_blocks_kernel(const sdf_minim_range *, int, long long, int, uint32_t *);
+// REV: some range of the launch carries SDF_MINIM_RC; <false> never reads the word
+template <bool REV>
+__global__ void minim_count_kernel(const sdf_minim_range *, int, const uint64_t *, const char *, long long, int, int, int, uint32_t *);
+__global__ void minim_first_kernel(const uint64_t *, int, const uint64_t *, uint64_t *);
+template <bool REV>
+__global__ void minim_emit_kernel(const sdf_minim_range *, int, const uint64_t *, const char *, long long, int, int, int,
+                                  const uint64_t *, sdf_minimizer *, uint64_t);
+__global__ void minim_keys_kernel(const sdf_minimizer *, long long, unsigned long long *, uint32_t *);
+__global__ void minim_heads_kernel(const unsigned long long *, const uint32_t *, const sdf_minimizer *, long long, sdf_minimizer *,
+                                   uint32_t *);
+__global__ void minim_starts_kernel(const uint32_t *, const uint32_t *, long long, uint32_t *);
+__global__ void minim_sizes_kernel(const unsigned long long *, const uint32_t *, long long, unsigned long long *);
+__global__ void minim_threshold_kernel(const unsigned long long *, long long, const uint64_t *, int, uint32_t *, uint32_t *);
 
 }  // namespace sdf

@@ -48,6 +48,11 @@ assert STATS_TASK_DTYPE.itemsize == 40 and STATS_COLS_DTYPE.itemsize == 64
 STATS_PIECE_DTYPE = np.dtype([("begin", "<i4"), ("end", "<i4"), ("t_begin", "<i4"), ("t_end", "<i4"), ("matches", "<i4"),
                               ("flags", "<i4"), ("reserved", "<i4", (2,))])
 assert STATS_PIECE_DTYPE.itemsize == 32
+# include/sedef_hip.h: sdf_minim_range / sdf_minimizer (pool_minimizers, pool_minimizer_index; MINIM_RC in `flags`)
+MINIM_RANGE_DTYPE = np.dtype([("off", "<i8"), ("len", "<i4"), ("flags", "<i4")])
+MINIMIZER_DTYPE = np.dtype([("hash", "<u4"), ("loc", "<i4"), ("status", "<i4"), ("range", "<i4")])
+MINIM_RC, MINIM_MAX_W, MINIM_THRESHOLD_NONE = 0x1, 1000, 1 << 31
+assert MINIM_RANGE_DTYPE.itemsize == 16 and MINIMIZER_DTYPE.itemsize == 16
 # strand bits of a stats task on the resident pool (include/sedef_hip.h: SDF_STATS_A_RC / SDF_STATS_B_RC; in `reserved`,
 # stats_columns_pairs only)
 STATS_A_RC, STATS_B_RC = 0x1, 0x2
@@ -169,6 +174,17 @@ def load_library():
     L.sdf_stats_columns_pairs_device.restype = C.c_int
     L.sdf_stats_columns_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
+    L.sdf_minimizer_block.restype = C.c_int
+    L.sdf_minimizer_block.argtypes = []
+    L.sdf_pool_minimizers.restype = C.c_int
+    L.sdf_pool_minimizers.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sdf_pool_minimizers_device.restype = C.c_int
+    L.sdf_pool_minimizers_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.sdf_pool_minimizer_index.restype = C.c_int
+    L.sdf_pool_minimizer_index.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -740,6 +756,73 @@ class Extz2Engine:
         self._check(self.lib.sdf_stats_cuts_pairs_device(self.ctx, d_tasks, n, int(bool(any_rc)), d_cigar, *[int(x) for x in scores],
                                                          d_first, d_pieces, cap, C.byref(used), stream))
         return int(used.value)
+
+    @staticmethod
+    def minim_ranges(ranges, rc=None):
+        """A MINIM_RANGE_DTYPE array from (off, len) pairs; rc: one truth value for all or one per range (MINIM_RC in
+        `flags`).  An array of that dtype passes through (rc must be None)."""
+        if isinstance(ranges, np.ndarray) and ranges.dtype == MINIM_RANGE_DTYPE:
+            assert rc is None
+            return np.ascontiguousarray(ranges)
+        pairs = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+        recs = np.zeros(len(pairs), MINIM_RANGE_DTYPE)
+        recs["off"], recs["len"] = pairs[:, 0], pairs[:, 1]
+        if rc is not None:
+            recs["flags"] = np.where(np.broadcast_to(np.asarray(rc, dtype=bool), len(pairs)), MINIM_RC, 0)
+        return recs
+
+    def pool_minimizers_raw(self, ranges, k=12, w=16, separate_lowercase=True, cap=None, out=None, index=False):
+        """sdf_pool_minimizers (index=True: sdf_pool_minimizer_index) as it is.  ranges: a MINIM_RANGE_DTYPE array; cap:
+        capacity in records (default: len(out), or what the ranges need, found by a first call); out: a MINIMIZER_DTYPE array
+        to fill.  Returns (rc, first, records, used), and (n_groups, threshold) behind them for the index."""
+        recs = np.ascontiguousarray(ranges, dtype=MINIM_RANGE_DTYPE)
+        n = len(recs)
+        first = np.zeros(n + 1, np.uint64)
+        n_groups, threshold = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        used = C.c_size_t(0)
+
+        def call(buf, c):
+            head = (self.ctx, recs.ctypes.data if n else None, n, int(k), int(w), int(bool(separate_lowercase)), first.ctypes.data,
+                    buf.ctypes.data if len(buf) else None, c, C.byref(used))
+            if index:
+                return self.lib.sdf_pool_minimizer_index(*head, n_groups.ctypes.data, threshold.ctypes.data)
+            return self.lib.sdf_pool_minimizers(*head)
+        if out is None:
+            if cap is None:
+                rc = call(np.zeros(0, MINIMIZER_DTYPE), 0)
+                if rc not in (0, -5):  # (SDF_ERR_CIGAR_OVERFLOW: *used holds the need)
+                    return (rc, first, np.zeros(0, MINIMIZER_DTYPE), int(used.value)) + ((n_groups, threshold) if index else ())
+                cap = int(used.value)
+            out = np.zeros(cap, MINIMIZER_DTYPE)
+        assert out.dtype == MINIMIZER_DTYPE and out.flags.c_contiguous
+        rc = call(out, len(out) if cap is None else cap)
+        return (rc, first, out, int(used.value)) + ((n_groups, threshold) if index else ())
+
+    def pool_minimizers(self, ranges, k=12, w=16, separate_lowercase=True, rc=None):
+        """sdf_pool_minimizers: the winnowed minimizers (the reference's get_minimizers) of ranges of the resident pool --
+        (off, len) pairs with rc as minim_ranges takes it, or a MINIM_RANGE_DTYPE array.  Returns (first, records): a
+        MINIMIZER_DTYPE array (hash, loc, status, range), records[first[i]:first[i + 1]] range i's in ascending loc; loc counts
+        in the reverse complement for a reversed range."""
+        code, first, out, used = self.pool_minimizers_raw(self.minim_ranges(ranges, rc), k, w, separate_lowercase)
+        self._check(code)
+        return first.astype(np.int64), out[:used]
+
+    def pool_minimizers_device(self, d_ranges, n, any_rc, d_first, d_out, cap, k=12, w=16, separate_lowercase=True, stream=None):
+        """The same over device pointers (ints) of ranges, first (n + 1 uint64) and records; on `stream` when one is given
+        (pool_sync() first), else returns the records the ranges have (raises when they exceed cap)."""
+        used = C.c_size_t(0)
+        self._check(self.lib.sdf_pool_minimizers_device(self.ctx, d_ranges, n, int(bool(any_rc)), int(k), int(w),
+                                                        int(bool(separate_lowercase)), d_first, d_out, cap, C.byref(used), stream))
+        return int(used.value)
+
+    def pool_minimizer_index(self, ranges, k=12, w=16, separate_lowercase=True, rc=None):
+        """sdf_pool_minimizer_index: the reference's Index of every range.  Returns (first, sorted, n_groups, threshold):
+        sorted[first[i]:first[i + 1]] are range i's minimizers in ascending (status, hash, loc) order -- a group is a run of equal
+        (status, hash) --, n_groups[i] its groups and threshold[i] the reference's cutoff (MINIM_THRESHOLD_NONE where none)."""
+        code, first, out, used, n_groups, threshold = self.pool_minimizers_raw(self.minim_ranges(ranges, rc), k, w,
+                                                                              separate_lowercase, index=True)
+        self._check(code)
+        return first.astype(np.int64), out[:used], n_groups, threshold
 
     def last_ms(self, which):
         return float(self.lib.sdf_last_ms(self.ctx, which))

@@ -74,7 +74,7 @@ struct CutsLds {  // per wavefront: the chunk's runs
 // Every unit of the alignment that holds a column of [lo, hi), in column order, 64 at a time: f(col, cnt, kind, opens,
 // wa, wb) is called by all lanes -- col: the unit's first column, cnt: its columns (0 for a lane past the last unit),
 // kind: 0 pair, 1 gap in b, 2 gap in a, opens: the unit's first column is a gap and the column before it is none in the
-// same sequence (or there is none), wa / wb: the characters ('-' where the side has none).  Chunks and rounds of 64 units
+// same sequence (or there is none; never for a lane past the last unit, whose sum is carried into the next chunk), wa / wb: the characters ('-' where the side has none).  Chunks and rounds of 64 units
 // that hold no column of the range are passed over without a load.  Returns 1 for a CIGAR that does not fit its
 // sequences (the checks of stats_count_alignment).
 template <bool REV, class F>
@@ -128,7 +128,7 @@ __device__ __forceinline__ int cuts_walk(const sdf_stats_task &T, const char *__
         const int pa = L.sa[j], pb = L.sb[j], o = L.so[j];
         uint64_t wa = pa >= 0 ? stats_fetch8<REV>(a, pa + d, a_len, wide_a, rc_a) : STATS_DASHES;
         uint64_t wb = pb >= 0 ? stats_fetch8<REV>(b, pb + d, b_len, wide_b, rc_b) : STATS_DASHES;
-        f(col, cnt, o & 3, (o & 4) != 0 && d == 0, wa, wb);
+        f(col, cnt, o & 3, valid && (o & 4) != 0 && d == 0, wa, wb);  // (a lane past the last unit opens no gap)
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();

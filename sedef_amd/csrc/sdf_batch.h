@@ -1,5 +1,5 @@
 // What the three host pieces of a batch call share: the planner's records (sdf_plan.hip), the progress of a call on the
-// device (sdf_launch.hip) and the functions sdf_api.hip calls in them.
+// device (sdf_launch.hip) and the functions the batch entry points (sdf_api.hip) call in them.
 #pragma once
 #include <utility>
 

@@ -1,7 +1,7 @@
 // Context, device / pinned buffers and the planning threads shared by the pieces of the C-ABI layer; the kernels they launch
 // are declared in sdf_kernels.h, the sizes they reserve come from extz2_geom.h
 // (sdf_context.hip: a context's lifecycle; sdf_plan.hip: batch cutting and chunk planning; sdf_launch.hip: uploads and
-// launches; sdf_api.hip: entry points).
+// launches; sdf_api.hip and sdf_*_api.hip: entry points, by family; sdf_entry.h: the checks those share).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>

@@ -1,6 +1,6 @@
 // Every kernel of the library that another file launches, declared once, with the records a kernel takes from the host.
 // Each kernel file includes this header, so a definition is checked against its declaration; the launcher and the entry
-// points (sdf_launch.hip, sdf_api.hip) can only name what is declared here.
+// points (sdf_launch.hip, sdf_api.hip, sdf_*_api.hip) can only name what is declared here.
 #pragma once
 #include <hip/hip_runtime.h>
 

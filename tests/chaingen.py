@@ -9,7 +9,7 @@ The two families of test_chain_oracle._chain_cases, each with an explicit number
     thousand anchors;
   * real anchors: host.anchors on mutated copies of 60-120 kb with a tandem repeat at k = 11 (thousands of anchors: the
     diagonal, the repeat's parallel diagonals and chance matches), a slice of m consecutive ones in generation order.
-The launch classes restate sdf_api.hip: sdf_chain_batch and extz2_geom.h: chain_wave_lds_bytes; what the device granted
+The launch classes restate sdf_seed_api.hip: sdf_chain_batch and extz2_geom.h: chain_wave_lds_bytes; what the device granted
 for class 5 comes from the library (sdf_last_chain_classes, word 7), never from here."""
 import numpy as np
 

@@ -1,6 +1,6 @@
 """GPU: every path behind sdf_chain_batch, at its size boundaries.
 
-The entry point routes a pair by its number of anchors m (sdf_api.hip): to one of six LDS classes of chain_wave_kernel
+The entry point routes a pair by its number of anchors m (sdf_seed_api.hip): to one of six LDS classes of chain_wave_kernel
 (one wavefront per pair, everything in LDS; the caps of classes 0..4 are 2..32 KiB, class 5 ends where the device's grant
 of dynamic LDS ends), or to chain_kernel (one thread per pair, scratch in HBM) -- pairs beyond class 5, the whole of class
 5 once a call holds more than 512 such pairs, and every pair under SDF_CHAIN_THREADS=1.  No test guesses the route:

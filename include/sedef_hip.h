@@ -624,6 +624,67 @@ int sdf_pool_minimizer_index(sdf_ctx *ctx, const sdf_minim_range *r, size_t n, i
                              uint64_t *first /* n + 1 */, sdf_minimizer *sorted, size_t cap, size_t *used,
                              uint32_t *n_groups /* n */, uint32_t *threshold /* n */);
 
+/* ---- search seeding: the reference intervals of every query window (search_seeds.hip) -----------------------------------------
+ * The front half of the reference's search() (src/search.cc:395-452) for EVERY query minimizer in one call, with an EMPTY
+ * tree: the exclusions of the SDs already found (pf->second.find(pos)) are out of scope, and with a non-empty tree the
+ * reference's answer differs.  Inputs: q[0, nq), the query range's minimizers in ascending loc as sdf_pool_minimizers writes
+ * them; r_sorted[0, nr), the reference range's records in ascending (status, hash, loc) as sdf_pool_minimizer_index writes them
+ * for ONE range (status 0..2, compared unsigned; `range` is not read); r_threshold, that range's threshold; len_q, the query
+ * sequence's length; limit[0, n_limit), the caller's table of relaxed_jaccard_estimate(query_size) (src/util.cc:85 -- the library
+ * never computes it).  For window i, with qs = q[i].loc:
+ *   1. qs + init_len > len_q: SDF_SEARCH_SHORT, every count 0, no intervals.
+ *   2. members: j = i, i + 1, ... while q[j].loc - qs <= init_len (inclusive); n_members of them.
+ *   3. query_size: the distinct (status, hash) among the members, whatever their status.
+ *   4. a member seeds when uppercase_seeds == 0 or its status is 0.  Its group is the run of r_sorted with its (status, hash);
+ *      absent, or of r_threshold records and more: skipped.  n_gathered: the sizes of the other groups added up, one term per
+ *      seeding member (two members with one key count their group twice), before any filter; 2^31 - 1 when the sum is larger.
+ *      Candidates: the locs of those groups, with same_genome only those >= qs + init_len, as a SET: ascending, distinct;
+ *      n_candidates of them.
+ *   5. query_size >= n_limit: SDF_SEARCH_NOLIMIT, no intervals (the counts stay).  Else L = limit[query_size].
+ *   6. for a = 0 .. n_candidates - L, b = a + L - 1: when c[b] - c[a] <= init_len, x = max(0, c[b] - init_len + 1) and
+ *      y = c[a] + 1; if there is a last interval and x < last.end (strictly) then last.end = max(last.end, y), else (x, y) is
+ *      pushed.
+ *   7. same_genome: start = max(start, qs + init_len), and an interval with start > end is dropped.
+ * out[first[i], first[i + 1]) are window i's intervals, in ascending order.
+ *
+ * SDF_SEARCH_WIDE: n_members > SDF_SEARCH_MAX_MEMBERS or n_gathered > SDF_SEARCH_MAX_GATHER -- both read off the inputs, so the
+ * flag does not depend on who computes.  The device form flags such a window, fills its counts except n_candidates (0) and
+ * writes no interval for it; sdf_search_windows completes it on the host (sdf_search_windows_host's code on the arrays it was
+ * given), into the same first[] / out layout, and keeps the flag: its answer is complete for every input.
+ *
+ * Overflow as for sdf_pool_minimizers: SDF_ERR_CIGAR_OVERFLOW when the windows have more than cap intervals -- *used holds the
+ * need, first[] and windows[] are filled, nothing is written to out; no record is ever written at or behind out[cap].
+ *   SDF_ERR_INVALID      a null pointer with nq > 0 (out may be null with cap == 0; r_sorted with nr == 0), init_len < 1
+ *   SDF_ERR_UNSUPPORTED  limit[s] < 1 for some s >= 1 (the reference indexes candidates[-1] there; the device form reads such
+ *                        an entry as 1 instead of checking), init_len > 2^30, nq > 2^30 - 1, nr or n_limit > 2^31 - 1
+ * Every check precedes the first launch.  nq == 0 is SDF_OK without a launch (*used = 0; the host forms set first[0] = 0, the
+ * device form leaves d_first as it is).  The call reads no
+ * pool; it uses the context's stream and buffers: calls on one context do not overlap. */
+#define SDF_SEARCH_SHORT 0x1
+#define SDF_SEARCH_NOLIMIT 0x2
+#define SDF_SEARCH_WIDE 0x4
+#define SDF_SEARCH_MAX_MEMBERS 1024
+#define SDF_SEARCH_MAX_GATHER 4096
+typedef struct { int32_t query_size, n_members, n_gathered, n_candidates; uint32_t flags; } sdf_search_window; /* 20 bytes */
+typedef struct { int32_t start, end; } sdf_search_interval;
+int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                       uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *limit,
+                       size_t n_limit, uint64_t *first /* nq + 1 */, sdf_search_window *windows /* nq */,
+                       sdf_search_interval *out, size_t cap, size_t *used);
+/* Device form: every array in HBM, nothing checked beyond the scalars, no host wait: the launches are enqueued on `stream` (NULL:
+ * the context's own, synchronised before returning -- then *used, if given, holds d_first[nq] and the call answers
+ * SDF_ERR_CIGAR_OVERFLOW when that exceeds cap).  WIDE windows as said above.  The intervals that lie below d_out[cap] are
+ * written whatever the need, none at or behind it; with a stream of its own the caller compares d_first[nq] with cap itself. */
+int sdf_search_windows_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted,
+                              size_t nr, uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                              const int32_t *d_limit, size_t n_limit, uint64_t *d_first, sdf_search_window *d_windows,
+                              sdf_search_interval *d_out, size_t cap, size_t *used, void *stream);
+/* No context, no GPU: steps 1 to 7 in plain C++, every window (WIDE ones flagged and completed).  Same checks and codes. */
+int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                            uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *limit,
+                            size_t n_limit, uint64_t *first /* nq + 1 */, sdf_search_window *windows /* nq */,
+                            sdf_search_interval *out, size_t cap, size_t *used);
+
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is
  * sharded over the GPUs of a node with no data-path collective; after the DP an RCCL all-gatherv over xGMI gives every GPU

@@ -327,6 +327,9 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(mz_ranges, None) X(mz_first, None) X(mz_out, None) /* sdf_pool_minimizers: the host form's copies */               \
   X(mz_keys, None) X(mz_vals, None) X(mz_groups, None) X(mz_tmp, None) /* sdf_pool_minimizer_index: sort keys (in, out), */ \
   X(mz_sorted, None) X(mz_res, None) /* ... places (in, out), heads / ranks / starts, sort scratch, sorted records, results */ \
+  X(sw_keys, None) X(sw_vals, None) X(sw_tmp, None) /* sdf_search_windows_device: sort keys and places (in, out), sort scratch, */ \
+  X(sw_look, None) X(sw_counts, None) /* ... a SearchLook per query minimizer, intervals per window */                  \
+  X(sw_q, None) X(sw_r, None) X(sw_limit, None) X(sw_first, None) X(sw_win, None) X(sw_out, None) /* sdf_search_windows: the host form's copies */ \
   X(h_pool, BatchCall) X(h_out, BatchCall) X(h_cig, BatchCall) /* device buffers of the host-buffer entry point */    \
   X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \

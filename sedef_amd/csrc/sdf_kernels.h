@@ -174,5 +174,22 @@ __global__ void minim_heads_kernel(const unsigned long long *, const uint32_t *,
 __global__ void minim_starts_kernel(const uint32_t *, const uint32_t *, long long, uint32_t *);
 __global__ void minim_sizes_kernel(const unsigned long long *, const uint32_t *, long long, unsigned long long *);
 __global__ void minim_threshold_kernel(const unsigned long long *, long long, const uint64_t *, int, uint32_t *, uint32_t *);
+// search_seeds.hip
+constexpr int SEARCH_MAX_MEMBERS = SDF_SEARCH_MAX_MEMBERS, SEARCH_MAX_GATHER = SDF_SEARCH_MAX_GATHER;  // a wavefront's LDS: 16-bit offsets, 32-bit positions
+static_assert(SEARCH_MAX_GATHER < 65535 && (SEARCH_MAX_GATHER & (SEARCH_MAX_GATHER - 1)) == 0, "search_seeds.hip: offsets are 16 bits wide");
+struct SearchLook {       // what search_lookup_kernel and search_prev_kernel leave per query minimizer j (16 bytes)
+  uint32_t start, size;   // j's group in r_sorted; size 0: j does not seed, or the group is absent or at / over the threshold
+  int32_t prev;           // the last minimizer before j with j's (status, hash), -1: none
+  int32_t end;            // the members of window j are [j, end)
+};
+static_assert(sizeof(SearchLook) == 16 && sizeof(sdf_search_window) == 20 && sizeof(sdf_search_interval) == 8, "include/sedef_hip.h");
+__global__ void search_keys_kernel(const sdf_minimizer *, int, unsigned long long *, uint32_t *);
+__global__ void search_prev_kernel(const unsigned long long *, const uint32_t *, int, SearchLook *);
+__global__ void search_lookup_kernel(const sdf_minimizer *, int, const sdf_minimizer *, int, uint32_t, int, int, SearchLook *);
+// EMIT false: the windows' records and interval counts; true: the intervals
+template <bool EMIT>
+__global__ void search_window_kernel(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, int, int,
+                                     const int32_t *, int, sdf_search_window *, uint32_t *, const uint64_t *, sdf_search_interval *,
+                                     uint64_t);
 
 }  // namespace sdf

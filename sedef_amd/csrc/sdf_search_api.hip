@@ -1,0 +1,277 @@
+// The C ABI: search seeding, the reference intervals of every query window (search_seeds.hip; include/sedef_hip.h states the
+// seven steps).  sdf_search_windows_host is those steps in plain C++; the host form completes with it what the kernels leave.
+#include <hip/hip_runtime.h>
+
+#include <hipcub/hipcub.hpp>
+
+#include "sdf_entry.h"
+
+using namespace sdf;
+
+namespace {
+struct SearchArgs {
+  const sdf_minimizer *q;
+  size_t nq;
+  int64_t len_q;
+  const sdf_minimizer *r;
+  size_t nr;
+  uint32_t r_threshold;
+  int32_t init_len;
+  bool same_genome, uppercase_seeds;
+  const int32_t *limit;
+  size_t n_limit;
+};
+struct SearchScratch {
+  std::vector<uint64_t> keys;
+  std::vector<int32_t> cand;
+};
+
+inline uint64_t search_host_key(const sdf_minimizer &m) { return (uint64_t)(uint32_t)m.status << 32 | m.hash; }
+
+// what every form checks of its scalars; *why: the refusal's text
+int search_scalars(size_t nq, size_t nr, int32_t init_len, size_t n_limit, const char **why) {
+  if (init_len < 1) return *why = "search windows: init_len < 1", SDF_ERR_INVALID;
+  if (init_len > (1 << 30)) return *why = "search windows implement init_len up to 2^30", SDF_ERR_UNSUPPORTED;
+  if (nq > 0x3fffffffu) return *why = "search windows: more than 2^30 - 1 query minimizers in one call", SDF_ERR_UNSUPPORTED;
+  if (nr > 0x7fffffffu || n_limit > 0x7fffffffu)
+    return *why = "search windows: more than 2^31 - 1 reference records or limit entries in one call", SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+// ... and the host forms of their arrays
+int search_arrays(const SearchArgs &A, const uint64_t *first, const sdf_search_window *windows, const void *out, size_t cap,
+                  const size_t *used, const char **why) {
+  if (!A.q || !first || !windows || !used || (cap && !out) || (A.nr && !A.r) || (A.n_limit && !A.limit))
+    return *why = "search windows: invalid arguments", SDF_ERR_INVALID;
+  if (int rc = search_scalars(A.nq, A.nr, A.init_len, A.n_limit, why)) return rc;
+  for (size_t s = 1; s < A.n_limit; s++)
+    if (A.limit[s] < 1) return *why = "search windows: a limit below 1 (the reference reads candidates[-1] there)", SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+
+// Window i as include/sedef_hip.h states it, step by step: its record, its intervals appended to T.
+void search_one_window(const SearchArgs &A, size_t i, sdf_search_window &W, std::vector<sdf_search_interval> &T, SearchScratch &S) {
+  W.query_size = W.n_members = W.n_gathered = W.n_candidates = 0, W.flags = 0;
+  const int64_t qs = A.q[i].loc;
+  if (qs + A.init_len > A.len_q) {  // 1
+    W.flags = SDF_SEARCH_SHORT;
+    return;
+  }
+  S.keys.clear();
+  S.cand.clear();
+  int64_t gathered = 0;
+  size_t j = i;
+  const auto key_less = [](const sdf_minimizer &m, uint64_t k) { return search_host_key(m) < k; };
+  const auto less_key = [](uint64_t k, const sdf_minimizer &m) { return k < search_host_key(m); };
+  for (; j < A.nq && (int64_t)A.q[j].loc - qs <= A.init_len; j++) {  // 2
+    const sdf_minimizer &m = A.q[j];
+    const uint64_t key = search_host_key(m);
+    S.keys.push_back(key);
+    if (A.uppercase_seeds && m.status != 0) continue;  // 4
+    const sdf_minimizer *g0 = std::lower_bound(A.r, A.r + A.nr, key, key_less), *g1 = std::upper_bound(g0, A.r + A.nr, key, less_key);
+    if (g0 == g1 || (uint64_t)(g1 - g0) >= A.r_threshold) continue;
+    gathered += g1 - g0;
+    for (const sdf_minimizer *p = g0; p < g1; p++)
+      if (!A.same_genome || (int64_t)p->loc >= qs + A.init_len) S.cand.push_back(p->loc);
+  }
+  W.n_members = (int32_t)(j - i);
+  W.n_gathered = gathered > 0x7fffffff ? 0x7fffffff : (int32_t)gathered;
+  if (W.n_members > SDF_SEARCH_MAX_MEMBERS || gathered > SDF_SEARCH_MAX_GATHER) W.flags |= SDF_SEARCH_WIDE;
+  std::sort(S.keys.begin(), S.keys.end());
+  W.query_size = (int32_t)(std::unique(S.keys.begin(), S.keys.end()) - S.keys.begin());  // 3
+  std::sort(S.cand.begin(), S.cand.end());
+  S.cand.erase(std::unique(S.cand.begin(), S.cand.end()), S.cand.end());
+  W.n_candidates = (int32_t)S.cand.size();
+  if ((size_t)W.query_size >= A.n_limit) {  // 5
+    W.flags |= SDF_SEARCH_NOLIMIT;
+    return;
+  }
+  const int64_t L = A.limit[W.query_size], n = (int64_t)S.cand.size();
+  const size_t t0 = T.size();
+  for (int64_t a = 0; a <= n - L; a++) {  // 6
+    const int64_t b = a + L - 1, ca = S.cand[a], cb = S.cand[b];
+    if (cb - ca > A.init_len) continue;
+    const int64_t x = std::max<int64_t>(0, cb - A.init_len + 1), y = ca + 1;
+    if (T.size() > t0 && x < T.back().end) T.back().end = (int32_t)std::max<int64_t>(T.back().end, y);
+    else T.push_back({(int32_t)x, (int32_t)y});
+  }
+  if (A.same_genome) {  // 7
+    size_t keep = t0;
+    for (size_t t = t0; t < T.size(); t++) {
+      sdf_search_interval I = T[t];
+      I.start = (int32_t)std::max<int64_t>(I.start, qs + A.init_len);
+      if (I.start <= I.end) T[keep++] = I;
+    }
+    T.resize(keep);
+  }
+}
+}  // namespace
+
+extern "C" int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                                       uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                       const int32_t *limit, size_t n_limit, uint64_t *first, sdf_search_window *windows,
+                                       sdf_search_interval *out, size_t cap, size_t *used) {
+  if (nq == 0) {
+    if (used) *used = 0;
+    if (first) first[0] = 0;
+    return SDF_OK;
+  }
+  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
+  const char *why = nullptr;
+  if (int rc = search_arrays(A, first, windows, out, cap, used, &why)) return rc;
+  // every window once; the intervals are kept here while they still fit below cap and reach `out` only when all of them do
+  SearchScratch S;
+  std::vector<sdf_search_interval> T, all;
+  uint64_t at = 0;
+  for (size_t i = 0; i < nq; i++) {
+    first[i] = at;
+    T.clear();
+    search_one_window(A, i, windows[i], T, S);
+    at += T.size();
+    if (at <= cap) all.insert(all.end(), T.begin(), T.end());
+  }
+  first[nq] = at;
+  *used = (size_t)at;
+  if (at > cap) return SDF_ERR_CIGAR_OVERFLOW;
+  if (at) memcpy(out, all.data(), (size_t)at * sizeof(sdf_search_interval));
+  return SDF_OK;
+}
+
+// The launches in front of the intervals, on `st`: keys, their sort, prev, lookup, the windows' records and counts, d_first.
+static int search_count(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r, size_t nr,
+                        uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *d_limit, size_t n_limit,
+                        uint64_t *d_first, sdf_search_window *d_windows, hipStream_t st) {
+  const int n = (int)nq;
+  SDF_HIP(ctx->sw_keys.reserve(2 * nq * 8));
+  SDF_HIP(ctx->sw_vals.reserve(2 * nq * 4));
+  SDF_HIP(ctx->sw_look.reserve(nq * sizeof(SearchLook)));
+  SDF_HIP(ctx->sw_counts.reserve(nq * 4));
+  unsigned long long *d_keys = (unsigned long long *)ctx->sw_keys.p, *d_keys2 = d_keys + nq;
+  uint32_t *d_vals = (uint32_t *)ctx->sw_vals.p, *d_vals2 = d_vals + nq;
+  SearchLook *d_look = (SearchLook *)ctx->sw_look.p;
+  uint32_t *d_counts = (uint32_t *)ctx->sw_counts.p;
+  size_t t_pairs = 0;
+  SDF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t_pairs, d_keys, d_keys2, d_vals, d_vals2, n, 0, 64, st));
+  SDF_HIP(ctx->sw_tmp.reserve(t_pairs + 256));
+  const dim3 grid((unsigned)((nq + 255) / 256)), block(256);
+  hipLaunchKernelGGL(search_keys_kernel, grid, block, 0, st, d_q, n, d_keys, d_vals);
+  SDF_HIP(hipcub::DeviceRadixSort::SortPairs(ctx->sw_tmp.p, t_pairs, d_keys, d_keys2, d_vals, d_vals2, n, 0, 64, st));
+  hipLaunchKernelGGL(search_prev_kernel, grid, block, 0, st, d_keys2, d_vals2, n, d_look);
+  hipLaunchKernelGGL(search_lookup_kernel, grid, block, 0, st, d_q, n, d_r, (int)nr, r_threshold, (int)init_len, uppercase_seeds, d_look);
+  hipLaunchKernelGGL(search_window_kernel<false>, dim3((unsigned)nq), dim3(64), 0, st, d_q, n, (long long)len_q, d_r, d_look, (int)init_len,
+                     same_genome, d_limit, (int)n_limit, d_windows, d_counts, (const uint64_t *)nullptr, (sdf_search_interval *)nullptr,
+                     (uint64_t)0);
+  hipLaunchKernelGGL(stats_cuts_scan_kernel, dim3(1), dim3(1024), 0, st, d_counts, n, d_first);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += 5;
+  return SDF_OK;
+}
+// the intervals (after search_count on the same stream)
+static int search_emit(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r, int32_t init_len,
+                       int same_genome, const int32_t *d_limit, size_t n_limit, const uint64_t *d_first, sdf_search_interval *d_out,
+                       size_t cap, hipStream_t st) {
+  hipLaunchKernelGGL(search_window_kernel<true>, dim3((unsigned)nq), dim3(64), 0, st, d_q, (int)nq, (long long)len_q, d_r,
+                     (const SearchLook *)ctx->sw_look.p, (int)init_len, same_genome, d_limit, (int)n_limit, (sdf_search_window *)nullptr,
+                     (uint32_t *)nullptr, d_first, d_out, (uint64_t)cap);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += 1;
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_windows_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted,
+                                         size_t nr, uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                         const int32_t *d_limit, size_t n_limit, uint64_t *d_first, sdf_search_window *d_windows,
+                                         sdf_search_interval *d_out, size_t cap, size_t *used, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0) {
+    if (used) *used = 0;
+    return SDF_OK;
+  }
+  if (!d_q || !d_first || !d_windows || (cap && !d_out) || (nr && !d_r_sorted) || (n_limit && !d_limit))
+    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_windows_device: invalid arguments");
+  const char *why = nullptr;
+  if (int rc = search_scalars(nq, nr, init_len, n_limit, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = search_count(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, d_limit,
+                            n_limit, d_first, d_windows, st))
+    return rc;
+  if (int rc = search_emit(ctx, d_q, nq, len_q, d_r_sorted, init_len, same_genome != 0, d_limit, n_limit, d_first, d_out, cap, st)) return rc;
+  if (stream) return SDF_OK;
+  return counted_need(ctx, d_first, nq, nullptr, st, cap, used, "the windows have ", " intervals, more than cap");
+}
+
+extern "C" int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                                  uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *limit,
+                                  size_t n_limit, uint64_t *first, sdf_search_window *windows, sdf_search_interval *out, size_t cap,
+                                  size_t *used) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0) {
+    if (used) *used = 0;
+    if (first) first[0] = 0;
+    return SDF_OK;
+  }
+  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
+  const char *why = nullptr;
+  if (int rc = search_arrays(A, first, windows, out, cap, used, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  SDF_HIP(ctx->sw_q.reserve(nq * sizeof(sdf_minimizer)));
+  SDF_HIP(ctx->sw_r.reserve(nr * sizeof(sdf_minimizer)));
+  SDF_HIP(ctx->sw_limit.reserve(n_limit * 4));
+  SDF_HIP(ctx->sw_first.reserve((nq + 1) * 8));
+  SDF_HIP(ctx->sw_win.reserve(nq * sizeof(sdf_search_window)));
+  const sdf_minimizer *d_q = (const sdf_minimizer *)ctx->sw_q.p, *d_r = (const sdf_minimizer *)ctx->sw_r.p;
+  const int32_t *d_limit = (const int32_t *)ctx->sw_limit.p;
+  uint64_t *d_first = (uint64_t *)ctx->sw_first.p;
+  SDF_HIP(hipMemcpyAsync(ctx->sw_q.p, q, nq * sizeof(sdf_minimizer), hipMemcpyHostToDevice, st));
+  if (nr) SDF_HIP(hipMemcpyAsync(ctx->sw_r.p, r_sorted, nr * sizeof(sdf_minimizer), hipMemcpyHostToDevice, st));
+  if (n_limit) SDF_HIP(hipMemcpyAsync(ctx->sw_limit.p, limit, n_limit * 4, hipMemcpyHostToDevice, st));
+  if (int rc = search_count(ctx, d_q, nq, len_q, d_r, nr, r_threshold, init_len, A.same_genome, A.uppercase_seeds, d_limit, n_limit, d_first,
+                            (sdf_search_window *)ctx->sw_win.p, st))
+    return rc;
+  SDF_HIP(hipMemcpyAsync(windows, ctx->sw_win.p, nq * sizeof(sdf_search_window), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipMemcpyAsync(first, d_first, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  const uint64_t dev_need = first[nq];
+  // the WIDE windows, on the host; their intervals in window order, wide_first[t] those of the wide windows before the t-th
+  std::vector<size_t> wide;
+  std::vector<uint64_t> wide_first(1, 0);
+  std::vector<sdf_search_interval> T;
+  SearchScratch S;
+  for (size_t i = 0; i < nq; i++) {
+    if (!(windows[i].flags & SDF_SEARCH_WIDE)) continue;
+    search_one_window(A, i, windows[i], T, S);
+    wide.push_back(i);
+    wide_first.push_back(T.size());
+  }
+  const uint64_t need = dev_need + T.size();
+  *used = (size_t)need;
+  if (!wide.empty()) {  // first[] with the wide windows' intervals in it
+    size_t t = 0;
+    for (size_t i = 0; i <= nq; i++) {
+      while (t < wide.size() && wide[t] < i) ++t;
+      first[i] += wide_first[t];
+    }
+  }
+  if (need > cap) return refuse(ctx, SDF_ERR_CIGAR_OVERFLOW, "the windows have " + std::to_string(need) + " intervals, more than cap");
+  if (dev_need) {
+    SDF_HIP(ctx->sw_out.reserve((size_t)dev_need * sizeof(sdf_search_interval)));
+    if (int rc = search_emit(ctx, d_q, nq, len_q, d_r, init_len, A.same_genome, d_limit, n_limit, d_first, (sdf_search_interval *)ctx->sw_out.p,
+                             (size_t)dev_need, st))
+      return rc;
+    SDF_HIP(hipMemcpyAsync(out, ctx->sw_out.p, (size_t)dev_need * sizeof(sdf_search_interval), hipMemcpyDeviceToHost, st));
+    SDF_HIP(hipStreamSynchronize(st));
+  }
+  // make room for the wide windows' intervals: from the last wide window down, what lies behind it moves up by what precedes it
+  uint64_t dev_end = dev_need;  // the device's records [.., dev_end) have not moved yet
+  for (size_t t = wide.size(); t-- > 0;) {
+    const size_t i = wide[t];
+    const uint64_t dev_at = first[i] - wide_first[t];  // where the device's records of the windows behind i begin
+    memmove(out + first[i + 1], out + dev_at, (size_t)(dev_end - dev_at) * sizeof(sdf_search_interval));
+    memcpy(out + first[i], T.data() + wide_first[t], (size_t)(wide_first[t + 1] - wide_first[t]) * sizeof(sdf_search_interval));
+    dev_end = dev_at;
+  }
+  return SDF_OK;
+}

@@ -53,6 +53,13 @@ MINIM_RANGE_DTYPE = np.dtype([("off", "<i8"), ("len", "<i4"), ("flags", "<i4")])
 MINIMIZER_DTYPE = np.dtype([("hash", "<u4"), ("loc", "<i4"), ("status", "<i4"), ("range", "<i4")])
 MINIM_RC, MINIM_MAX_W, MINIM_THRESHOLD_NONE = 0x1, 1000, 1 << 31
 assert MINIM_RANGE_DTYPE.itemsize == 16 and MINIMIZER_DTYPE.itemsize == 16
+# include/sedef_hip.h: sdf_search_window / sdf_search_interval (search_windows; SEARCH_* in `flags`)
+SEARCH_WINDOW_DTYPE = np.dtype([("query_size", "<i4"), ("n_members", "<i4"), ("n_gathered", "<i4"), ("n_candidates", "<i4"),
+                                ("flags", "<u4")])
+SEARCH_INTERVAL_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4")])
+SEARCH_SHORT, SEARCH_NOLIMIT, SEARCH_WIDE = 0x1, 0x2, 0x4
+SEARCH_MAX_MEMBERS, SEARCH_MAX_GATHER = 1024, 4096
+assert SEARCH_WINDOW_DTYPE.itemsize == 20 and SEARCH_INTERVAL_DTYPE.itemsize == 8
 # strand bits of a stats task on the resident pool (include/sedef_hip.h: SDF_STATS_A_RC / SDF_STATS_B_RC; in `reserved`,
 # stats_columns_pairs only)
 STATS_A_RC, STATS_B_RC = 0x1, 0x2
@@ -185,6 +192,14 @@ def load_library():
     L.sdf_pool_minimizer_index.restype = C.c_int
     L.sdf_pool_minimizer_index.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]
+    _search = [C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_int, C.c_int, C.c_void_p,
+               C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sdf_search_windows.restype = C.c_int
+    L.sdf_search_windows.argtypes = [C.c_void_p] + _search
+    L.sdf_search_windows_device.restype = C.c_int
+    L.sdf_search_windows_device.argtypes = [C.c_void_p] + _search + [C.c_void_p]
+    L.sdf_search_windows_host.restype = C.c_int
+    L.sdf_search_windows_host.argtypes = _search
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -824,6 +839,43 @@ class Extz2Engine:
         self._check(code)
         return first.astype(np.int64), out[:used], n_groups, threshold
 
+    def search_windows_raw(self, q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, cap=None,
+                           out=None):
+        """sdf_search_windows as it is.  q: the query's minimizers in loc order, r_sorted: the reference's in index order
+        (MINIMIZER_DTYPE arrays); limit: the table of relaxed_jaccard_estimate by query_size; cap: capacity in intervals
+        (default: len(out), or what the windows need, found by a first call); out: a SEARCH_INTERVAL_DTYPE array to fill.
+        Returns (rc, first, windows, intervals, used)."""
+        return search_windows_call(self.lib.sdf_search_windows, (self.ctx,), q, r_sorted, r_threshold, len_q, init_len, same_genome,
+                                   uppercase_seeds, limit, cap, out)
+
+    def search_windows_device(self, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome, uppercase_seeds, d_limit,
+                              n_limit, d_first, d_windows, d_out, cap, stream=None):
+        """The same over device pointers (ints) of the records, the table, first (nq + 1 uint64), windows and intervals; on
+        `stream` when one is given, else returns the intervals the windows have (raises when they exceed cap).  A WIDE window
+        is flagged and has no interval."""
+        used = C.c_size_t(0)
+        self._check(self.lib.sdf_search_windows_device(self.ctx, d_q, nq, int(len_q), d_r_sorted, nr, int(r_threshold), int(init_len),
+                                                       int(bool(same_genome)), int(bool(uppercase_seeds)), d_limit, n_limit, d_first,
+                                                       d_windows, d_out, cap, C.byref(used), stream))
+        return int(used.value)
+
+    def search_windows(self, q_range, r_range, k=12, w=16, separate_lowercase=True, init_len=700, same_genome=False,
+                       uppercase_seeds=True, limit=(), r_threshold=None):
+        """The reference intervals of every query window (the front half of the reference's search(), empty tree): q_range and
+        r_range are (off, len) or (off, len, rc) ranges of the resident pool; the query's minimizers come from pool_minimizers,
+        the reference's index and threshold from pool_minimizer_index (r_threshold: another threshold).  Returns (first,
+        windows, intervals): SEARCH_WINDOW_DTYPE and SEARCH_INTERVAL_DTYPE arrays, intervals[first[i]:first[i + 1]] those of
+        query minimizer i."""
+        def one(rng):
+            return self.minim_ranges([rng[:2]], rc=bool(rng[2]) if len(rng) > 2 else None)
+        _, q = self.pool_minimizers(one(q_range), k, w, separate_lowercase)
+        _, r_sorted, _, threshold = self.pool_minimizer_index(one(r_range), k, w, separate_lowercase)
+        threshold = int(threshold[0]) if r_threshold is None else int(r_threshold)
+        code, first, windows, out, used = self.search_windows_raw(q, r_sorted, threshold, int(q_range[1]), init_len, same_genome,
+                                                                  uppercase_seeds, limit)
+        self._check(code)
+        return first.astype(np.int64), windows, out[:used]
+
     def last_ms(self, which):
         return float(self.lib.sdf_last_ms(self.ctx, which))
 
@@ -855,6 +907,40 @@ class Extz2Engine:
     def last_reran(self):
         """Tasks of the last batch that a stripe kernel gave up and the call ran again on another kernel."""
         return int(self.lib.sdf_last_reran(self.ctx))
+
+
+def search_windows_call(fn, head, q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, cap=None, out=None):
+    """sdf_search_windows (head: its context) or sdf_search_windows_host (head: nothing) on numpy arrays; the overflow protocol
+    as Extz2Engine.pool_minimizers_raw has it.  Returns (rc, first, windows, intervals, used)."""
+    q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
+    r_sorted = np.ascontiguousarray(r_sorted, dtype=MINIMIZER_DTYPE)
+    limit = np.ascontiguousarray(limit, dtype=np.int32)
+    first, windows = np.zeros(len(q) + 1, np.uint64), np.zeros(len(q), SEARCH_WINDOW_DTYPE)
+    used = C.c_size_t(0)
+
+    def ptr(a):
+        return a.ctypes.data if len(a) else None
+
+    def call(buf, c):
+        return fn(*head, ptr(q), len(q), int(len_q), ptr(r_sorted), len(r_sorted), int(r_threshold), int(init_len),
+                  int(bool(same_genome)), int(bool(uppercase_seeds)), ptr(limit), len(limit), first.ctypes.data, ptr(windows),
+                  ptr(buf), c, C.byref(used))
+    if out is None:
+        if cap is None:
+            rc = call(np.zeros(0, SEARCH_INTERVAL_DTYPE), 0)
+            if rc not in (0, -5):  # (SDF_ERR_CIGAR_OVERFLOW: *used holds the need)
+                return rc, first, windows, np.zeros(0, SEARCH_INTERVAL_DTYPE), int(used.value)
+            cap = int(used.value)
+        out = np.zeros(cap, SEARCH_INTERVAL_DTYPE)
+    assert out.dtype == SEARCH_INTERVAL_DTYPE and out.flags.c_contiguous
+    rc = call(out, len(out) if cap is None else cap)
+    return rc, first, windows, out, int(used.value)
+
+
+def search_windows_host(q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, cap=None, out=None):
+    """sdf_search_windows_host: search_windows_raw without a context or a GPU, in plain C++ on one thread."""
+    return search_windows_call(load_library().sdf_search_windows_host, (), q, r_sorted, r_threshold, len_q, init_len, same_genome,
+                               uppercase_seeds, limit, cap, out)
 
 
 _default_engine = None

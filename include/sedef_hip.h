@@ -685,6 +685,69 @@ int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, co
                             size_t n_limit, uint64_t *first /* nq + 1 */, sdf_search_window *windows /* nq */,
                             sdf_search_interval *out, size_t cap, size_t *used);
 
+/* ---- search roll: every reference interval rolled to its best initial match (search_roll.hip) ----------------------------------
+ * The first loop of the reference's search_in_reference_interval (src/search.cc:274-314, "Roll until we find best inital
+ * match") for EVERY interval of sdf_search_windows in one call.  It reads no tree; is_overlap, filter, extend and the tree
+ * update that follow it in the reference are not built.  Inputs: q[0, nq), windows[0, nq), first[0, nq + 1] and
+ * intervals[0, first[nq]) as sdf_search_windows takes and writes them; r[0, nr), the reference range's minimizers in ASCENDING
+ * LOC (sdf_pool_minimizers' list, not the sorted index); len_r, the reference sequence's length; init_len; limit[0, n_limit),
+ * the same table.
+ *
+ * Interval t belongs to window i, first[i] <= t < first[i + 1]; its members are q[i .. i + windows[i].n_members) and
+ * L = limit[windows[i].query_size].  A key is (status, hash), compared as status << 32 | hash, unsigned.  The state is the
+ * reference's SlidingMap as it behaves, not a clean pair of sets: bits[key] in {0, 1, 2, 3} (1: query, 2: reference; a key is
+ * STORED while bits != 0), a boundary key B and a counter I.  At the start bits = 1 for every distinct member key, whatever
+ * its status, B is the largest member key and I = 0.
+ *   add(record)     nothing for status 2.  Else, k its key: bits[k] & 2: nothing.  bits[k] == 1: bits[k] = 3, and I += 1 when
+ *                   k < B -- strictly: an add that lands on B itself is never counted (quirk 1).  bits[k] == 0: bits[k] = 2,
+ *                   and when k < B: I -= (bits[B] == 3), then B becomes the largest stored key below B (that may be k).
+ *   remove(record)  nothing for status 2, or when bits[k] & 2 == 0 (the key came twice and an earlier remove cleared the bit:
+ *                   two adds set one bit and one remove clears it -- quirk 2, the count depends on the path).  Else, when
+ *                   k <= B: I -= (bits[k] == 3), and when bits[k] == 2, B becomes the smallest stored key above B and
+ *                   I += (bits[B] == 3).  Then bits[k] &= ~2.
+ *   J = I >= L ? I : I - L.  I may go negative; J is defined all the same.
+ *   walk   1. s = start, e = min(start + init_len, len_r).
+ *          2. ws = the first index with r[ws].loc >= s (nr: none); we = ws.
+ *          3. while we < nr and r[we].loc < e: add(r[we++]).
+ *          4. best = (s, e, ws, we, J).
+ *          5. while s < end and e < len_r:  if ws < nr and r[ws].loc <= s: remove(r[ws++]);  if we < nr and r[we].loc == e:
+ *             add(r[we++]);  if J > best.J (strictly): best = (s, e, ws, we, J);  s++, e++.
+ * out[t] = best as {ref_start, ref_end, winnow_start, winnow_end, jaccard, flags}.
+ *
+ * The device keeps a key in 32 bits, status << 30 | hash: hash < 2^30 is the contract (k <= 15, as sdf_pool_minimizers writes
+ * them), and status is 0, 1 or 2.  The host form compares whole keys.
+ *
+ * SDF_ROLL_WIDE: windows[i].n_members > SDF_SEARCH_MAX_MEMBERS, or more than SDF_ROLL_MAX_SPAN records of r have
+ * start <= loc <= end + init_len -- both read off the inputs, so the flag does not depend on who computes.  The device form
+ * flags such an interval and writes the rest of its record as zero; sdf_search_roll completes it on the host
+ * (sdf_search_roll_host's code) and keeps the flag.  SDF_ROLL_BADWINDOW (device form only, which checks no array): the
+ * window's query_size is outside the table or its n_members outside 1 .. nq - i; the rest of the record is zero.
+ *   SDF_ERR_INVALID      a null array with nq > 0 (intervals and out may be null when first[nq] == 0), init_len < 1, len_r < 0,
+ *                        nr == 0 with any interval; host forms: first[] not ascending from 0, an interval with start > end or
+ *                        start < 0, and on a window that has intervals query_size outside [0, n_limit) or n_members outside
+ *                        1 .. nq - i
+ *   SDF_ERR_UNSUPPORTED  init_len > 2^30, nq > 2^30 - 1, nr, n_limit, len_r or the number of intervals > 2^31 - 1
+ * Every check precedes the first launch.  nq == 0 or no interval is SDF_OK without a launch. */
+#define SDF_ROLL_WIDE 0x1
+#define SDF_ROLL_BADWINDOW 0x2
+#define SDF_ROLL_MAX_SPAN 3072
+typedef struct { int32_t ref_start, ref_end, winnow_start, winnow_end, jaccard; uint32_t flags; } sdf_search_roll_rec; /* 24 bytes */
+int sdf_search_roll(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                    const sdf_search_interval *intervals, const sdf_minimizer *r, size_t nr, int64_t len_r, int32_t init_len,
+                    const int32_t *limit, size_t n_limit, sdf_search_roll_rec *out /* first[nq] */);
+/* Device form: every array in HBM, nothing checked beyond the scalars, no host wait, so that it follows
+ * sdf_search_windows_device on one stream: n_max wavefronts are enqueued on `stream` (NULL: the context's own, synchronised
+ * before returning), those at or beyond d_first[nq] leave at once.  d_out has n_max records; nothing is written at or behind
+ * d_out[n_max], and an interval at or behind n_max has no record.  n_max == 0 is SDF_OK without a launch. */
+int sdf_search_roll_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                           const uint64_t *d_first, const sdf_search_interval *d_intervals, size_t n_max, const sdf_minimizer *d_r,
+                           size_t nr, int64_t len_r, int32_t init_len, const int32_t *d_limit, size_t n_limit,
+                           sdf_search_roll_rec *d_out, void *stream);
+/* No context, no GPU: the same in plain C++, every interval (WIDE ones flagged and completed).  Same checks and codes. */
+int sdf_search_roll_host(const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                         const sdf_search_interval *intervals, const sdf_minimizer *r, size_t nr, int64_t len_r, int32_t init_len,
+                         const int32_t *limit, size_t n_limit, sdf_search_roll_rec *out /* first[nq] */);
+
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is
  * sharded over the GPUs of a node with no data-path collective; after the DP an RCCL all-gatherv over xGMI gives every GPU

@@ -191,5 +191,12 @@ template <bool EMIT>
 __global__ void search_window_kernel(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, int, int,
                                      const int32_t *, int, sdf_search_window *, uint32_t *, const uint64_t *, sdf_search_interval *,
                                      uint64_t);
+// search_roll.hip
+constexpr int ROLL_MAX_SPAN = SDF_ROLL_MAX_SPAN, ROLL_MAX_KEYS = SEARCH_MAX_MEMBERS + ROLL_MAX_SPAN;  // a wavefront's LDS: 32-bit keys, 16-bit slots
+static_assert(ROLL_MAX_KEYS < 65535 && sizeof(sdf_search_roll_rec) == 24, "search_roll.hip: slots are 16 bits wide; include/sedef_hip.h");
+// WALK false (profiles/search_roll.py): the set-up alone, and a record that is not the interval's
+template <bool WALK>
+__global__ void search_roll_kernel(const sdf_minimizer *, int, const sdf_search_window *, const uint64_t *, const sdf_search_interval *,
+                                   const sdf_minimizer *, int, long long, int, const int32_t *, int, sdf_search_roll_rec *);
 
 }  // namespace sdf

@@ -1,8 +1,11 @@
 // The C ABI: search seeding, the reference intervals of every query window (search_seeds.hip; include/sedef_hip.h states the
-// seven steps).  sdf_search_windows_host is those steps in plain C++; the host form completes with it what the kernels leave.
+// seven steps), and the roll of every interval to its best initial match (search_roll.hip; the header states its rules).
+// sdf_search_windows_host and sdf_search_roll_host are those in plain C++; the host forms complete with them what the kernels leave.
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
+
+#include <map>
 
 #include "sdf_entry.h"
 
@@ -273,5 +276,227 @@ extern "C" int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t n
     memcpy(out + first[i], T.data() + wide_first[t], (size_t)(wide_first[t + 1] - wide_first[t]) * sizeof(sdf_search_interval));
     dev_end = dev_at;
   }
+  return SDF_OK;
+}
+
+// ---- the roll ----
+
+namespace {
+struct RollArgs {
+  const sdf_minimizer *q;
+  size_t nq;
+  const sdf_search_window *windows;
+  const uint64_t *first;
+  const sdf_search_interval *intervals;
+  const sdf_minimizer *r;
+  size_t nr;
+  int64_t len_r;
+  int32_t init_len;
+  const int32_t *limit;
+  size_t n_limit;
+};
+
+// what every form checks of its scalars (n: the intervals, or the wavefronts of the device form)
+int roll_scalars(size_t nq, size_t n, size_t nr, int64_t len_r, int32_t init_len, size_t n_limit, const char **why) {
+  if (init_len < 1) return *why = "search roll: init_len < 1", SDF_ERR_INVALID;
+  if (len_r < 0) return *why = "search roll: len_r < 0", SDF_ERR_INVALID;
+  if (init_len > (1 << 30)) return *why = "search roll implements init_len up to 2^30", SDF_ERR_UNSUPPORTED;
+  if (nq > 0x3fffffffu) return *why = "search roll: more than 2^30 - 1 query minimizers in one call", SDF_ERR_UNSUPPORTED;
+  if (nr > 0x7fffffffu || n_limit > 0x7fffffffu || n > 0x7fffffffu || len_r > 0x7fffffff)
+    return *why = "search roll: more than 2^31 - 1 reference records, limit entries, intervals or bases in one call", SDF_ERR_UNSUPPORTED;
+  if (n > 0 && nr == 0) return *why = "search roll: intervals without a reference record", SDF_ERR_INVALID;
+  return SDF_OK;
+}
+// ... and the host forms of their arrays
+int roll_arrays(const RollArgs &A, const void *out, const char **why) {
+  if (!A.q || !A.windows || !A.first) return *why = "search roll: invalid arguments", SDF_ERR_INVALID;
+  if (A.first[0] != 0) return *why = "search roll: first[0] != 0", SDF_ERR_INVALID;
+  for (size_t i = 0; i < A.nq; i++)
+    if (A.first[i + 1] < A.first[i]) return *why = "search roll: first[] does not ascend", SDF_ERR_INVALID;
+  const uint64_t n = A.first[A.nq];
+  if (n > 0x7fffffffu) return roll_scalars(A.nq, (size_t)0x80000000u, A.nr, A.len_r, A.init_len, A.n_limit, why);
+  if (int rc = roll_scalars(A.nq, (size_t)n, A.nr, A.len_r, A.init_len, A.n_limit, why)) return rc;
+  if (n && (!A.intervals || !out || !A.r || !A.limit)) return *why = "search roll: invalid arguments", SDF_ERR_INVALID;
+  for (size_t i = 0; i < A.nq; i++) {
+    if (A.first[i + 1] == A.first[i]) continue;
+    const sdf_search_window &W = A.windows[i];
+    if (W.query_size < 0 || (size_t)W.query_size >= A.n_limit)
+      return *why = "search roll: a window with intervals has a query_size outside the limit table", SDF_ERR_INVALID;
+    if (W.n_members < 1 || (size_t)W.n_members > A.nq - i)
+      return *why = "search roll: a window with intervals has n_members outside 1 .. nq - i", SDF_ERR_INVALID;
+    for (uint64_t t = A.first[i]; t < A.first[i + 1]; t++)
+      if (A.intervals[t].start < 0 || A.intervals[t].start > A.intervals[t].end)
+        return *why = "search roll: an interval with start < 0 or start > end", SDF_ERR_INVALID;
+  }
+  return SDF_OK;
+}
+
+// Interval T of window i as include/sedef_hip.h states it: a map in place of the reference's, the walk from event to event.
+void roll_one(const RollArgs &A, size_t i, const sdf_search_interval &T, sdf_search_roll_rec &R, std::map<uint64_t, uint8_t> &M) {
+  const sdf_search_window &W = A.windows[i];
+  const auto loc_less = [](const sdf_minimizer &m, int64_t loc) { return (int64_t)m.loc < loc; };
+  const auto less_loc = [](int64_t loc, const sdf_minimizer &m) { return loc < (int64_t)m.loc; };
+  const sdf_minimizer *r = A.r, *r_end = A.r + A.nr;
+  const size_t span0 = (size_t)(std::lower_bound(r, r_end, (int64_t)T.start, loc_less) - r);
+  const size_t span1 = (size_t)(std::upper_bound(r + span0, r_end, (int64_t)T.end + A.init_len, less_loc) - r);
+  R.flags = W.n_members > SDF_SEARCH_MAX_MEMBERS || span1 - span0 > SDF_ROLL_MAX_SPAN ? SDF_ROLL_WIDE : 0;
+  M.clear();
+  for (int32_t j = 0; j < W.n_members; j++) M[search_host_key(A.q[i + j])] = 1;
+  auto B = std::prev(M.end());
+  int64_t I = 0;
+  const int64_t L = A.limit[W.query_size];
+  const auto add = [&](const sdf_minimizer &m) {
+    if (m.status == 2) return;
+    const uint64_t k = search_host_key(m);
+    auto it = M.lower_bound(k);
+    if (it != M.end() && it->first == k) {
+      if (it->second & 2) return;
+      it->second = 3;
+      I += k < B->first;
+      return;
+    }
+    M.insert(it, {k, (uint8_t)2});
+    if (k < B->first) {
+      I -= B->second == 3;
+      --B;
+    }
+  };
+  const auto remove = [&](const sdf_minimizer &m) {
+    if (m.status == 2) return;
+    const uint64_t k = search_host_key(m);
+    auto it = M.find(k);
+    if (it == M.end() || !(it->second & 2)) return;
+    if (k <= B->first) {
+      I -= it->second == 3;
+      if (it->second == 2 && std::next(B) != M.end()) {
+        ++B;
+        I += B->second == 3;
+      }
+    }
+    if (it->second == 2) M.erase(it);
+    else it->second = 1;
+  };
+  const auto J = [&]() { return (int32_t)(I >= L ? I : I - L); };
+  const int64_t len_r = A.len_r, init_len = A.init_len;
+  int64_t s = T.start, e = std::min(s + init_len, len_r);
+  size_t ws = span0, we = span0;
+  while (we < A.nr && (int64_t)r[we].loc < e) add(r[we++]);
+  R.ref_start = (int32_t)s, R.ref_end = (int32_t)e, R.winnow_start = (int32_t)ws, R.winnow_end = (int32_t)we, R.jaccard = J();
+  while (s < T.end && e < len_r) {  // (e was not clamped: e == s + init_len)
+    // the next step with an event: a remove at the first s' >= s with loc <= s', an add at loc == s' + init_len
+    int64_t next = -1;
+    if (ws < A.nr) next = std::max<int64_t>(r[ws].loc, s);
+    if (we < A.nr && (int64_t)r[we].loc >= e) {
+      const int64_t at = (int64_t)r[we].loc - init_len;
+      next = next < 0 || at < next ? at : next;
+    }
+    if (next < 0 || next >= T.end || next + init_len >= len_r) break;
+    s = next, e = next + init_len;
+    if (ws < A.nr && (int64_t)r[ws].loc <= s) remove(r[ws++]);
+    if (we < A.nr && (int64_t)r[we].loc == e) add(r[we++]);
+    if (J() > R.jaccard)
+      R.ref_start = (int32_t)s, R.ref_end = (int32_t)e, R.winnow_start = (int32_t)ws, R.winnow_end = (int32_t)we, R.jaccard = J();
+    s++, e++;
+  }
+}
+
+// the launch: n wavefronts on `st`
+template <bool WALK>
+int roll_launch(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows, const uint64_t *d_first,
+                const sdf_search_interval *d_intervals, size_t n, const sdf_minimizer *d_r, size_t nr, int64_t len_r, int32_t init_len,
+                const int32_t *d_limit, size_t n_limit, sdf_search_roll_rec *d_out, hipStream_t st) {
+  hipLaunchKernelGGL(search_roll_kernel<WALK>, dim3((unsigned)n), dim3(64), 0, st, d_q, (int)nq, d_windows, d_first, d_intervals, d_r, (int)nr,
+                     (long long)len_r, (int)init_len, d_limit, (int)n_limit, d_out);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += 1;
+  return SDF_OK;
+}
+
+int roll_device(sdf_ctx *ctx, bool walk, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows, const uint64_t *d_first,
+                const sdf_search_interval *d_intervals, size_t n_max, const sdf_minimizer *d_r, size_t nr, int64_t len_r, int32_t init_len,
+                const int32_t *d_limit, size_t n_limit, sdf_search_roll_rec *d_out, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0 || n_max == 0) return SDF_OK;
+  if (!d_q || !d_windows || !d_first || !d_intervals || !d_r || !d_limit || !d_out)
+    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_roll_device: invalid arguments");
+  const char *why = nullptr;
+  if (int rc = roll_scalars(nq, n_max, nr, len_r, init_len, n_limit, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = walk ? roll_launch<true>(ctx, d_q, nq, d_windows, d_first, d_intervals, n_max, d_r, nr, len_r, init_len, d_limit, n_limit, d_out, st)
+                    : roll_launch<false>(ctx, d_q, nq, d_windows, d_first, d_intervals, n_max, d_r, nr, len_r, init_len, d_limit, n_limit, d_out, st))
+    return rc;
+  if (!stream) SDF_HIP(hipStreamSynchronize(st));
+  return SDF_OK;
+}
+}  // namespace
+
+extern "C" int sdf_search_roll_host(const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                                    const sdf_search_interval *intervals, const sdf_minimizer *r, size_t nr, int64_t len_r, int32_t init_len,
+                                    const int32_t *limit, size_t n_limit, sdf_search_roll_rec *out) {
+  if (nq == 0) return SDF_OK;
+  const RollArgs A{q, nq, windows, first, intervals, r, nr, len_r, init_len, limit, n_limit};
+  const char *why = nullptr;
+  if (int rc = roll_arrays(A, out, &why)) return rc;
+  std::map<uint64_t, uint8_t> M;
+  for (size_t i = 0; i < nq; i++)
+    for (uint64_t t = first[i]; t < first[i + 1]; t++) roll_one(A, i, intervals[t], out[t], M);
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_roll_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                                      const uint64_t *d_first, const sdf_search_interval *d_intervals, size_t n_max, const sdf_minimizer *d_r,
+                                      size_t nr, int64_t len_r, int32_t init_len, const int32_t *d_limit, size_t n_limit,
+                                      sdf_search_roll_rec *d_out, void *stream) {
+  return roll_device(ctx, true, d_q, nq, d_windows, d_first, d_intervals, n_max, d_r, nr, len_r, init_len, d_limit, n_limit, d_out, stream);
+}
+
+// For profiles/search_roll.py, not in the header: the device form whose wavefronts leave after the set-up (gather, sort, slots),
+// so that its time against the whole call's is the walk's share.  d_out's records are NOT the intervals'.
+extern "C" int sdf_search_roll_setup_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                                            const uint64_t *d_first, const sdf_search_interval *d_intervals, size_t n_max,
+                                            const sdf_minimizer *d_r, size_t nr, int64_t len_r, int32_t init_len, const int32_t *d_limit,
+                                            size_t n_limit, sdf_search_roll_rec *d_out, void *stream) {
+  return roll_device(ctx, false, d_q, nq, d_windows, d_first, d_intervals, n_max, d_r, nr, len_r, init_len, d_limit, n_limit, d_out, stream);
+}
+
+extern "C" int sdf_search_roll(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                               const sdf_search_interval *intervals, const sdf_minimizer *r, size_t nr, int64_t len_r, int32_t init_len,
+                               const int32_t *limit, size_t n_limit, sdf_search_roll_rec *out) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0) return SDF_OK;
+  const RollArgs A{q, nq, windows, first, intervals, r, nr, len_r, init_len, limit, n_limit};
+  const char *why = nullptr;
+  if (int rc = roll_arrays(A, out, &why)) return refuse(ctx, rc, why);
+  const size_t n = (size_t)first[nq];
+  if (n == 0) return SDF_OK;
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  struct Copy {
+    DevBuf &buf;
+    const void *src;
+    size_t bytes;
+  } copies[] = {{ctx->sr_q, q, nq * sizeof(sdf_minimizer)},  {ctx->sr_win, windows, nq * sizeof(sdf_search_window)},
+                {ctx->sr_first, first, (nq + 1) * 8},        {ctx->sr_iv, intervals, n * sizeof(sdf_search_interval)},
+                {ctx->sr_r, r, nr * sizeof(sdf_minimizer)},  {ctx->sr_limit, limit, n_limit * 4}};
+  for (Copy &c : copies) {
+    SDF_HIP(c.buf.reserve(c.bytes));
+    SDF_HIP(hipMemcpyAsync(c.buf.p, c.src, c.bytes, hipMemcpyHostToDevice, st));
+  }
+  SDF_HIP(ctx->sr_out.reserve(n * sizeof(sdf_search_roll_rec)));
+  if (int rc = roll_launch<true>(ctx, (const sdf_minimizer *)ctx->sr_q.p, nq, (const sdf_search_window *)ctx->sr_win.p,
+                                 (const uint64_t *)ctx->sr_first.p, (const sdf_search_interval *)ctx->sr_iv.p, n,
+                                 (const sdf_minimizer *)ctx->sr_r.p, nr, len_r, init_len, (const int32_t *)ctx->sr_limit.p, n_limit,
+                                 (sdf_search_roll_rec *)ctx->sr_out.p, st))
+    return rc;
+  SDF_HIP(hipMemcpyAsync(out, ctx->sr_out.p, n * sizeof(sdf_search_roll_rec), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  // the WIDE intervals, on the host
+  std::map<uint64_t, uint8_t> M;
+  for (size_t i = 0; i < nq; i++)
+    for (uint64_t t = first[i]; t < first[i + 1]; t++)
+      if (out[t].flags & SDF_ROLL_WIDE) roll_one(A, i, intervals[t], out[t], M);
   return SDF_OK;
 }

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sdf_kernels.h"
+#include "search_dev.h"
 #include "stats_dev.h"
 
 namespace sdf {
@@ -82,33 +83,6 @@ __global__ __launch_bounds__(256) void search_lookup_kernel(const sdf_minimizer 
   }
   look[j].start = start;
   look[j].size = size;
-}
-
-// ascending sort of a[0 .. n) in LDS by the workgroup's single wavefront: chain_sort_u64's network (chain.hip) on 32-bit keys
-__device__ __forceinline__ void search_sort_u32(uint32_t *a, const int n, const int lane) {
-  int np2 = 1;
-  while (np2 < n) np2 <<= 1;
-  for (int k = 2; k <= np2; k <<= 1) {
-    for (int idx = lane; idx < np2 / 2; idx += 64) {
-      const int blk = idx / (k / 2), off = idx % (k / 2);
-      const int i = blk * k + off, j = blk * k + k - 1 - off;
-      if (j < n) {
-        const uint32_t x = a[i], y = a[j];
-        if (x > y) a[i] = y, a[j] = x;
-      }
-    }
-    __syncthreads();
-    for (int jj = k / 4; jj >= 1; jj >>= 1) {
-      for (int idx = lane; idx < np2 / 2; idx += 64) {
-        const int i = (idx / jj) * 2 * jj + idx % jj, j = i + jj;
-        if (j < n) {
-          const uint32_t x = a[i], y = a[j];
-          if (x > y) a[i] = y, a[j] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
 }
 
 // a loc as a sort key whose unsigned order is the locs' signed order, and back; kSearchGone: a filtered loc (sorts last)
@@ -190,20 +164,7 @@ __global__ __launch_bounds__(64) void search_window_kernel(const sdf_minimizer *
   search_sort_u32(c, ng, lane);
   // the set: distinct keys to the front
   const int nv = ng - gone;
-  int nc = 0;
-  uint32_t before = 0;  // the key in front of this round's first (not read in the first round)
-  for (int s0 = 0; s0 < nv; s0 += 64) {
-    const int s = s0 + lane;
-    const uint32_t mine = s < nv ? c[s] : 0u;
-    const uint32_t left = (uint32_t)__builtin_amdgcn_ds_bpermute((lane - 1) << 2, (int)mine);
-    const bool fresh = s < nv && (s == 0 || mine != (lane ? left : before));
-    const unsigned long long m = __ballot(fresh);
-    before = (uint32_t)__builtin_amdgcn_readlane((int)mine, 63);
-    __syncthreads();
-    if (fresh) c[nc + __popcll(m & ((1ull << lane) - 1ull))] = mine;
-    nc += __popcll(m);
-    __syncthreads();
-  }
+  const int nc = search_compact_u32(c, nv, lane);
   W.n_candidates = nc;
   if (W.query_size >= n_limit) {
     W.flags = SDF_SEARCH_NOLIMIT;

@@ -60,6 +60,11 @@ SEARCH_INTERVAL_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4")])
 SEARCH_SHORT, SEARCH_NOLIMIT, SEARCH_WIDE = 0x1, 0x2, 0x4
 SEARCH_MAX_MEMBERS, SEARCH_MAX_GATHER = 1024, 4096
 assert SEARCH_WINDOW_DTYPE.itemsize == 20 and SEARCH_INTERVAL_DTYPE.itemsize == 8
+# include/sedef_hip.h: sdf_search_roll_rec (search_roll; ROLL_* in `flags`)
+SEARCH_ROLL_DTYPE = np.dtype([("ref_start", "<i4"), ("ref_end", "<i4"), ("winnow_start", "<i4"), ("winnow_end", "<i4"),
+                              ("jaccard", "<i4"), ("flags", "<u4")])
+ROLL_WIDE, ROLL_BADWINDOW, ROLL_MAX_SPAN = 0x1, 0x2, 3072
+assert SEARCH_ROLL_DTYPE.itemsize == 24
 # strand bits of a stats task on the resident pool (include/sedef_hip.h: SDF_STATS_A_RC / SDF_STATS_B_RC; in `reserved`,
 # stats_columns_pairs only)
 STATS_A_RC, STATS_B_RC = 0x1, 0x2
@@ -200,6 +205,15 @@ def load_library():
     L.sdf_search_windows_device.argtypes = [C.c_void_p] + _search + [C.c_void_p]
     L.sdf_search_windows_host.restype = C.c_int
     L.sdf_search_windows_host.argtypes = _search
+    _roll = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]  # q, nq, windows, first, intervals
+    _roll_tail = [C.c_void_p, C.c_size_t, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]  # r .. out
+    L.sdf_search_roll.restype = C.c_int
+    L.sdf_search_roll.argtypes = [C.c_void_p] + _roll + _roll_tail
+    L.sdf_search_roll_host.restype = C.c_int
+    L.sdf_search_roll_host.argtypes = _roll + _roll_tail
+    for fn in (L.sdf_search_roll_device, L.sdf_search_roll_setup_device):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + _roll + [C.c_size_t] + _roll_tail + [C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -876,6 +890,37 @@ class Extz2Engine:
         self._check(code)
         return first.astype(np.int64), windows, out[:used]
 
+    def search_roll_raw(self, q, windows, first, intervals, r, len_r, init_len, limit):
+        """sdf_search_roll as it is.  q, windows, first, intervals: as search_windows_raw takes and returns them; r: the
+        reference's minimizers in loc order (MINIMIZER_DTYPE); limit: the same table.  Returns (rc, rolls): a
+        SEARCH_ROLL_DTYPE record per interval."""
+        return search_roll_call(self.lib.sdf_search_roll, (self.ctx,), q, windows, first, intervals, r, len_r, init_len, limit)
+
+    def search_roll_device(self, d_q, nq, d_windows, d_first, d_intervals, n_max, d_r, nr, len_r, init_len, d_limit, n_limit, d_out,
+                           stream=None):
+        """The same over device pointers (ints), behind search_windows_device on one stream without a host read: n_max
+        wavefronts, d_out holds n_max records.  A WIDE interval is flagged and the rest of its record is zero."""
+        self._check(self.lib.sdf_search_roll_device(self.ctx, d_q, nq, d_windows, d_first, d_intervals, n_max, d_r, nr, int(len_r),
+                                                    int(init_len), d_limit, n_limit, d_out, stream))
+
+    def search_roll(self, q_range, r_range, k=12, w=16, separate_lowercase=True, init_len=700, same_genome=False,
+                    uppercase_seeds=True, limit=(), r_threshold=None):
+        """search_windows, and every interval rolled to its best initial match (the first loop of the reference's
+        search_in_reference_interval).  Returns (first, windows, intervals, rolls): rolls[t] is the SEARCH_ROLL_DTYPE record
+        of intervals[t]."""
+        def one(rng):
+            return self.minim_ranges([rng[:2]], rc=bool(rng[2]) if len(rng) > 2 else None)
+        _, q = self.pool_minimizers(one(q_range), k, w, separate_lowercase)
+        _, r = self.pool_minimizers(one(r_range), k, w, separate_lowercase)
+        _, r_sorted, _, threshold = self.pool_minimizer_index(one(r_range), k, w, separate_lowercase)
+        threshold = int(threshold[0]) if r_threshold is None else int(r_threshold)
+        code, first, windows, out, used = self.search_windows_raw(q, r_sorted, threshold, int(q_range[1]), init_len, same_genome,
+                                                                  uppercase_seeds, limit)
+        self._check(code)
+        code, rolls = self.search_roll_raw(q, windows, first, out[:used], r, int(r_range[1]), init_len, limit)
+        self._check(code)
+        return first.astype(np.int64), windows, out[:used], rolls
+
     def last_ms(self, which):
         return float(self.lib.sdf_last_ms(self.ctx, which))
 
@@ -941,6 +986,29 @@ def search_windows_host(q, r_sorted, r_threshold, len_q, init_len, same_genome, 
     """sdf_search_windows_host: search_windows_raw without a context or a GPU, in plain C++ on one thread."""
     return search_windows_call(load_library().sdf_search_windows_host, (), q, r_sorted, r_threshold, len_q, init_len, same_genome,
                                uppercase_seeds, limit, cap, out)
+
+
+def search_roll_call(fn, head, q, windows, first, intervals, r, len_r, init_len, limit):
+    """sdf_search_roll (head: its context) or sdf_search_roll_host (head: nothing) on numpy arrays.  Returns (rc, rolls)."""
+    q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
+    r = np.ascontiguousarray(r, dtype=MINIMIZER_DTYPE)
+    windows = np.ascontiguousarray(windows, dtype=SEARCH_WINDOW_DTYPE)
+    intervals = np.ascontiguousarray(intervals, dtype=SEARCH_INTERVAL_DTYPE)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    limit = np.ascontiguousarray(limit, dtype=np.int32)
+    assert len(first) == len(q) + 1 and len(windows) == len(q) and len(intervals) >= int(first[-1])
+    out = np.zeros(int(first[-1]), SEARCH_ROLL_DTYPE)
+
+    def ptr(a):
+        return a.ctypes.data if len(a) else None
+    rc = fn(*head, ptr(q), len(q), ptr(windows), first.ctypes.data, ptr(intervals), ptr(r), len(r), int(len_r), int(init_len),
+            ptr(limit), len(limit), ptr(out))
+    return rc, out
+
+
+def search_roll_host(q, windows, first, intervals, r, len_r, init_len, limit):
+    """sdf_search_roll_host: search_roll_raw without a context or a GPU, in plain C++ on one thread."""
+    return search_roll_call(load_library().sdf_search_roll_host, (), q, windows, first, intervals, r, len_r, init_len, limit)
 
 
 _default_engine = None

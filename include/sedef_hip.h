@@ -748,6 +748,93 @@ int sdf_search_roll_host(const sdf_minimizer *q, size_t nq, const sdf_search_win
                          const sdf_search_interval *intervals, const sdf_minimizer *r, size_t nr, int64_t len_r, int32_t init_len,
                          const int32_t *limit, size_t n_limit, sdf_search_roll_rec *out /* first[nq] */);
 
+/* ---- search filter: uppercase and q-gram verdicts per pair of pool ranges (search_filter.hip) -----------------------------------
+ * The reference's filter() (src/filter.cc; called at src/search.cc:337, 356 and 374: once per rolled interval whose jaccard is
+ * at least 0, once per hit after extend) for many pairs in one call.  It reads nothing but the resident pool.  is_overlap,
+ * extend and the tree are not built.
+ *
+ * The sequence s of a side is pool[off, off + len) as it lies, or -- SDF_FILTER_Q_RC / SDF_FILTER_R_RC -- its reverse
+ * complement by rev_dna: s[i] = rev_dna(pool[off + len - 1 - i]).  off is the first byte of the range in pool order whatever the
+ * strand, as for sdf_pool_fetch_ranges.  Characters are taken & 127 on either strand.
+ *   up      the number of i with 'A' <= s[i] <= 'Z'.  rev_dna turns n and every unknown byte into 'N', so on the reverse strand
+ *           up counts every byte that is not acgt -- a forward 'n' is not uppercase, a reversed one is: the one place where the
+ *           strand changes a count.
+ *   dist    with h(c) = 0, 1, 2, 3 for Aa, Cc, Gg, Tt and 0 for anything else, the q-gram at i >= 4 is h(s[i - 4]) .. h(s[i]),
+ *           first character most significant, 10 bits; dist = the sum over the 1,024 grams of min(count in q, count in r).  A side
+ *           shorter than 5 has no grams.
+ *   minqg   with l = max(q_len, r_len):
+ *             (int)(l * (1 - (max_error - max_edit_error) - 5 * max_edit_error) - (gap_frequency * l + 1) * 4)
+ *           in double, in exactly this association, no fused multiply-add, truncated toward zero (beyond the int32 range -- which
+ *           the reference's parameters never reach -- it takes the nearest end).
+ *   flags   SDF_FILTER_UPPER_FAIL when q_up < min_uppercase or r_up < min_uppercase; else SDF_FILTER_QGRAM_FAIL when
+ *           dist < minqg.  SDF_FILTER_SHORT when minqg < 10, where the reference asserts: the verdict is that of its NDEBUG build.
+ * q_up, r_up, dist and minqg are filled whatever the verdict, so a record does not depend on who computed it.  A task that
+ * carries SDF_FILTER_SKIP is not read: its record is zero with SDF_FILTER_SKIPPED.
+ *
+ * A task is of one of two classes, read off its lengths alone: both sides up to SDF_FILTER_WAVE_MAX_LEN characters -- one
+ * wavefront, 16-bit counts --, or longer -- a workgroup of four wavefronts, 32-bit counts.  The answer does not depend on it.
+ *
+ * Host form.  Every check precedes the first launch, and a refused call launches nothing (sdf_last_launches() as it was) and
+ * writes nothing:
+ *   SDF_ERR_INVALID      a range outside sdf_pool_bytes(ctx), a negative len, params / tasks / out == NULL with n > 0, a
+ *                        parameter that is not finite
+ *   SDF_ERR_UNSUPPORTED  a flags bit other than the three above, reserved != 0 (task or parameters), n > 2^31 - 1
+ * n == 0 is SDF_OK without a launch.  One launch, two when a task is of the long class, per 2^22 tasks (a grid has fewer than
+ * 2^32 lanes: the call cuts a larger n into pieces itself).  Works on a view (sdf_pool_share) like
+ * every reader of the pool; enqueued on the context's stream behind the pool's uploads, returns with everything filled. */
+#define SDF_FILTER_Q_RC 0x1
+#define SDF_FILTER_R_RC 0x2
+#define SDF_FILTER_SKIP 0x4          /* task flag: answer a zero record that carries SKIPPED */
+#define SDF_FILTER_WAVE_MAX_LEN 4096 /* a task with a longer side goes to a workgroup of four wavefronts */
+typedef struct { int64_t q_off, r_off; int32_t q_len, r_len; uint32_t flags; int32_t reserved; /* 0 */ } sdf_filter_task; /* 32 bytes */
+typedef struct { int32_t min_uppercase, reserved; double max_error, max_edit_error, gap_frequency; } sdf_filter_params;
+#define SDF_FILTER_UPPER_FAIL 0x1    /* what the reference reports: "upper (q_up, r_up) < min" */
+#define SDF_FILTER_QGRAM_FAIL 0x2    /* "q-grams dist < minqg"; set only when UPPER_FAIL is not */
+#define SDF_FILTER_SHORT      0x4    /* minqg < 10: the reference's assert; verdict as with NDEBUG */
+#define SDF_FILTER_SKIPPED    0x8
+typedef struct { int32_t q_up, r_up, dist, minqg; uint32_t flags; } sdf_filter_rec; /* 20 bytes */
+int sdf_search_filter(sdf_ctx *ctx, const sdf_filter_params *params, const sdf_filter_task *tasks, size_t n, sdf_filter_rec *out);
+/* Device form: tasks and d_out (n records) in HBM, asynchronous on `stream` (NULL: the context's own, synchronised before
+ * returning).  The parameters and n are checked as above; the tasks are not, but a task that does not lie in the pool, has a
+ * negative length, carries an unknown flag or reserved != 0 answers a zero record with SDF_FILTER_SKIPPED and is not read.
+ * any_rc == 0 with a task that carries a strand flag reads that side forward.  Two launches per 2^22 tasks, the second for the
+ * long class (its workgroups leave at once on a task of the other: profiles/search_filter.txt has what that costs).  The pool's uploads as for sdf_stats_columns_pairs_device
+ * (sdf_pool_sync() first). */
+int sdf_search_filter_device(sdf_ctx *ctx, const sdf_filter_params *params, const sdf_filter_task *d_tasks, size_t n, int any_rc,
+                             sdf_filter_rec *d_out, void *stream);
+/* No context, no GPU: the same over pool[0, pool_bytes) in plain C++ on one thread.  Same checks and codes. */
+int sdf_search_filter_host(const char *pool, size_t pool_bytes, const sdf_filter_params *params, const sdf_filter_task *tasks,
+                           size_t n, sdf_filter_rec *out);
+/* The tasks of the rolled intervals: out[t] for interval t of sdf_search_roll, t < first[nq] -- no compaction, out[t] stays
+ * aligned with rolls[t].  q, windows, first and intervals as sdf_search_roll takes them, rolls as it writes them; the query
+ * sequence is pool[q_off, q_off + len_q), the reference sequence pool[r_off, r_off + len_r), each read reverse-complemented when
+ * its q_rc / r_rc is not 0 (the task then carries the strand flag).  Interval t of window i:
+ *   query side      positions [q[i].loc, q[i].loc + init_len) of the query sequence
+ *   reference side  allow_extend == 0: the roll's best, [ref_start, ref_end) (src/search.cc:374).  allow_extend != 0: where the
+ *                   walk ENDED, not its best -- src/search.cc:337-338 passes ref_start and ref_end, and the quirk is kept --:
+ *                   with e0 = min(start + init_len, len_r) and steps = max(0, min(end - start, len_r - e0)) of the interval,
+ *                   [start + steps, e0 + steps).
+ * Positions [a, b) of a sequence map to pool order as off = base + a, or on the reverse strand off = base + len_seq - b.
+ * The task carries SDF_FILTER_SKIP (every other field zero) when the roll has jaccard < 0, SDF_ROLL_BADWINDOW, or SDF_ROLL_WIDE
+ * on a record nobody completed (ref_end == 0), when the window is SHORT or NOLIMIT, or when a side does not lie inside its
+ * sequence.
+ *   SDF_ERR_INVALID      a null array with nq > 0 (intervals, rolls and out may be null when first[nq] == 0), init_len < 1,
+ *                        len_q or len_r < 0, q_off or r_off < 0, first[] not ascending from 0
+ *   SDF_ERR_UNSUPPORTED  init_len > 2^30, len_q or len_r or the number of intervals > 2^31 - 1 */
+int sdf_search_filter_tasks_host(const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                                 const sdf_search_interval *intervals, const sdf_search_roll_rec *rolls, int64_t len_q,
+                                 int64_t len_r, int32_t init_len, int64_t q_off, int q_rc, int64_t r_off, int r_rc,
+                                 int allow_extend, sdf_filter_task *out /* first[nq] */);
+/* Device form: every array in HBM, the scalars checked, no host wait -- one lane per interval, behind sdf_search_roll_device on
+ * one stream and in front of sdf_search_filter_device.  n_max as for sdf_search_roll_device, but the lanes at or beyond
+ * d_first[nq] write a SKIP task (no roll record is read there), so that sdf_search_filter_device may take all n_max; nothing is
+ * written at or behind d_out[n_max].  nq == 0 or n_max == 0 is SDF_OK without a launch. */
+int sdf_search_filter_tasks_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                                   const uint64_t *d_first, const sdf_search_interval *d_intervals,
+                                   const sdf_search_roll_rec *d_rolls, size_t n_max, int64_t len_q, int64_t len_r, int32_t init_len,
+                                   int64_t q_off, int q_rc, int64_t r_off, int r_rc, int allow_extend, sdf_filter_task *d_out,
+                                   void *stream);
+
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is
  * sharded over the GPUs of a node with no data-path collective; after the DP an RCCL all-gatherv over xGMI gives every GPU

@@ -1,4 +1,4 @@
-// The checks the entry points of the C ABI share (sdf_pool_api.hip, sdf_stats_api.hip, sdf_minim_api.hip, sdf_search_api.hip): is a range inside
+// The checks the entry points of the C ABI share (sdf_pool_api.hip, sdf_stats_api.hip, sdf_minim_api.hip, sdf_search_api.hip, sdf_filter_api.hip): is a range inside
 // its pool, the tasks of the stats calls, and the tail of a call whose output the device counts first.
 #pragma once
 #include "sdf_ctx.h"

@@ -198,5 +198,68 @@ static_assert(ROLL_MAX_KEYS < 65535 && sizeof(sdf_search_roll_rec) == 24, "searc
 template <bool WALK>
 __global__ void search_roll_kernel(const sdf_minimizer *, int, const sdf_search_window *, const uint64_t *, const sdf_search_interval *,
                                    const sdf_minimizer *, int, long long, int, const int32_t *, int, sdf_search_roll_rec *);
+// search_filter.hip
+constexpr int FILTER_WAVE_MAX_LEN = SDF_FILTER_WAVE_MAX_LEN, FILTER_LONG_WAVES = 4, FILTER_GRAMS = 1024;
+static_assert(FILTER_WAVE_MAX_LEN < 65536, "search_filter.hip: the wavefront class counts in 16 bits");
+static_assert(sizeof(sdf_filter_task) == 32 && sizeof(sdf_filter_rec) == 20 && sizeof(sdf_filter_params) == 32, "include/sedef_hip.h");
+// minqg of include/sedef_hip.h, the one form the kernel and sdf_search_filter_host share: no contraction into a fused
+// multiply-add on either side
+__host__ __device__ inline int32_t filter_minqg(const int32_t l, const sdf_filter_params &P) {
+#pragma clang fp contract(off)
+  const double v = l * (1 - (P.max_error - P.max_edit_error) - 5 * P.max_edit_error) - (P.gap_frequency * l + 1) * 4;
+  return v >= 2147483647.0 ? 2147483647 : v <= -2147483648.0 ? (int32_t)-2147483647 - 1 : v != v ? 0 : (int32_t)v;
+}
+// a task nobody reads (device forms): a range that does not lie in the pool, an unknown flag, reserved != 0
+__host__ __device__ inline bool filter_task_bad(const sdf_filter_task &T, const long long pool_bytes) {
+  const auto outside = [&](long long off, long long len) { return off < 0 || len < 0 || off > pool_bytes || len > pool_bytes - off; };
+  return (T.flags & ~(uint32_t)(SDF_FILTER_Q_RC | SDF_FILTER_R_RC | SDF_FILTER_SKIP)) || T.reserved != 0 || outside(T.q_off, T.q_len) ||
+         outside(T.r_off, T.r_len);
+}
+// the verdict of a pair's counts
+__host__ __device__ inline sdf_filter_rec filter_verdict(int32_t q_up, int32_t r_up, int32_t dist, int32_t l, const sdf_filter_params &P) {
+  sdf_filter_rec R{q_up, r_up, dist, filter_minqg(l, P), 0u};
+  if (q_up < P.min_uppercase || r_up < P.min_uppercase) R.flags = SDF_FILTER_UPPER_FAIL;
+  else if (dist < R.minqg) R.flags = SDF_FILTER_QGRAM_FAIL;
+  if (R.minqg < 10) R.flags |= SDF_FILTER_SHORT;
+  return R;
+}
+// WAVES wavefronts per task: 1 (16-bit counts, every task up to FILTER_WAVE_MAX_LEN) or FILTER_LONG_WAVES (32-bit counts, the
+// others); a workgroup whose task is of the other class leaves at once.  REV as for the stats kernels.  MINSUM false
+// (profiles/search_filter.py): the histogram pass alone, and a record that is not the pair's.
+// A launch takes at most FILTER_LAUNCH_TASKS tasks: a grid of more than 2^32 - 1 lanes is refused.
+constexpr size_t FILTER_LAUNCH_TASKS = (size_t)1 << 22;
+template <int WAVES, bool REV, bool MINSUM>
+__global__ void search_filter_kernel(const sdf_filter_task *, int, const char *, long long, sdf_filter_params, sdf_filter_rec *);
+// the scalars of sdf_search_filter_tasks_*, and the task of one rolled interval of window W whose query minimizer lies at q_loc
+// (include/sedef_hip.h states the rules); the one form the kernel and the host form share
+struct FilterTaskArgs {
+  long long len_q, len_r, q_off, r_off;
+  int init_len, q_rc, r_rc, allow_extend;
+};
+__host__ __device__ inline sdf_filter_task filter_task_of(const FilterTaskArgs &A, const long long q_loc, const sdf_search_window &W,
+                                                          const sdf_search_interval &T, const sdf_search_roll_rec &R) {
+  const sdf_filter_task skip{0, 0, 0, 0, SDF_FILTER_SKIP, 0};
+  if (R.jaccard < 0 || (R.flags & SDF_ROLL_BADWINDOW) || ((R.flags & SDF_ROLL_WIDE) && R.ref_end == 0) ||
+      (W.flags & (SDF_SEARCH_SHORT | SDF_SEARCH_NOLIMIT)))
+    return skip;
+  const long long qa = q_loc, qb = q_loc + A.init_len;
+  long long ra = R.ref_start, rb = R.ref_end;
+  if (A.allow_extend) {  // where the walk ended
+    const long long start = T.start, end = T.end, e0 = start + A.init_len < A.len_r ? start + A.init_len : A.len_r;
+    long long steps = end - start < A.len_r - e0 ? end - start : A.len_r - e0;
+    steps = steps < 0 ? 0 : steps;
+    ra = start + steps, rb = e0 + steps;
+  }
+  if (qa < 0 || qb > A.len_q || ra < 0 || rb < ra || rb > A.len_r) return skip;
+  sdf_filter_task O;
+  O.q_off = A.q_rc ? A.q_off + A.len_q - qb : A.q_off + qa;
+  O.r_off = A.r_rc ? A.r_off + A.len_r - rb : A.r_off + ra;
+  O.q_len = (int32_t)(qb - qa), O.r_len = (int32_t)(rb - ra);
+  O.flags = (A.q_rc ? SDF_FILTER_Q_RC : 0u) | (A.r_rc ? SDF_FILTER_R_RC : 0u), O.reserved = 0;
+  return O;
+}
+__global__ void search_filter_tasks_kernel(const sdf_minimizer *, int, const sdf_search_window *, const uint64_t *,
+                                           const sdf_search_interval *, const sdf_search_roll_rec *, int, FilterTaskArgs,
+                                           sdf_filter_task *);
 
 }  // namespace sdf

@@ -65,6 +65,15 @@ SEARCH_ROLL_DTYPE = np.dtype([("ref_start", "<i4"), ("ref_end", "<i4"), ("winnow
                               ("jaccard", "<i4"), ("flags", "<u4")])
 ROLL_WIDE, ROLL_BADWINDOW, ROLL_MAX_SPAN = 0x1, 0x2, 3072
 assert SEARCH_ROLL_DTYPE.itemsize == 24
+# sdf_filter_task / sdf_filter_rec (the parameters: _FilterParams)
+FILTER_TASK_DTYPE = np.dtype([("q_off", "<i8"), ("r_off", "<i8"), ("q_len", "<i4"), ("r_len", "<i4"), ("flags", "<u4"),
+                              ("reserved", "<i4")])
+FILTER_REC_DTYPE = np.dtype([("q_up", "<i4"), ("r_up", "<i4"), ("dist", "<i4"), ("minqg", "<i4"), ("flags", "<u4")])
+assert FILTER_TASK_DTYPE.itemsize == 32 and FILTER_REC_DTYPE.itemsize == 20
+FILTER_Q_RC, FILTER_R_RC, FILTER_SKIP = 1, 2, 4
+FILTER_UPPER_FAIL, FILTER_QGRAM_FAIL, FILTER_SHORT, FILTER_SKIPPED = 1, 2, 4, 8
+FILTER_WAVE_MAX_LEN = 4096
+FILTER_DEFAULTS = dict(min_uppercase=12, max_error=0.30, max_edit_error=0.15, gap_frequency=0.005)  # the reference's own
 # strand bits of a stats task on the resident pool (include/sedef_hip.h: SDF_STATS_A_RC / SDF_STATS_B_RC; in `reserved`,
 # stats_columns_pairs only)
 STATS_A_RC, STATS_B_RC = 0x1, 0x2
@@ -72,6 +81,16 @@ STATS_A_RC, STATS_B_RC = 0x1, 0x2
 
 class SdfError(RuntimeError):
     pass
+
+
+class _FilterParams(C.Structure):
+    _fields_ = [("min_uppercase", C.c_int32), ("reserved", C.c_int32), ("max_error", C.c_double), ("max_edit_error", C.c_double),
+                ("gap_frequency", C.c_double)]
+
+
+def filter_params(min_uppercase=12, max_error=0.30, max_edit_error=0.15, gap_frequency=0.005, reserved=0):
+    """sdf_filter_params; the defaults are the reference's (src/globals.cc)."""
+    return _FilterParams(int(min_uppercase), int(reserved), float(max_error), float(max_edit_error), float(gap_frequency))
 
 
 class _Scoring(C.Structure):
@@ -214,6 +233,21 @@ def load_library():
     for fn in (L.sdf_search_roll_device, L.sdf_search_roll_setup_device):
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p] + _roll + [C.c_size_t] + _roll_tail + [C.c_void_p]
+    L.sdf_search_filter.restype = C.c_int
+    L.sdf_search_filter.argtypes = [C.c_void_p, C.POINTER(_FilterParams), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdf_search_filter_device.restype = C.c_int
+    L.sdf_search_filter_device.argtypes = [C.c_void_p, C.POINTER(_FilterParams), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    L.sdf_search_filter_phase_device.restype = C.c_int  # (profiles/search_filter.py; not in the header)
+    L.sdf_search_filter_phase_device.argtypes = [C.c_void_p, C.POINTER(_FilterParams), C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p]
+    L.sdf_search_filter_host.restype = C.c_int
+    L.sdf_search_filter_host.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_FilterParams), C.c_void_p, C.c_size_t, C.c_void_p]
+    _ftasks = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # q, nq, windows, first, intervals, rolls
+    _ftasks_tail = [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]  # len_q .. out
+    L.sdf_search_filter_tasks_host.restype = C.c_int
+    L.sdf_search_filter_tasks_host.argtypes = _ftasks + _ftasks_tail
+    L.sdf_search_filter_tasks_device.restype = C.c_int
+    L.sdf_search_filter_tasks_device.argtypes = [C.c_void_p] + _ftasks + [C.c_size_t] + _ftasks_tail + [C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -903,11 +937,8 @@ class Extz2Engine:
         self._check(self.lib.sdf_search_roll_device(self.ctx, d_q, nq, d_windows, d_first, d_intervals, n_max, d_r, nr, int(len_r),
                                                     int(init_len), d_limit, n_limit, d_out, stream))
 
-    def search_roll(self, q_range, r_range, k=12, w=16, separate_lowercase=True, init_len=700, same_genome=False,
-                    uppercase_seeds=True, limit=(), r_threshold=None):
-        """search_windows, and every interval rolled to its best initial match (the first loop of the reference's
-        search_in_reference_interval).  Returns (first, windows, intervals, rolls): rolls[t] is the SEARCH_ROLL_DTYPE record
-        of intervals[t]."""
+    def _search_roll(self, q_range, r_range, k, w, separate_lowercase, init_len, same_genome, uppercase_seeds, limit, r_threshold):
+        """search_roll with the query's minimizers in front: (q, first, windows, intervals, rolls)."""
         def one(rng):
             return self.minim_ranges([rng[:2]], rc=bool(rng[2]) if len(rng) > 2 else None)
         _, q = self.pool_minimizers(one(q_range), k, w, separate_lowercase)
@@ -919,7 +950,56 @@ class Extz2Engine:
         self._check(code)
         code, rolls = self.search_roll_raw(q, windows, first, out[:used], r, int(r_range[1]), init_len, limit)
         self._check(code)
-        return first.astype(np.int64), windows, out[:used], rolls
+        return q, first.astype(np.int64), windows, out[:used], rolls
+
+    def search_roll(self, q_range, r_range, k=12, w=16, separate_lowercase=True, init_len=700, same_genome=False,
+                    uppercase_seeds=True, limit=(), r_threshold=None):
+        """search_windows, and every interval rolled to its best initial match (the first loop of the reference's
+        search_in_reference_interval).  Returns (first, windows, intervals, rolls): rolls[t] is the SEARCH_ROLL_DTYPE record
+        of intervals[t]."""
+        return self._search_roll(q_range, r_range, k, w, separate_lowercase, init_len, same_genome, uppercase_seeds, limit, r_threshold)[1:]
+
+    def search_filter_raw(self, tasks, params=None, out=None):
+        """sdf_search_filter as it is.  tasks: a FILTER_TASK_DTYPE array of pairs of ranges of the resident pool; params: what
+        filter_params makes (default: the reference's defaults); out: a FILTER_REC_DTYPE array to fill.  Returns (rc, records)."""
+        tasks = np.ascontiguousarray(tasks, dtype=FILTER_TASK_DTYPE)
+        if out is None:
+            out = np.zeros(len(tasks), FILTER_REC_DTYPE)
+        assert out.dtype == FILTER_REC_DTYPE and out.flags.c_contiguous and len(out) >= len(tasks)
+        params = filter_params() if params is None else params
+        rc = self.lib.sdf_search_filter(self.ctx, C.byref(params), tasks.ctypes.data if len(tasks) else None, len(tasks),
+                                        out.ctypes.data if len(out) else None)
+        return rc, out
+
+    def search_filter_device(self, d_tasks, n, any_rc, d_out, params=None, stream=None):
+        """The same over device pointers (ints) of n tasks and n records; on `stream` when one is given.  A task that does not
+        lie in the pool or carries an unknown flag answers a zero record with FILTER_SKIPPED."""
+        params = filter_params() if params is None else params
+        self._check(self.lib.sdf_search_filter_device(self.ctx, C.byref(params), d_tasks, n, int(bool(any_rc)), d_out, stream))
+
+    def search_filter_tasks_device(self, d_q, nq, d_windows, d_first, d_intervals, d_rolls, n_max, len_q, len_r, init_len, q_off, q_rc,
+                                   r_off, r_rc, allow_extend, d_out, stream=None):
+        """sdf_search_filter_tasks_device: a FILTER_TASK_DTYPE record per interval behind search_roll_device on one stream, n_max
+        of them; those at or beyond d_first[nq] carry FILTER_SKIP."""
+        self._check(self.lib.sdf_search_filter_tasks_device(self.ctx, d_q, nq, d_windows, d_first, d_intervals, d_rolls, n_max, int(len_q),
+                                                            int(len_r), int(init_len), int(q_off), int(bool(q_rc)), int(r_off),
+                                                            int(bool(r_rc)), int(bool(allow_extend)), d_out, stream))
+
+    def search_filter(self, q_range, r_range, k=12, w=16, separate_lowercase=True, init_len=700, same_genome=False,
+                      uppercase_seeds=True, limit=(), r_threshold=None, params=None, allow_extend=True):
+        """search_roll, and the filter's verdict on every rolled interval whose jaccard is at least 0 (the reference's filter()
+        as search_in_reference_interval calls it in front of extend, or with allow_extend=False in its place).  Returns
+        (first, windows, intervals, rolls, records): records[t] is the FILTER_REC_DTYPE record of intervals[t], FILTER_SKIPPED
+        where the reference does not filter."""
+        q, first, windows, intervals, rolls = self._search_roll(q_range, r_range, k, w, separate_lowercase, init_len, same_genome,
+                                                                uppercase_seeds, limit, r_threshold)
+        code, tasks = search_filter_tasks_host(q, windows, first, intervals, rolls, int(q_range[1]), int(r_range[1]), init_len,
+                                               int(q_range[0]), len(q_range) > 2 and bool(q_range[2]), int(r_range[0]),
+                                               len(r_range) > 2 and bool(r_range[2]), allow_extend)
+        self._check(code)
+        code, recs = self.search_filter_raw(tasks, params)
+        self._check(code)
+        return first, windows, intervals, rolls, recs
 
     def last_ms(self, which):
         return float(self.lib.sdf_last_ms(self.ctx, which))
@@ -1009,6 +1089,40 @@ def search_roll_call(fn, head, q, windows, first, intervals, r, len_r, init_len,
 def search_roll_host(q, windows, first, intervals, r, len_r, init_len, limit):
     """sdf_search_roll_host: search_roll_raw without a context or a GPU, in plain C++ on one thread."""
     return search_roll_call(load_library().sdf_search_roll_host, (), q, windows, first, intervals, r, len_r, init_len, limit)
+
+
+def search_filter_host(pool, tasks, params=None, out=None, pool_bytes=None):
+    """sdf_search_filter_host: search_filter_raw without a context or a GPU, over the characters `pool` (bytes)."""
+    tasks = np.ascontiguousarray(tasks, dtype=FILTER_TASK_DTYPE)
+    if out is None:
+        out = np.zeros(len(tasks), FILTER_REC_DTYPE)
+    assert out.dtype == FILTER_REC_DTYPE and out.flags.c_contiguous and len(out) >= len(tasks)
+    params = filter_params() if params is None else params
+    pool = bytes(pool)
+    rc = load_library().sdf_search_filter_host(pool, len(pool) if pool_bytes is None else pool_bytes, C.byref(params),
+                                               tasks.ctypes.data if len(tasks) else None, len(tasks),
+                                               out.ctypes.data if len(out) else None)
+    return rc, out
+
+
+def search_filter_tasks_host(q, windows, first, intervals, rolls, len_q, len_r, init_len, q_off, q_rc, r_off, r_rc, allow_extend,
+                             out=None):
+    """sdf_search_filter_tasks_host: the FILTER_TASK_DTYPE record of every rolled interval.  Returns (rc, tasks)."""
+    q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
+    windows = np.ascontiguousarray(windows, dtype=SEARCH_WINDOW_DTYPE)
+    intervals = np.ascontiguousarray(intervals, dtype=SEARCH_INTERVAL_DTYPE)
+    rolls = np.ascontiguousarray(rolls, dtype=SEARCH_ROLL_DTYPE)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    assert len(first) == len(q) + 1 and len(windows) == len(q)
+    if out is None:
+        out = np.zeros(int(first[-1]) if len(q) else 0, FILTER_TASK_DTYPE)
+
+    def ptr(a):
+        return a.ctypes.data if len(a) else None
+    rc = load_library().sdf_search_filter_tasks_host(ptr(q), len(q), ptr(windows), first.ctypes.data, ptr(intervals), ptr(rolls),
+                                                     int(len_q), int(len_r), int(init_len), int(q_off), int(bool(q_rc)), int(r_off),
+                                                     int(bool(r_rc)), int(bool(allow_extend)), ptr(out))
+    return rc, out
 
 
 _default_engine = None

@@ -687,8 +687,8 @@ int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, co
 
 /* ---- search roll: every reference interval rolled to its best initial match (search_roll.hip) ----------------------------------
  * The first loop of the reference's search_in_reference_interval (src/search.cc:274-314, "Roll until we find best inital
- * match") for EVERY interval of sdf_search_windows in one call.  It reads no tree; is_overlap, filter, extend and the tree
- * update that follow it in the reference are not built.  Inputs: q[0, nq), windows[0, nq), first[0, nq + 1] and
+ * match") for EVERY interval of sdf_search_windows in one call.  It reads no tree; filter and extend follow it in their own
+ * sections, is_overlap and the tree update are not built.  Inputs: q[0, nq), windows[0, nq), first[0, nq + 1] and
  * intervals[0, first[nq]) as sdf_search_windows takes and writes them; r[0, nr), the reference range's minimizers in ASCENDING
  * LOC (sdf_pool_minimizers' list, not the sorted index); len_r, the reference sequence's length; init_len; limit[0, n_limit),
  * the same table.
@@ -750,8 +750,8 @@ int sdf_search_roll_host(const sdf_minimizer *q, size_t nq, const sdf_search_win
 
 /* ---- search filter: uppercase and q-gram verdicts per pair of pool ranges (search_filter.hip) -----------------------------------
  * The reference's filter() (src/filter.cc; called at src/search.cc:337, 356 and 374: once per rolled interval whose jaccard is
- * at least 0, once per hit after extend) for many pairs in one call.  It reads nothing but the resident pool.  is_overlap,
- * extend and the tree are not built.
+ * at least 0, once per hit after extend) for many pairs in one call.  It reads nothing but the resident pool.  is_overlap
+ * and the tree are not built.
  *
  * The sequence s of a side is pool[off, off + len) as it lies, or -- SDF_FILTER_Q_RC / SDF_FILTER_R_RC -- its reverse
  * complement by rev_dna: s[i] = rev_dna(pool[off + len - 1 - i]).  off is the first byte of the range in pool order whatever the
@@ -834,6 +834,117 @@ int sdf_search_filter_tasks_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_
                                    const sdf_search_roll_rec *d_rolls, size_t n_max, int64_t len_q, int64_t len_r, int32_t init_len,
                                    int64_t q_off, int q_rc, int64_t r_off, int r_rc, int allow_extend, sdf_filter_task *d_out,
                                    void *stream);
+
+/* ---- search extend: every rolled interval grown to its hit (search_extend.hip) ---------------------------------------------------
+ * The reference's extend() (src/search.cc:95-259) for EVERY interval of sdf_search_roll in one call, as the reference calls it
+ * with an EMPTY tree; is_overlap and the tree remain unbuilt.  Inputs: q, windows, first, intervals, r (ascending loc), nr,
+ * len_r, init_len, limit, n_limit as sdf_search_roll takes them; rolls[t] as it writes them; len_q; filter[t], the first
+ * filter's verdicts (sdf_search_filter on the tasks with allow_extend != 0), or NULL; the parameters (the reference's defaults:
+ * 0.30, 0.15, 1,048,576).
+ *
+ * Interval t of window i RUNS when rolls[t].jaccard >= 0, the record carries no SDF_ROLL_BADWINDOW and no SDF_ROLL_WIDE with
+ * ref_end == 0, lo <= winnow_start <= winnow_end <= nr (lo: the first index with r[lo].loc >= start), and filter is NULL or
+ * filter[t].flags has none of UPPER_FAIL | QGRAM_FAIL | SKIPPED.  Every other interval gets a zero record with
+ * SDF_EXTEND_SKIPPED.
+ *
+ * Entry state: the roll's best_winnow, which its record does not carry -- the state is path-dependent (the roll's quirk 2).  It
+ * is the state of the roll's walk (steps 1-5 there) at the FIRST evaluation of J, step 4 or a round of step 5, at which
+ * ws >= rolls[t].winnow_start and we >= rolls[t].winnow_end (the walk's end when there is none): for a record the roll wrote,
+ * the evaluation that last assigned `best` (ref_start alone does not tell step 4 from the round at s = start).  bits, B and I
+ * stand as they are there;  query_size = windows[i].query_size, L = limit[query_size];  qws = i, qwe = i + n_members,
+ * rws = rolls[t].winnow_start, rwe = rolls[t].winnow_end.
+ *
+ * The map, in the roll section's terms, B now a key or NONE.  below(B) / above(B): the largest stored key < B / the smallest
+ * stored key > B.  Every comparison with B is false while B is NONE or query_size == 0.
+ *   add(k, BIT)      bits[k] & BIT: false, nothing changes.  Else was = bits[k], bits[k] |= BIT; when k < B: I += (bits[k] == 3),
+ *                    and when was == 0: I -= (bits[B] == 3), B = below(B).  True.
+ *   remove(k, BIT)   bits[k] & BIT == 0: false.  Else, when k <= B: I -= (bits[k] == 3), and when bits[k] == BIT and above(B)
+ *                    exists: B = above(B), I += (bits[B] == 3).  Then bits[k] &= ~BIT.  True.
+ *   add_to_reference / remove_from_reference (record): nothing for status 2, else add / remove(k, 2) -- the roll's.
+ *   add_to_query(record): its status does NOT matter.  add(k, 1) false: nothing more -- query_size, L and B stay.  Else
+ *                    query_size += 1, L = limit[query_size];  B = the smallest stored key when B is NONE, else above(B) when
+ *                    that exists;  I += (bits[B] == 3).
+ *   remove_from_query(record): remove(k, 1) false: nothing more.  Else query_size -= 1 (not below 0), L = limit[query_size];  when B is not
+ *                    NONE: I -= (bits[B] == 3), B = below(B), NONE when there is none.
+ * bits[B] of a key that is not stored counts as 0.  Where above(B) does not exist the reference steps its boundary past the
+ * last key (and reads it at once, or in the next call), and a remove of a key above every stored one reads lower_bound() ==
+ * end(): the rules above make each a no-op at that point.  tests/golden/make_golden_search_extend.py guards the same spots and
+ * keeps no case that reached one.
+ *
+ * The extension (src/search.cc:201-258).  With nq, nr the record counts:
+ *   query_start = qws ? q[qws - 1].loc + 1 : 0,  query_end = qwe < nq ? q[qwe].loc : len_q;  ref_start, ref_end likewise.
+ *   loop:  G = max_error - max_edit_error, all in double, this association, no fused multiply-add, correctly rounded division:
+ *     max_match = same_genome ? min(max_sd_size, (int)((1.0 / G + .5) * |query_start - ref_start|)) : max_sd_size  (the
+ *                 conversion takes the nearest int32 end beyond the range);
+ *     aln_len = max(query_end - query_start, ref_end - ref_start), seq_len = their min;
+ *     stop when aln_len > max_match;  stop when 100.0 * seq_len / aln_len < 100 * (1 - 2 * G);
+ *     same_genome: overlap = query_end - ref_start; stop when overlap > 0 and
+ *                 100.0 * overlap / (ref_end - ref_start) > 100 * max_error;
+ *     try both_both, both_right, both_left in this order; the first that passes its precheck and leaves J >= 0 is kept and the
+ *     loop goes on; one that leaves J < 0 is undone; stop when none is kept.
+ *   prechecks    left: qws != 0 and rws != 0;  right: rwe < nr and qwe < nq;  both_both: both.
+ *   do           left:  add_to_query(q[--qws]), query_start = qws ? q[qws - 1].loc + 1 : 0;  add_to_reference(r[--rws]),
+ *                       ref_start likewise.   right: add_to_query(q[qwe++]), query_end = qwe < nq ? q[qwe].loc : len_q;
+ *                       add_to_reference(r[rwe++]), ref_end likewise.   both_both: left, then right.
+ *   undo         right: remove_from_reference(r[--rwe]), ref_end = r[rwe].loc;  remove_from_query(q[--qwe]),
+ *                       query_end = q[qwe].loc.   left: ref_start = r[rws].loc + 1, remove_from_reference(r[rws++]);
+ *                       query_start = q[qws].loc + 1, remove_from_query(q[qws++]).   both_both: right, then left.
+ * THE UNDO IS THESE REMOVES, NOT A RESTORE OF A SAVED STATE: they are not the inverse of the do steps.  An add_to_query that
+ * returned false is still undone by a remove_from_query that clears the bit and lowers query_size; a form that snapshots and
+ * restores gives other hits.
+ * out[t] = {query_start, query_end, ref_start, ref_end, J, qws, qwe, rws, rwe, flags}, aligned with rolls[t].
+ *
+ * SDF_EXTEND_MAX_GROW: the records by which either end of either side's winnow range may grow beyond its entry value in a
+ * wavefront's LDS.  1,792 records are some 15 kb of a k = 12, w = 16 sequence (two records in 17 bases) per end, and
+ * 1,024 + 3,072 + 4 * 1,792 keys of seven bytes are 77 KB: two wavefronts share a CU's 160 KB.  SDF_EXTEND_WIDE: a do step,
+ * kept or undone, would take a range beyond that growth; or the replay does not fit: the roll record carries SDF_ROLL_WIDE,
+ * n_members > SDF_SEARCH_MAX_MEMBERS, or winnow_end - lo > SDF_ROLL_MAX_SPAN.  The flag follows from the inputs and the walk
+ * alone.  The device form flags such an interval and writes the rest of its record as zero; sdf_search_extend completes it with
+ * the host form and keeps the flag.  SDF_EXTEND_NOLIMIT: an add_to_query needs limit[s] with s >= n_limit; the rest of the
+ * record is zero, in every form.  The two together: the cap is looked at for every side of a step (both sides of both_both)
+ * before the step's first add, and the device form ends there, so it writes WIDE alone whenever the growth comes first; the
+ * host form walks on, and when a later add then needs the table beyond its end the completed record is zero with
+ * WIDE | NOLIMIT.  WIDE is set by the same walk in every form; NOLIMIT without WIDE is the same in every form.  The device keeps a key in 32 bits as the roll does (hash < 2^30).
+ * Refusals as for sdf_search_roll, and SDF_ERR_INVALID for len_q < 0, rolls or params == NULL with an interval, a parameter
+ * that is not finite, max_error - max_edit_error <= 0;  SDF_ERR_UNSUPPORTED for len_q > 2^31 - 1, reserved != 0.  Every check
+ * precedes the first launch.  nq == 0 or no interval is SDF_OK without a launch. */
+#define SDF_EXTEND_SKIPPED 0x1
+#define SDF_EXTEND_WIDE 0x2
+#define SDF_EXTEND_NOLIMIT 0x4
+#define SDF_EXTEND_MAX_GROW 1792
+typedef struct { double max_error, max_edit_error; int32_t max_sd_size, same_genome; int32_t reserved[2]; /* 0 */ } sdf_extend_params;
+typedef struct { int32_t query_start, query_end, ref_start, ref_end, jaccard; int32_t q_winnow_start, q_winnow_end, r_winnow_start,
+                 r_winnow_end; uint32_t flags; } sdf_search_hit; /* 40 bytes */
+int sdf_search_extend(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                      const sdf_search_interval *intervals, const sdf_search_roll_rec *rolls, const sdf_filter_rec *filter /* or NULL */,
+                      const sdf_minimizer *r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *limit,
+                      size_t n_limit, const sdf_extend_params *params, sdf_search_hit *out /* first[nq] */);
+/* Device form: every array in HBM, nothing checked beyond the scalars, no host wait, behind sdf_search_filter_device on one
+ * stream: n_max wavefronts on `stream` (NULL: the context's own, synchronised before returning), those at or beyond
+ * d_first[nq] leave at once.  Nothing is written at or behind d_out[n_max].  A window whose query_size is outside the table or
+ * whose n_members is outside 1 .. nq - i answers SDF_EXTEND_SKIPPED.  n_max == 0 is SDF_OK without a launch. */
+int sdf_search_extend_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                             const uint64_t *d_first, const sdf_search_interval *d_intervals, const sdf_search_roll_rec *d_rolls,
+                             const sdf_filter_rec *d_filter /* or NULL */, size_t n_max, const sdf_minimizer *d_r, size_t nr,
+                             int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *d_limit, size_t n_limit,
+                             const sdf_extend_params *params, sdf_search_hit *d_out, void *stream);
+/* No context, no GPU: the same in plain C++ with a std::map, every interval (WIDE ones flagged and completed). */
+int sdf_search_extend_host(const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                           const sdf_search_interval *intervals, const sdf_search_roll_rec *rolls, const sdf_filter_rec *filter,
+                           const sdf_minimizer *r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *limit,
+                           size_t n_limit, const sdf_extend_params *params, sdf_search_hit *out /* first[nq] */);
+/* The filter task of every hit, for the reference's second filter() (src/search.cc:356): out[t] for hits[t], n of them.  The
+ * query side is positions [query_start, query_end) of the query sequence, the reference side [ref_start, ref_end) of the
+ * reference's; sequences, strands and pool offsets as for sdf_search_filter_tasks_*.  SDF_FILTER_SKIP (every other field zero)
+ * for a hit that carries SKIPPED or NOLIMIT, or WIDE on a record nobody completed (query_end == 0), or whose sides do not lie
+ * inside their sequences.  SDF_ERR_INVALID: hits or out == NULL with n > 0, a negative length or offset;
+ * SDF_ERR_UNSUPPORTED: n, len_q or len_r > 2^31 - 1.  The device form: one lane per hit on `stream`, no host wait; d_count
+ * (or NULL) points at the number of hits that were written -- d_first + nq behind sdf_search_extend_device --, and the lanes at
+ * or beyond it write a SKIP task without reading a hit, so that sdf_search_filter_device may take all n. */
+int sdf_search_hit_tasks_host(const sdf_search_hit *hits, size_t n, int64_t len_q, int64_t len_r, int64_t q_off, int q_rc,
+                              int64_t r_off, int r_rc, sdf_filter_task *out);
+int sdf_search_hit_tasks_device(sdf_ctx *ctx, const sdf_search_hit *d_hits, size_t n, const uint64_t *d_count, int64_t len_q,
+                                int64_t len_r, int64_t q_off, int q_rc, int64_t r_off, int r_rc, sdf_filter_task *d_out, void *stream);
 
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is

@@ -213,3 +213,45 @@ extern "C" int sdf_search_filter_tasks_device(sdf_ctx *ctx, const sdf_minimizer 
   if (!stream) SDF_HIP(hipStreamSynchronize(st));
   return SDF_OK;
 }
+
+// ---- the tasks of the hits (the reference's second filter(), src/search.cc:356) ----
+
+namespace {
+// what both forms of the hits' task builder check of their scalars
+int hit_tasks_scalars(size_t n, int64_t len_q, int64_t len_r, int64_t q_off, int64_t r_off, const char **why) {
+  if (len_q < 0 || len_r < 0 || q_off < 0 || r_off < 0) return *why = "search hit tasks: a negative length or offset", SDF_ERR_INVALID;
+  if (n > 0x7fffffffu || len_q > 0x7fffffff || len_r > 0x7fffffff)
+    return *why = "search hit tasks: more than 2^31 - 1 hits or bases in one call", SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+}  // namespace
+
+extern "C" int sdf_search_hit_tasks_host(const sdf_search_hit *hits, size_t n, int64_t len_q, int64_t len_r, int64_t q_off, int q_rc,
+                                         int64_t r_off, int r_rc, sdf_filter_task *out) {
+  if (n == 0) return SDF_OK;
+  const char *why = nullptr;
+  if (int rc = hit_tasks_scalars(n, len_q, len_r, q_off, r_off, &why)) return rc;
+  if (!hits || !out) return SDF_ERR_INVALID;
+  const FilterTaskArgs A{len_q, len_r, q_off, r_off, 0, q_rc != 0, r_rc != 0, 0};
+  for (size_t t = 0; t < n; t++) out[t] = hit_task_of(A, hits[t]);
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_hit_tasks_device(sdf_ctx *ctx, const sdf_search_hit *d_hits, size_t n, const uint64_t *d_count, int64_t len_q,
+                                           int64_t len_r, int64_t q_off, int q_rc, int64_t r_off, int r_rc, sdf_filter_task *d_out,
+                                           void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (n == 0) return SDF_OK;
+  const char *why = nullptr;
+  if (int rc = hit_tasks_scalars(n, len_q, len_r, q_off, r_off, &why)) return refuse(ctx, rc, why);
+  if (!d_hits || !d_out) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_hit_tasks_device: invalid arguments");
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  const FilterTaskArgs A{len_q, len_r, q_off, r_off, 0, q_rc != 0, r_rc != 0, 0};
+  hipLaunchKernelGGL(search_hit_tasks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_hits, (int)n, d_count, A, d_out);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += 1;
+  if (!stream) SDF_HIP(hipStreamSynchronize(st));
+  return SDF_OK;
+}

@@ -261,5 +261,58 @@ __host__ __device__ inline sdf_filter_task filter_task_of(const FilterTaskArgs &
 __global__ void search_filter_tasks_kernel(const sdf_minimizer *, int, const sdf_search_window *, const uint64_t *,
                                            const sdf_search_interval *, const sdf_search_roll_rec *, int, FilterTaskArgs,
                                            sdf_filter_task *);
+// search_extend.hip
+// a wavefront's LDS: the members and the roll span, and EXT_GROW records on either end of either side; seven bytes a key
+constexpr int EXT_GROW = SDF_EXTEND_MAX_GROW, EXT_MAX_Q = SEARCH_MAX_MEMBERS + 2 * EXT_GROW, EXT_MAX_R = ROLL_MAX_SPAN + 2 * EXT_GROW,
+              EXT_MAX_KEYS = EXT_MAX_Q + EXT_MAX_R;
+static_assert(EXT_MAX_KEYS < 65535 && 7 * EXT_MAX_KEYS <= 80 * 1024, "search_extend.hip: slots are 16 bits wide, two wavefronts share a CU's 160 KB");
+static_assert(sizeof(sdf_search_hit) == 40 && sizeof(sdf_extend_params) == 32, "include/sedef_hip.h");
+// Which intervals run, which do not fit a wavefront's replay, and the three stop tests of a round (0: go on; 1: aln_len >
+// max_match, 2: the length ratio, 3: the overlap of one genome) as include/sedef_hip.h states them: the one form the kernel and
+// the host form share.  lo: the first record of r with loc >= the interval's start.
+__host__ __device__ inline bool extend_skips(const sdf_search_roll_rec &R, const sdf_filter_rec *F, const long long lo, const long long nr) {
+  if (R.jaccard < 0 || (R.flags & SDF_ROLL_BADWINDOW) || ((R.flags & SDF_ROLL_WIDE) && R.ref_end == 0)) return true;
+  if (F && (F->flags & (SDF_FILTER_UPPER_FAIL | SDF_FILTER_QGRAM_FAIL | SDF_FILTER_SKIPPED))) return true;
+  return !(lo <= R.winnow_start && R.winnow_start <= R.winnow_end && R.winnow_end <= nr);
+}
+__host__ __device__ inline bool extend_replay_wide(const sdf_search_roll_rec &R, const int n_members, const long long lo) {
+  return (R.flags & SDF_ROLL_WIDE) || n_members > SEARCH_MAX_MEMBERS || R.winnow_end - lo > ROLL_MAX_SPAN;
+}
+__host__ __device__ inline int extend_stops(const sdf_extend_params &P, const int qs, const int qe, const int rs, const int re) {
+#pragma clang fp contract(off)
+  const double gap = P.max_error - P.max_edit_error;
+  int max_match = P.max_sd_size;
+  if (P.same_genome) {
+    const int apart = qs > rs ? qs - rs : rs - qs;
+    const double v = (1.0 / gap + .5) * apart;
+    const int m = v >= 2147483647.0 ? 2147483647 : v <= -2147483648.0 ? (int)-2147483647 - 1 : v != v ? 0 : (int)v;
+    max_match = m < max_match ? m : max_match;
+  }
+  const int a = qe - qs, b = re - rs, aln_len = a > b ? a : b, seq_len = a > b ? b : a;
+  if (aln_len > max_match) return 1;
+  if (100.0 * (double)seq_len / (double)aln_len < 100 * (1 - 2 * gap)) return 2;
+  if (P.same_genome) {
+    const int overlap = qe - rs;
+    if (overlap > 0 && 100.0 * (double)overlap / (double)b > 100 * P.max_error) return 3;
+  }
+  return 0;
+}
+__global__ void search_extend_kernel(const sdf_minimizer *, int, const sdf_search_window *, const uint64_t *, const sdf_search_interval *,
+                                     const sdf_search_roll_rec *, const sdf_filter_rec *, const sdf_minimizer *, int, long long, long long, int,
+                                     const int32_t *, int, sdf_extend_params, sdf_search_hit *);
+// the filter task of a hit (include/sedef_hip.h: sdf_search_hit_tasks_*); of A, init_len and allow_extend are not read
+__host__ __device__ inline sdf_filter_task hit_task_of(const FilterTaskArgs &A, const sdf_search_hit &H) {
+  const sdf_filter_task skip{0, 0, 0, 0, SDF_FILTER_SKIP, 0};
+  if ((H.flags & (SDF_EXTEND_SKIPPED | SDF_EXTEND_NOLIMIT)) || ((H.flags & SDF_EXTEND_WIDE) && H.query_end == 0)) return skip;
+  const long long qa = H.query_start, qb = H.query_end, ra = H.ref_start, rb = H.ref_end;
+  if (qa < 0 || qb < qa || qb > A.len_q || ra < 0 || rb < ra || rb > A.len_r) return skip;
+  sdf_filter_task O;
+  O.q_off = A.q_rc ? A.q_off + A.len_q - qb : A.q_off + qa;
+  O.r_off = A.r_rc ? A.r_off + A.len_r - rb : A.r_off + ra;
+  O.q_len = (int32_t)(qb - qa), O.r_len = (int32_t)(rb - ra);
+  O.flags = (A.q_rc ? SDF_FILTER_Q_RC : 0u) | (A.r_rc ? SDF_FILTER_R_RC : 0u), O.reserved = 0;
+  return O;
+}
+__global__ void search_hit_tasks_kernel(const sdf_search_hit *, int, const uint64_t *, FilterTaskArgs, sdf_filter_task *);
 
 }  // namespace sdf

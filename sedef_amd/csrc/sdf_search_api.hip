@@ -1,6 +1,7 @@
 // The C ABI: search seeding, the reference intervals of every query window (search_seeds.hip; include/sedef_hip.h states the
 // seven steps), and the roll of every interval to its best initial match (search_roll.hip; the header states its rules).
 // sdf_search_windows_host and sdf_search_roll_host are those in plain C++; the host forms complete with them what the kernels leave.
+// Behind them the extension of every rolled interval to its hit (search_extend.hip), sdf_search_extend_host likewise.
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
@@ -331,6 +332,33 @@ int roll_arrays(const RollArgs &A, const void *out, const char **why) {
   return SDF_OK;
 }
 
+// The walk of include/sedef_hip.h (steps 1 to 5) for interval T, from event to event; span0: the first record with
+// loc >= T.start.  eval(s, e, ws, we) at every evaluation of J -- step 4 and every round with an event --; true ends the walk.
+template <class Add, class Remove, class Eval>
+void roll_walk(const RollArgs &A, const sdf_search_interval &T, size_t span0, Add add, Remove remove, Eval eval) {
+  const sdf_minimizer *r = A.r;
+  const int64_t len_r = A.len_r, init_len = A.init_len;
+  int64_t s = T.start, e = std::min(s + init_len, len_r);
+  size_t ws = span0, we = span0;
+  while (we < A.nr && (int64_t)r[we].loc < e) add(r[we++]);
+  if (eval(s, e, ws, we)) return;
+  while (s < T.end && e < len_r) {  // (e was not clamped: e == s + init_len)
+    // the next step with an event: a remove at the first s' >= s with loc <= s', an add at loc == s' + init_len
+    int64_t next = -1;
+    if (ws < A.nr) next = std::max<int64_t>(r[ws].loc, s);
+    if (we < A.nr && (int64_t)r[we].loc >= e) {
+      const int64_t at = (int64_t)r[we].loc - init_len;
+      next = next < 0 || at < next ? at : next;
+    }
+    if (next < 0 || next >= T.end || next + init_len >= len_r) break;
+    s = next, e = next + init_len;
+    if (ws < A.nr && (int64_t)r[ws].loc <= s) remove(r[ws++]);
+    if (we < A.nr && (int64_t)r[we].loc == e) add(r[we++]);
+    if (eval(s, e, ws, we)) return;
+    s++, e++;
+  }
+}
+
 // Interval T of window i as include/sedef_hip.h states it: a map in place of the reference's, the walk from event to event.
 void roll_one(const RollArgs &A, size_t i, const sdf_search_interval &T, sdf_search_roll_rec &R, std::map<uint64_t, uint8_t> &M) {
   const sdf_search_window &W = A.windows[i];
@@ -377,27 +405,13 @@ void roll_one(const RollArgs &A, size_t i, const sdf_search_interval &T, sdf_sea
     else it->second = 1;
   };
   const auto J = [&]() { return (int32_t)(I >= L ? I : I - L); };
-  const int64_t len_r = A.len_r, init_len = A.init_len;
-  int64_t s = T.start, e = std::min(s + init_len, len_r);
-  size_t ws = span0, we = span0;
-  while (we < A.nr && (int64_t)r[we].loc < e) add(r[we++]);
-  R.ref_start = (int32_t)s, R.ref_end = (int32_t)e, R.winnow_start = (int32_t)ws, R.winnow_end = (int32_t)we, R.jaccard = J();
-  while (s < T.end && e < len_r) {  // (e was not clamped: e == s + init_len)
-    // the next step with an event: a remove at the first s' >= s with loc <= s', an add at loc == s' + init_len
-    int64_t next = -1;
-    if (ws < A.nr) next = std::max<int64_t>(r[ws].loc, s);
-    if (we < A.nr && (int64_t)r[we].loc >= e) {
-      const int64_t at = (int64_t)r[we].loc - init_len;
-      next = next < 0 || at < next ? at : next;
-    }
-    if (next < 0 || next >= T.end || next + init_len >= len_r) break;
-    s = next, e = next + init_len;
-    if (ws < A.nr && (int64_t)r[ws].loc <= s) remove(r[ws++]);
-    if (we < A.nr && (int64_t)r[we].loc == e) add(r[we++]);
-    if (J() > R.jaccard)
+  bool any = false;
+  roll_walk(A, T, span0, add, remove, [&](int64_t s, int64_t e, size_t ws, size_t we) {
+    if (!any || J() > R.jaccard)
       R.ref_start = (int32_t)s, R.ref_end = (int32_t)e, R.winnow_start = (int32_t)ws, R.winnow_end = (int32_t)we, R.jaccard = J();
-    s++, e++;
-  }
+    any = true;
+    return false;
+  });
 }
 
 // the launch: n wavefronts on `st`
@@ -498,5 +512,268 @@ extern "C" int sdf_search_roll(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, 
   for (size_t i = 0; i < nq; i++)
     for (uint64_t t = first[i]; t < first[i + 1]; t++)
       if (out[t].flags & SDF_ROLL_WIDE) roll_one(A, i, intervals[t], out[t], M);
+  return SDF_OK;
+}
+
+// ---- the extension ----
+
+namespace {
+struct ExtendArgs {
+  RollArgs R;
+  const sdf_search_roll_rec *rolls;
+  const sdf_filter_rec *filter;  // or null
+  int64_t len_q;
+  sdf_extend_params P;
+};
+
+int extend_scalars(int64_t len_q, const sdf_extend_params *P, const char **why) {
+  if (!P) return *why = "search extend: invalid arguments", SDF_ERR_INVALID;
+  if (len_q < 0) return *why = "search extend: len_q < 0", SDF_ERR_INVALID;
+  if (!std::isfinite(P->max_error) || !std::isfinite(P->max_edit_error)) return *why = "search extend: a parameter that is not finite", SDF_ERR_INVALID;
+  if (!(P->max_error - P->max_edit_error > 0)) return *why = "search extend: max_error - max_edit_error <= 0", SDF_ERR_INVALID;
+  if (len_q > 0x7fffffff) return *why = "search extend: more than 2^31 - 1 query bases", SDF_ERR_UNSUPPORTED;
+  if (P->reserved[0] || P->reserved[1]) return *why = "search extend: reserved != 0", SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+
+// The SlidingMap of include/sedef_hip.h: bits by key (a key is stored while its bits are not 0), the boundary key B or none, I.
+struct ExtendMap {
+  std::map<uint64_t, uint8_t> M;
+  bool has_B = false;
+  uint64_t B = 0;
+  int64_t I = 0;
+  bool full(uint64_t k) const {
+    const auto it = M.find(k);
+    return it != M.end() && it->second == 3;
+  }
+  void to_below() {  // B = the largest stored key below B, or none
+    auto it = M.lower_bound(B);
+    if (it == M.begin()) has_B = false;
+    else B = std::prev(it)->first;
+  }
+  bool to_above() {  // B = the smallest stored key above B; false, and B stays: there is none
+    const auto it = M.upper_bound(B);
+    if (it == M.end()) return false;
+    B = it->first;
+    return true;
+  }
+  bool add(uint64_t k, uint8_t BIT, bool counted) {
+    uint8_t &b = M[k];
+    if (b & BIT) return false;
+    const uint8_t was = b;
+    b |= BIT;
+    if (counted && has_B && k < B) {
+      I += b == 3;
+      if (was == 0) {
+        I -= full(B);
+        to_below();
+      }
+    }
+    return true;
+  }
+  bool remove(uint64_t k, uint8_t BIT, bool counted) {
+    const auto it = M.find(k);
+    if (it == M.end() || !(it->second & BIT)) return false;
+    if (counted && has_B && k <= B) {
+      I -= it->second == 3;
+      if (it->second == BIT && to_above()) I += full(B);
+    }
+    if (it->second == BIT) M.erase(it);
+    else it->second &= (uint8_t)~BIT;
+    return true;
+  }
+};
+
+// Interval t of window i as include/sedef_hip.h states it: the entry state by the roll's walk, then the extension.
+void extend_one(const ExtendArgs &A, size_t i, uint64_t t, sdf_search_hit &H, ExtendMap &S) {
+  const RollArgs &RA = A.R;
+  const sdf_search_window &W = RA.windows[i];
+  const sdf_search_interval &T = RA.intervals[t];
+  const sdf_search_roll_rec &Roll = A.rolls[t];
+  const sdf_minimizer *q = RA.q, *r = RA.r;
+  const int64_t nq = (int64_t)RA.nq, nr = (int64_t)RA.nr;
+  H = sdf_search_hit{0, 0, 0, 0, 0, 0, 0, 0, 0, 0u};
+  const int64_t lo = std::lower_bound(r, r + nr, (int64_t)T.start, [](const sdf_minimizer &m, int64_t loc) { return (int64_t)m.loc < loc; }) - r;
+  if (extend_skips(Roll, A.filter ? &A.filter[t] : nullptr, lo, nr)) {
+    H.flags = SDF_EXTEND_SKIPPED;
+    return;
+  }
+  bool wide = extend_replay_wide(Roll, W.n_members, lo), nolimit = false;
+  // the entry state
+  S.M.clear();
+  for (int32_t j = 0; j < W.n_members; j++) S.M[search_host_key(q[i + j])] = 1;
+  S.has_B = true, S.B = std::prev(S.M.end())->first, S.I = 0;
+  const int64_t rws0 = Roll.winnow_start, rwe0 = Roll.winnow_end;
+  roll_walk(
+      RA, T, (size_t)lo, [&](const sdf_minimizer &m) { m.status == 2 ? false : S.add(search_host_key(m), 2, true); },
+      [&](const sdf_minimizer &m) { m.status == 2 ? false : S.remove(search_host_key(m), 2, true); },
+      [&](int64_t, int64_t, size_t ws, size_t we) { return (int64_t)ws >= rws0 && (int64_t)we >= rwe0; });
+  int64_t qsz = W.query_size, L = RA.limit[qsz];
+  int64_t qws = (int64_t)i, qwe = (int64_t)i + W.n_members, rws = rws0, rwe = rwe0;
+  const int64_t qws0 = qws, qwe0 = qwe;
+  const auto add_to_query = [&](const sdf_minimizer &m) {
+    if (!S.add(search_host_key(m), 1, qsz != 0)) return;
+    if (++qsz >= (int64_t)RA.n_limit) {
+      nolimit = true;
+      return;
+    }
+    L = RA.limit[qsz];
+    if (!S.has_B) S.has_B = true, S.B = S.M.begin()->first;
+    else S.to_above();
+    S.I += S.full(S.B);
+  };
+  const auto remove_from_query = [&](const sdf_minimizer &m) {
+    if (!S.remove(search_host_key(m), 1, qsz != 0)) return;
+    if (qsz > 0) --qsz;
+    L = RA.limit[qsz];
+    if (!S.has_B) return;
+    S.I -= S.full(S.B);
+    S.to_below();
+  };
+  const auto add_to_reference = [&](const sdf_minimizer &m) {
+    if (m.status != 2) S.add(search_host_key(m), 2, qsz != 0);
+  };
+  const auto remove_from_reference = [&](const sdf_minimizer &m) {
+    if (m.status != 2) S.remove(search_host_key(m), 2, qsz != 0);
+  };
+  const auto J = [&]() { return (int32_t)(S.I >= L ? S.I : S.I - L); };
+  int32_t qs = qws ? q[qws - 1].loc + 1 : 0, qe = qwe < nq ? (int32_t)q[qwe].loc : (int32_t)A.len_q;
+  int32_t rs = rws ? r[rws - 1].loc + 1 : 0, re = rwe < nr ? (int32_t)r[rwe].loc : (int32_t)RA.len_r;
+  while (!nolimit && !extend_stops(A.P, qs, qe, rs, re)) {
+    bool extended = false;
+    for (int way = 0; way < 3 && !extended && !nolimit; way++) {  // both_both, both_right, both_left
+      const bool left = way != 1, right = way != 2;
+      if (left && (!qws || !rws)) continue;
+      if (right && (rwe >= nr || qwe >= nq)) continue;
+      // the growth cap, for every side of the step before its first add (the kernel ends here)
+      wide |= left && (qws0 - qws >= SDF_EXTEND_MAX_GROW || rws0 - rws >= SDF_EXTEND_MAX_GROW);
+      wide |= right && (qwe - qwe0 >= SDF_EXTEND_MAX_GROW || rwe - rwe0 >= SDF_EXTEND_MAX_GROW);
+      if (left) {
+        add_to_query(q[--qws]), qs = qws ? q[qws - 1].loc + 1 : 0;
+        add_to_reference(r[--rws]), rs = rws ? r[rws - 1].loc + 1 : 0;
+      }
+      if (right && !nolimit) {
+        add_to_query(q[qwe++]), qe = qwe < nq ? (int32_t)q[qwe].loc : (int32_t)A.len_q;
+        add_to_reference(r[rwe++]), re = rwe < nr ? (int32_t)r[rwe].loc : (int32_t)RA.len_r;
+      }
+      if (nolimit) break;
+      if (J() >= 0) {
+        extended = true;
+        break;
+      }
+      if (right) {  // the reference's undo: removes in its order, not a restore
+        remove_from_reference(r[--rwe]), re = (int32_t)r[rwe].loc;
+        remove_from_query(q[--qwe]), qe = (int32_t)q[qwe].loc;
+      }
+      if (left) {
+        rs = (int32_t)r[rws].loc + 1, remove_from_reference(r[rws++]);
+        qs = (int32_t)q[qws].loc + 1, remove_from_query(q[qws++]);
+      }
+    }
+    if (!extended) break;
+  }
+  if (nolimit) {
+    H.flags = SDF_EXTEND_NOLIMIT | (wide ? (uint32_t)SDF_EXTEND_WIDE : 0u);
+    return;
+  }
+  H = sdf_search_hit{qs, qe, rs, re, J(), (int32_t)qws, (int32_t)qwe, (int32_t)rws, (int32_t)rwe, wide ? (uint32_t)SDF_EXTEND_WIDE : 0u};
+}
+
+int extend_launch(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows, const uint64_t *d_first,
+                  const sdf_search_interval *d_intervals, const sdf_search_roll_rec *d_rolls, const sdf_filter_rec *d_filter, size_t n,
+                  const sdf_minimizer *d_r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *d_limit, size_t n_limit,
+                  const sdf_extend_params &P, sdf_search_hit *d_out, hipStream_t st) {
+  hipLaunchKernelGGL(search_extend_kernel, dim3((unsigned)n), dim3(64), 0, st, d_q, (int)nq, d_windows, d_first, d_intervals, d_rolls, d_filter,
+                     d_r, (int)nr, (long long)len_q, (long long)len_r, (int)init_len, d_limit, (int)n_limit, P, d_out);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += 1;
+  return SDF_OK;
+}
+}  // namespace
+
+extern "C" int sdf_search_extend_host(const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                                      const sdf_search_interval *intervals, const sdf_search_roll_rec *rolls, const sdf_filter_rec *filter,
+                                      const sdf_minimizer *r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *limit,
+                                      size_t n_limit, const sdf_extend_params *params, sdf_search_hit *out) {
+  if (nq == 0) return SDF_OK;
+  const RollArgs RA{q, nq, windows, first, intervals, r, nr, len_r, init_len, limit, n_limit};
+  const char *why = nullptr;
+  if (int rc = roll_arrays(RA, out, &why)) return rc;
+  if (first[nq] == 0) return SDF_OK;
+  if (!rolls) return SDF_ERR_INVALID;
+  if (int rc = extend_scalars(len_q, params, &why)) return rc;
+  const ExtendArgs A{RA, rolls, filter, len_q, *params};
+  ExtendMap S;
+  for (size_t i = 0; i < nq; i++)
+    for (uint64_t t = first[i]; t < first[i + 1]; t++) extend_one(A, i, t, out[t], S);
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_extend_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                                        const uint64_t *d_first, const sdf_search_interval *d_intervals, const sdf_search_roll_rec *d_rolls,
+                                        const sdf_filter_rec *d_filter, size_t n_max, const sdf_minimizer *d_r, size_t nr, int64_t len_q,
+                                        int64_t len_r, int32_t init_len, const int32_t *d_limit, size_t n_limit,
+                                        const sdf_extend_params *params, sdf_search_hit *d_out, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0 || n_max == 0) return SDF_OK;
+  if (!d_q || !d_windows || !d_first || !d_intervals || !d_rolls || !d_r || !d_limit || !d_out)
+    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_extend_device: invalid arguments");
+  const char *why = nullptr;
+  if (int rc = roll_scalars(nq, n_max, nr, len_r, init_len, n_limit, &why)) return refuse(ctx, rc, why);
+  if (int rc = extend_scalars(len_q, params, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = extend_launch(ctx, d_q, nq, d_windows, d_first, d_intervals, d_rolls, d_filter, n_max, d_r, nr, len_q, len_r, init_len, d_limit,
+                             n_limit, *params, d_out, st))
+    return rc;
+  if (!stream) SDF_HIP(hipStreamSynchronize(st));
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_extend(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
+                                 const sdf_search_interval *intervals, const sdf_search_roll_rec *rolls, const sdf_filter_rec *filter,
+                                 const sdf_minimizer *r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *limit,
+                                 size_t n_limit, const sdf_extend_params *params, sdf_search_hit *out) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0) return SDF_OK;
+  const RollArgs RA{q, nq, windows, first, intervals, r, nr, len_r, init_len, limit, n_limit};
+  const char *why = nullptr;
+  if (int rc = roll_arrays(RA, out, &why)) return refuse(ctx, rc, why);
+  const size_t n = (size_t)first[nq];
+  if (n == 0) return SDF_OK;
+  if (!rolls) return refuse(ctx, SDF_ERR_INVALID, "search extend: invalid arguments");
+  if (int rc = extend_scalars(len_q, params, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  struct Copy {
+    DevBuf &buf;
+    const void *src;
+    size_t bytes;
+  } copies[] = {{ctx->sr_q, q, nq * sizeof(sdf_minimizer)},          {ctx->sr_win, windows, nq * sizeof(sdf_search_window)},
+                {ctx->sr_first, first, (nq + 1) * 8},                {ctx->sr_iv, intervals, n * sizeof(sdf_search_interval)},
+                {ctx->sr_r, r, nr * sizeof(sdf_minimizer)},          {ctx->sr_limit, limit, n_limit * 4},
+                {ctx->se_rolls, rolls, n * sizeof(sdf_search_roll_rec)}, {ctx->se_filter, filter, filter ? n * sizeof(sdf_filter_rec) : 0}};
+  for (Copy &c : copies) {
+    if (!c.bytes) continue;
+    SDF_HIP(c.buf.reserve(c.bytes));
+    SDF_HIP(hipMemcpyAsync(c.buf.p, c.src, c.bytes, hipMemcpyHostToDevice, st));
+  }
+  SDF_HIP(ctx->se_out.reserve(n * sizeof(sdf_search_hit)));
+  if (int rc = extend_launch(ctx, (const sdf_minimizer *)ctx->sr_q.p, nq, (const sdf_search_window *)ctx->sr_win.p,
+                             (const uint64_t *)ctx->sr_first.p, (const sdf_search_interval *)ctx->sr_iv.p,
+                             (const sdf_search_roll_rec *)ctx->se_rolls.p, filter ? (const sdf_filter_rec *)ctx->se_filter.p : nullptr, n,
+                             (const sdf_minimizer *)ctx->sr_r.p, nr, len_q, len_r, init_len, (const int32_t *)ctx->sr_limit.p, n_limit, *params,
+                             (sdf_search_hit *)ctx->se_out.p, st))
+    return rc;
+  SDF_HIP(hipMemcpyAsync(out, ctx->se_out.p, n * sizeof(sdf_search_hit), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  // the WIDE intervals, on the host
+  const ExtendArgs A{RA, rolls, filter, len_q, *params};
+  ExtendMap S;
+  for (size_t i = 0; i < nq; i++)
+    for (uint64_t t = first[i]; t < first[i + 1]; t++)
+      if (out[t].flags & SDF_EXTEND_WIDE) extend_one(A, i, t, out[t], S);
   return SDF_OK;
 }

@@ -1,4 +1,4 @@
-// Device helpers the search kernels share (search_seeds.hip, search_roll.hip): a workgroup is ONE wavefront, its keys lie in LDS.
+// Device helpers the search kernels share (search_seeds.hip, search_roll.hip, search_extend.hip): a workgroup is ONE wavefront, its keys lie in LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -73,6 +73,126 @@ __device__ __forceinline__ int search_wave_bound(const int n, P pred, const int 
     }
   }
   return lo;
+}
+
+// A key of the roll and the extension in 32 bits: status << 30 | hash (hash < 2^30: the header's contract).
+__device__ __forceinline__ uint32_t roll_key(const sdf_minimizer &M) { return ((uint32_t)M.status & 3u) << 30 | (M.hash & 0x3FFFFFFFu); }
+
+// the slot of a key that is among keys[0 .. nd)
+__device__ __forceinline__ int roll_slot(const uint32_t *keys, const int nd, const uint32_t key) {
+  int lo = 0, hi = nd - 1;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (keys[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// The sort and the slots of the keys in keys[0 .. n): keys[0 .. nd) are the distinct keys in ascending order and bits[] is 0 on
+// them afterwards; returns nd.  (The caller looks its records' slots up with roll_slot and syncs before it reuses keys[].)
+__device__ __forceinline__ int search_slots_setup(uint32_t *keys, uint8_t *bits, const int n, const int lane) {
+  __syncthreads();
+  search_sort_u32(keys, n, lane);
+  const int nd = search_compact_u32(keys, n, lane);
+  for (int x = lane; x < nd; x += 64) bits[x] = 0;
+  __syncthreads();
+  return nd;
+}
+
+// The SlidingMap of include/sedef_hip.h over slots: bits[slot], the boundary slot B (-1: none) and the counter I.  Wave-uniform:
+// every lane carries B and I and makes every write to bits[] itself, so a lane reads back only what it wrote and nothing here
+// needs a barrier.  The boundary's predecessor and successor are the one place the lanes share work: 64 neighbouring slots a
+// round, a ballot over bits != 0.
+struct SearchMap {
+  uint8_t *bits;
+  int nd, B, I;
+  __device__ __forceinline__ int bit(const int sl) const { return __builtin_amdgcn_readfirstlane((int)bits[sl]); }
+  __device__ __forceinline__ bool full(const int sl) const { return sl >= 0 && bit(sl) == 3; }
+  // the largest stored slot below b (-1: none), the smallest above b (nd: none)
+  __device__ __forceinline__ int below(const int b, const int lane) const {
+    for (int base = b - 1; base >= 0; base -= 64) {
+      const int x = base - lane;
+      const unsigned long long m = __ballot(x >= 0 && bits[x] != 0);
+      if (m) return base - __builtin_ctzll(m);
+    }
+    return -1;
+  }
+  __device__ __forceinline__ int above(const int b, const int lane) const {
+    for (int base = b + 1; base < nd; base += 64) {
+      const int x = base + lane;
+      const unsigned long long m = __ballot(x < nd && bits[x] != 0);
+      if (m) return base + __builtin_ctzll(m);
+    }
+    return nd;
+  }
+  // add(k, BIT) and remove(k, BIT) of the header; counted: query_size != 0
+  __device__ __forceinline__ bool add(const int sl, const int BIT, const bool counted, const int lane) {
+    const int b = bit(sl);
+    if (b & BIT) return false;
+    bits[sl] = (uint8_t)(b | BIT);
+    if (counted && sl < B) {
+      I += (b | BIT) == 3 ? 1 : 0;
+      if (b == 0) {
+        I -= full(B) ? 1 : 0;
+        B = below(B, lane);  // sl at the latest
+      }
+    }
+    return true;
+  }
+  __device__ __forceinline__ bool remove(const int sl, const int BIT, const bool counted, const int lane) {
+    const int b = bit(sl);
+    if (!(b & BIT)) return false;
+    if (counted && sl <= B) {
+      I -= b == 3 ? 1 : 0;
+      if (b == BIT) {
+        const int up = above(B, lane);
+        if (up < nd) {
+          B = up;
+          I += full(B) ? 1 : 0;
+        }
+      }
+    }
+    bits[sl] = (uint8_t)(b & ~BIT);
+    return true;
+  }
+};
+
+// The roll's walk (include/sedef_hip.h, steps 1 to 5) over the span's records x = 0 .. nspan): slot[x] (no_slot: status 2) and
+// locs[x] in LDS.  It jumps from event to event (a step without one cannot change J).  eval(s, e, ws, we) is called at every
+// evaluation of J -- step 4 and every round with an event -- and ends the walk by returning true.  ws, we count from the span's
+// first record.
+template <class F>
+__device__ __forceinline__ void search_roll_walk(SearchMap &S, const uint16_t *slot, const int32_t *locs, const int nspan, const long long start,
+                                                 const long long end, const int init_len, const long long len_r, const int lane, F eval) {
+  constexpr int no_slot = 0xFFFF;
+  auto add = [&](int x) {
+    const int sl = __builtin_amdgcn_readfirstlane((int)slot[x]);
+    if (sl != no_slot) S.add(sl, 2, true, lane);
+  };
+  auto remove = [&](int x) {
+    const int sl = __builtin_amdgcn_readfirstlane((int)slot[x]);
+    if (sl != no_slot) S.remove(sl, 2, true, lane);
+  };
+  long long s = start, e = start + init_len < len_r ? start + init_len : len_r;
+  int ws = 0, we = 0;
+  while (we < nspan && (long long)locs[we] < e) add(we++);
+  if (eval(s, e, ws, we)) return;
+  while (s < end && e < len_r) {  // (e was not clamped: e == s + init_len)
+    // the next step with an event: a remove at the first s' >= s with loc <= s', an add at loc == s' + init_len
+    long long next = -1;
+    if (ws < nspan) next = (long long)locs[ws] > s ? (long long)locs[ws] : s;
+    if (we < nspan && (long long)locs[we] >= e) {
+      const long long at = (long long)locs[we] - init_len;
+      next = next < 0 || at < next ? at : next;
+    }
+    if (next < 0 || next >= end || next + init_len >= len_r) break;
+    s = next, e = next + init_len;
+    if (ws < nspan && (long long)locs[ws] <= s) remove(ws++);
+    if (we < nspan && (long long)locs[we] == e) add(we++);
+    if (eval(s, e, ws, we)) return;
+    s++, e++;
+  }
 }
 
 }  // namespace sdf

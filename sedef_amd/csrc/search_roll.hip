@@ -23,19 +23,6 @@
 
 namespace sdf {
 
-__device__ __forceinline__ uint32_t roll_key(const sdf_minimizer &M) { return ((uint32_t)M.status & 3u) << 30 | (M.hash & 0x3FFFFFFFu); }
-
-// the slot of a key that is among keys[0 .. nd)
-__device__ __forceinline__ int roll_slot(const uint32_t *keys, const int nd, const uint32_t key) {
-  int lo = 0, hi = nd - 1;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (keys[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 template <bool WALK>
 __global__ __launch_bounds__(64) void search_roll_kernel(const sdf_minimizer *__restrict__ q, int nq, const sdf_search_window *__restrict__ windows,
                                                          const uint64_t *__restrict__ first, const sdf_search_interval *__restrict__ intervals,
@@ -72,12 +59,7 @@ __global__ __launch_bounds__(64) void search_roll_kernel(const sdf_minimizer *__
     const sdf_minimizer M = r[lo + x];
     keys[nm + x] = M.status == 2 ? roll_key(q[i]) : roll_key(M);
   }
-  __syncthreads();
-  search_sort_u32(keys, nm + nspan, lane);
-  const int nd = search_compact_u32(keys, nm + nspan, lane);
-  // slots
-  for (int x = lane; x < nd; x += 64) bits[x] = 0;
-  __syncthreads();
+  const int nd = search_slots_setup(keys, bits, nm + nspan, lane);  // slots
   int B = 0;
   for (int j = lane; j < nm; j += 64) {
     const int sl = roll_slot(keys, nd, roll_key(q[i + j]));
@@ -103,72 +85,16 @@ __global__ __launch_bounds__(64) void search_roll_kernel(const sdf_minimizer *__
     return;
   }
   // the walk: wave-uniform from here on
-  int I = 0;
-  auto stored = [&](int x, int n) { return x >= 0 && x < n && bits[x] != 0; };
-  auto add = [&](int x) {
-    const int sl = __builtin_amdgcn_readfirstlane((int)slot[x]);
-    if (sl == kNoSlot) return;
-    const int b = __builtin_amdgcn_readfirstlane((int)bits[sl]);
-    if (b & 2) return;
-    if (b == 1) {
-      bits[sl] = 3;
-      I += sl < B ? 1 : 0;
-      return;
-    }
-    bits[sl] = 2;
-    if (sl >= B) return;
-    I -= __builtin_amdgcn_readfirstlane((int)bits[B]) == 3 ? 1 : 0;
-    for (int base = B - 1; base >= 0; base -= 64) {  // the largest stored slot below B: sl at the latest
-      const unsigned long long m = __ballot(stored(base - lane, nd));
-      if (m) {
-        B = base - __builtin_ctzll(m);
-        break;
-      }
-    }
-  };
-  auto remove = [&](int x) {
-    const int sl = __builtin_amdgcn_readfirstlane((int)slot[x]);
-    if (sl == kNoSlot) return;
-    const int b = __builtin_amdgcn_readfirstlane((int)bits[sl]);
-    if (!(b & 2)) return;
-    if (sl <= B) {
-      I -= b == 3 ? 1 : 0;
-      if (b == 2) {
-        for (int base = B + 1; base < nd; base += 64) {  // the smallest stored slot above B (a member's: as many slots are stored at or below B as there are member keys)
-          const unsigned long long m = __ballot(stored(base + lane, nd));
-          if (m) {
-            B = base + __builtin_ctzll(m);
-            I += __builtin_amdgcn_readfirstlane((int)bits[B]) == 3 ? 1 : 0;
-            break;
-          }
-        }
-      }
-    }
-    bits[sl] = (uint8_t)(b & 1);
-  };
-  auto J = [&]() { return I >= L ? I : I - L; };
-  const long long end = T.end;
-  long long s = start, e = start + init_len < len_r ? start + init_len : len_r;
-  int ws = 0, we = 0;  // counted from lo
-  while (we < nspan && (long long)locs[we] < e) add(we++);
-  long long best_s = s, best_e = e;
-  int best_ws = ws, best_we = we, best_J = J();
-  while (s < end && e < len_r) {  // (e was not clamped: e == s + init_len)
-    // the next step with an event: a remove at the first s' >= s with loc <= s', an add at loc == s' + init_len
-    long long next = -1;
-    if (ws < nspan) next = (long long)locs[ws] > s ? (long long)locs[ws] : s;
-    if (we < nspan && (long long)locs[we] >= e) {
-      const long long at = (long long)locs[we] - init_len;
-      next = next < 0 || at < next ? at : next;
-    }
-    if (next < 0 || next >= end || next + init_len >= len_r) break;
-    s = next, e = next + init_len;
-    if (ws < nspan && (long long)locs[ws] <= s) remove(ws++);
-    if (we < nspan && (long long)locs[we] == e) add(we++);
-    const int now = J();
-    if (now > best_J) best_s = s, best_e = e, best_ws = ws, best_we = we, best_J = now;
-    s++, e++;
-  }
+  SearchMap S{bits, nd, B, 0};
+  long long best_s = 0, best_e = 0;
+  int best_ws = 0, best_we = 0, best_J = 0;
+  bool any = false;
+  search_roll_walk(S, slot, locs, nspan, start, T.end, init_len, len_r, lane, [&](long long s, long long e, int ws, int we) {
+    const int now = S.I >= L ? S.I : S.I - L;
+    if (!any || now > best_J) best_s = s, best_e = e, best_ws = ws, best_we = we, best_J = now;
+    any = true;
+    return false;
+  });
   if (lane == 0) {
     R.ref_start = (int32_t)best_s, R.ref_end = (int32_t)best_e;
     R.winnow_start = lo + best_ws, R.winnow_end = lo + best_we, R.jaccard = best_J;

@@ -70,6 +70,12 @@ FILTER_TASK_DTYPE = np.dtype([("q_off", "<i8"), ("r_off", "<i8"), ("q_len", "<i4
                               ("reserved", "<i4")])
 FILTER_REC_DTYPE = np.dtype([("q_up", "<i4"), ("r_up", "<i4"), ("dist", "<i4"), ("minqg", "<i4"), ("flags", "<u4")])
 assert FILTER_TASK_DTYPE.itemsize == 32 and FILTER_REC_DTYPE.itemsize == 20
+# include/sedef_hip.h: sdf_search_hit (search_extend; EXTEND_* in `flags`)
+SEARCH_HIT_DTYPE = np.dtype([("query_start", "<i4"), ("query_end", "<i4"), ("ref_start", "<i4"), ("ref_end", "<i4"), ("jaccard", "<i4"),
+                             ("q_winnow_start", "<i4"), ("q_winnow_end", "<i4"), ("r_winnow_start", "<i4"), ("r_winnow_end", "<i4"),
+                             ("flags", "<u4")])
+EXTEND_SKIPPED, EXTEND_WIDE, EXTEND_NOLIMIT, EXTEND_MAX_GROW = 0x1, 0x2, 0x4, 1792
+assert SEARCH_HIT_DTYPE.itemsize == 40
 FILTER_Q_RC, FILTER_R_RC, FILTER_SKIP = 1, 2, 4
 FILTER_UPPER_FAIL, FILTER_QGRAM_FAIL, FILTER_SHORT, FILTER_SKIPPED = 1, 2, 4, 8
 FILTER_WAVE_MAX_LEN = 4096
@@ -91,6 +97,16 @@ class _FilterParams(C.Structure):
 def filter_params(min_uppercase=12, max_error=0.30, max_edit_error=0.15, gap_frequency=0.005, reserved=0):
     """sdf_filter_params; the defaults are the reference's (src/globals.cc)."""
     return _FilterParams(int(min_uppercase), int(reserved), float(max_error), float(max_edit_error), float(gap_frequency))
+
+
+class _ExtendParams(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("max_edit_error", C.c_double), ("max_sd_size", C.c_int32), ("same_genome", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+def extend_params(max_error=0.30, max_edit_error=0.15, max_sd_size=1 << 20, same_genome=False, reserved=(0, 0)):
+    """sdf_extend_params; the defaults are the reference's (src/globals.cc)."""
+    return _ExtendParams(float(max_error), float(max_edit_error), int(max_sd_size), int(bool(same_genome)), (C.c_int32 * 2)(*reserved))
 
 
 class _Scoring(C.Structure):
@@ -248,6 +264,20 @@ def load_library():
     L.sdf_search_filter_tasks_host.argtypes = _ftasks + _ftasks_tail
     L.sdf_search_filter_tasks_device.restype = C.c_int
     L.sdf_search_filter_tasks_device.argtypes = [C.c_void_p] + _ftasks + [C.c_size_t] + _ftasks_tail + [C.c_void_p]
+    _extend = _roll + [C.c_void_p, C.c_void_p]  # ... rolls, filter
+    _extend_tail = [C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(_ExtendParams),
+                    C.c_void_p]  # r .. out
+    L.sdf_search_extend.restype = C.c_int
+    L.sdf_search_extend.argtypes = [C.c_void_p] + _extend + _extend_tail
+    L.sdf_search_extend_host.restype = C.c_int
+    L.sdf_search_extend_host.argtypes = _extend + _extend_tail
+    L.sdf_search_extend_device.restype = C.c_int
+    L.sdf_search_extend_device.argtypes = [C.c_void_p] + _extend + [C.c_size_t] + _extend_tail + [C.c_void_p]
+    _htasks = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p]  # len_q .. out
+    L.sdf_search_hit_tasks_host.restype = C.c_int
+    L.sdf_search_hit_tasks_host.argtypes = [C.c_void_p, C.c_size_t] + _htasks
+    L.sdf_search_hit_tasks_device.restype = C.c_int
+    L.sdf_search_hit_tasks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p] + _htasks + [C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -1001,6 +1031,52 @@ class Extz2Engine:
         self._check(code)
         return first, windows, intervals, rolls, recs
 
+    def search_extend_raw(self, q, windows, first, intervals, rolls, filt, r, len_q, len_r, init_len, limit, params=None):
+        """sdf_search_extend as it is.  q .. limit: as search_roll_raw takes them; rolls: as it returns them; filt: the first
+        filter's FILTER_REC_DTYPE records or None; params: what extend_params makes (default: the reference's defaults).
+        Returns (rc, hits): a SEARCH_HIT_DTYPE record per interval, the WIDE ones completed on the host."""
+        return search_extend_call(self.lib.sdf_search_extend, (self.ctx,), q, windows, first, intervals, rolls, filt, r, len_q, len_r,
+                                  init_len, limit, params)
+
+    def search_extend_device(self, d_q, nq, d_windows, d_first, d_intervals, d_rolls, d_filter, n_max, d_r, nr, len_q, len_r, init_len,
+                             d_limit, n_limit, d_out, params=None, stream=None):
+        """The same over device pointers (ints; d_filter may be None), behind search_filter_device on one stream without a host
+        read: n_max wavefronts, d_out holds n_max records.  A WIDE interval is flagged and the rest of its record is zero."""
+        params = extend_params() if params is None else params
+        self._check(self.lib.sdf_search_extend_device(self.ctx, d_q, nq, d_windows, d_first, d_intervals, d_rolls, d_filter, n_max, d_r,
+                                                      nr, int(len_q), int(len_r), int(init_len), d_limit, n_limit, C.byref(params),
+                                                      d_out, stream))
+
+    def search_hit_tasks_device(self, d_hits, n, d_count, len_q, len_r, q_off, q_rc, r_off, r_rc, d_out, stream=None):
+        """sdf_search_hit_tasks_device: the FILTER_TASK_DTYPE record of n hits, those at or beyond *d_count (None: none) SKIP."""
+        self._check(self.lib.sdf_search_hit_tasks_device(self.ctx, d_hits, n, d_count, int(len_q), int(len_r), int(q_off),
+                                                         int(bool(q_rc)), int(r_off), int(bool(r_rc)), d_out, stream))
+
+    def search_extend(self, q_range, r_range, k=12, w=16, separate_lowercase=True, init_len=700, same_genome=False,
+                      uppercase_seeds=True, limit=(), r_threshold=None, params=None, extend=None):
+        """The reference's search() on two pool ranges with an empty tree, to its end: search_filter (allow_extend), every
+        interval that passed grown to its hit, and the filter's verdict on every hit.  extend: what extend_params makes
+        (default: the reference's defaults with this same_genome).  Returns (first, windows, intervals, rolls, records, hits,
+        hit_records): hits[t] is the SEARCH_HIT_DTYPE record of intervals[t], hit_records[t] its FILTER_REC_DTYPE record."""
+        q, first, windows, intervals, rolls = self._search_roll(q_range, r_range, k, w, separate_lowercase, init_len, same_genome,
+                                                                uppercase_seeds, limit, r_threshold)
+        _, r = self.pool_minimizers(self.minim_ranges([r_range[:2]], rc=bool(r_range[2]) if len(r_range) > 2 else None), k, w,
+                                    separate_lowercase)
+        len_q, len_r = int(q_range[1]), int(r_range[1])
+        strands = (int(q_range[0]), len(q_range) > 2 and bool(q_range[2]), int(r_range[0]), len(r_range) > 2 and bool(r_range[2]))
+        code, tasks = search_filter_tasks_host(q, windows, first, intervals, rolls, len_q, len_r, init_len, *strands, True)
+        self._check(code)
+        code, recs = self.search_filter_raw(tasks, params)
+        self._check(code)
+        extend = extend_params(same_genome=same_genome) if extend is None else extend
+        code, hits = self.search_extend_raw(q, windows, first, intervals, rolls, recs, r, len_q, len_r, init_len, limit, extend)
+        self._check(code)
+        code, tasks = search_hit_tasks_host(hits, len_q, len_r, *strands)
+        self._check(code)
+        code, hit_recs = self.search_filter_raw(tasks, params)
+        self._check(code)
+        return first, windows, intervals, rolls, recs, hits, hit_recs
+
     def last_ms(self, which):
         return float(self.lib.sdf_last_ms(self.ctx, which))
 
@@ -1122,6 +1198,45 @@ def search_filter_tasks_host(q, windows, first, intervals, rolls, len_q, len_r, 
     rc = load_library().sdf_search_filter_tasks_host(ptr(q), len(q), ptr(windows), first.ctypes.data, ptr(intervals), ptr(rolls),
                                                      int(len_q), int(len_r), int(init_len), int(q_off), int(bool(q_rc)), int(r_off),
                                                      int(bool(r_rc)), int(bool(allow_extend)), ptr(out))
+    return rc, out
+
+
+def search_extend_call(fn, head, q, windows, first, intervals, rolls, filt, r, len_q, len_r, init_len, limit, params=None):
+    """sdf_search_extend (head: its context) or sdf_search_extend_host (head: nothing) on numpy arrays.  Returns (rc, hits)."""
+    q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
+    r = np.ascontiguousarray(r, dtype=MINIMIZER_DTYPE)
+    windows = np.ascontiguousarray(windows, dtype=SEARCH_WINDOW_DTYPE)
+    intervals = np.ascontiguousarray(intervals, dtype=SEARCH_INTERVAL_DTYPE)
+    rolls = np.ascontiguousarray(rolls, dtype=SEARCH_ROLL_DTYPE)
+    filt = None if filt is None else np.ascontiguousarray(filt, dtype=FILTER_REC_DTYPE)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    limit = np.ascontiguousarray(limit, dtype=np.int32)
+    n = int(first[-1])
+    assert len(first) == len(q) + 1 and len(windows) == len(q) and len(intervals) >= n and len(rolls) >= n
+    assert filt is None or len(filt) >= n
+    out = np.zeros(n, SEARCH_HIT_DTYPE)
+    params = extend_params() if params is None else params
+
+    def ptr(a):
+        return a.ctypes.data if a is not None and len(a) else None
+    rc = fn(*head, ptr(q), len(q), ptr(windows), first.ctypes.data, ptr(intervals), ptr(rolls), ptr(filt), ptr(r), len(r), int(len_q),
+            int(len_r), int(init_len), ptr(limit), len(limit), C.byref(params), ptr(out))
+    return rc, out
+
+
+def search_extend_host(q, windows, first, intervals, rolls, filt, r, len_q, len_r, init_len, limit, params=None):
+    """sdf_search_extend_host: search_extend_raw without a context or a GPU, in plain C++ on one thread."""
+    return search_extend_call(load_library().sdf_search_extend_host, (), q, windows, first, intervals, rolls, filt, r, len_q, len_r,
+                              init_len, limit, params)
+
+
+def search_hit_tasks_host(hits, len_q, len_r, q_off, q_rc, r_off, r_rc, out=None):
+    """sdf_search_hit_tasks_host: the FILTER_TASK_DTYPE record of every hit.  Returns (rc, tasks)."""
+    hits = np.ascontiguousarray(hits, dtype=SEARCH_HIT_DTYPE)
+    if out is None:
+        out = np.zeros(len(hits), FILTER_TASK_DTYPE)
+    rc = load_library().sdf_search_hit_tasks_host(hits.ctypes.data if len(hits) else None, len(hits), int(len_q), int(len_r), int(q_off),
+                                                  int(bool(q_rc)), int(r_off), int(bool(r_rc)), out.ctypes.data if len(out) else None)
     return rc, out
 
 

@@ -933,6 +933,39 @@ int sdf_search_extend_host(const sdf_minimizer *q, size_t nq, const sdf_search_w
                            const sdf_search_interval *intervals, const sdf_search_roll_rec *rolls, const sdf_filter_rec *filter,
                            const sdf_minimizer *r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *limit,
                            size_t n_limit, const sdf_extend_params *params, sdf_search_hit *out /* first[nq] */);
+/* The long form of the device form: it completes, in place in d_hits and on the same stream without a host wait, intervals that
+ * sdf_search_extend_device flagged SDF_EXTEND_WIDE for their GROWTH.  Inputs as for sdf_search_extend_device; d_hits: what that
+ * call wrote (n_max records).  Record t < min(d_first[nq], n_max) is a CANDIDATE when its flags are exactly SDF_EXTEND_WIDE, its
+ * query_end is 0 (nobody completed it) and its replay fits a wavefront: the roll record carries no SDF_ROLL_WIDE, n_members <=
+ * SDF_SEARCH_MAX_MEMBERS and winnow_end - lo <= SDF_ROLL_MAX_SPAN.  No byte of any other record changes -- SKIPPED, NOLIMIT,
+ * completed ones, and those that are WIDE because of the replay.  The first n_long_max candidates in ascending t are TAKEN
+ * (not in the order wavefronts arrive: which ones are taken follows from the inputs).  A taken candidate is walked exactly as
+ * the section above states, with long_grow records per end where the short form allows SDF_EXTEND_MAX_GROW:
+ *   the walk ends inside long_grow           the hit, flags = SDF_EXTEND_WIDE (the 1,792 rule set the flag; every form keeps it)
+ *   an add_to_query needs limit[s], s >= n_limit   a zero record with SDF_EXTEND_WIDE | SDF_EXTEND_NOLIMIT
+ *   a do step would pass long_grow (looked at for every side of a step before its first add)   unchanged: zero, WIDE
+ * Every record is what sdf_search_extend_host writes for it, or untouched.  *d_left (device memory, or NULL) receives the
+ * number of candidates that were not taken or not finished.
+ * SDF_EXTEND_LONG_MAX_GROW: bits[] of a wavefront is one byte per key in LDS, 1,024 + 3,072 + 4 * 16,384 = 69,632 bytes, so that
+ * two wavefronts share a CU's 160 KB as they do in the short form; 16,384 records are some 139 kb per end at k = 12, w = 16.
+ * The keys' sort and the slots lie in a workspace of the context's, `batch` intervals at a time (0: 128), 32 bytes per entry
+ * of a batch slot's 1,024 + 3,072 + 4 * long_grow plus the sort's scratch: batch is taken down to n_long_max, and up to 4,096.
+ * The number of launches -- 3, and 6 per batch -- and the workspace follow from n_max, n_long_max, long_grow and batch, never
+ * from the data.
+ * Refusals as for sdf_search_extend_device (d_hits for d_out), and SDF_ERR_INVALID for long_grow <= SDF_EXTEND_MAX_GROW or
+ * > SDF_EXTEND_LONG_MAX_GROW;  SDF_ERR_NOMEM when the workspace is more than the context's workspace budget or cannot be
+ * allocated.  Every check precedes the first launch.  nq == 0, n_max == 0 or n_long_max == 0 is SDF_OK without a launch, and
+ * *d_left is not written then.
+ * sdf_search_extend runs this form (long_grow = SDF_EXTEND_LONG_MAX_GROW, n_long_max = its candidates) on the arrays it has
+ * uploaded when the short form left candidates, and completes on the host only what is still WIDE with query_end == 0
+ * afterwards; without a candidate it launches what it launched before. */
+#define SDF_EXTEND_LONG_MAX_GROW 16384
+int sdf_search_extend_long_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                                  const uint64_t *d_first, const sdf_search_interval *d_intervals, const sdf_search_roll_rec *d_rolls,
+                                  const sdf_filter_rec *d_filter /* or NULL */, size_t n_max, const sdf_minimizer *d_r, size_t nr,
+                                  int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *d_limit, size_t n_limit,
+                                  const sdf_extend_params *params, int32_t long_grow, size_t n_long_max, size_t batch /* 0: default */,
+                                  sdf_search_hit *d_hits /* in and out */, uint64_t *d_left /* or NULL */, void *stream);
 /* The filter task of every hit, for the reference's second filter() (src/search.cc:356): out[t] for hits[t], n of them.  The
  * query side is positions [query_start, query_end) of the query sequence, the reference side [ref_start, ref_end) of the
  * reference's; sequences, strands and pool offsets as for sdf_search_filter_tasks_*.  SDF_FILTER_SKIP (every other field zero)

@@ -333,6 +333,7 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(sr_q, None) X(sr_win, None) X(sr_first, None) X(sr_iv, None) X(sr_r, None) X(sr_limit, None) X(sr_out, None) /* sdf_search_roll: the host form's copies */ \
   X(sf_tasks, None) X(sf_out, None) /* sdf_search_filter: the host form's copies */ \
   X(se_rolls, None) X(se_filter, None) X(se_out, None) /* sdf_search_extend: the host form's copies (the rest: sdf_search_roll's) */ \
+  X(sl_ws, None) X(sl_tmp, None) /* sdf_search_extend_long_device: flags, list, a batch's keys / payloads / heads / slots; hipCUB scratch */ \
   X(h_pool, BatchCall) X(h_out, BatchCall) X(h_cig, BatchCall) /* device buffers of the host-buffer entry point */    \
   X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \

@@ -314,5 +314,32 @@ __host__ __device__ inline sdf_filter_task hit_task_of(const FilterTaskArgs &A, 
   return O;
 }
 __global__ void search_hit_tasks_kernel(const sdf_search_hit *, int, const uint64_t *, FilterTaskArgs, sdf_filter_task *);
+// search_extend_long.hip
+// a wavefront's LDS: bits[] alone, one byte per key of the largest universe; the keys' sort and the slots lie in HBM
+constexpr int EXT_LONG_GROW = SDF_EXTEND_LONG_MAX_GROW, EXT_LONG_MAX_KEYS = SEARCH_MAX_MEMBERS + ROLL_MAX_SPAN + 4 * EXT_LONG_GROW;
+static_assert(EXT_LONG_MAX_KEYS <= 80 * 1024, "search_extend_long.hip: two wavefronts share a CU's 160 KB");
+constexpr uint32_t kLongNoSlot = 0xFFFFFFFFu, kLongPayloadNoSlot = 0x80000000u;  // a status-2 reference record: in slots[], in the sort's payload
+constexpr int kLongPadBit = 32, kLongSlotShift = 33;                              // a sort key: slot << 33 | pad << 32 | roll_key
+struct ExtLongCand {  // a taken candidate: its interval, its window, the first record of r with loc >= the interval's start
+  uint32_t t;
+  int32_t i, lo;
+};
+struct ExtLongArgs {  // what the launches of sdf_search_extend_long_device share
+  const sdf_minimizer *q, *r;
+  const sdf_search_window *windows;
+  const uint64_t *first;
+  const sdf_search_interval *intervals;
+  const sdf_search_roll_rec *rolls;
+  const sdf_filter_rec *filter;
+  int nq, nr, n_limit, grow, stride;  // grow: long_grow; stride: U, the universe entries a batch slot owns
+};
+__global__ void search_extend_long_flag_kernel(ExtLongArgs, const sdf_search_hit *, int, uint32_t *);
+__global__ void search_extend_long_list_kernel(ExtLongArgs, const sdf_search_hit *, const uint32_t *, const uint32_t *, int, uint32_t, ExtLongCand *, uint32_t *,
+                                               unsigned long long *);
+__global__ void search_extend_long_keys_kernel(ExtLongArgs, const ExtLongCand *, const uint32_t *, uint32_t, unsigned long long *, uint32_t *);
+__global__ void search_extend_long_heads_kernel(const unsigned long long *, int, int, uint32_t *);
+__global__ void search_extend_long_slots_kernel(const unsigned long long *, const uint32_t *, const uint32_t *, int, int, uint32_t *, uint32_t *);
+__global__ void search_extend_long_kernel(ExtLongArgs, const ExtLongCand *, const uint32_t *, uint32_t, const uint32_t *, const uint32_t *,
+                                          long long, long long, int, const int32_t *, sdf_extend_params, sdf_search_hit *, unsigned long long *);
 
 }  // namespace sdf

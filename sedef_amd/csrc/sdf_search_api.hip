@@ -731,6 +731,115 @@ extern "C" int sdf_search_extend_device(sdf_ctx *ctx, const sdf_minimizer *d_q, 
   return SDF_OK;
 }
 
+// ---- the extension, long form (search_extend_long.hip) ----
+
+namespace {
+constexpr size_t kExtendLongBatch = 128;  // batch slots by default: 128 * 69,632 entries of 32 bytes are 272 MiB at the largest long_grow
+constexpr size_t kExtendLongMaxBatch = 4096;
+
+// The workspace of a call and the launches that fill it.  Everything here follows from n_max, n_long_max, long_grow and batch.
+struct ExtendLongPlan {
+  size_t batch, stride, items, batches;
+  size_t off_flag, off_pos, off_list, off_meta, off_nds, off_keys, off_keys2, off_vals, off_vals2, off_incl, off_slots, bytes, tmp_bytes;
+  int end_bit;
+};
+int extend_long_plan(sdf_ctx *ctx, size_t n_max, size_t n_long_max, int32_t long_grow, size_t batch, ExtendLongPlan &L, hipStream_t st) {
+  L.batch = std::min(std::min(batch ? batch : kExtendLongBatch, kExtendLongMaxBatch), n_long_max);
+  L.stride = (size_t)SDF_SEARCH_MAX_MEMBERS + SDF_ROLL_MAX_SPAN + 4 * (size_t)long_grow;
+  L.items = L.batch * L.stride;
+  L.batches = (n_long_max + L.batch - 1) / L.batch;
+  size_t at = 0;
+  const auto take = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  L.off_flag = take((n_max + 1) * 4), L.off_pos = take((n_max + 1) * 4), L.off_list = take(n_long_max * sizeof(ExtLongCand));
+  L.off_meta = take(16), L.off_nds = take(L.batch * 4);
+  L.off_keys = take(L.items * 8), L.off_keys2 = take(L.items * 8), L.off_vals = take(L.items * 4), L.off_vals2 = take(L.items * 4);
+  L.off_incl = take(L.items * 4), L.off_slots = take(L.items * 4);
+  L.bytes = at;
+  L.end_bit = kLongSlotShift;
+  while (((size_t)1 << (L.end_bit - kLongSlotShift)) < L.batch) ++L.end_bit;
+  size_t t_sort = 0, t_scan = 0, t_sel = 0;
+  SDF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
+                                             (uint32_t *)nullptr, (int)L.items, 0, L.end_bit, st));
+  SDF_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, t_scan, (uint32_t *)nullptr, (uint32_t *)nullptr, (int)L.items, st));
+  SDF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t_sel, (uint32_t *)nullptr, (uint32_t *)nullptr, (int)(n_max + 1), st));
+  L.tmp_bytes = std::max(t_sort, std::max(t_scan, t_sel)) + 256;
+  return SDF_OK;
+}
+
+// the launches, on `st`; d_left or null
+int extend_long_run(sdf_ctx *ctx, const ExtLongArgs &A, size_t n_max, size_t n_long_max, size_t batch, int64_t len_q, int64_t len_r,
+                    int32_t init_len, const int32_t *d_limit, const sdf_extend_params &P, sdf_search_hit *d_hits, uint64_t *d_left, hipStream_t st) {
+  ExtendLongPlan L;
+  if (int rc = extend_long_plan(ctx, n_max, n_long_max, A.grow, batch, L, st)) return rc;
+  if (L.items > 0x7fffffffu) return refuse(ctx, SDF_ERR_UNSUPPORTED, "search extend, long form: a batch of more than 2^31 - 1 universe entries");
+  if (L.bytes + L.tmp_bytes > ctx->ws_budget || ctx->sl_ws.reserve(L.bytes) != hipSuccess || ctx->sl_tmp.reserve(L.tmp_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return refuse(ctx, SDF_ERR_NOMEM, "search extend, long form: " + std::to_string((L.bytes + L.tmp_bytes) >> 20) + " MiB of workspace cannot be had (a smaller batch needs less)");
+  }
+  uint8_t *ws = (uint8_t *)ctx->sl_ws.p;
+  uint32_t *d_flag = (uint32_t *)(ws + L.off_flag), *d_pos = (uint32_t *)(ws + L.off_pos), *d_meta = (uint32_t *)(ws + L.off_meta);
+  uint32_t *d_nds = (uint32_t *)(ws + L.off_nds), *d_vals = (uint32_t *)(ws + L.off_vals), *d_vals2 = (uint32_t *)(ws + L.off_vals2);
+  uint32_t *d_incl = (uint32_t *)(ws + L.off_incl), *d_slots = (uint32_t *)(ws + L.off_slots), *d_heads = d_vals;  // (the payloads are sorted by then)
+  ExtLongCand *d_list = (ExtLongCand *)(ws + L.off_list);
+  unsigned long long *d_keys = (unsigned long long *)(ws + L.off_keys), *d_keys2 = (unsigned long long *)(ws + L.off_keys2);
+  const int n = (int)n_max, items = (int)L.items, stride = (int)L.stride;
+  const dim3 block(256), grid_n((unsigned)((n_max + 1 + 255) / 256)), grid_items((unsigned)((L.items + 255) / 256));
+  size_t tmp = L.tmp_bytes;
+  hipLaunchKernelGGL(search_extend_long_flag_kernel, grid_n, block, 0, st, A, (const sdf_search_hit *)d_hits, n, d_flag);
+  SDF_HIP(hipcub::DeviceScan::ExclusiveSum(ctx->sl_tmp.p, tmp, d_flag, d_pos, n + 1, st));
+  hipLaunchKernelGGL(search_extend_long_list_kernel, grid_n, block, 0, st, A, (const sdf_search_hit *)d_hits, (const uint32_t *)d_flag,
+                     (const uint32_t *)d_pos, n, (uint32_t)n_long_max, d_list, d_meta, (unsigned long long *)d_left);
+  ctx->launches += 3;
+  for (size_t b = 0; b < L.batches; b++) {
+    const uint32_t base = (uint32_t)(b * L.batch);
+    hipLaunchKernelGGL(search_extend_long_keys_kernel, dim3((unsigned)((L.stride + 255) / 256), (unsigned)L.batch), block, 0, st, A,
+                       (const ExtLongCand *)d_list, (const uint32_t *)d_meta, base, d_keys, d_vals);
+    tmp = L.tmp_bytes;
+    SDF_HIP(hipcub::DeviceRadixSort::SortPairs(ctx->sl_tmp.p, tmp, d_keys, d_keys2, d_vals, d_vals2, items, 0, L.end_bit, st));
+    hipLaunchKernelGGL(search_extend_long_heads_kernel, grid_items, block, 0, st, (const unsigned long long *)d_keys2, items, stride, d_heads);
+    tmp = L.tmp_bytes;
+    SDF_HIP(hipcub::DeviceScan::InclusiveSum(ctx->sl_tmp.p, tmp, d_heads, d_incl, items, st));
+    hipLaunchKernelGGL(search_extend_long_slots_kernel, grid_items, block, 0, st, (const unsigned long long *)d_keys2, (const uint32_t *)d_vals2,
+                       (const uint32_t *)d_incl, items, stride, d_slots, d_nds);
+    hipLaunchKernelGGL(search_extend_long_kernel, dim3((unsigned)L.batch), dim3(64), 0, st, A, (const ExtLongCand *)d_list, (const uint32_t *)d_meta,
+                       base, (const uint32_t *)d_slots, (const uint32_t *)d_nds, (long long)len_q, (long long)len_r, (int)init_len, d_limit, P,
+                       d_hits, (unsigned long long *)d_left);
+    ctx->launches += 6;
+  }
+  SDF_HIP(hipGetLastError());
+  return SDF_OK;
+}
+}  // namespace
+
+extern "C" int sdf_search_extend_long_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const sdf_search_window *d_windows,
+                                             const uint64_t *d_first, const sdf_search_interval *d_intervals,
+                                             const sdf_search_roll_rec *d_rolls, const sdf_filter_rec *d_filter, size_t n_max,
+                                             const sdf_minimizer *d_r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len,
+                                             const int32_t *d_limit, size_t n_limit, const sdf_extend_params *params, int32_t long_grow,
+                                             size_t n_long_max, size_t batch, sdf_search_hit *d_hits, uint64_t *d_left, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0 || n_max == 0 || n_long_max == 0) return SDF_OK;
+  if (!d_q || !d_windows || !d_first || !d_intervals || !d_rolls || !d_r || !d_limit || !d_hits)
+    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_extend_long_device: invalid arguments");
+  const char *why = nullptr;
+  if (int rc = roll_scalars(nq, n_max, nr, len_r, init_len, n_limit, &why)) return refuse(ctx, rc, why);
+  if (int rc = extend_scalars(len_q, params, &why)) return refuse(ctx, rc, why);
+  if (long_grow <= SDF_EXTEND_MAX_GROW || long_grow > SDF_EXTEND_LONG_MAX_GROW)
+    return refuse(ctx, SDF_ERR_INVALID, "search extend, long form: long_grow outside SDF_EXTEND_MAX_GROW + 1 .. SDF_EXTEND_LONG_MAX_GROW");
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  const ExtLongArgs A{d_q, d_r, d_windows, d_first, d_intervals, d_rolls, d_filter, (int)nq, (int)nr, (int)n_limit, (int)long_grow,
+                      SDF_SEARCH_MAX_MEMBERS + SDF_ROLL_MAX_SPAN + 4 * (int)long_grow};
+  if (int rc = extend_long_run(ctx, A, n_max, std::min(n_long_max, n_max), batch, len_q, len_r, init_len, d_limit, *params, d_hits, d_left, st)) return rc;
+  if (!stream) SDF_HIP(hipStreamSynchronize(st));
+  return SDF_OK;
+}
+
 extern "C" int sdf_search_extend(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, const sdf_search_window *windows, const uint64_t *first,
                                  const sdf_search_interval *intervals, const sdf_search_roll_rec *rolls, const sdf_filter_rec *filter,
                                  const sdf_minimizer *r, size_t nr, int64_t len_q, int64_t len_r, int32_t init_len, const int32_t *limit,
@@ -769,11 +878,39 @@ extern "C" int sdf_search_extend(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq
     return rc;
   SDF_HIP(hipMemcpyAsync(out, ctx->se_out.p, n * sizeof(sdf_search_hit), hipMemcpyDeviceToHost, st));
   SDF_HIP(hipStreamSynchronize(st));
-  // the WIDE intervals, on the host
+  // the intervals that are WIDE for their growth, by the long form on the arrays that are there already
+  size_t n_long = 0;
+  for (size_t i = 0; i < nq; i++)
+    for (uint64_t t = first[i]; t < first[i + 1]; t++) {
+      if (out[t].flags != SDF_EXTEND_WIDE) continue;
+      const int64_t lo = std::lower_bound(r, r + nr, (int64_t)intervals[t].start, [](const sdf_minimizer &m, int64_t loc) { return (int64_t)m.loc < loc; }) - r;
+      n_long += !extend_replay_wide(rolls[t], windows[i].n_members, lo);
+    }
+  if (n_long) {
+    const ExtLongArgs LA{(const sdf_minimizer *)ctx->sr_q.p, (const sdf_minimizer *)ctx->sr_r.p, (const sdf_search_window *)ctx->sr_win.p,
+                         (const uint64_t *)ctx->sr_first.p, (const sdf_search_interval *)ctx->sr_iv.p, (const sdf_search_roll_rec *)ctx->se_rolls.p,
+                         filter ? (const sdf_filter_rec *)ctx->se_filter.p : nullptr, (int)nq, (int)nr, (int)n_limit, SDF_EXTEND_LONG_MAX_GROW,
+                         SDF_SEARCH_MAX_MEMBERS + SDF_ROLL_MAX_SPAN + 4 * SDF_EXTEND_LONG_MAX_GROW};
+    // (no room for the default batch's workspace: smaller batches -- more launches, less in flight -- before the host takes over)
+    int rc = SDF_ERR_NOMEM;
+    for (size_t batch = kExtendLongBatch; rc == SDF_ERR_NOMEM && batch; batch /= 4)
+      rc = extend_long_run(ctx, LA, n, n_long, batch, len_q, len_r, init_len, (const int32_t *)ctx->sr_limit.p, *params,
+                           (sdf_search_hit *)ctx->se_out.p, nullptr, st);
+    if (rc == SDF_OK) {
+      SDF_HIP(hipMemcpyAsync(out, ctx->se_out.p, n * sizeof(sdf_search_hit), hipMemcpyDeviceToHost, st));
+      SDF_HIP(hipStreamSynchronize(st));
+    } else if (rc == SDF_ERR_NOMEM) {
+      // not even one interval's workspace: the host completes them, as it does those beyond the long cap; sdf_last_error() says so
+      ctx->err = "sdf_search_extend: no workspace for the long form, " + std::to_string(n_long) + " intervals completed on the host (" + ctx->err + ")";
+    } else {
+      return rc;
+    }
+  }
+  // what is still WIDE and nobody completed -- the replay does not fit, or the growth passes the long form's cap --, on the host
   const ExtendArgs A{RA, rolls, filter, len_q, *params};
   ExtendMap S;
   for (size_t i = 0; i < nq; i++)
     for (uint64_t t = first[i]; t < first[i + 1]; t++)
-      if (out[t].flags & SDF_EXTEND_WIDE) extend_one(A, i, t, out[t], S);
+      if (out[t].flags == SDF_EXTEND_WIDE && out[t].query_end == 0) extend_one(A, i, t, out[t], S);
   return SDF_OK;
 }

@@ -158,14 +158,15 @@ struct SearchMap {
   }
 };
 
-// The roll's walk (include/sedef_hip.h, steps 1 to 5) over the span's records x = 0 .. nspan): slot[x] (no_slot: status 2) and
-// locs[x] in LDS.  It jumps from event to event (a step without one cannot change J).  eval(s, e, ws, we) is called at every
-// evaluation of J -- step 4 and every round with an event -- and ends the walk by returning true.  ws, we count from the span's
-// first record.
-template <class F>
-__device__ __forceinline__ void search_roll_walk(SearchMap &S, const uint16_t *slot, const int32_t *locs, const int nspan, const long long start,
+// The roll's walk (include/sedef_hip.h, steps 1 to 5) over the span's records x = 0 .. nspan): slot[x] (NO_SLOT: status 2) and
+// locs[x] -- pointers into LDS (search_roll.hip, search_extend.hip), or anything else with a wave-uniform operator[]
+// (search_extend_long.hip: windows on HBM).  It jumps from event to event (a step without one cannot change J).
+// eval(s, e, ws, we) is called at every evaluation of J -- step 4 and every round with an event -- and ends the walk by returning
+// true.  ws, we count from the span's first record.
+template <int NO_SLOT = 0xFFFF, class Slots, class Locs, class F>
+__device__ __forceinline__ void search_roll_walk(SearchMap &S, Slots slot, Locs locs, const int nspan, const long long start,
                                                  const long long end, const int init_len, const long long len_r, const int lane, F eval) {
-  constexpr int no_slot = 0xFFFF;
+  constexpr int no_slot = NO_SLOT;
   auto add = [&](int x) {
     const int sl = __builtin_amdgcn_readfirstlane((int)slot[x]);
     if (sl != no_slot) S.add(sl, 2, true, lane);

@@ -75,6 +75,7 @@ SEARCH_HIT_DTYPE = np.dtype([("query_start", "<i4"), ("query_end", "<i4"), ("ref
                              ("q_winnow_start", "<i4"), ("q_winnow_end", "<i4"), ("r_winnow_start", "<i4"), ("r_winnow_end", "<i4"),
                              ("flags", "<u4")])
 EXTEND_SKIPPED, EXTEND_WIDE, EXTEND_NOLIMIT, EXTEND_MAX_GROW = 0x1, 0x2, 0x4, 1792
+EXTEND_LONG_MAX_GROW = 16384  # SDF_EXTEND_LONG_MAX_GROW: the largest long_grow of search_extend_long_device
 assert SEARCH_HIT_DTYPE.itemsize == 40
 FILTER_Q_RC, FILTER_R_RC, FILTER_SKIP = 1, 2, 4
 FILTER_UPPER_FAIL, FILTER_QGRAM_FAIL, FILTER_SHORT, FILTER_SKIPPED = 1, 2, 4, 8
@@ -273,6 +274,9 @@ def load_library():
     L.sdf_search_extend_host.argtypes = _extend + _extend_tail
     L.sdf_search_extend_device.restype = C.c_int
     L.sdf_search_extend_device.argtypes = [C.c_void_p] + _extend + [C.c_size_t] + _extend_tail + [C.c_void_p]
+    L.sdf_search_extend_long_device.restype = C.c_int  # ... params, long_grow, n_long_max, batch, d_hits, d_left, stream
+    L.sdf_search_extend_long_device.argtypes = [C.c_void_p] + _extend + [C.c_size_t] + _extend_tail[:-1] + \
+        [C.c_int32, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     _htasks = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p]  # len_q .. out
     L.sdf_search_hit_tasks_host.restype = C.c_int
     L.sdf_search_hit_tasks_host.argtypes = [C.c_void_p, C.c_size_t] + _htasks
@@ -1046,6 +1050,21 @@ class Extz2Engine:
         self._check(self.lib.sdf_search_extend_device(self.ctx, d_q, nq, d_windows, d_first, d_intervals, d_rolls, d_filter, n_max, d_r,
                                                       nr, int(len_q), int(len_r), int(init_len), d_limit, n_limit, C.byref(params),
                                                       d_out, stream))
+
+    def search_extend_long_device(self, d_q, nq, d_windows, d_first, d_intervals, d_rolls, d_filter, n_max, d_r, nr, len_q, len_r,
+                                  init_len, d_limit, n_limit, d_hits, long_grow=EXTEND_LONG_MAX_GROW, n_long_max=None, batch=0,
+                                  d_left=None, params=None, stream=None, check=True):
+        """sdf_search_extend_long_device, behind search_extend_device on one stream: the first n_long_max (default: n_max)
+        records of d_hits that are WIDE for their growth are completed in place, up to long_grow records an end; d_left (a
+        device pointer to eight bytes, or None) receives how many were not.  Returns the code; check: raise on a refusal."""
+        params = extend_params() if params is None else params
+        rc = self.lib.sdf_search_extend_long_device(self.ctx, d_q, nq, d_windows, d_first, d_intervals, d_rolls, d_filter, n_max, d_r, nr,
+                                                    int(len_q), int(len_r), int(init_len), d_limit, n_limit, C.byref(params),
+                                                    int(long_grow), n_max if n_long_max is None else n_long_max, batch, d_hits, d_left,
+                                                    stream)
+        if check:
+            self._check(rc)
+        return rc
 
     def search_hit_tasks_device(self, d_hits, n, d_count, len_q, len_r, q_off, q_rc, r_off, r_rc, d_out, stream=None):
         """sdf_search_hit_tasks_device: the FILTER_TASK_DTYPE record of n hits, those at or beyond *d_count (None: none) SKIP."""

@@ -626,8 +626,8 @@ int sdf_pool_minimizer_index(sdf_ctx *ctx, const sdf_minim_range *r, size_t n, i
 
 /* ---- search seeding: the reference intervals of every query window (search_seeds.hip) -----------------------------------------
  * The front half of the reference's search() (src/search.cc:395-452) for EVERY query minimizer in one call, with an EMPTY
- * tree: the exclusions of the SDs already found (pf->second.find(pos)) are out of scope, and with a non-empty tree the
- * reference's answer differs.  Inputs: q[0, nq), the query range's minimizers in ascending loc as sdf_pool_minimizers writes
+ * tree: the exclusions of the SDs already found (pf->second.find(pos)) are sdf_search_windows_found's, in the section behind
+ * this one.  Inputs: q[0, nq), the query range's minimizers in ascending loc as sdf_pool_minimizers writes
  * them; r_sorted[0, nr), the reference range's records in ascending (status, hash, loc) as sdf_pool_minimizer_index writes them
  * for ONE range (status 0..2, compared unsigned; `range` is not read); r_threshold, that range's threshold; len_q, the query
  * sequence's length; limit[0, n_limit), the caller's table of relaxed_jaccard_estimate(query_size) (src/util.cc:85 -- the library
@@ -685,10 +685,80 @@ int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, co
                             size_t n_limit, uint64_t *first /* nq + 1 */, sdf_search_window *windows /* nq */,
                             sdf_search_interval *out, size_t cap, size_t *used);
 
+/* ---- search against the SDs already found: the tree's two queries (search_found.hip) --------------------------------------------
+ * The reference's Tree (src/search.h: Boost.ICL interval maps that aggregate by set union) is read in two places: search()
+ * drops a gathered position `pos` of the member at `loc` when the tree's segment at loc covers pos (src/search.cc:420-434), and
+ * search_in_reference_interval asks is_overlap (src/search.cc:35-71, called at :335) before it filters and extends.  Both are
+ * answered here for every window and every rolled interval of a call at once, against an explicit list found[0, nf) of records
+ * {q_start, q_end, r_start, r_end} in the order the hits were added: a hit is added as a = [query_start, query_end) and
+ * b = [ref_start, ref_end), both right-open.  The tree only grows as far as a later query can see -- the reference's
+ * tree -= Interval(0, query_start - MIN_READ_SIZE) removes only points below every loc a later window asks for --, so what a
+ * query sees is a PREFIX found[0, v) of the list:
+ *   tree.find(loc)->second.find(pos) != end()   exactly when a visible record has q_start <= loc < q_end and
+ *                                               r_start <= pos < r_end;
+ *   is_overlap iterates                         exactly the visible records with q_start <= pf_pos < q_end and
+ *                                               r_start <= pfp_pos < r_end;
+ *   a record with q_start >= q_end or r_start >= r_end is never visible (ICL adds nothing for an empty interval and absorbs an
+ *   empty Subtree).
+ * The prefix is per WINDOW for the exclusions (the tree is read before the window's intervals are walked) and per INTERVAL for
+ * is_overlap (a hit of a window's first interval is in the tree when its second is tested).  tests/found_model.py holds the
+ * record-list statement and a point-level model of the ICL tree that ties it to the reference's text.  The round-based driver
+ * of initial_search, parse_hits and next_to_attain are not built.
+ *
+ * sdf_search_windows_found*: sdf_search_windows* with found, nf and visible[0, nq) -- window i sees found[0, visible[i]).  Steps
+ * 1 to 7 as written there, with one addition in step 4: a gathered position pos of the member at loc is dropped when a visible
+ * record has q_start <= loc < q_end && r_start <= pos < r_end.  The exclusion is per (member, position): a position dropped for
+ * one member stays a candidate when another member gathers it and no record excludes it there.  n_gathered is unchanged (it is
+ * counted before any filter), n_candidates counts what is left.  With nf == 0, or every visible[i] == 0, the output equals
+ * sdf_search_windows* byte for byte.
+ *
+ * SDF_SEARCH_FOUND_WIDE: more than SDF_SEARCH_MAX_FOUND distinct visible, non-empty records have q_start <= qs + init_len and
+ * q_end > qs -- the records that can contain a member's loc.  Read off the inputs, so the flag does not depend on who computes;
+ * a SHORT window carries SHORT alone.  The device form flags such a window, fills its counts except n_candidates (0) and writes
+ * no interval for it, as for WIDE (a window may carry both); sdf_search_windows_found completes it on the host and keeps the
+ * flag.
+ *
+ * The device keeps a bin index over the query axis, rebuilt by every call: the bin of a base is base >>
+ * SDF_SEARCH_FOUND_BIN_SHIFT (a base below 0 counts as 0), and a non-empty record is entered in every bin that
+ * [q_start, q_end) touches.  The forms that take host arrays size the index themselves; the device forms take
+ * found_entries_cap, the entries the caller grants (sdf_search_found_entries counts them for a host list), and write the need to
+ * *d_found_entries (device memory, or NULL).  When the need exceeds the grant the index is incomplete and the outputs of the
+ * call are NOT the answer -- no entry is written at or behind the grant, and none is read --; with the context's own stream the
+ * call then answers SDF_ERR_CIGAR_OVERFLOW (the need in sdf_last_error's text and in *d_found_entries), with a stream of its
+ * own the caller compares *d_found_entries with the grant itself.
+ *   SDF_ERR_INVALID      as for sdf_search_windows; found == NULL with nf > 0, visible == NULL; checked forms: visible[i] > nf
+ *                        (the device form reads such a prefix as nf)
+ *   SDF_ERR_UNSUPPORTED  as for sdf_search_windows; nf > 2^31 - 1, more than 2^31 - 1 bin entries (found_entries_cap beyond it)
+ * Every check precedes the first launch.  The device form enqueues on the caller's stream without a host wait: three launches
+ * for the index, then those of sdf_search_windows_device. */
+typedef struct { int32_t q_start, q_end, r_start, r_end; } sdf_search_found; /* 16 bytes */
+#define SDF_SEARCH_FOUND_WIDE 0x8   /* window flag, next to SHORT / NOLIMIT / WIDE */
+#define SDF_SEARCH_MAX_FOUND 256
+#define SDF_SEARCH_FOUND_BIN_SHIFT 12
+/* the bin entries of a list: what found_entries_cap must grant */
+int sdf_search_found_entries(const sdf_search_found *found, size_t nf, uint64_t *entries);
+int sdf_search_windows_found(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                             uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *limit,
+                             size_t n_limit, const sdf_search_found *found, size_t nf, const uint32_t *visible /* nq */,
+                             uint64_t *first /* nq + 1 */, sdf_search_window *windows /* nq */, sdf_search_interval *out, size_t cap,
+                             size_t *used);
+int sdf_search_windows_found_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted,
+                                    size_t nr, uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                    const int32_t *d_limit, size_t n_limit, const sdf_search_found *d_found, size_t nf,
+                                    size_t found_entries_cap, uint64_t *d_found_entries /* or NULL */, const uint32_t *d_visible,
+                                    uint64_t *d_first, sdf_search_window *d_windows, sdf_search_interval *d_out, size_t cap,
+                                    size_t *used, void *stream);
+int sdf_search_windows_found_host(const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                                  uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *limit,
+                                  size_t n_limit, const sdf_search_found *found, size_t nf, const uint32_t *visible /* nq */,
+                                  uint64_t *first /* nq + 1 */, sdf_search_window *windows /* nq */, sdf_search_interval *out,
+                                  size_t cap, size_t *used);
+/* (sdf_search_overlap*, the tree's second query, stand behind the filter's section: they take its tasks) */
+
 /* ---- search roll: every reference interval rolled to its best initial match (search_roll.hip) ----------------------------------
  * The first loop of the reference's search_in_reference_interval (src/search.cc:274-314, "Roll until we find best inital
  * match") for EVERY interval of sdf_search_windows in one call.  It reads no tree; filter and extend follow it in their own
- * sections, is_overlap and the tree update are not built.  Inputs: q[0, nq), windows[0, nq), first[0, nq + 1] and
+ * sections, is_overlap in its own behind them; the tree update is the caller's list.  Inputs: q[0, nq), windows[0, nq), first[0, nq + 1] and
  * intervals[0, first[nq]) as sdf_search_windows takes and writes them; r[0, nr), the reference range's minimizers in ASCENDING
  * LOC (sdf_pool_minimizers' list, not the sorted index); len_r, the reference sequence's length; init_len; limit[0, n_limit),
  * the same table.
@@ -751,7 +821,7 @@ int sdf_search_roll_host(const sdf_minimizer *q, size_t nq, const sdf_search_win
 /* ---- search filter: uppercase and q-gram verdicts per pair of pool ranges (search_filter.hip) -----------------------------------
  * The reference's filter() (src/filter.cc; called at src/search.cc:337, 356 and 374: once per rolled interval whose jaccard is
  * at least 0, once per hit after extend) for many pairs in one call.  It reads nothing but the resident pool.  is_overlap
- * and the tree are not built.
+ * stands behind this section.
  *
  * The sequence s of a side is pool[off, off + len) as it lies, or -- SDF_FILTER_Q_RC / SDF_FILTER_R_RC -- its reverse
  * complement by rev_dna: s[i] = rev_dna(pool[off + len - 1 - i]).  off is the first byte of the range in pool order whatever the
@@ -835,9 +905,48 @@ int sdf_search_filter_tasks_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_
                                    int64_t q_off, int q_rc, int64_t r_off, int r_rc, int allow_extend, sdf_filter_task *d_out,
                                    void *stream);
 
+/* ---- search against the SDs already found, second query: is_overlap for every rolled interval (search_found.hip) ----------------
+ * The found records, their prefixes and the bin index as stated behind the search seeding.  out[t] = 1 or 0 for interval t of sdf_search_roll, first[i] <= t < first[i + 1] for its
+ * window i; interval t sees found[0, visible_iv[t]).  min_read_size is the reference's Globals::Search::MIN_READ_SIZE -- a
+ * separate argument: initial_search passes the same number as init_len, but is_overlap reads the global.  With
+ * pf_pos = q[i].loc, pf_end = pf_pos + init_len, pfp_pos = rolls[t].ref_start and pfp_end = rolls[t].ref_end:
+ *   1. every visible, non-empty record with q_start <= pf_pos < q_end and r_start <= pfp_pos < r_end is looked at; sA, eA, sB,
+ *      eB are its four fields;
+ *   2. pf_pos >= sA && pf_end <= eA && pfp_pos >= sB && pfp_end <= eB: the answer is 1;
+ *   3. else min(eA - sA, eB - sB) < min_read_size * 1.5 (in double, as the reference's): the next record;
+ *   4. else eA - pf_pos >= min_read_size && eB - pfp_pos >= min_read_size: the answer is 1;
+ *   5. no record answered 1: the answer is 0.
+ * The verdict is computed from the roll record as given, whatever its flags; no field beyond those four is read.
+ *   SDF_ERR_INVALID      a null array with nq > 0 (rolls, visible_iv and out may be null when first[nq] == 0; found with
+ *                        nf == 0), init_len < 1, min_read_size < 0; checked forms: first[] not ascending from 0,
+ *                        visible_iv[t] > nf
+ *   SDF_ERR_UNSUPPORTED  init_len > 2^30, nq > 2^30 - 1, nf or the number of intervals > 2^31 - 1, more than 2^31 - 1 bin
+ *                        entries
+ * nq == 0 or no interval is SDF_OK without a launch. */
+int sdf_search_overlap(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, const uint64_t *first, const sdf_search_roll_rec *rolls,
+                       const sdf_search_found *found, size_t nf, const uint32_t *visible_iv /* first[nq] */, int32_t init_len,
+                       int32_t min_read_size, uint32_t *out /* first[nq] */);
+/* Device form: every array in HBM, the scalars checked, no host wait -- three launches for the index and one lane per interval,
+ * behind sdf_search_filter_tasks_device on one stream and in front of sdf_search_filter_device.  n_max as for
+ * sdf_search_roll_device: d_out and d_visible_iv have n_max entries, the lanes at or beyond d_first[nq] write 0 and read
+ * neither a roll record nor a prefix; nothing is written at or behind d_out[n_max].  d_filter_tasks (or NULL): the n_max tasks
+ * sdf_search_filter_tasks_device wrote; where the verdict is 1 the interval's task is replaced by the skip task
+ * {0, 0, 0, 0, SDF_FILTER_SKIP, 0}, so that sdf_search_filter_device answers SDF_FILTER_SKIPPED and sdf_search_extend_device
+ * SDF_EXTEND_SKIPPED for it -- the reference's INTERVAL_FAILED branch; no other task is touched.  found_entries_cap and
+ * d_found_entries as above. */
+int sdf_search_overlap_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const uint64_t *d_first,
+                              const sdf_search_roll_rec *d_rolls, size_t n_max, const sdf_search_found *d_found, size_t nf,
+                              size_t found_entries_cap, uint64_t *d_found_entries /* or NULL */, const uint32_t *d_visible_iv,
+                              int32_t init_len, int32_t min_read_size, uint32_t *d_out, sdf_filter_task *d_filter_tasks /* or NULL */,
+                              void *stream);
+/* No context, no GPU: the same in plain C++, a linear pass over found[0, visible).  Same checks and codes. */
+int sdf_search_overlap_host(const sdf_minimizer *q, size_t nq, const uint64_t *first, const sdf_search_roll_rec *rolls,
+                            const sdf_search_found *found, size_t nf, const uint32_t *visible_iv /* first[nq] */, int32_t init_len,
+                            int32_t min_read_size, uint32_t *out /* first[nq] */);
+
 /* ---- search extend: every rolled interval grown to its hit (search_extend.hip) ---------------------------------------------------
  * The reference's extend() (src/search.cc:95-259) for EVERY interval of sdf_search_roll in one call, as the reference calls it
- * with an EMPTY tree; is_overlap and the tree remain unbuilt.  Inputs: q, windows, first, intervals, r (ascending loc), nr,
+ * with an EMPTY tree (sdf_search_overlap_device turns an overlapped interval's task into a skip).  Inputs: q, windows, first, intervals, r (ascending loc), nr,
  * len_r, init_len, limit, n_limit as sdf_search_roll takes them; rolls[t] as it writes them; len_q; filter[t], the first
  * filter's verdicts (sdf_search_filter on the tasks with allow_extend != 0), or NULL; the parameters (the reference's defaults:
  * 0.30, 0.15, 1,048,576).

@@ -330,6 +330,8 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(sw_keys, None) X(sw_vals, None) X(sw_tmp, None) /* sdf_search_windows_device: sort keys and places (in, out), sort scratch, */ \
   X(sw_look, None) X(sw_counts, None) /* ... a SearchLook per query minimizer, intervals per window */                  \
   X(sw_q, None) X(sw_r, None) X(sw_limit, None) X(sw_first, None) X(sw_win, None) X(sw_out, None) /* sdf_search_windows: the host form's copies */ \
+  X(fo_counts, None) X(fo_start, None) X(fo_ent, None) X(fo_need, None) X(fo_tmp, None) /* the bin index of the found records: counts / cursors, bin starts, entries, the need, hipCUB scratch */ \
+  X(fo_found, None) X(fo_vis, None) X(fo_q, None) X(fo_first, None) X(fo_rolls, None) X(fo_out, None) /* sdf_search_windows_found, sdf_search_overlap: the host forms' copies */ \
   X(sr_q, None) X(sr_win, None) X(sr_first, None) X(sr_iv, None) X(sr_r, None) X(sr_limit, None) X(sr_out, None) /* sdf_search_roll: the host form's copies */ \
   X(sf_tasks, None) X(sf_out, None) /* sdf_search_filter: the host form's copies */ \
   X(se_rolls, None) X(se_filter, None) X(se_out, None) /* sdf_search_extend: the host form's copies (the rest: sdf_search_roll's) */ \

@@ -54,4 +54,14 @@ inline int counted_need(sdf_ctx *ctx, const uint64_t *d_first, size_t n, uint64_
   if (used) *used = (size_t)need;
   return need > cap ? refuse(ctx, SDF_ERR_CIGAR_OVERFLOW, before + std::to_string(need) + after) : SDF_OK;
 }
+
+// The found records of a search call (sdf_found_api.hip).  found_scalars: what every form checks of nf and of the bin entries
+// the index may hold.  found_index: the launches that build the bin index of d_found[0, nf) on `st` into the context's fo_*
+// buffers, at most `cap` entries; the need goes to fo_need and, when given, to *d_need; *F: the index as the kernels take it,
+// with `d_visible` as its prefixes.  found_index_need: behind a wait on the stream, SDF_ERR_CIGAR_OVERFLOW when the need
+// exceeded `cap`.
+int found_scalars(size_t nf, size_t cap, const char **why);
+int found_index(sdf_ctx *ctx, const sdf_search_found *d_found, size_t nf, size_t cap, uint64_t *d_need, const uint32_t *d_visible,
+                hipStream_t st, FoundIndex *F);
+int found_index_need(sdf_ctx *ctx, size_t cap);
 }  // namespace sdf

@@ -186,11 +186,50 @@ static_assert(sizeof(SearchLook) == 16 && sizeof(sdf_search_window) == 20 && siz
 __global__ void search_keys_kernel(const sdf_minimizer *, int, unsigned long long *, uint32_t *);
 __global__ void search_prev_kernel(const unsigned long long *, const uint32_t *, int, SearchLook *);
 __global__ void search_lookup_kernel(const sdf_minimizer *, int, const sdf_minimizer *, int, uint32_t, int, int, SearchLook *);
-// EMIT false: the windows' records and interval counts; true: the intervals
-template <bool EMIT>
+// search_found.hip: the bin index over the query axis of the found records, as the kernels that read it take it
+constexpr int FOUND_MAX = SDF_SEARCH_MAX_FOUND, FOUND_BIN_SHIFT = SDF_SEARCH_FOUND_BIN_SHIFT;
+constexpr int FOUND_BINS = 1 << (31 - FOUND_BIN_SHIFT);  // every base a 32-bit loc can name; a base below 0 counts as 0
+static_assert(sizeof(sdf_search_found) == 16, "include/sedef_hip.h");
+struct FoundIndex {
+  const sdf_search_found *found;
+  const unsigned long long *start;  // FOUND_BINS + 1: bin b's entries are entries[start[b], start[b + 1])
+  const uint32_t *entries;          // record ids; none at or behind entries[cap]
+  const uint32_t *visible;          // a prefix length per window (search_window_kernel) or per interval (search_overlap_kernel)
+  unsigned long long cap;
+  uint32_t nf;
+};
+__host__ __device__ inline int found_bin(const long long base) {
+  return base < 0 ? 0 : base > 0x7fffffffll ? FOUND_BINS - 1 : (int)(base >> FOUND_BIN_SHIFT);
+}
+__host__ __device__ inline bool found_empty(const sdf_search_found &R) { return R.q_start >= R.q_end || R.r_start >= R.r_end; }
+__host__ __device__ inline bool found_covers(const sdf_search_found &R, const long long loc, const long long pos) {
+  return R.q_start <= loc && loc < R.q_end && R.r_start <= pos && pos < R.r_end;
+}
+// a record that can contain the loc of a member of the window at qs: the ones SDF_SEARCH_FOUND_WIDE counts
+__host__ __device__ inline bool found_meets_window(const sdf_search_found &R, const long long qs, const long long init_len) {
+  return !found_empty(R) && R.q_start <= qs + init_len && R.q_end > qs;
+}
+// is_overlap's answer on ONE record that covers (pf_pos, pfp_pos): rules 2 to 4 of include/sedef_hip.h; the one form the
+// kernel and the host form share
+__host__ __device__ inline bool found_overlaps(const sdf_search_found &R, const long long pf_pos, const long long pf_end,
+                                               const long long pfp_pos, const long long pfp_end, const int min_read_size) {
+  const long long sA = R.q_start, eA = R.q_end, sB = R.r_start, eB = R.r_end;
+  if (pf_pos >= sA && pf_end <= eA && pfp_pos >= sB && pfp_end <= eB) return true;
+  const long long small = eA - sA < eB - sB ? eA - sA : eB - sB;
+  if ((double)small < min_read_size * 1.5) return false;
+  return eA - pf_pos >= min_read_size && eB - pfp_pos >= min_read_size;
+}
+__global__ void found_count_kernel(const sdf_search_found *, int, unsigned long long *);
+__global__ void found_fill_kernel(const sdf_search_found *, int, const unsigned long long *, unsigned long long *, uint32_t *,
+                                  unsigned long long, unsigned long long *);
+__global__ void search_overlap_kernel(const sdf_minimizer *, int, const uint64_t *, const sdf_search_roll_rec *, int, FoundIndex, int, int,
+                                      uint32_t *, sdf_filter_task *);
+// EMIT false: the windows' records and interval counts; true: the intervals.  FOUND: with the exclusions of the found records
+// (the index is read by these instantiations alone)
+template <bool EMIT, bool FOUND>
 __global__ void search_window_kernel(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, int, int,
                                      const int32_t *, int, sdf_search_window *, uint32_t *, const uint64_t *, sdf_search_interval *,
-                                     uint64_t);
+                                     uint64_t, FoundIndex);
 // search_roll.hip
 constexpr int ROLL_MAX_SPAN = SDF_ROLL_MAX_SPAN, ROLL_MAX_KEYS = SEARCH_MAX_MEMBERS + ROLL_MAX_SPAN;  // a wavefront's LDS: 32-bit keys, 16-bit slots
 static_assert(ROLL_MAX_KEYS < 65535 && sizeof(sdf_search_roll_rec) == 24, "search_roll.hip: slots are 16 bits wide; include/sedef_hip.h");

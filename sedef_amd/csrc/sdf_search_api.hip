@@ -25,6 +25,11 @@ struct SearchArgs {
   const int32_t *limit;
   size_t n_limit;
 };
+// the found records one window sees (include/sedef_hip.h, the section of the found records): found[0, visible)
+struct FoundView {
+  const sdf_search_found *found;
+  size_t visible;
+};
 struct SearchScratch {
   std::vector<uint64_t> keys;
   std::vector<int32_t> cand;
@@ -52,8 +57,10 @@ int search_arrays(const SearchArgs &A, const uint64_t *first, const sdf_search_w
   return SDF_OK;
 }
 
-// Window i as include/sedef_hip.h states it, step by step: its record, its intervals appended to T.
-void search_one_window(const SearchArgs &A, size_t i, sdf_search_window &W, std::vector<sdf_search_interval> &T, SearchScratch &S) {
+// Window i as include/sedef_hip.h states it, step by step: its record, its intervals appended to T.  F: the found records the
+// window sees, a linear pass per gathered position (null: an empty tree).
+void search_one_window(const SearchArgs &A, size_t i, sdf_search_window &W, std::vector<sdf_search_interval> &T, SearchScratch &S,
+                       const FoundView *F = nullptr) {
   W.query_size = W.n_members = W.n_gathered = W.n_candidates = 0, W.flags = 0;
   const int64_t qs = A.q[i].loc;
   if (qs + A.init_len > A.len_q) {  // 1
@@ -62,6 +69,17 @@ void search_one_window(const SearchArgs &A, size_t i, sdf_search_window &W, std:
   }
   S.keys.clear();
   S.cand.clear();
+  if (F) {
+    size_t meet = 0;
+    for (size_t f = 0; f < F->visible; f++) meet += found_meets_window(F->found[f], qs, A.init_len);
+    if (meet > SDF_SEARCH_MAX_FOUND) W.flags |= SDF_SEARCH_FOUND_WIDE;
+  }
+  const auto excluded = [&](int64_t loc, int64_t pos) {
+    if (!F) return false;
+    for (size_t f = 0; f < F->visible; f++)
+      if (!found_empty(F->found[f]) && found_covers(F->found[f], loc, pos)) return true;
+    return false;
+  };
   int64_t gathered = 0;
   size_t j = i;
   const auto key_less = [](const sdf_minimizer &m, uint64_t k) { return search_host_key(m) < k; };
@@ -75,7 +93,7 @@ void search_one_window(const SearchArgs &A, size_t i, sdf_search_window &W, std:
     if (g0 == g1 || (uint64_t)(g1 - g0) >= A.r_threshold) continue;
     gathered += g1 - g0;
     for (const sdf_minimizer *p = g0; p < g1; p++)
-      if (!A.same_genome || (int64_t)p->loc >= qs + A.init_len) S.cand.push_back(p->loc);
+      if ((!A.same_genome || (int64_t)p->loc >= qs + A.init_len) && !excluded(m.loc, p->loc)) S.cand.push_back(p->loc);
   }
   W.n_members = (int32_t)(j - i);
   W.n_gathered = gathered > 0x7fffffff ? 0x7fffffff : (int32_t)gathered;
@@ -110,18 +128,33 @@ void search_one_window(const SearchArgs &A, size_t i, sdf_search_window &W, std:
 }
 }  // namespace
 
-extern "C" int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
-                                       uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
-                                       const int32_t *limit, size_t n_limit, uint64_t *first, sdf_search_window *windows,
-                                       sdf_search_interval *out, size_t cap, size_t *used) {
+namespace {
+// what the forms that take host arrays check of a list of found records and its prefixes (n of them, each at most nf);
+// *entries: the bin entries of the list
+int found_arrays(const sdf_search_found *found, size_t nf, const uint32_t *visible, size_t n, uint64_t *entries, const char **why) {
+  if ((nf && !found) || (n && !visible)) return *why = "search found: invalid arguments", SDF_ERR_INVALID;
+  if (nf > 0x7fffffffu) return *why = "search found: more than 2^31 - 1 found records in one call", SDF_ERR_UNSUPPORTED;
+  for (size_t t = 0; t < n; t++)
+    if (visible[t] > nf) return *why = "search found: a prefix longer than the list", SDF_ERR_INVALID;
+  sdf_search_found_entries(found, nf, entries);
+  if (*entries > 0x7fffffffu) return *why = "search found: more than 2^31 - 1 bin entries in one call", SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+
+// sdf_search_windows_host, and with found != nullptr or nf > 0 sdf_search_windows_found_host
+int windows_host(const SearchArgs &A, bool with_found, const sdf_search_found *found, size_t nf, const uint32_t *visible, uint64_t *first,
+                 sdf_search_window *windows, sdf_search_interval *out, size_t cap, size_t *used) {
+  const size_t nq = A.nq;
   if (nq == 0) {
     if (used) *used = 0;
     if (first) first[0] = 0;
     return SDF_OK;
   }
-  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
   const char *why = nullptr;
   if (int rc = search_arrays(A, first, windows, out, cap, used, &why)) return rc;
+  uint64_t entries = 0;
+  if (with_found)
+    if (int rc = found_arrays(found, nf, visible, nq, &entries, &why)) return rc;
   // every window once; the intervals are kept here while they still fit below cap and reach `out` only when all of them do
   SearchScratch S;
   std::vector<sdf_search_interval> T, all;
@@ -129,7 +162,8 @@ extern "C" int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_
   for (size_t i = 0; i < nq; i++) {
     first[i] = at;
     T.clear();
-    search_one_window(A, i, windows[i], T, S);
+    const FoundView F{found, with_found ? (size_t)visible[i] : 0};
+    search_one_window(A, i, windows[i], T, S, with_found ? &F : nullptr);
     at += T.size();
     if (at <= cap) all.insert(all.end(), T.begin(), T.end());
   }
@@ -139,11 +173,29 @@ extern "C" int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_
   if (at) memcpy(out, all.data(), (size_t)at * sizeof(sdf_search_interval));
   return SDF_OK;
 }
+}  // namespace
+
+extern "C" int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                                       uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                       const int32_t *limit, size_t n_limit, uint64_t *first, sdf_search_window *windows,
+                                       sdf_search_interval *out, size_t cap, size_t *used) {
+  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
+  return windows_host(A, false, nullptr, 0, nullptr, first, windows, out, cap, used);
+}
+
+extern "C" int sdf_search_windows_found_host(const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                                             uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                             const int32_t *limit, size_t n_limit, const sdf_search_found *found, size_t nf,
+                                             const uint32_t *visible, uint64_t *first, sdf_search_window *windows,
+                                             sdf_search_interval *out, size_t cap, size_t *used) {
+  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
+  return windows_host(A, true, found, nf, visible, first, windows, out, cap, used);
+}
 
 // The launches in front of the intervals, on `st`: keys, their sort, prev, lookup, the windows' records and counts, d_first.
 static int search_count(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r, size_t nr,
                         uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *d_limit, size_t n_limit,
-                        uint64_t *d_first, sdf_search_window *d_windows, hipStream_t st) {
+                        uint64_t *d_first, sdf_search_window *d_windows, hipStream_t st, const FoundIndex *F = nullptr) {
   const int n = (int)nq;
   SDF_HIP(ctx->sw_keys.reserve(2 * nq * 8));
   SDF_HIP(ctx->sw_vals.reserve(2 * nq * 4));
@@ -161,9 +213,10 @@ static int search_count(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64
   SDF_HIP(hipcub::DeviceRadixSort::SortPairs(ctx->sw_tmp.p, t_pairs, d_keys, d_keys2, d_vals, d_vals2, n, 0, 64, st));
   hipLaunchKernelGGL(search_prev_kernel, grid, block, 0, st, d_keys2, d_vals2, n, d_look);
   hipLaunchKernelGGL(search_lookup_kernel, grid, block, 0, st, d_q, n, d_r, (int)nr, r_threshold, (int)init_len, uppercase_seeds, d_look);
-  hipLaunchKernelGGL(search_window_kernel<false>, dim3((unsigned)nq), dim3(64), 0, st, d_q, n, (long long)len_q, d_r, d_look, (int)init_len,
+  const auto kernel = F ? search_window_kernel<false, true> : search_window_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(64), 0, st, d_q, n, (long long)len_q, d_r, (const SearchLook *)d_look, (int)init_len,
                      same_genome, d_limit, (int)n_limit, d_windows, d_counts, (const uint64_t *)nullptr, (sdf_search_interval *)nullptr,
-                     (uint64_t)0);
+                     (uint64_t)0, F ? *F : FoundIndex{});
   hipLaunchKernelGGL(stats_cuts_scan_kernel, dim3(1), dim3(1024), 0, st, d_counts, n, d_first);
   SDF_HIP(hipGetLastError());
   ctx->launches += 5;
@@ -172,55 +225,106 @@ static int search_count(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64
 // the intervals (after search_count on the same stream)
 static int search_emit(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r, int32_t init_len,
                        int same_genome, const int32_t *d_limit, size_t n_limit, const uint64_t *d_first, sdf_search_interval *d_out,
-                       size_t cap, hipStream_t st) {
-  hipLaunchKernelGGL(search_window_kernel<true>, dim3((unsigned)nq), dim3(64), 0, st, d_q, (int)nq, (long long)len_q, d_r,
+                       size_t cap, hipStream_t st, const FoundIndex *F = nullptr) {
+  const auto kernel = F ? search_window_kernel<true, true> : search_window_kernel<true, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(64), 0, st, d_q, (int)nq, (long long)len_q, d_r,
                      (const SearchLook *)ctx->sw_look.p, (int)init_len, same_genome, d_limit, (int)n_limit, (sdf_search_window *)nullptr,
-                     (uint32_t *)nullptr, d_first, d_out, (uint64_t)cap);
+                     (uint32_t *)nullptr, d_first, d_out, (uint64_t)cap, F ? *F : FoundIndex{});
   SDF_HIP(hipGetLastError());
   ctx->launches += 1;
   return SDF_OK;
+}
+
+// sdf_search_windows_device, and with_found sdf_search_windows_found_device (a list without a record runs the plain kernels)
+static int windows_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted, size_t nr,
+                          uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *d_limit, size_t n_limit,
+                          bool with_found, const sdf_search_found *d_found, size_t nf, size_t found_entries_cap, uint64_t *d_found_entries,
+                          const uint32_t *d_visible, uint64_t *d_first, sdf_search_window *d_windows, sdf_search_interval *d_out, size_t cap,
+                          size_t *used, void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (nq == 0) {
+    if (used) *used = 0;
+    return SDF_OK;
+  }
+  if (!d_q || !d_first || !d_windows || (cap && !d_out) || (nr && !d_r_sorted) || (n_limit && !d_limit) ||
+      (with_found && ((nf && !d_found) || !d_visible)))
+    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_windows_device: invalid arguments");
+  const char *why = nullptr;
+  if (int rc = search_scalars(nq, nr, init_len, n_limit, &why)) return refuse(ctx, rc, why);
+  if (with_found)
+    if (int rc = found_scalars(nf, found_entries_cap, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  FoundIndex F{};
+  if (with_found)
+    if (int rc = found_index(ctx, d_found, nf, found_entries_cap, d_found_entries, d_visible, st, &F)) return rc;
+  const FoundIndex *Fp = with_found && nf ? &F : nullptr;
+  if (int rc = search_count(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, d_limit,
+                            n_limit, d_first, d_windows, st, Fp))
+    return rc;
+  if (int rc = search_emit(ctx, d_q, nq, len_q, d_r_sorted, init_len, same_genome != 0, d_limit, n_limit, d_first, d_out, cap, st, Fp)) return rc;
+  if (stream) return SDF_OK;
+  const int rc = counted_need(ctx, d_first, nq, nullptr, st, cap, used, "the windows have ", " intervals, more than cap");
+  if (rc == SDF_ERR_HIP || !with_found) return rc;
+  // (an index that did not fit comes first: the intervals counted on it are not the answer)
+  if (int short_index = found_index_need(ctx, found_entries_cap)) return short_index;
+  return rc;
 }
 
 extern "C" int sdf_search_windows_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted,
                                          size_t nr, uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
                                          const int32_t *d_limit, size_t n_limit, uint64_t *d_first, sdf_search_window *d_windows,
                                          sdf_search_interval *d_out, size_t cap, size_t *used, void *stream) {
-  if (!ctx) return SDF_ERR_INVALID;
-  ctx->err.clear();
-  if (nq == 0) {
-    if (used) *used = 0;
-    return SDF_OK;
-  }
-  if (!d_q || !d_first || !d_windows || (cap && !d_out) || (nr && !d_r_sorted) || (n_limit && !d_limit))
-    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_windows_device: invalid arguments");
-  const char *why = nullptr;
-  if (int rc = search_scalars(nq, nr, init_len, n_limit, &why)) return refuse(ctx, rc, why);
-  SDF_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  if (int rc = search_count(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, d_limit,
-                            n_limit, d_first, d_windows, st))
-    return rc;
-  if (int rc = search_emit(ctx, d_q, nq, len_q, d_r_sorted, init_len, same_genome != 0, d_limit, n_limit, d_first, d_out, cap, st)) return rc;
-  if (stream) return SDF_OK;
-  return counted_need(ctx, d_first, nq, nullptr, st, cap, used, "the windows have ", " intervals, more than cap");
+  return windows_device(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome, uppercase_seeds, d_limit, n_limit, false,
+                        nullptr, 0, 0, nullptr, nullptr, d_first, d_windows, d_out, cap, used, stream);
 }
 
-extern "C" int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
-                                  uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *limit,
-                                  size_t n_limit, uint64_t *first, sdf_search_window *windows, sdf_search_interval *out, size_t cap,
-                                  size_t *used) {
+extern "C" int sdf_search_windows_found_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q,
+                                               const sdf_minimizer *d_r_sorted, size_t nr, uint32_t r_threshold, int32_t init_len,
+                                               int same_genome, int uppercase_seeds, const int32_t *d_limit, size_t n_limit,
+                                               const sdf_search_found *d_found, size_t nf, size_t found_entries_cap,
+                                               uint64_t *d_found_entries, const uint32_t *d_visible, uint64_t *d_first,
+                                               sdf_search_window *d_windows, sdf_search_interval *d_out, size_t cap, size_t *used,
+                                               void *stream) {
+  return windows_device(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome, uppercase_seeds, d_limit, n_limit, true,
+                        d_found, nf, found_entries_cap, d_found_entries, d_visible, d_first, d_windows, d_out, cap, used, stream);
+}
+
+// sdf_search_windows, and with_found sdf_search_windows_found: the device form on copies, what it left completed on the host
+static int windows_checked(sdf_ctx *ctx, const SearchArgs &A, bool with_found, const sdf_search_found *found, size_t nf,
+                           const uint32_t *visible, uint64_t *first, sdf_search_window *windows, sdf_search_interval *out, size_t cap,
+                           size_t *used) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
+  const size_t nq = A.nq, nr = A.nr, n_limit = A.n_limit;
+  const sdf_minimizer *q = A.q, *r_sorted = A.r;
+  const int32_t *limit = A.limit;
+  const int64_t len_q = A.len_q;
+  const int32_t init_len = A.init_len;
   if (nq == 0) {
     if (used) *used = 0;
     if (first) first[0] = 0;
     return SDF_OK;
   }
-  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
   const char *why = nullptr;
   if (int rc = search_arrays(A, first, windows, out, cap, used, &why)) return refuse(ctx, rc, why);
+  uint64_t entries = 0;
+  if (with_found)
+    if (int rc = found_arrays(found, nf, visible, nq, &entries, &why)) return refuse(ctx, rc, why);
   SDF_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
+  FoundIndex F{};
+  const FoundIndex *Fp = nullptr;
+  if (with_found && nf) {
+    SDF_HIP(ctx->fo_found.reserve(nf * sizeof(sdf_search_found)));
+    SDF_HIP(ctx->fo_vis.reserve(nq * 4));
+    SDF_HIP(hipMemcpyAsync(ctx->fo_found.p, found, nf * sizeof(sdf_search_found), hipMemcpyHostToDevice, st));
+    SDF_HIP(hipMemcpyAsync(ctx->fo_vis.p, visible, nq * 4, hipMemcpyHostToDevice, st));
+    if (int rc = found_index(ctx, (const sdf_search_found *)ctx->fo_found.p, nf, (size_t)entries, nullptr, (const uint32_t *)ctx->fo_vis.p, st, &F))
+      return rc;
+    Fp = &F;
+  }
   SDF_HIP(ctx->sw_q.reserve(nq * sizeof(sdf_minimizer)));
   SDF_HIP(ctx->sw_r.reserve(nr * sizeof(sdf_minimizer)));
   SDF_HIP(ctx->sw_limit.reserve(n_limit * 4));
@@ -232,21 +336,22 @@ extern "C" int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t n
   SDF_HIP(hipMemcpyAsync(ctx->sw_q.p, q, nq * sizeof(sdf_minimizer), hipMemcpyHostToDevice, st));
   if (nr) SDF_HIP(hipMemcpyAsync(ctx->sw_r.p, r_sorted, nr * sizeof(sdf_minimizer), hipMemcpyHostToDevice, st));
   if (n_limit) SDF_HIP(hipMemcpyAsync(ctx->sw_limit.p, limit, n_limit * 4, hipMemcpyHostToDevice, st));
-  if (int rc = search_count(ctx, d_q, nq, len_q, d_r, nr, r_threshold, init_len, A.same_genome, A.uppercase_seeds, d_limit, n_limit, d_first,
-                            (sdf_search_window *)ctx->sw_win.p, st))
+  if (int rc = search_count(ctx, d_q, nq, len_q, d_r, nr, A.r_threshold, init_len, A.same_genome, A.uppercase_seeds, d_limit, n_limit, d_first,
+                            (sdf_search_window *)ctx->sw_win.p, st, Fp))
     return rc;
   SDF_HIP(hipMemcpyAsync(windows, ctx->sw_win.p, nq * sizeof(sdf_search_window), hipMemcpyDeviceToHost, st));
   SDF_HIP(hipMemcpyAsync(first, d_first, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
   SDF_HIP(hipStreamSynchronize(st));
   const uint64_t dev_need = first[nq];
-  // the WIDE windows, on the host; their intervals in window order, wide_first[t] those of the wide windows before the t-th
+  // the WIDE (and FOUND_WIDE) windows, on the host; their intervals in window order, wide_first[t] those of the wide windows before the t-th
   std::vector<size_t> wide;
   std::vector<uint64_t> wide_first(1, 0);
   std::vector<sdf_search_interval> T;
   SearchScratch S;
   for (size_t i = 0; i < nq; i++) {
-    if (!(windows[i].flags & SDF_SEARCH_WIDE)) continue;
-    search_one_window(A, i, windows[i], T, S);
+    if (!(windows[i].flags & (SDF_SEARCH_WIDE | SDF_SEARCH_FOUND_WIDE))) continue;
+    const FoundView V{found, with_found ? (size_t)visible[i] : 0};
+    search_one_window(A, i, windows[i], T, S, with_found ? &V : nullptr);
     wide.push_back(i);
     wide_first.push_back(T.size());
   }
@@ -263,7 +368,7 @@ extern "C" int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t n
   if (dev_need) {
     SDF_HIP(ctx->sw_out.reserve((size_t)dev_need * sizeof(sdf_search_interval)));
     if (int rc = search_emit(ctx, d_q, nq, len_q, d_r, init_len, A.same_genome, d_limit, n_limit, d_first, (sdf_search_interval *)ctx->sw_out.p,
-                             (size_t)dev_need, st))
+                             (size_t)dev_need, st, Fp))
       return rc;
     SDF_HIP(hipMemcpyAsync(out, ctx->sw_out.p, (size_t)dev_need * sizeof(sdf_search_interval), hipMemcpyDeviceToHost, st));
     SDF_HIP(hipStreamSynchronize(st));
@@ -278,6 +383,23 @@ extern "C" int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t n
     dev_end = dev_at;
   }
   return SDF_OK;
+}
+
+extern "C" int sdf_search_windows(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted, size_t nr,
+                                  uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *limit,
+                                  size_t n_limit, uint64_t *first, sdf_search_window *windows, sdf_search_interval *out, size_t cap,
+                                  size_t *used) {
+  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
+  return windows_checked(ctx, A, false, nullptr, 0, nullptr, first, windows, out, cap, used);
+}
+
+extern "C" int sdf_search_windows_found(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq, int64_t len_q, const sdf_minimizer *r_sorted,
+                                        size_t nr, uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                        const int32_t *limit, size_t n_limit, const sdf_search_found *found, size_t nf,
+                                        const uint32_t *visible, uint64_t *first, sdf_search_window *windows, sdf_search_interval *out,
+                                        size_t cap, size_t *used) {
+  const SearchArgs A{q, nq, len_q, r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, limit, n_limit};
+  return windows_checked(ctx, A, true, found, nf, visible, first, windows, out, cap, used);
 }
 
 // ---- the roll ----

@@ -90,16 +90,20 @@ constexpr uint32_t kSearchGone = 0xFFFFFFFFu;
 __device__ __forceinline__ uint32_t search_loc_key(int loc) { return (uint32_t)loc ^ 0x80000000u; }
 __device__ __forceinline__ long long search_key_loc(uint32_t k) { return (long long)(int)(k ^ 0x80000000u); }
 
-// EMIT false: windows[i] and counts[i] (the window's intervals); true: the intervals, from out[first[i]], none at or behind out[cap]
-template <bool EMIT>
+// EMIT false: windows[i] and counts[i] (the window's intervals); true: the intervals, from out[first[i]], none at or behind out[cap].
+// FOUND (include/sedef_hip.h, the section of the found records): the visible records that meet the window are staged in LDS
+// from the bins the window touches, and a gathered position that one of them covers at its member's loc is dropped like one
+// the same_genome filter drops; more than FOUND_MAX of them: SDF_SEARCH_FOUND_WIDE, and the window is left like a WIDE one.
+template <bool EMIT, bool FOUND>
 __global__ __launch_bounds__(64) void search_window_kernel(const sdf_minimizer *__restrict__ q, int nq, long long len_q,
                                                            const sdf_minimizer *__restrict__ r, const SearchLook *__restrict__ look,
                                                            int init_len, int same_genome, const int32_t *__restrict__ limit, int n_limit,
                                                            sdf_search_window *__restrict__ windows, uint32_t *__restrict__ counts,
                                                            const uint64_t *__restrict__ first, sdf_search_interval *__restrict__ out,
-                                                           uint64_t cap) {
+                                                           uint64_t cap, FoundIndex F) {
   __shared__ uint32_t c[SEARCH_MAX_GATHER];
   __shared__ uint16_t offs[SEARCH_MAX_MEMBERS + 1];
+  __shared__ sdf_search_found staged[FOUND_MAX];  // (FOUND alone refers to it)
   const int lane = threadIdx.x, i = blockIdx.x;
   uint64_t base = 0;
   if (EMIT) {
@@ -115,6 +119,34 @@ __global__ __launch_bounds__(64) void search_window_kernel(const sdf_minimizer *
   if (floor_loc > len_q) {
     W.flags = SDF_SEARCH_SHORT;
     return leave(0);
+  }
+  // the found records: every bin the window touches, 64 entries a round; a record is kept in the first of them that holds it,
+  // so once however many bins it spans, and the COUNT of the kept ones decides FOUND_WIDE
+  int n_found = 0;
+  if constexpr (FOUND) {
+    const uint32_t vis = F.visible[i] < F.nf ? F.visible[i] : F.nf;
+    const int b0 = found_bin(qs), b1 = found_bin(floor_loc);
+    for (int b = b0; b <= b1; b++) {
+      unsigned long long k0 = F.start[b], k1 = F.start[b + 1];
+      k1 = k1 < F.cap ? k1 : F.cap;
+      for (; k0 < k1; k0 += 64) {
+        const unsigned long long k = k0 + lane;
+        sdf_search_found R{0, 0, 0, 0};
+        bool take = false;
+        if (k < k1) {
+          const uint32_t id = F.entries[k];
+          if (id < vis) {
+            R = F.found[id];
+            const int rb = found_bin(R.q_start);
+            take = found_meets_window(R, qs, init_len) && b == (rb > b0 ? rb : b0);
+          }
+        }
+        const unsigned long long m = __ballot(take);
+        const int slot = n_found + __popcll(m & ((1ull << lane) - 1ull));
+        if (take && slot < FOUND_MAX) staged[slot] = R;
+        n_found += __popcll(m);
+      }
+    }
   }
   // counts: the members' records, 64 a round
   const int e = look[i].end, nm = e - i;
@@ -141,7 +173,15 @@ __global__ __launch_bounds__(64) void search_window_kernel(const sdf_minimizer *
   if (nm > SEARCH_MAX_MEMBERS || gathered > SEARCH_MAX_GATHER) {
     W.flags = SDF_SEARCH_WIDE;
     if (W.query_size >= n_limit) W.flags |= SDF_SEARCH_NOLIMIT;
+    if constexpr (FOUND) W.flags |= n_found > FOUND_MAX ? SDF_SEARCH_FOUND_WIDE : 0;
     return leave(0);
+  }
+  if constexpr (FOUND) {
+    if (n_found > FOUND_MAX) {
+      W.flags = SDF_SEARCH_FOUND_WIDE;
+      if (W.query_size >= n_limit) W.flags |= SDF_SEARCH_NOLIMIT;
+      return leave(0);
+    }
   }
   const int ng = (int)gathered;
   __syncthreads();
@@ -155,7 +195,11 @@ __global__ __launch_bounds__(64) void search_window_kernel(const sdf_minimizer *
       else hi = mid;
     }
     const int loc = r[(long long)look[i + lo].start + (s - (int)offs[lo])].loc;
-    const bool keep = !same_genome || (long long)loc >= floor_loc;
+    bool keep = !same_genome || (long long)loc >= floor_loc;
+    if constexpr (FOUND) {
+      const long long at = q[i + lo].loc;  // the member's loc
+      for (int f = 0; keep && f < n_found; f++) keep = !found_covers(staged[f], at, loc);
+    }
     c[s] = keep ? search_loc_key(loc) : kSearchGone;
     gone += keep ? 0 : 1;
   }
@@ -199,11 +243,14 @@ __global__ __launch_bounds__(64) void search_window_kernel(const sdf_minimizer *
   leave(heads);
 }
 
-template __global__ void search_window_kernel<false>(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, int, int,
-                                                     const int32_t *, int, sdf_search_window *, uint32_t *, const uint64_t *,
-                                                     sdf_search_interval *, uint64_t);
-template __global__ void search_window_kernel<true>(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, int, int,
-                                                    const int32_t *, int, sdf_search_window *, uint32_t *, const uint64_t *,
-                                                    sdf_search_interval *, uint64_t);
+#define SDF_SEARCH_WINDOW_KERNEL(EMIT, FOUND)                                                                                            \
+  template __global__ void search_window_kernel<EMIT, FOUND>(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, \
+                                                             int, int, const int32_t *, int, sdf_search_window *, uint32_t *,               \
+                                                             const uint64_t *, sdf_search_interval *, uint64_t, FoundIndex);
+SDF_SEARCH_WINDOW_KERNEL(false, false)
+SDF_SEARCH_WINDOW_KERNEL(true, false)
+SDF_SEARCH_WINDOW_KERNEL(false, true)
+SDF_SEARCH_WINDOW_KERNEL(true, true)
+#undef SDF_SEARCH_WINDOW_KERNEL
 
 }  // namespace sdf

@@ -60,6 +60,10 @@ SEARCH_INTERVAL_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4")])
 SEARCH_SHORT, SEARCH_NOLIMIT, SEARCH_WIDE = 0x1, 0x2, 0x4
 SEARCH_MAX_MEMBERS, SEARCH_MAX_GATHER = 1024, 4096
 assert SEARCH_WINDOW_DTYPE.itemsize == 20 and SEARCH_INTERVAL_DTYPE.itemsize == 8
+# include/sedef_hip.h: sdf_search_found (search_windows_found, search_overlap; SEARCH_FOUND_WIDE in a window's `flags`)
+SEARCH_FOUND_DTYPE = np.dtype([("q_start", "<i4"), ("q_end", "<i4"), ("r_start", "<i4"), ("r_end", "<i4")])
+SEARCH_FOUND_WIDE, SEARCH_MAX_FOUND, SEARCH_FOUND_BIN_SHIFT = 0x8, 256, 12
+assert SEARCH_FOUND_DTYPE.itemsize == 16
 # include/sedef_hip.h: sdf_search_roll_rec (search_roll; ROLL_* in `flags`)
 SEARCH_ROLL_DTYPE = np.dtype([("ref_start", "<i4"), ("ref_end", "<i4"), ("winnow_start", "<i4"), ("winnow_end", "<i4"),
                               ("jaccard", "<i4"), ("flags", "<u4")])
@@ -241,6 +245,24 @@ def load_library():
     L.sdf_search_windows_device.argtypes = [C.c_void_p] + _search + [C.c_void_p]
     L.sdf_search_windows_host.restype = C.c_int
     L.sdf_search_windows_host.argtypes = _search
+    _found = [C.c_void_p, C.c_size_t, C.c_void_p]  # found, nf, visible
+    _found_dev = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]  # d_found, nf, found_entries_cap, d_found_entries, d_visible
+    L.sdf_search_found_entries.restype = C.c_int
+    L.sdf_search_found_entries.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.sdf_search_windows_found.restype = C.c_int
+    L.sdf_search_windows_found.argtypes = [C.c_void_p] + _search[:11] + _found + _search[11:]
+    L.sdf_search_windows_found_device.restype = C.c_int
+    L.sdf_search_windows_found_device.argtypes = [C.c_void_p] + _search[:11] + _found_dev + _search[11:] + [C.c_void_p]
+    L.sdf_search_windows_found_host.restype = C.c_int
+    L.sdf_search_windows_found_host.argtypes = _search[:11] + _found + _search[11:]
+    _overlap = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]  # q, nq, first, rolls
+    _overlap_tail = [C.c_int32, C.c_int32, C.c_void_p]  # init_len, min_read_size, out
+    L.sdf_search_overlap.restype = C.c_int
+    L.sdf_search_overlap.argtypes = [C.c_void_p] + _overlap + _found + _overlap_tail
+    L.sdf_search_overlap_host.restype = C.c_int
+    L.sdf_search_overlap_host.argtypes = _overlap + _found + _overlap_tail
+    L.sdf_search_overlap_device.restype = C.c_int
+    L.sdf_search_overlap_device.argtypes = [C.c_void_p] + _overlap + [C.c_size_t] + _found_dev + _overlap_tail + [C.c_void_p, C.c_void_p]
     _roll = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]  # q, nq, windows, first, intervals
     _roll_tail = [C.c_void_p, C.c_size_t, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]  # r .. out
     L.sdf_search_roll.restype = C.c_int
@@ -958,6 +980,44 @@ class Extz2Engine:
         self._check(code)
         return first.astype(np.int64), windows, out[:used]
 
+    def search_windows_found_raw(self, q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, found, visible,
+                                 cap=None, out=None):
+        """sdf_search_windows_found as it is: search_windows_raw with the exclusions of the found records.  found: a
+        SEARCH_FOUND_DTYPE array in the order the hits were added; visible: per query minimizer the length of the prefix of
+        `found` its window sees.  Returns (rc, first, windows, intervals, used)."""
+        return search_windows_call(self.lib.sdf_search_windows_found, (self.ctx,), q, r_sorted, r_threshold, len_q, init_len,
+                                   same_genome, uppercase_seeds, limit, cap, out, found=found, visible=visible)
+
+    def search_windows_found_device(self, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome, uppercase_seeds, d_limit,
+                                    n_limit, d_found, nf, found_entries_cap, d_found_entries, d_visible, d_first, d_windows, d_out, cap,
+                                    stream=None):
+        """The same over device pointers (ints); found_entries_cap: the bin entries the index may hold (found_entries counts
+        them), d_found_entries: eight bytes that receive the need, or None.  On `stream` when one is given, else returns the
+        intervals the windows have (raises when they exceed cap, or the entries found_entries_cap).  A WIDE or FOUND_WIDE
+        window is flagged and has no interval."""
+        used = C.c_size_t(0)
+        self._check(self.lib.sdf_search_windows_found_device(
+            self.ctx, d_q, nq, int(len_q), d_r_sorted, nr, int(r_threshold), int(init_len), int(bool(same_genome)),
+            int(bool(uppercase_seeds)), d_limit, n_limit, d_found, nf, found_entries_cap, d_found_entries, d_visible, d_first, d_windows,
+            d_out, cap, C.byref(used), stream))
+        return int(used.value)
+
+    def search_overlap_raw(self, q, first, rolls, found, visible_iv, init_len, min_read_size):
+        """sdf_search_overlap as it is: the reference's is_overlap for every rolled interval.  q, first: as search_windows_raw
+        takes and returns them; rolls: search_roll_raw's records; found: a SEARCH_FOUND_DTYPE array; visible_iv: per interval
+        the length of the prefix of `found` it sees; min_read_size: the reference's MIN_READ_SIZE.  Returns (rc, verdicts):
+        uint32, 1 or 0."""
+        return search_overlap_call(self.lib.sdf_search_overlap, (self.ctx,), q, first, rolls, found, visible_iv, init_len, min_read_size)
+
+    def search_overlap_device(self, d_q, nq, d_first, d_rolls, n_max, d_found, nf, found_entries_cap, d_found_entries, d_visible_iv,
+                              init_len, min_read_size, d_out, d_filter_tasks=None, stream=None):
+        """The same over device pointers (ints), behind search_filter_tasks_device on one stream: n_max lanes, d_out and
+        d_visible_iv hold n_max entries.  d_filter_tasks: the tasks search_filter_tasks_device wrote, or None; where the verdict
+        is 1 the task becomes the skip task, so that the filter and the extension skip the interval."""
+        self._check(self.lib.sdf_search_overlap_device(self.ctx, d_q, nq, d_first, d_rolls, n_max, d_found, nf, found_entries_cap,
+                                                       d_found_entries, d_visible_iv, int(init_len), int(min_read_size), d_out,
+                                                       d_filter_tasks, stream))
+
     def search_roll_raw(self, q, windows, first, intervals, r, len_r, init_len, limit):
         """sdf_search_roll as it is.  q, windows, first, intervals: as search_windows_raw takes and returns them; r: the
         reference's minimizers in loc order (MINIMIZER_DTYPE); limit: the same table.  Returns (rc, rolls): a
@@ -1129,9 +1189,11 @@ class Extz2Engine:
         return int(self.lib.sdf_last_reran(self.ctx))
 
 
-def search_windows_call(fn, head, q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, cap=None, out=None):
+def search_windows_call(fn, head, q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, cap=None, out=None,
+                        found=None, visible=None):
     """sdf_search_windows (head: its context) or sdf_search_windows_host (head: nothing) on numpy arrays; the overflow protocol
-    as Extz2Engine.pool_minimizers_raw has it.  Returns (rc, first, windows, intervals, used)."""
+    as Extz2Engine.pool_minimizers_raw has it.  found and visible: for the _found forms of the two (a SEARCH_FOUND_DTYPE array,
+    a prefix length per query minimizer).  Returns (rc, first, windows, intervals, used)."""
     q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
     r_sorted = np.ascontiguousarray(r_sorted, dtype=MINIMIZER_DTYPE)
     limit = np.ascontiguousarray(limit, dtype=np.int32)
@@ -1141,9 +1203,16 @@ def search_windows_call(fn, head, q, r_sorted, r_threshold, len_q, init_len, sam
     def ptr(a):
         return a.ctypes.data if len(a) else None
 
+    mid = ()
+    if found is not None:
+        found = np.ascontiguousarray(found, dtype=SEARCH_FOUND_DTYPE)
+        visible = np.ascontiguousarray(visible, dtype=np.uint32)
+        assert len(visible) == len(q)
+        mid = (ptr(found), len(found), ptr(visible))
+
     def call(buf, c):
         return fn(*head, ptr(q), len(q), int(len_q), ptr(r_sorted), len(r_sorted), int(r_threshold), int(init_len),
-                  int(bool(same_genome)), int(bool(uppercase_seeds)), ptr(limit), len(limit), first.ctypes.data, ptr(windows),
+                  int(bool(same_genome)), int(bool(uppercase_seeds)), ptr(limit), len(limit), *mid, first.ctypes.data, ptr(windows),
                   ptr(buf), c, C.byref(used))
     if out is None:
         if cap is None:
@@ -1161,6 +1230,47 @@ def search_windows_host(q, r_sorted, r_threshold, len_q, init_len, same_genome, 
     """sdf_search_windows_host: search_windows_raw without a context or a GPU, in plain C++ on one thread."""
     return search_windows_call(load_library().sdf_search_windows_host, (), q, r_sorted, r_threshold, len_q, init_len, same_genome,
                                uppercase_seeds, limit, cap, out)
+
+
+def search_windows_found_host(q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, found, visible, cap=None,
+                              out=None):
+    """sdf_search_windows_found_host: search_windows_found_raw without a context or a GPU, in plain C++ on one thread."""
+    return search_windows_call(load_library().sdf_search_windows_found_host, (), q, r_sorted, r_threshold, len_q, init_len, same_genome,
+                               uppercase_seeds, limit, cap, out, found=found, visible=visible)
+
+
+def found_entries(found):
+    """sdf_search_found_entries: the bin entries of a list of found records -- what found_entries_cap of the device forms must
+    grant."""
+    found = np.ascontiguousarray(found, dtype=SEARCH_FOUND_DTYPE)
+    n = C.c_uint64(0)
+    rc = load_library().sdf_search_found_entries(found.ctypes.data if len(found) else None, len(found), C.byref(n))
+    assert rc == 0
+    return int(n.value)
+
+
+def search_overlap_call(fn, head, q, first, rolls, found, visible_iv, init_len, min_read_size):
+    """sdf_search_overlap (head: its context) or sdf_search_overlap_host (head: nothing) on numpy arrays.  Returns
+    (rc, verdicts)."""
+    q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    rolls = np.ascontiguousarray(rolls, dtype=SEARCH_ROLL_DTYPE)
+    found = np.ascontiguousarray(found, dtype=SEARCH_FOUND_DTYPE)
+    visible_iv = np.ascontiguousarray(visible_iv, dtype=np.uint32)
+    n = int(first[-1])
+    assert len(first) == len(q) + 1 and len(rolls) >= n and len(visible_iv) >= n
+    out = np.zeros(n, np.uint32)
+
+    def ptr(a):
+        return a.ctypes.data if len(a) else None
+    rc = fn(*head, ptr(q), len(q), first.ctypes.data, ptr(rolls), ptr(found), len(found), ptr(visible_iv), int(init_len),
+            int(min_read_size), ptr(out))
+    return rc, out
+
+
+def search_overlap_host(q, first, rolls, found, visible_iv, init_len, min_read_size):
+    """sdf_search_overlap_host: search_overlap_raw without a context or a GPU, in plain C++ on one thread."""
+    return search_overlap_call(load_library().sdf_search_overlap_host, (), q, first, rolls, found, visible_iv, init_len, min_read_size)
 
 
 def search_roll_call(fn, head, q, windows, first, intervals, r, len_r, init_len, limit):

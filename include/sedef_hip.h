@@ -702,8 +702,8 @@ int sdf_search_windows_host(const sdf_minimizer *q, size_t nq, int64_t len_q, co
  *   empty Subtree).
  * The prefix is per WINDOW for the exclusions (the tree is read before the window's intervals are walked) and per INTERVAL for
  * is_overlap (a hit of a window's first interval is in the tree when its second is tested).  tests/found_model.py holds the
- * record-list statement and a point-level model of the ICL tree that ties it to the reference's text.  The round-based driver
- * of initial_search, parse_hits and next_to_attain are not built.
+ * record-list statement and a point-level model of the ICL tree that ties it to the reference's text.  parse_hits,
+ * next_to_attain and the acceptance step of a round-based driver stand in the search driver's section, behind the extension.
  *
  * sdf_search_windows_found*: sdf_search_windows* with found, nf and visible[0, nq) -- window i sees found[0, visible[i]).  Steps
  * 1 to 7 as written there, with one addition in step 4: a gathered position pos of the member at loc is dropped when a visible
@@ -1087,6 +1087,154 @@ int sdf_search_hit_tasks_host(const sdf_search_hit *hits, size_t n, int64_t len_
                               int64_t r_off, int r_rc, sdf_filter_task *out);
 int sdf_search_hit_tasks_device(sdf_ctx *ctx, const sdf_search_hit *d_hits, size_t n, const uint64_t *d_count, int64_t len_q,
                                 int64_t len_r, int64_t q_off, int q_rc, int64_t r_off, int r_rc, sdf_filter_task *d_out, void *stream);
+
+/* ---- search driver: a pair's hits in the reference's order (search_accept.hip, sdf_driver_api.hip) -------------------------------
+ * initial_search (src/search_main.cc:41-82) over the stages above.  Three facts of the reference's text carry the design:
+ *   1. The windows that run do not depend on the hits.  initial_search calls search() with init_len = MIN_READ_SIZE and
+ *      allow_extend; every reported hit comes out of extend(), which first snaps the query range outward to minimizer boundaries
+ *      and whose undo only restores them, so query_end - query_start >= init_len for every hit, min_len >= MIN_READ_SIZE, and
+ *      next_to_attain = (int)(loc + (MIN_READ_SIZE * MAX_ERROR) / 2) after every window that is not skipped: the schedule is a
+ *      greedy walk over q[].loc and q[].status.
+ *   2. Only the tree couples windows, and it is read in the two places the found-record sections answer.  A record can change
+ *      window j, at qs_j = q[j].loc, only if its q_end > qs_j: both queries need a visible record whose query interval contains a
+ *      position in [qs_j, qs_j + init_len], and every record of an earlier window has q_start <= qs_j.
+ *   3. Inside one window the tree enters only through is_overlap: intervals and rolls are fixed once the window's exclusions
+ *      are known, filter and extend read no tree.  The order-dependent part is a replay of is_overlap against the hits of the
+ *      window's own earlier intervals.
+ * So many windows may run speculatively against the found list as it stood, and the ACCEPTANCE STEP below takes, in order,
+ * every window that no newly kept record reaches.
+ *
+ * sdf_search_pair_host: the reference-order statement in plain C++, no context, no GPU.  The query sequence is
+ * pool[q_range.off, + len), the reference's pool[r_range.off, + len), each reverse-complemented under SDF_MINIM_RC; minimizers
+ * and index as the minimizer section states them (k, w, separate_lowercase), init_len = is_overlap's min_read_size =
+ * params->min_read_size, MAX_ERROR = params->filter.max_error.  For window i over q[0, nq) in order, next = 0 at the start:
+ *   skip       q[i].loc < next, or uppercase_seeds and q[i].status != 0.
+ *   window     sdf_search_windows_found's window i with the whole found list visible; SHORT or NOLIMIT: no intervals, no hits.
+ *   intervals  in order, attempted += 1, then: the roll's jaccard < 0: jaccard_failed += 1.  Else is_overlap (rules 1 to 5 of
+ *              the sdf_search_overlap section) against the whole current list, the records of this window's earlier intervals
+ *              included: interval_failed += 1.  Else the first filter (the task of sdf_search_filter_tasks_* with
+ *              allow_extend != 0) fails: nothing.  Else extend; SDF_EXTEND_SKIPPED or SDF_EXTEND_NOLIMIT is no hit, a WIDE record
+ *              is completed and is one.  Else the second filter (sdf_search_hit_tasks_*) fails: nothing.  Else the hit joins the
+ *              window's list and {query_start, query_end, ref_start, ref_end} is appended to the found list.
+ *   parse_hits hit h of the window's list is dropped when some OTHER hit p of it has h.ref_start >= p.ref_start, h.ref_end <=
+ *              p.ref_end, h.query_start >= p.query_start and h.query_end <= p.query_end; two identical hits drop each other.
+ *              The survivors are reported in list order.  A dropped hit stays in the found list.
+ *   next       min_len = the minimum of len_q and the reported hits' query lengths; next = min_len >= min_read_size ?
+ *              (int)(q[i].loc + (min_read_size * max_error) / 2) : q[i].loc, in double, this association, truncated.
+ * out[0, *used) are the reported hits, `window` the index i; stats the three counters (rounds 0, the three window counts the
+ * windows that were not skipped).  More than cap hits: SDF_ERR_CIGAR_OVERFLOW, *used the need, nothing written.
+ *   SDF_ERR_INVALID      a null pointer (out may be null with cap == 0), a range with off < 0, len < 0 or outside the pool,
+ *                        min_read_size < 1, same_genome with different ranges or a strand flag, a parameter that is not finite,
+ *                        max_error - max_edit_error <= 0
+ *   SDF_ERR_UNSUPPORTED  k outside 1..15, w outside 1..SDF_MINIM_MAX_W, a range flag other than SDF_MINIM_RC, limit[s] < 1 for
+ *                        some s >= 1, n_limit > 2^31 - 1, min_read_size > 2^30, reserved != 0
+ *
+ * The acceptance step, sdf_search_accept*: ONE ROUND -- the ascending window indices act[0, na) that ran, and what the chain
+ * wrote for them: windows, first, rolls, the is_overlap verdicts against the found list as it stood (`overlap`), the first
+ * filter's records, the hits and the second filter's records, all indexed as the stages write them (n_max: the records the
+ * per-interval arrays hold) -- against found[0, nf) and out[0, n_out).
+ *   per window, in interval order   attempted += 1.  jaccard < 0: jaccard_failed += 1.  Else verdict != 0: interval_failed += 1.
+ *              Else is_overlap with pf_pos = q[i].loc and the roll's range answers 1 against the records KEPT so far in this
+ *              window: interval_failed += 1.  Else the interval is a candidate -- its first filter has none of UPPER_FAIL |
+ *              QGRAM_FAIL | SKIPPED, its hit neither SKIPPED nor NOLIMIT, its second filter passed likewise --: it is kept.
+ *              parse_hits over the kept hits as above.
+ *   incomplete the device left a record for the host: window flags WIDE or FOUND_WIDE; a roll with SDF_ROLL_WIDE and
+ *              ref_end == 0, or BADWINDOW; a hit with SDF_EXTEND_WIDE and query_end == 0; more than SDF_ACCEPT_MAX_KEPT kept
+ *              hits; first[i + 1] > n_max (device form: act[j] >= nq or first[] descending too).
+ *   frontier   reach_j: the maximum q_end over the records kept by the round's windows before act[j] (0: none).  The frontier
+ *              is the first j with reach_j > q[act[j]].loc -- strictly: q_end == qs_j does not reach -- or act[j] incomplete; na
+ *              when there is none.  The windows before it are ACCEPTED.
+ *   append     in window order, then interval order: the kept records of accepted windows to found[nf ..], their survivors to
+ *              out[n_out ..] as {window_base + i, query_start, query_end, ref_start, ref_end, jaccard}; the counters of accepted
+ *              windows added up.  Nothing of a window at or behind the frontier is written anywhere.
+ *   status     {frontier, flags, nf, n_out, need_found, need_out, attempted, jaccard_failed, interval_failed}: the new counts
+ *              (need_* equal them), SDF_ACCEPT_INCOMPLETE when the frontier window is incomplete.  A capacity is short
+ *              (need_found > found_cap or need_out > out_cap): SDF_ACCEPT_OVERFLOW alone, the needs, frontier 0, nf and n_out as
+ *              given, the counters 0, and nothing is written: the round is not accepted.
+ * SDF_ACCEPT_MAX_KEPT: a wavefront keeps a window's kept records in LDS, 16 bytes of coordinates, the interval's index and a
+ * byte: 512 of them are 10.5 KB, so fifteen wavefronts share a CU's 160 KB and LDS does not bound the occupancy before the
+ * wavefront slots do at one wavefront per workgroup.
+ * The device form: every array of the round in HBM (the struct itself on the host), nothing checked beyond the scalars, no host
+ * wait, on `stream` (NULL: the context's own, synchronised before returning): one wavefront per round window, one workgroup for
+ * the frontier (prefix maximum, first-true, exclusive sums), one wavefront per round window for the append -- three launches, one
+ * when na == 0.  Nothing is written at or behind d_found[found_cap] or d_out[out_cap].  sdf_search_accept takes host arrays,
+ * runs the device form on copies and brings found[nf, status->nf), out[n_out, status->n_out) and the status back.  The host form
+ * is the same rules in plain C++; the three agree byte for byte, the status included.
+ *   SDF_ERR_INVALID      a null pointer where a count is not 0, init_len < 1, min_read_size < 0, nf > found_cap,
+ *                        n_out > out_cap; checked forms: act[] not strictly ascending or >= nq, first[] not ascending from 0
+ *   SDF_ERR_UNSUPPORTED  init_len > 2^30, nq > 2^30 - 1, na, n_max, found_cap or out_cap > 2^31 - 1, reserved != 0
+ *
+ * sdf_search_pair: the driver, over two ranges of the resident pool; out, *used and the three counters of stats equal what
+ * sdf_search_pair_host writes for the same characters, byte for byte, for every round_windows.  Set-up: sdf_pool_minimizers of
+ * both ranges and sdf_pool_minimizer_index of the reference's (host copies serve the schedule and the host step; the device
+ * copies stay in HBM for every round), and the schedule by fact 1, one pass over q.  A round takes the next round_windows
+ * scheduled windows (0: 64, not measured) and enqueues on the context's stream: sdf_search_windows_found_device on the slice of q
+ * from the round's first window to the last member of its last one, every window seeing the whole list (the tail of first[]
+ * behind the slice is filled, so that every later call takes all of q and the windows outside the slice have no intervals),
+ * roll, filter tasks, overlap with the skip-task rewrite, filter, extend, extend-long (16 candidates a round, batches of 8),
+ * hit tasks, the second filter, sdf_search_accept_device with act = the scheduled windows -- the windows of the slice that are
+ * not scheduled run but are not in act and contribute nothing.  Then ONE wait for 80 bytes: the status, the bin entries the
+ * index needed and the intervals the slice had; when the round added records, they are copied to the host's mirrors of found
+ * and out behind a second wait.  After it the next round starts at the frontier.  SDF_ACCEPT_INCOMPLETE: the host runs the
+ * frontier window by the per-window step of sdf_search_pair_host on characters fetched from the pool once, uploads its
+ * records and goes on behind it; with debug_host_every = d it does the same for every d-th scheduled window.  A capacity that
+ * was short -- bin entries, intervals (4,096 at the start) -- is doubled beyond the need and the round repeated (a round whose
+ * first windows had their records is taken as far as they go); found and the round's out are sized for the round beforehand.
+ * A round that accepts nothing, hands nothing to the host and raised no capacity is SDF_ERR_HIP, "internal error".  stats:
+ * rounds, windows_run (round windows, repeats counted, and host windows), windows_scheduled, windows_host -- these alone may
+ * differ between forms and round sizes.  Refusals as for sdf_search_pair_host, ranges against sdf_pool_bytes(ctx); every check
+ * precedes the first launch.  Overflow of out as for sdf_pool_minimizers.  The host form scans the whole found list per
+ * interval and keeps a window record per query minimizer: a statement to compare with, not to time at chromosome size.
+ * What remains of `sedef search`: the command line (FASTA reading, BED text, the -r coordinate flip of to_bed, -t translation). */
+#define SDF_ACCEPT_MAX_KEPT 512
+#define SDF_ACCEPT_INCOMPLETE 0x1
+#define SDF_ACCEPT_OVERFLOW 0x2
+typedef struct { int32_t window, query_start, query_end, ref_start, ref_end, jaccard; } sdf_search_pair_hit; /* 24 bytes */
+typedef struct {
+  uint32_t frontier, flags;
+  uint64_t nf, n_out, need_found, need_out;
+  int64_t attempted, jaccard_failed, interval_failed;
+} sdf_search_accept_status; /* 64 bytes */
+typedef struct {
+  const sdf_minimizer *q;
+  size_t nq;
+  const uint32_t *act;
+  size_t na;
+  const sdf_search_window *windows; /* nq */
+  const uint64_t *first;            /* nq + 1 */
+  size_t n_max;
+  const sdf_search_roll_rec *rolls; /* n_max, as the four behind it */
+  const uint32_t *overlap;
+  const sdf_filter_rec *filter;
+  const sdf_search_hit *hits;
+  const sdf_filter_rec *hit_filter;
+  int32_t init_len, min_read_size, window_base, reserved; /* 0 */
+} sdf_search_accept_round;
+int sdf_search_accept(sdf_ctx *ctx, const sdf_search_accept_round *round, sdf_search_found *found, size_t nf, size_t found_cap,
+                      sdf_search_pair_hit *out, size_t n_out, size_t out_cap, sdf_search_accept_status *status);
+int sdf_search_accept_device(sdf_ctx *ctx, const sdf_search_accept_round *round /* its arrays in HBM */, sdf_search_found *d_found,
+                             size_t nf, size_t found_cap, sdf_search_pair_hit *d_out, size_t n_out, size_t out_cap,
+                             sdf_search_accept_status *d_status, void *stream);
+int sdf_search_accept_host(const sdf_search_accept_round *round, sdf_search_found *found, size_t nf, size_t found_cap,
+                           sdf_search_pair_hit *out, size_t n_out, size_t out_cap, sdf_search_accept_status *status);
+typedef struct {
+  int32_t k, w, separate_lowercase, uppercase_seeds, min_read_size, same_genome;
+  sdf_filter_params filter;
+  sdf_extend_params extend;
+  const int32_t *limit;
+  size_t n_limit;
+  size_t round_windows;    /* the driver's: 0 means a default */
+  size_t debug_host_every; /* the driver's: 0 means off */
+} sdf_search_pair_params;
+typedef struct {
+  int64_t attempted, jaccard_failed, interval_failed;
+  int64_t rounds, windows_run, windows_scheduled, windows_host;
+} sdf_search_pair_stats; /* 56 bytes */
+int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
+                    sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats);
+int sdf_search_pair_host(const char *pool, size_t pool_bytes, const sdf_minim_range *q_range, const sdf_minim_range *r_range,
+                         const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
+                         sdf_search_pair_stats *stats);
 
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is

@@ -336,6 +336,11 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(sf_tasks, None) X(sf_out, None) /* sdf_search_filter: the host form's copies */ \
   X(se_rolls, None) X(se_filter, None) X(se_out, None) /* sdf_search_extend: the host form's copies (the rest: sdf_search_roll's) */ \
   X(sl_ws, None) X(sl_tmp, None) /* sdf_search_extend_long_device: flags, list, a batch's keys / payloads / heads / slots; hipCUB scratch */ \
+  X(ac_win, None) X(ac_kept, None) X(ac_off, None) X(ac_go, None) /* sdf_search_accept_device: an AcceptWin and an AcceptOff per round window, the kept entries, the windows the append may write */ \
+  X(ac_in, None) X(ac_found, None) X(ac_out, None) X(ac_status, None) /* sdf_search_accept: the host form's copies (the round's arrays in one piece) */ \
+  X(dr_q, None) X(dr_r, None) X(dr_rs, None) X(dr_limit, None) X(dr_found, None) /* sdf_search_pair: minimizers of both ranges, the reference's index, the limit table, the found list */ \
+  X(dr_first, None) X(dr_win, None) X(dr_vis, None) X(dr_act, None) X(dr_iv, None) X(dr_rolls, None) X(dr_tasks, None) X(dr_verd, None) /* ... a round: per window, per interval */ \
+  X(dr_frec, None) X(dr_hits, None) X(dr_htasks, None) X(dr_hrec, None) X(dr_out, None) X(dr_status, None) /* ... the round's hits and status (with the two needs behind it) */ \
   X(h_pool, BatchCall) X(h_out, BatchCall) X(h_cig, BatchCall) /* device buffers of the host-buffer entry point */    \
   X(h_brief, BatchCall) /* ... 16-byte result records (sdf_extz2_batch_brief) */                                      \
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \

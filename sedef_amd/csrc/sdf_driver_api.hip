@@ -1,0 +1,620 @@
+// The C ABI: the search driver (include/sedef_hip.h states the rules) -- the acceptance step of a round (search_accept.hip),
+// sdf_search_accept_host being the same rules in plain C++; sdf_search_pair_host, initial_search window by window on the host
+// over the per-window forms of the stages (sdf_search_api.hip) with minimizers and index computed here as tests/minim_model.py
+// states them; and sdf_search_pair, the stages and the acceptance step in rounds on the resident pool.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <deque>
+#include <map>
+#include <string>
+
+#include "sdf_entry.h"
+
+using namespace sdf;
+
+namespace {
+// what every form of the acceptance step checks of its scalars and of the pointers a count makes necessary
+int accept_scalars(const sdf_search_accept_round *R, const void *found, size_t nf, size_t found_cap, const void *out, size_t n_out,
+                   size_t out_cap, const void *status, const char **why) {
+  if (!R || !status) return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
+  if (R->init_len < 1) return *why = "search accept: init_len < 1", SDF_ERR_INVALID;
+  if (R->min_read_size < 0) return *why = "search accept: min_read_size < 0", SDF_ERR_INVALID;
+  if (nf > found_cap || n_out > out_cap) return *why = "search accept: a count beyond its capacity", SDF_ERR_INVALID;
+  if ((found_cap && !found) || (out_cap && !out)) return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
+  if (R->na && (!R->act || !R->q || !R->windows || !R->first)) return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
+  if (R->na && R->n_max && (!R->rolls || !R->overlap || !R->filter || !R->hits || !R->hit_filter))
+    return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
+  if (R->init_len > (1 << 30)) return *why = "search accept implements init_len up to 2^30", SDF_ERR_UNSUPPORTED;
+  if (R->nq > 0x3fffffffu) return *why = "search accept: more than 2^30 - 1 query minimizers in one call", SDF_ERR_UNSUPPORTED;
+  if (R->na > 0x7fffffffu || R->n_max > 0x7fffffffu || found_cap > 0x7fffffffu || out_cap > 0x7fffffffu)
+    return *why = "search accept: more than 2^31 - 1 round windows, intervals or records in one call", SDF_ERR_UNSUPPORTED;
+  if (R->reserved != 0) return *why = "search accept: reserved != 0", SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+// ... and the forms that take host arrays of those
+int accept_arrays(const sdf_search_accept_round *R, const char **why) {
+  if (!R->na) return SDF_OK;
+  for (size_t j = 0; j < R->na; j++)
+    if (R->act[j] >= R->nq || (j && R->act[j] <= R->act[j - 1]))
+      return *why = "search accept: act[] does not ascend strictly inside [0, nq)", SDF_ERR_INVALID;
+  if (R->first[0] != 0) return *why = "search accept: first[0] != 0", SDF_ERR_INVALID;
+  for (size_t i = 0; i < R->nq; i++)
+    if (R->first[i + 1] < R->first[i]) return *why = "search accept: first[] does not ascend", SDF_ERR_INVALID;
+  return SDF_OK;
+}
+
+// the three launches on `st` (one when the round is empty)
+int accept_launch(sdf_ctx *ctx, const sdf_search_accept_round *R, sdf_search_found *d_found, size_t nf, size_t found_cap,
+                  sdf_search_pair_hit *d_out, size_t n_out, size_t out_cap, sdf_search_accept_status *d_status, hipStream_t st) {
+  const size_t na = R->na;
+  SDF_HIP(ctx->ac_win.reserve((na + 1) * sizeof(AcceptWin)));
+  SDF_HIP(ctx->ac_off.reserve((na + 1) * sizeof(AcceptOff)));
+  SDF_HIP(ctx->ac_kept.reserve((R->n_max + 1) * 4));
+  SDF_HIP(ctx->ac_go.reserve(4));
+  const AcceptRound A{R->q,    R->act,        R->windows,         R->first,    R->rolls,     R->overlap,          R->filter,
+                      R->hits, R->hit_filter, (long long)R->n_max, (int)R->nq, (int)na, (int)R->init_len, (int)R->min_read_size, (int)R->window_base};
+  AcceptWin *d_win = (AcceptWin *)ctx->ac_win.p;
+  AcceptOff *d_off = (AcceptOff *)ctx->ac_off.p;
+  uint32_t *d_kept = (uint32_t *)ctx->ac_kept.p, *d_go = (uint32_t *)ctx->ac_go.p;
+  if (na) hipLaunchKernelGGL(search_accept_window_kernel, dim3((unsigned)na), dim3(64), 0, st, A, d_win, d_kept);
+  hipLaunchKernelGGL(search_accept_frontier_kernel, dim3(1), dim3(1024), 0, st, (const AcceptWin *)d_win, (int)na, (unsigned long long)nf,
+                     (unsigned long long)found_cap, (unsigned long long)n_out, (unsigned long long)out_cap, d_off, d_status, d_go);
+  if (na)
+    hipLaunchKernelGGL(search_accept_append_kernel, dim3((unsigned)na), dim3(64), 0, st, A, (const AcceptWin *)d_win, (const uint32_t *)d_kept,
+                       (const AcceptOff *)d_off, (const uint32_t *)d_go, d_found, (unsigned long long)nf, (unsigned long long)found_cap, d_out,
+                       (unsigned long long)n_out, (unsigned long long)out_cap);
+  SDF_HIP(hipGetLastError());
+  ctx->launches += na ? 3 : 1;
+  return SDF_OK;
+}
+}  // namespace
+
+extern "C" int sdf_search_accept_host(const sdf_search_accept_round *R, sdf_search_found *found, size_t nf, size_t found_cap,
+                                      sdf_search_pair_hit *out, size_t n_out, size_t out_cap, sdf_search_accept_status *status) {
+  const char *why = nullptr;
+  if (int rc = accept_scalars(R, found, nf, found_cap, out, n_out, out_cap, status, &why)) return rc;
+  if (int rc = accept_arrays(R, &why)) return rc;
+  struct Kept {
+    uint64_t t;
+    bool dropped;
+  };
+  std::vector<Kept> kept;  // of the windows in front of the frontier, in order
+  std::vector<sdf_search_found> recs;
+  int64_t attempted = 0, jaccard_failed = 0, interval_failed = 0;
+  uint64_t n_found = 0, n_reported = 0;
+  int32_t reach = 0;
+  size_t frontier = R->na;
+  bool incomplete = false;
+  for (size_t j = 0; j < R->na; j++) {
+    const size_t i = R->act[j];
+    const long long pf_pos = R->q[i].loc, pf_end = pf_pos + R->init_len;
+    const uint64_t t0 = R->first[i], t1 = R->first[i + 1];
+    incomplete = t1 > R->n_max || (R->windows[i].flags & (SDF_SEARCH_WIDE | SDF_SEARCH_FOUND_WIDE));
+    int64_t att = 0, jf = 0, ivf = 0;
+    int32_t reach_w = 0;
+    recs.clear();
+    const size_t kept0 = kept.size();
+    for (uint64_t t = t0; t < t1 && t1 <= R->n_max; t++) {
+      const sdf_search_roll_rec &roll = R->rolls[t];
+      const sdf_search_hit &H = R->hits[t];
+      incomplete |= accept_unfinished(roll, H);
+      att += 1;
+      const int cls = accept_class(roll, R->overlap[t], R->filter[t], H, R->hit_filter[t]);
+      if (cls == 0) jf += 1;
+      if (cls == 1) ivf += 1;
+      if (cls < 2) continue;
+      bool hit = false;
+      for (size_t k = 0; k < recs.size() && !hit; k++)
+        hit = !found_empty(recs[k]) && found_covers(recs[k], pf_pos, roll.ref_start) &&
+              found_overlaps(recs[k], pf_pos, pf_end, roll.ref_start, roll.ref_end, R->min_read_size);
+      if (hit) {
+        ivf += 1;
+      } else if (cls == 3) {
+        if (recs.size() < SDF_ACCEPT_MAX_KEPT) {
+          recs.push_back(sdf_search_found{H.query_start, H.query_end, H.ref_start, H.ref_end});
+          kept.push_back(Kept{t, false});
+          reach_w = std::max(reach_w, H.query_end);
+        } else {
+          incomplete = true;
+        }
+      }
+    }
+    if (reach > pf_pos || incomplete) {
+      kept.resize(kept0);
+      frontier = j;
+      break;
+    }
+    incomplete = false;
+    uint64_t survivors = 0;
+    for (size_t h = 0; h < recs.size(); h++) {  // parse_hits
+      bool dropped = false;
+      for (size_t p = 0; p < recs.size() && !dropped; p++) dropped = p != h && accept_contains(recs[p], recs[h]);
+      kept[kept0 + h].dropped = dropped;
+      survivors += !dropped;
+    }
+    n_found += recs.size(), n_reported += survivors;
+    attempted += att, jaccard_failed += jf, interval_failed += ivf;
+    reach = std::max(reach, reach_w);
+  }
+  sdf_search_accept_status S;
+  S.need_found = nf + n_found, S.need_out = n_out + n_reported;
+  const bool over = S.need_found > found_cap || S.need_out > out_cap;
+  S.frontier = over ? 0u : (uint32_t)frontier;
+  S.flags = over ? SDF_ACCEPT_OVERFLOW : incomplete ? SDF_ACCEPT_INCOMPLETE : 0u;
+  S.nf = over ? nf : S.need_found, S.n_out = over ? n_out : S.need_out;
+  S.attempted = over ? 0 : attempted, S.jaccard_failed = over ? 0 : jaccard_failed, S.interval_failed = over ? 0 : interval_failed;
+  *status = S;
+  if (over) return SDF_OK;
+  // the append: window order, then interval order -- the order of `kept`
+  size_t w = 0;
+  for (size_t j = 0; j < frontier; j++) {
+    const size_t i = R->act[j];
+    for (; w < kept.size() && kept[w].t < R->first[i + 1]; w++) {
+      const sdf_search_hit &H = R->hits[kept[w].t];
+      found[nf++] = sdf_search_found{H.query_start, H.query_end, H.ref_start, H.ref_end};
+      if (!kept[w].dropped)
+        out[n_out++] = sdf_search_pair_hit{(int32_t)(R->window_base + (int32_t)i), H.query_start, H.query_end, H.ref_start, H.ref_end, H.jaccard};
+    }
+  }
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_accept_device(sdf_ctx *ctx, const sdf_search_accept_round *R, sdf_search_found *d_found, size_t nf, size_t found_cap,
+                                        sdf_search_pair_hit *d_out, size_t n_out, size_t out_cap, sdf_search_accept_status *d_status,
+                                        void *stream) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  const char *why = nullptr;
+  if (int rc = accept_scalars(R, d_found, nf, found_cap, d_out, n_out, out_cap, d_status, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = accept_launch(ctx, R, d_found, nf, found_cap, d_out, n_out, out_cap, d_status, st)) return rc;
+  if (!stream) SDF_HIP(hipStreamSynchronize(st));
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_accept(sdf_ctx *ctx, const sdf_search_accept_round *R, sdf_search_found *found, size_t nf, size_t found_cap,
+                                 sdf_search_pair_hit *out, size_t n_out, size_t out_cap, sdf_search_accept_status *status) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  const char *why = nullptr;
+  if (int rc = accept_scalars(R, found, nf, found_cap, out, n_out, out_cap, status, &why)) return refuse(ctx, rc, why);
+  if (int rc = accept_arrays(R, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // the round's arrays in one piece; the per-interval ones hold what the windows name and no more than n_max
+  const size_t n = R->na ? (size_t)std::min<uint64_t>(R->first[R->nq], R->n_max) : 0, nq = R->na ? R->nq : 0;
+  struct Piece {
+    const void *src;
+    size_t bytes, at;
+  } P[] = {{R->q, nq * sizeof(sdf_minimizer), 0},        {R->act, R->na * 4, 0},
+           {R->windows, nq * sizeof(sdf_search_window), 0}, {R->first, R->na ? (nq + 1) * 8 : 0, 0},
+           {R->rolls, n * sizeof(sdf_search_roll_rec), 0},  {R->overlap, n * 4, 0},
+           {R->filter, n * sizeof(sdf_filter_rec), 0},      {R->hits, n * sizeof(sdf_search_hit), 0},
+           {R->hit_filter, n * sizeof(sdf_filter_rec), 0}};
+  size_t total = 0;
+  for (Piece &p : P) p.at = total, total += (p.bytes + 255) / 256 * 256;
+  SDF_HIP(ctx->ac_in.reserve(total + 256));
+  SDF_HIP(ctx->ac_found.reserve((found_cap + 1) * sizeof(sdf_search_found)));
+  SDF_HIP(ctx->ac_out.reserve((out_cap + 1) * sizeof(sdf_search_pair_hit)));
+  SDF_HIP(ctx->ac_status.reserve(sizeof(sdf_search_accept_status)));
+  uint8_t *base = (uint8_t *)ctx->ac_in.p;
+  for (const Piece &p : P)
+    if (p.bytes) SDF_HIP(hipMemcpyAsync(base + p.at, p.src, p.bytes, hipMemcpyHostToDevice, st));
+  if (nf) SDF_HIP(hipMemcpyAsync(ctx->ac_found.p, found, nf * sizeof(sdf_search_found), hipMemcpyHostToDevice, st));
+  sdf_search_accept_round D = *R;
+  D.q = (const sdf_minimizer *)(base + P[0].at), D.act = (const uint32_t *)(base + P[1].at);
+  D.windows = (const sdf_search_window *)(base + P[2].at), D.first = (const uint64_t *)(base + P[3].at);
+  D.rolls = (const sdf_search_roll_rec *)(base + P[4].at), D.overlap = (const uint32_t *)(base + P[5].at);
+  D.filter = (const sdf_filter_rec *)(base + P[6].at), D.hits = (const sdf_search_hit *)(base + P[7].at);
+  D.hit_filter = (const sdf_filter_rec *)(base + P[8].at);
+  D.n_max = n;  // (a window whose records lie beyond R->n_max has them beyond n too)
+  sdf_search_found *d_found = (sdf_search_found *)ctx->ac_found.p;
+  sdf_search_pair_hit *d_out = (sdf_search_pair_hit *)ctx->ac_out.p;
+  if (int rc = accept_launch(ctx, &D, d_found, nf, found_cap, d_out, n_out, out_cap, (sdf_search_accept_status *)ctx->ac_status.p, st)) return rc;
+  SDF_HIP(hipMemcpyAsync(status, ctx->ac_status.p, sizeof *status, hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  if (status->nf > nf)
+    SDF_HIP(hipMemcpyAsync(found + nf, d_found + nf, (size_t)(status->nf - nf) * sizeof(sdf_search_found), hipMemcpyDeviceToHost, st));
+  if (status->n_out > n_out)
+    SDF_HIP(hipMemcpyAsync(out + n_out, d_out + n_out, (size_t)(status->n_out - n_out) * sizeof(sdf_search_pair_hit), hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));
+  return SDF_OK;
+}
+
+// ---- sdf_search_pair_host ----
+
+namespace {
+inline char host_rev_dna(const char c) {
+  switch (c) {
+    case 'A': return 'T';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'T': return 'A';
+    case 'a': return 't';
+    case 'c': return 'g';
+    case 'g': return 'c';
+    case 't': return 'a';
+    default: return 'N';
+  }
+}
+// the sequence of a range: its characters & 127, reverse-complemented by rev_dna under SDF_MINIM_RC
+std::string host_sequence(const char *pool, const sdf_minim_range &r) {
+  std::string s((size_t)r.len, 'N');
+  for (int32_t x = 0; x < r.len; x++) {
+    const char c = (char)(pool[r.off + x] & 127);
+    if (r.flags & SDF_MINIM_RC) s[(size_t)(r.len - 1 - x)] = host_rev_dna(c);
+    else s[(size_t)x] = c;
+  }
+  return s;
+}
+// get_minimizers (src/hash.cc:53-100) as tests/minim_model.py holds it, the deque loop as written
+std::vector<sdf_minimizer> host_minimizers(const std::string &s, int k, int w, bool separate_lowercase) {
+  std::vector<sdf_minimizer> out;
+  struct Item {
+    uint64_t key;
+    int64_t loc;
+  };
+  std::deque<Item> window;
+  const uint32_t mask = (uint32_t)((1ull << (2 * k)) - 1);
+  uint32_t h = 0;
+  int64_t last_n = -(int64_t)k - w, last_u = last_n;
+  for (int64_t i = 0; i < (int64_t)s.size(); i++) {
+    const char c = s[(size_t)i];
+    if (c == 'N' || c == 'n') last_n = i;
+    else if (c >= 'A' && c <= 'Z') last_u = i;
+    const uint32_t code = c == 'C' || c == 'c' ? 1u : c == 'G' || c == 'g' ? 2u : c == 'T' || c == 't' ? 3u : 0u;
+    h = ((h << 2) | code) & mask;
+    if (i < k - 1) continue;
+    const int64_t at = i - k + 1;
+    uint32_t status = last_n >= at ? 2u : last_u >= at ? 0u : 1u;
+    if (!separate_lowercase && status == 1u) status = 0u;
+    const uint64_t key = (uint64_t)status << 32 | h;
+    while (!window.empty() && !(window.back().key < key)) window.pop_back();
+    while (!window.empty() && window.back().loc < at - w) window.pop_front();
+    window.push_back(Item{key, at});
+    if (at < w) continue;
+    const Item &f = window.front();
+    if (out.empty() || !((int64_t)out.back().loc == f.loc && ((uint64_t)(uint32_t)out.back().status << 32 | out.back().hash) == f.key))
+      out.push_back(sdf_minimizer{(uint32_t)f.key, (int32_t)f.loc, (int32_t)(f.key >> 32), 0});
+  }
+  return out;
+}
+// Index::Index (src/hash.cc:113-141): the records in ascending (status, hash, loc), and the threshold
+uint32_t host_index(const std::vector<sdf_minimizer> &m, std::vector<sdf_minimizer> &sorted) {
+  const auto key = [](const sdf_minimizer &x) { return (uint64_t)(uint32_t)x.status << 32 | x.hash; };
+  sorted = m;
+  std::stable_sort(sorted.begin(), sorted.end(), [&](const sdf_minimizer &a, const sdf_minimizer &b) { return key(a) < key(b); });
+  std::map<uint64_t, uint64_t> hist;  // group size -> groups
+  for (size_t a = 0; a < sorted.size();) {
+    size_t b = a;
+    while (b < sorted.size() && key(sorted[b]) == key(sorted[a])) ++b;
+    hist[b - a] += 1;
+    a = b;
+  }
+  const int ignore = (int)(((double)m.size() * 0.001) / 100.0);
+  uint64_t total = 0;
+  uint32_t threshold = 0x80000000u;
+  for (auto it = hist.rbegin(); it != hist.rend(); ++it) {
+    total += it->second;
+    if (total > (uint64_t)ignore) break;
+    threshold = (uint32_t)it->first;
+  }
+  return threshold;
+}
+
+int pair_checks(size_t pool_bytes, const sdf_minim_range *Q, const sdf_minim_range *R, const sdf_search_pair_params *P) {
+  if (!Q || !R || !P || (P->n_limit && !P->limit)) return SDF_ERR_INVALID;
+  for (const sdf_minim_range *r : {Q, R})
+    if (!in_range(r->off, (int64_t)r->len, pool_bytes)) return SDF_ERR_INVALID;
+  if (P->min_read_size < 1) return SDF_ERR_INVALID;
+  if (P->same_genome && (Q->off != R->off || Q->len != R->len || Q->flags || R->flags)) return SDF_ERR_INVALID;
+  const sdf_filter_params &F = P->filter;
+  const sdf_extend_params &E = P->extend;
+  if (!std::isfinite(F.max_error) || !std::isfinite(F.max_edit_error) || !std::isfinite(F.gap_frequency) || !std::isfinite(E.max_error) ||
+      !std::isfinite(E.max_edit_error) || !(E.max_error - E.max_edit_error > 0))
+    return SDF_ERR_INVALID;
+  if (P->k < 1 || P->k > 15 || P->w < 1 || P->w > SDF_MINIM_MAX_W) return SDF_ERR_UNSUPPORTED;
+  if ((Q->flags | R->flags) & ~SDF_MINIM_RC) return SDF_ERR_UNSUPPORTED;
+  if (P->n_limit > 0x7fffffffu || P->min_read_size > (1 << 30)) return SDF_ERR_UNSUPPORTED;
+  for (size_t s = 1; s < P->n_limit; s++)
+    if (P->limit[s] < 1) return SDF_ERR_UNSUPPORTED;
+  if (F.reserved || E.reserved[0] || E.reserved[1]) return SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+}  // namespace
+
+extern "C" int sdf_search_pair_host(const char *pool, size_t pool_bytes, const sdf_minim_range *q_range, const sdf_minim_range *r_range,
+                                    const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
+                                    sdf_search_pair_stats *stats) {
+  if (!used || !stats || (cap && !out) || (pool_bytes && !pool)) return SDF_ERR_INVALID;
+  if (int rc = pair_checks(pool_bytes, q_range, r_range, params)) return rc;
+  const sdf_search_pair_params &P = *params;
+  const std::string qs = host_sequence(pool, *q_range);
+  const std::vector<sdf_minimizer> q = host_minimizers(qs, P.k, P.w, P.separate_lowercase != 0);
+  std::vector<sdf_minimizer> r_own, r_sorted;
+  if (!P.same_genome) r_own = host_minimizers(host_sequence(pool, *r_range), P.k, P.w, P.separate_lowercase != 0);
+  const std::vector<sdf_minimizer> &r = P.same_genome ? q : r_own;
+  const uint32_t threshold = host_index(r, r_sorted);
+  sdf_extend_params E = P.extend;
+  E.same_genome = P.same_genome != 0;
+  const PairHostArgs A{pool,          pool_bytes,    q.data(),           q.size(),        r.data(),
+                       r_sorted.data(), r.size(),      threshold,          q_range->len,    r_range->len,
+                       q_range->off,  r_range->off,  (int)(q_range->flags & SDF_MINIM_RC), (int)(r_range->flags & SDF_MINIM_RC),
+                       P.min_read_size, P.same_genome != 0, P.uppercase_seeds != 0, P.limit, P.n_limit, P.filter, E};
+  std::vector<sdf_search_found> found;
+  std::vector<sdf_search_pair_hit> all;
+  PairHostWindow W;
+  sdf_search_pair_stats S{0, 0, 0, 0, 0, 0, 0};
+  int64_t next = 0;
+  for (size_t i = 0; i < q.size(); i++) {
+    if ((int64_t)q[i].loc < next) continue;
+    if (P.uppercase_seeds && q[i].status != 0) continue;
+    if (int rc = pair_host_window(A, i, found, W)) return rc;
+    S.attempted += W.attempted, S.jaccard_failed += W.jaccard_failed, S.interval_failed += W.interval_failed;
+    S.windows_run += 1, S.windows_scheduled += 1, S.windows_host += 1;
+    int64_t min_len = q_range->len;
+    for (const sdf_search_pair_hit &h : W.reported) min_len = std::min<int64_t>(min_len, (int64_t)h.query_end - h.query_start);
+    all.insert(all.end(), W.reported.begin(), W.reported.end());
+    next = min_len >= P.min_read_size ? (int64_t)(int)((double)q[i].loc + ((double)P.min_read_size * P.filter.max_error) / 2) : (int64_t)q[i].loc;
+  }
+  *stats = S;
+  *used = all.size();
+  if (all.size() > cap) return SDF_ERR_CIGAR_OVERFLOW;
+  if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(sdf_search_pair_hit));
+  return SDF_OK;
+}
+
+// ---- sdf_search_pair: the stages and the acceptance step in rounds, on the resident pool ----
+
+namespace {
+constexpr size_t kPairRoundWindows = 64;  // round_windows == 0; not measured (profiles/search_driver.py has the sweep)
+constexpr size_t kPairLongMax = 16, kPairLongBatch = 8;  // long growths a round finishes on the device; the host takes the rest
+
+struct PairDriver {
+  sdf_ctx *ctx;
+  hipStream_t st;
+  const sdf_search_pair_params &P;
+  sdf_minim_range Q, R;
+  std::vector<sdf_minimizer> q, r_own, r_sorted;
+  uint32_t threshold = 0x80000000u;
+  std::vector<sdf_search_found> found;  // the host's mirror of the device list
+  std::vector<sdf_search_pair_hit> out;
+  std::string chars;  // both ranges as they lie in the pool, fetched when the host first completes a window
+  PairHostWindow W;
+  sdf_search_pair_stats S{0, 0, 0, 0, 0, 0, 0};
+  size_t cap_iv = 4096, ent_cap = 4096, found_cap = 0;
+  const std::vector<sdf_minimizer> &r() const { return P.same_genome ? q : r_own; }
+};
+
+int pair_minimizers(sdf_ctx *ctx, const sdf_minim_range &range, const sdf_search_pair_params &P, bool index, std::vector<sdf_minimizer> &out,
+                    uint32_t *threshold) {
+  uint64_t first[2] = {0, 0};
+  uint32_t groups = 0, thr = 0;
+  size_t used = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    const int rc = index ? sdf_pool_minimizer_index(ctx, &range, 1, P.k, P.w, P.separate_lowercase, first, out.data(), out.size(), &used, &groups, &thr)
+                         : sdf_pool_minimizers(ctx, &range, 1, P.k, P.w, P.separate_lowercase, first, out.data(), out.size(), &used);
+    if (rc == SDF_OK) break;
+    if (rc != SDF_ERR_CIGAR_OVERFLOW || pass) return rc;
+    out.resize(used);
+  }
+  out.resize(used);
+  if (threshold) *threshold = thr;
+  return SDF_OK;
+}
+
+int pair_upload(sdf_ctx *ctx, DevBuf &buf, const void *src, size_t bytes, hipStream_t st) {
+  SDF_HIP(buf.reserve(bytes + 256));
+  if (bytes) SDF_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
+  return SDF_OK;
+}
+
+// the device list behind the host's mirror: room for `want` records, records [from, found.size()) uploaded
+int pair_sync_found(PairDriver &D, size_t want, size_t from) {
+  sdf_ctx *ctx = D.ctx;
+  if (want > D.found_cap) {
+    D.found_cap = 2 * want + 1024;
+    SDF_HIP(ctx->dr_found.reserve(D.found_cap * sizeof(sdf_search_found)));
+    from = 0;  // (a buffer that grew is a new one)
+  }
+  if (D.found.size() > from)
+    SDF_HIP(hipMemcpyAsync((sdf_search_found *)ctx->dr_found.p + from, D.found.data() + from, (D.found.size() - from) * sizeof(sdf_search_found),
+                           hipMemcpyHostToDevice, D.st));
+  return SDF_OK;
+}
+
+// window i by the per-window step of sdf_search_pair_host, its records to both lists
+int pair_host_one(PairDriver &D, size_t i) {
+  sdf_ctx *ctx = D.ctx;
+  if (D.chars.empty()) {
+    D.chars.resize((size_t)D.Q.len + (D.P.same_genome ? 0 : (size_t)D.R.len));
+    const sdf_pool_fetch F[2] = {{D.Q.off, D.Q.len, 0, 0}, {D.R.off, D.R.len, 0, D.Q.len}};
+    if (int rc = sdf_pool_fetch_ranges(ctx, F, D.P.same_genome ? 1 : 2, &D.chars[0], D.chars.size())) return rc;
+  }
+  sdf_extend_params E = D.P.extend;
+  E.same_genome = D.P.same_genome != 0;
+  const std::vector<sdf_minimizer> &r = D.r();
+  const PairHostArgs A{D.chars.data(), D.chars.size(), D.q.data(), D.q.size(), r.data(), D.r_sorted.data(), r.size(), D.threshold,
+                       D.Q.len, D.R.len, 0, D.P.same_genome ? 0 : (int64_t)D.Q.len, (int)(D.Q.flags & SDF_MINIM_RC), (int)(D.R.flags & SDF_MINIM_RC),
+                       D.P.min_read_size, D.P.same_genome != 0, D.P.uppercase_seeds != 0, D.P.limit, D.P.n_limit, D.P.filter, E};
+  const size_t nf0 = D.found.size();
+  if (int rc = pair_host_window(A, i, D.found, D.W)) return refuse(ctx, rc, "sdf_search_pair: the host step of a window failed");
+  D.out.insert(D.out.end(), D.W.reported.begin(), D.W.reported.end());
+  D.S.attempted += D.W.attempted, D.S.jaccard_failed += D.W.jaccard_failed, D.S.interval_failed += D.W.interval_failed;
+  D.S.windows_host += 1, D.S.windows_run += 1;
+  return pair_sync_found(D, D.found.size(), nf0);
+}
+
+// One round over the scheduled windows act[0, na) (ascending indices into q): the chain on the context's stream, one wait.
+// *status: the acceptance step's; *grew: a capacity was short and has been raised -- the status is then not to be used.
+int pair_round(PairDriver &D, const uint32_t *act, size_t na, sdf_search_accept_status *status, bool *grew) {
+  sdf_ctx *ctx = D.ctx;
+  hipStream_t st = D.st;
+  const sdf_search_pair_params &P = D.P;
+  const size_t nq = D.q.size(), nr = D.r().size(), nf = D.found.size(), n = D.cap_iv;
+  const int32_t init_len = P.min_read_size;
+  const int64_t len_q = D.Q.len, len_r = D.R.len;
+  const int q_rc = (int)(D.Q.flags & SDF_MINIM_RC), r_rc = (int)(D.R.flags & SDF_MINIM_RC);
+  // the slice of q the round's windows and their members lie in
+  const size_t i0 = act[0];
+  size_t e = act[na - 1];
+  while (e < nq && (int64_t)D.q[e].loc - D.q[act[na - 1]].loc <= init_len) ++e;
+  const size_t ns = e - i0;
+  if (int rc = pair_sync_found(D, nf + n, nf)) return rc;
+  SDF_HIP(ctx->dr_vis.reserve((std::max(nq, n) + 1) * 4));
+  SDF_HIP(ctx->dr_iv.reserve((n + 1) * sizeof(sdf_search_interval)));
+  SDF_HIP(ctx->dr_rolls.reserve((n + 1) * sizeof(sdf_search_roll_rec)));
+  SDF_HIP(ctx->dr_tasks.reserve((n + 1) * sizeof(sdf_filter_task)));
+  SDF_HIP(ctx->dr_verd.reserve((n + 1) * 4));
+  SDF_HIP(ctx->dr_frec.reserve((n + 1) * sizeof(sdf_filter_rec)));
+  SDF_HIP(ctx->dr_hits.reserve((n + 1) * sizeof(sdf_search_hit)));
+  SDF_HIP(ctx->dr_htasks.reserve((n + 1) * sizeof(sdf_filter_task)));
+  SDF_HIP(ctx->dr_hrec.reserve((n + 1) * sizeof(sdf_filter_rec)));
+  SDF_HIP(ctx->dr_out.reserve((n + 1) * sizeof(sdf_search_pair_hit)));
+  SDF_HIP(ctx->dr_status.reserve(sizeof(sdf_search_accept_status) + 16));
+  if (int rc = pair_upload(ctx, ctx->dr_act, act, na * 4, st)) return rc;
+  const sdf_minimizer *d_q = (const sdf_minimizer *)ctx->dr_q.p, *d_r = P.same_genome ? d_q : (const sdf_minimizer *)ctx->dr_r.p;
+  const sdf_minimizer *d_rs = (const sdf_minimizer *)ctx->dr_rs.p;
+  const int32_t *d_limit = (const int32_t *)ctx->dr_limit.p;
+  uint64_t *d_first = (uint64_t *)ctx->dr_first.p;
+  sdf_search_window *d_win = (sdf_search_window *)ctx->dr_win.p;
+  uint32_t *d_vis = (uint32_t *)ctx->dr_vis.p, *d_verd = (uint32_t *)ctx->dr_verd.p;
+  sdf_search_interval *d_iv = (sdf_search_interval *)ctx->dr_iv.p;
+  sdf_search_roll_rec *d_rolls = (sdf_search_roll_rec *)ctx->dr_rolls.p;
+  sdf_filter_task *d_tasks = (sdf_filter_task *)ctx->dr_tasks.p, *d_htasks = (sdf_filter_task *)ctx->dr_htasks.p;
+  sdf_filter_rec *d_frec = (sdf_filter_rec *)ctx->dr_frec.p, *d_hrec = (sdf_filter_rec *)ctx->dr_hrec.p;
+  sdf_search_hit *d_hits = (sdf_search_hit *)ctx->dr_hits.p;
+  sdf_search_found *d_found = (sdf_search_found *)ctx->dr_found.p;
+  sdf_search_accept_status *d_status = (sdf_search_accept_status *)ctx->dr_status.p;
+  uint64_t *d_need = (uint64_t *)(d_status + 1);
+  sdf_extend_params E = P.extend;
+  E.same_genome = P.same_genome != 0;
+  void *s = (void *)st;
+  // every window and interval of the round sees the whole list as it stands
+  SDF_HIP(hipMemsetD32Async((hipDeviceptr_t)d_vis, (int)nf, std::max(nq, n), st));
+  if (i0) SDF_HIP(hipMemsetAsync(d_first, 0, i0 * 8, st));
+  if (int rc = sdf_search_windows_found_device(ctx, d_q + i0, ns, len_q, d_rs, nr, D.threshold, init_len, P.same_genome, P.uppercase_seeds, d_limit,
+                                               P.n_limit, d_found, nf, D.ent_cap, d_need, d_vis, d_first + i0, d_win + i0, d_iv, n, nullptr, s))
+    return rc;
+  if (e < nq) {
+    hipLaunchKernelGGL(search_accept_tail_kernel, dim3((unsigned)((nq - e + 255) / 256)), dim3(256), 0, st, d_first, (int)e, (int)nq);
+    SDF_HIP(hipGetLastError());
+    ctx->launches += 1;
+  }
+  if (int rc = sdf_search_roll_device(ctx, d_q, nq, d_win, d_first, d_iv, n, d_r, nr, len_r, init_len, d_limit, P.n_limit, d_rolls, s)) return rc;
+  if (int rc = sdf_search_filter_tasks_device(ctx, d_q, nq, d_win, d_first, d_iv, d_rolls, n, len_q, len_r, init_len, D.Q.off, q_rc, D.R.off, r_rc, 1,
+                                              d_tasks, s))
+    return rc;
+  if (int rc = sdf_search_overlap_device(ctx, d_q, nq, d_first, d_rolls, n, d_found, nf, D.ent_cap, nullptr, d_vis, init_len, P.min_read_size, d_verd,
+                                         d_tasks, s))
+    return rc;
+  if (int rc = sdf_search_filter_device(ctx, &P.filter, d_tasks, n, q_rc | r_rc, d_frec, s)) return rc;
+  if (int rc = sdf_search_extend_device(ctx, d_q, nq, d_win, d_first, d_iv, d_rolls, d_frec, n, d_r, nr, len_q, len_r, init_len, d_limit, P.n_limit, &E,
+                                        d_hits, s))
+    return rc;
+  {  // long growths; without room for its workspace the host completes them
+    const int rc = sdf_search_extend_long_device(ctx, d_q, nq, d_win, d_first, d_iv, d_rolls, d_frec, n, d_r, nr, len_q, len_r, init_len, d_limit,
+                                                 P.n_limit, &E, SDF_EXTEND_LONG_MAX_GROW, kPairLongMax, kPairLongBatch, d_hits, nullptr, s);
+    if (rc != SDF_OK && rc != SDF_ERR_NOMEM) return rc;
+  }
+  if (int rc = sdf_search_hit_tasks_device(ctx, d_hits, n, d_first + nq, len_q, len_r, D.Q.off, q_rc, D.R.off, r_rc, d_htasks, s)) return rc;
+  if (int rc = sdf_search_filter_device(ctx, &P.filter, d_htasks, n, q_rc | r_rc, d_hrec, s)) return rc;
+  const sdf_search_accept_round A{d_q,   nq,     (const uint32_t *)ctx->dr_act.p, na,     d_win,  d_first,          n,          d_rolls,
+                                  d_verd, d_frec, d_hits,                          d_hrec, init_len, P.min_read_size, 0, 0};
+  if (int rc = sdf_search_accept_device(ctx, &A, d_found, nf, D.found_cap, (sdf_search_pair_hit *)ctx->dr_out.p, 0, n, d_status, s)) return rc;
+  SDF_HIP(hipMemcpyAsync(d_need + 1, d_first + nq, 8, hipMemcpyDeviceToDevice, st));
+  struct {
+    sdf_search_accept_status status;
+    uint64_t entries, intervals;
+  } back;
+  SDF_HIP(hipMemcpyAsync(&back, d_status, sizeof back, hipMemcpyDeviceToHost, st));
+  SDF_HIP(hipStreamSynchronize(st));  // the round's one wait
+  D.S.rounds += 1, D.S.windows_run += (int64_t)na;
+  *grew = false;
+  if (back.entries > D.ent_cap) D.ent_cap = 2 * (size_t)back.entries, *grew = true;  // the index was incomplete: nothing of the round holds
+  if (back.intervals > n && (*grew || back.status.frontier == 0)) D.cap_iv = 2 * (size_t)back.intervals, *grew = true;
+  else if (back.intervals > n) D.cap_iv = 2 * (size_t)back.intervals;  // (the windows whose records were there are taken; the next round has room)
+  if (back.status.flags & SDF_ACCEPT_OVERFLOW) return refuse(ctx, SDF_ERR_HIP, "sdf_search_pair: internal error, a round overflowed lists sized for it");
+  if (back.intervals > n) back.status.flags &= ~(uint32_t)SDF_ACCEPT_INCOMPLETE;  // (incomplete for want of room, not for the host)
+  *status = back.status;
+  if (*grew) return SDF_OK;
+  // the round's new records, to the host's mirrors
+  const size_t add_f = (size_t)(back.status.nf - nf), add_o = (size_t)back.status.n_out;
+  D.found.resize(nf + add_f);
+  const size_t o0 = D.out.size();
+  D.out.resize(o0 + add_o);
+  if (add_f) SDF_HIP(hipMemcpyAsync(D.found.data() + nf, d_found + nf, add_f * sizeof(sdf_search_found), hipMemcpyDeviceToHost, st));
+  if (add_o) SDF_HIP(hipMemcpyAsync(D.out.data() + o0, ctx->dr_out.p, add_o * sizeof(sdf_search_pair_hit), hipMemcpyDeviceToHost, st));
+  if (add_f || add_o) SDF_HIP(hipStreamSynchronize(st));
+  D.S.attempted += back.status.attempted, D.S.jaccard_failed += back.status.jaccard_failed, D.S.interval_failed += back.status.interval_failed;
+  return SDF_OK;
+}
+}  // namespace
+
+extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
+                               sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (!used || !stats || (cap && !out)) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair: invalid arguments");
+  if (int rc = pair_checks(sdf_pool_bytes(ctx), q_range, r_range, params)) return refuse(ctx, rc, "sdf_search_pair: a range or a parameter is refused");
+  SDF_HIP(hipSetDevice(ctx->device));
+  PairDriver D{ctx, ctx->stream, *params, *q_range, *r_range};
+  const sdf_search_pair_params &P = *params;
+  // set-up: minimizers of both ranges, the reference's index; they stay in HBM for every round
+  if (int rc = pair_minimizers(ctx, D.Q, P, false, D.q, nullptr)) return rc;
+  if (!P.same_genome)
+    if (int rc = pair_minimizers(ctx, D.R, P, false, D.r_own, nullptr)) return rc;
+  if (int rc = pair_minimizers(ctx, D.R, P, true, D.r_sorted, &D.threshold)) return rc;
+  const size_t nq = D.q.size();
+  std::vector<uint32_t> sched;  // fact 1: the windows that run, from loc and status alone
+  {
+    int64_t next = 0;
+    for (size_t i = 0; i < nq; i++) {
+      if ((int64_t)D.q[i].loc < next || (P.uppercase_seeds && D.q[i].status != 0)) continue;
+      sched.push_back((uint32_t)i);
+      next = (int64_t)(int)((double)D.q[i].loc + ((double)P.min_read_size * P.filter.max_error) / 2);
+    }
+  }
+  D.S.windows_scheduled = (int64_t)sched.size();
+  if (!sched.empty()) {
+    hipStream_t st = D.st;
+    if (int rc = pair_upload(ctx, ctx->dr_q, D.q.data(), nq * sizeof(sdf_minimizer), st)) return rc;
+    if (!P.same_genome)
+      if (int rc = pair_upload(ctx, ctx->dr_r, D.r_own.data(), D.r_own.size() * sizeof(sdf_minimizer), st)) return rc;
+    if (int rc = pair_upload(ctx, ctx->dr_rs, D.r_sorted.data(), D.r_sorted.size() * sizeof(sdf_minimizer), st)) return rc;
+    if (int rc = pair_upload(ctx, ctx->dr_limit, P.limit, P.n_limit * 4, st)) return rc;
+    SDF_HIP(ctx->dr_first.reserve((nq + 1) * 8));
+    SDF_HIP(ctx->dr_win.reserve((nq + 1) * sizeof(sdf_search_window)));
+    SDF_HIP(hipMemsetAsync(ctx->dr_win.p, 0, nq * sizeof(sdf_search_window), st));
+    const size_t round = P.round_windows ? P.round_windows : kPairRoundWindows, every = P.debug_host_every;
+    size_t s0 = 0;
+    while (s0 < sched.size()) {
+      if (every && s0 % every == every - 1) {  // debug: this window on the host
+        if (int rc = pair_host_one(D, sched[s0])) return rc;
+        ++s0;
+        continue;
+      }
+      size_t na = std::min(round, sched.size() - s0);
+      if (every) na = std::min(na, every - 1 - s0 % every);  // (the round ends in front of the next one the host takes)
+      sdf_search_accept_status status;
+      bool grew = false;
+      if (int rc = pair_round(D, sched.data() + s0, na, &status, &grew)) return rc;
+      if (grew) continue;  // the same round again, with room
+      s0 += status.frontier;
+      if (status.flags & SDF_ACCEPT_INCOMPLETE) {
+        if (int rc = pair_host_one(D, sched[s0])) return rc;
+        ++s0;
+      } else if (status.frontier == 0) {
+        return refuse(ctx, SDF_ERR_HIP, "sdf_search_pair: internal error, a round accepted nothing and handed nothing to the host");
+      }
+    }
+  }
+  *stats = D.S;
+  *used = D.out.size();
+  if (D.out.size() > cap) return refuse(ctx, SDF_ERR_CIGAR_OVERFLOW, "the pair has " + std::to_string(D.out.size()) + " hits, more than cap");
+  if (!D.out.empty()) memcpy(out, D.out.data(), D.out.size() * sizeof(sdf_search_pair_hit));
+  return SDF_OK;
+}

@@ -64,4 +64,32 @@ int found_scalars(size_t nf, size_t cap, const char **why);
 int found_index(sdf_ctx *ctx, const sdf_search_found *d_found, size_t nf, size_t cap, uint64_t *d_need, const uint32_t *d_visible,
                 hipStream_t st, FoundIndex *F);
 int found_index_need(sdf_ctx *ctx, size_t cap);
+
+// One window of initial_search on the host (sdf_search_api.hip, where the per-window forms of the stages live), for
+// sdf_search_pair_host (sdf_driver_api.hip): include/sedef_hip.h states the steps.  pair_host_window runs window i against the
+// whole of `found`, appends the records it keeps to it as it goes, and leaves the parse_hits survivors and the counters in W.
+struct PairHostArgs {
+  const char *pool;
+  size_t pool_bytes;
+  const sdf_minimizer *q;
+  size_t nq;
+  const sdf_minimizer *r, *r_sorted;  // ascending loc; ascending (status, hash, loc)
+  size_t nr;
+  uint32_t r_threshold;
+  int64_t len_q, len_r, q_off, r_off;
+  int q_rc, r_rc;
+  int32_t min_read_size;
+  bool same_genome, uppercase_seeds;
+  const int32_t *limit;
+  size_t n_limit;
+  sdf_filter_params filter;
+  sdf_extend_params extend;
+};
+struct PairHostWindow {
+  std::vector<sdf_search_pair_hit> reported;
+  int64_t attempted = 0, jaccard_failed = 0, interval_failed = 0;
+  std::vector<sdf_search_window> windows;  // scratch: nq records, of which the call fills its own
+  std::vector<sdf_search_pair_hit> hits;
+};
+int pair_host_window(const PairHostArgs &A, size_t i, std::vector<sdf_search_found> &found, PairHostWindow &W);
 }  // namespace sdf

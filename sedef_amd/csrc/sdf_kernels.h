@@ -380,5 +380,57 @@ __global__ void search_extend_long_heads_kernel(const unsigned long long *, int,
 __global__ void search_extend_long_slots_kernel(const unsigned long long *, const uint32_t *, const uint32_t *, int, int, uint32_t *, uint32_t *);
 __global__ void search_extend_long_kernel(ExtLongArgs, const ExtLongCand *, const uint32_t *, uint32_t, const uint32_t *, const uint32_t *,
                                           long long, long long, int, const int32_t *, sdf_extend_params, sdf_search_hit *, unsigned long long *);
+// search_accept.hip
+// a wavefront's LDS: the kept records of its window, their intervals' indices and a byte each
+constexpr int ACCEPT_MAX_KEPT = SDF_ACCEPT_MAX_KEPT;
+constexpr int ACCEPT_KEPT_BYTES = (int)(sizeof(sdf_search_found) + sizeof(uint32_t) + sizeof(uint8_t));  // record, interval index, dropped
+static_assert(ACCEPT_MAX_KEPT >= 64 && ACCEPT_MAX_KEPT % 64 == 0 && ACCEPT_MAX_KEPT * ACCEPT_KEPT_BYTES <= 160 * 1024 / 15,
+              "search_accept.hip: fifteen wavefronts share a CU's 160 KB (include/sedef_hip.h)");
+static_assert(sizeof(sdf_search_pair_hit) == 24 && sizeof(sdf_search_accept_status) == 64, "include/sedef_hip.h");
+struct AcceptRound {  // sdf_search_accept_round as the kernels take it
+  const sdf_minimizer *q;
+  const uint32_t *act;
+  const sdf_search_window *windows;
+  const uint64_t *first;
+  const sdf_search_roll_rec *rolls;
+  const uint32_t *overlap;
+  const sdf_filter_rec *filter;
+  const sdf_search_hit *hits;
+  const sdf_filter_rec *hit_filter;
+  long long n_max;
+  int nq, na, init_len, min_read_size, window_base;
+};
+struct AcceptWin {  // what the first launch leaves per round window (32 bytes)
+  int32_t n_kept, n_out, reach, incomplete;  // reach: the largest q_end of a kept record, 0: none
+  int32_t attempted, jaccard_failed, interval_failed, qs;
+};
+struct AcceptOff {  // where an accepted window's records go, counted from nf and n_out
+  uint32_t found, out;
+};
+constexpr uint32_t kAcceptDropped = 0x80000000u;  // in a kept entry: parse_hits dropped the hit
+// An interval's class in the acceptance step (include/sedef_hip.h): 0 jaccard failed, 1 overlapped by the found list as it stood,
+// 2 goes on to the replay of is_overlap but cannot be kept, 3 a candidate; and whether the device left its record for the host.
+// The one form the kernel and the host form share.
+__host__ __device__ inline int accept_class(const sdf_search_roll_rec &R, const uint32_t verdict, const sdf_filter_rec &F,
+                                            const sdf_search_hit &H, const sdf_filter_rec &HF) {
+  constexpr uint32_t fail = SDF_FILTER_UPPER_FAIL | SDF_FILTER_QGRAM_FAIL | SDF_FILTER_SKIPPED;
+  if (R.jaccard < 0) return 0;
+  if (verdict) return 1;
+  return (F.flags & fail) || (H.flags & (SDF_EXTEND_SKIPPED | SDF_EXTEND_NOLIMIT)) || (HF.flags & fail) ? 2 : 3;
+}
+__host__ __device__ inline bool accept_unfinished(const sdf_search_roll_rec &R, const sdf_search_hit &H) {
+  return ((R.flags & SDF_ROLL_WIDE) && R.ref_end == 0) || (R.flags & SDF_ROLL_BADWINDOW) || ((H.flags & SDF_EXTEND_WIDE) && H.query_end == 0);
+}
+// parse_hits: p makes h drop
+__host__ __device__ inline bool accept_contains(const sdf_search_found &p, const sdf_search_found &h) {
+  return h.r_start >= p.r_start && h.r_end <= p.r_end && h.q_start >= p.q_start && h.q_end <= p.q_end;
+}
+__global__ void search_accept_window_kernel(AcceptRound, AcceptWin *, uint32_t *);
+__global__ void search_accept_frontier_kernel(const AcceptWin *, int, unsigned long long, unsigned long long, unsigned long long,
+                                              unsigned long long, AcceptOff *, sdf_search_accept_status *, uint32_t *);
+__global__ void search_accept_tail_kernel(uint64_t *, int, int);
+__global__ void search_accept_append_kernel(AcceptRound, const AcceptWin *, const uint32_t *, const AcceptOff *, const uint32_t *,
+                                            sdf_search_found *, unsigned long long, unsigned long long, sdf_search_pair_hit *,
+                                            unsigned long long, unsigned long long);
 
 }  // namespace sdf

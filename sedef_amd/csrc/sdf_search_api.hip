@@ -482,6 +482,8 @@ void roll_walk(const RollArgs &A, const sdf_search_interval &T, size_t span0, Ad
 }
 
 // Interval T of window i as include/sedef_hip.h states it: a map in place of the reference's, the walk from event to event.
+// (Of A it reads windows[i] alone and never first[]: sdf::pair_host_window passes one window's intervals with first == nullptr;
+// extend_one likewise, with intervals[] and rolls[] indexed from the window's first interval.)
 void roll_one(const RollArgs &A, size_t i, const sdf_search_interval &T, sdf_search_roll_rec &R, std::map<uint64_t, uint8_t> &M) {
   const sdf_search_window &W = A.windows[i];
   const auto loc_less = [](const sdf_minimizer &m, int64_t loc) { return (int64_t)m.loc < loc; };
@@ -1034,5 +1036,64 @@ extern "C" int sdf_search_extend(sdf_ctx *ctx, const sdf_minimizer *q, size_t nq
   for (size_t i = 0; i < nq; i++)
     for (uint64_t t = first[i]; t < first[i + 1]; t++)
       if (out[t].flags == SDF_EXTEND_WIDE && out[t].query_end == 0) extend_one(A, i, t, out[t], S);
+  return SDF_OK;
+}
+
+// ---- one window of initial_search, for sdf_search_pair_host (sdf_entry.h) ----
+
+int sdf::pair_host_window(const PairHostArgs &A, size_t i, std::vector<sdf_search_found> &found, PairHostWindow &W) {
+  constexpr uint32_t fail = SDF_FILTER_UPPER_FAIL | SDF_FILTER_QGRAM_FAIL | SDF_FILTER_SKIPPED;
+  W.reported.clear(), W.hits.clear();
+  W.attempted = W.jaccard_failed = W.interval_failed = 0;
+  if (W.windows.size() < A.nq) W.windows.resize(A.nq);
+  const int32_t init_len = A.min_read_size;
+  const SearchArgs SA{A.q, A.nq, A.len_q, A.r_sorted, A.nr, A.r_threshold, init_len, A.same_genome, A.uppercase_seeds, A.limit, A.n_limit};
+  sdf_search_window &win = W.windows[i];
+  std::vector<sdf_search_interval> T;
+  SearchScratch S;
+  const FoundView V{found.data(), found.size()};
+  search_one_window(SA, i, win, T, S, &V);
+  if (T.empty()) return SDF_OK;
+  const RollArgs RA{A.q, A.nq, W.windows.data(), nullptr, T.data(), A.r, A.nr, A.len_r, init_len, A.limit, A.n_limit};
+  std::vector<sdf_search_roll_rec> rolls(T.size(), sdf_search_roll_rec{0, 0, 0, 0, 0, 0});
+  const ExtendArgs EA{RA, rolls.data(), nullptr, A.len_q, A.extend};
+  const FilterTaskArgs FA{A.len_q, A.len_r, A.q_off, A.r_off, init_len, A.q_rc, A.r_rc, 1};
+  std::map<uint64_t, uint8_t> M;
+  ExtendMap ES;
+  const long long pf_pos = A.q[i].loc, pf_end = pf_pos + init_len;
+  for (size_t t = 0; t < T.size(); t++) {
+    W.attempted += 1;
+    roll_one(RA, i, T[t], rolls[t], M);
+    if (rolls[t].jaccard < 0) {
+      W.jaccard_failed += 1;
+      continue;
+    }
+    bool overlapped = false;
+    for (size_t f = 0; f < found.size() && !overlapped; f++)
+      overlapped = !found_empty(found[f]) && found_covers(found[f], pf_pos, rolls[t].ref_start) &&
+                   found_overlaps(found[f], pf_pos, pf_end, rolls[t].ref_start, rolls[t].ref_end, A.min_read_size);
+    if (overlapped) {
+      W.interval_failed += 1;
+      continue;
+    }
+    const sdf_filter_task task = filter_task_of(FA, pf_pos, win, T[t], rolls[t]);
+    sdf_filter_rec rec;
+    if (int rc = sdf_search_filter_host(A.pool, A.pool_bytes, &A.filter, &task, 1, &rec)) return rc;
+    if (rec.flags & fail) continue;
+    sdf_search_hit H;
+    extend_one(EA, i, t, H, ES);  // (a WIDE record is completed here, and is a hit)
+    if (H.flags & (SDF_EXTEND_SKIPPED | SDF_EXTEND_NOLIMIT)) continue;
+    const sdf_filter_task htask = hit_task_of(FA, H);
+    if (int rc = sdf_search_filter_host(A.pool, A.pool_bytes, &A.filter, &htask, 1, &rec)) return rc;
+    if (rec.flags & fail) continue;
+    W.hits.push_back(sdf_search_pair_hit{(int32_t)i, H.query_start, H.query_end, H.ref_start, H.ref_end, H.jaccard});
+    found.push_back(sdf_search_found{H.query_start, H.query_end, H.ref_start, H.ref_end});
+  }
+  const auto rec_of = [](const sdf_search_pair_hit &h) { return sdf_search_found{h.query_start, h.query_end, h.ref_start, h.ref_end}; };
+  for (size_t h = 0; h < W.hits.size(); h++) {  // parse_hits
+    bool dropped = false;
+    for (size_t p = 0; p < W.hits.size() && !dropped; p++) dropped = p != h && accept_contains(rec_of(W.hits[p]), rec_of(W.hits[h]));
+    if (!dropped) W.reported.push_back(W.hits[h]);
+  }
   return SDF_OK;
 }

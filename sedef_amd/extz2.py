@@ -81,6 +81,15 @@ SEARCH_HIT_DTYPE = np.dtype([("query_start", "<i4"), ("query_end", "<i4"), ("ref
 EXTEND_SKIPPED, EXTEND_WIDE, EXTEND_NOLIMIT, EXTEND_MAX_GROW = 0x1, 0x2, 0x4, 1792
 EXTEND_LONG_MAX_GROW = 16384  # SDF_EXTEND_LONG_MAX_GROW: the largest long_grow of search_extend_long_device
 assert SEARCH_HIT_DTYPE.itemsize == 40
+# include/sedef_hip.h: sdf_search_pair_hit, sdf_search_accept_status, sdf_search_pair_stats (the search driver's section)
+SEARCH_PAIR_HIT_DTYPE = np.dtype([("window", "<i4"), ("query_start", "<i4"), ("query_end", "<i4"), ("ref_start", "<i4"),
+                                  ("ref_end", "<i4"), ("jaccard", "<i4")])
+ACCEPT_STATUS_DTYPE = np.dtype([("frontier", "<u4"), ("flags", "<u4"), ("nf", "<u8"), ("n_out", "<u8"), ("need_found", "<u8"),
+                                ("need_out", "<u8"), ("attempted", "<i8"), ("jaccard_failed", "<i8"), ("interval_failed", "<i8")])
+PAIR_STATS_DTYPE = np.dtype([(f, "<i8") for f in ("attempted", "jaccard_failed", "interval_failed", "rounds", "windows_run",
+                                                  "windows_scheduled", "windows_host")])
+ACCEPT_MAX_KEPT, ACCEPT_INCOMPLETE, ACCEPT_OVERFLOW = 512, 0x1, 0x2
+assert SEARCH_PAIR_HIT_DTYPE.itemsize == 24 and ACCEPT_STATUS_DTYPE.itemsize == 64 and PAIR_STATS_DTYPE.itemsize == 56
 FILTER_Q_RC, FILTER_R_RC, FILTER_SKIP = 1, 2, 4
 FILTER_UPPER_FAIL, FILTER_QGRAM_FAIL, FILTER_SHORT, FILTER_SKIPPED = 1, 2, 4, 8
 FILTER_WAVE_MAX_LEN = 4096
@@ -112,6 +121,31 @@ class _ExtendParams(C.Structure):
 def extend_params(max_error=0.30, max_edit_error=0.15, max_sd_size=1 << 20, same_genome=False, reserved=(0, 0)):
     """sdf_extend_params; the defaults are the reference's (src/globals.cc)."""
     return _ExtendParams(float(max_error), float(max_edit_error), int(max_sd_size), int(bool(same_genome)), (C.c_int32 * 2)(*reserved))
+
+
+class _AcceptRound(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("nq", C.c_size_t), ("act", C.c_void_p), ("na", C.c_size_t), ("windows", C.c_void_p),
+                ("first", C.c_void_p), ("n_max", C.c_size_t), ("rolls", C.c_void_p), ("overlap", C.c_void_p), ("filter", C.c_void_p),
+                ("hits", C.c_void_p), ("hit_filter", C.c_void_p), ("init_len", C.c_int32), ("min_read_size", C.c_int32),
+                ("window_base", C.c_int32), ("reserved", C.c_int32)]
+
+
+def accept_round(q, nq, act, na, windows, first, n_max, rolls, overlap, filt, hits, hit_filter, init_len, min_read_size,
+                 window_base=0, reserved=0):
+    """sdf_search_accept_round over pointers (ints or None): host memory for search_accept_host / search_accept_raw, device
+    memory for search_accept_device."""
+    return _AcceptRound(q, int(nq), act, int(na), windows, first, int(n_max), rolls, overlap, filt, hits, hit_filter, int(init_len),
+                        int(min_read_size), int(window_base), int(reserved))
+
+
+class _PairParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("w", C.c_int32), ("separate_lowercase", C.c_int32), ("uppercase_seeds", C.c_int32),
+                ("min_read_size", C.c_int32), ("same_genome", C.c_int32), ("filter", _FilterParams), ("extend", _ExtendParams),
+                ("limit", C.c_void_p), ("n_limit", C.c_size_t), ("round_windows", C.c_size_t), ("debug_host_every", C.c_size_t)]
+
+
+class _MinimRange(C.Structure):
+    _fields_ = [("off", C.c_int64), ("len", C.c_int32), ("flags", C.c_int32)]
 
 
 class _Scoring(C.Structure):
@@ -304,6 +338,19 @@ def load_library():
     L.sdf_search_hit_tasks_host.argtypes = [C.c_void_p, C.c_size_t] + _htasks
     L.sdf_search_hit_tasks_device.restype = C.c_int
     L.sdf_search_hit_tasks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p] + _htasks + [C.c_void_p]
+    _accept = [C.POINTER(_AcceptRound), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.sdf_search_accept.restype = C.c_int  # round, found, nf, found_cap, out, n_out, out_cap, status
+    L.sdf_search_accept.argtypes = [C.c_void_p] + _accept
+    L.sdf_search_accept_host.restype = C.c_int
+    L.sdf_search_accept_host.argtypes = _accept
+    L.sdf_search_accept_device.restype = C.c_int
+    L.sdf_search_accept_device.argtypes = [C.c_void_p] + _accept + [C.c_void_p]
+    L.sdf_search_pair_host.restype = C.c_int  # pool, pool_bytes, q_range, r_range, params, out, cap, used, stats
+    L.sdf_search_pair_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_MinimRange), C.POINTER(_MinimRange), C.POINTER(_PairParams),
+                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.sdf_search_pair.restype = C.c_int  # ctx, q_range, r_range, params, out, cap, used, stats
+    L.sdf_search_pair.argtypes = [C.c_void_p, C.POINTER(_MinimRange), C.POINTER(_MinimRange), C.POINTER(_PairParams), C.c_void_p,
+                                  C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -1018,6 +1065,24 @@ class Extz2Engine:
                                                        d_found_entries, d_visible_iv, int(init_len), int(min_read_size), d_out,
                                                        d_filter_tasks, stream))
 
+    def search_pair(self, q_range, r_range, **kw):
+        """sdf_search_pair: the SDs of two ranges of the resident pool as `sedef search` reports them, the stages and the
+        acceptance step run in rounds on the device.  Arguments and result as search_pair_host's, and round_windows (0: the
+        default) and debug_host_every (every n-th scheduled window on the host)."""
+        return search_pair_call(self.lib.sdf_search_pair, (self.ctx,), q_range, r_range, **kw)
+
+    def search_accept_raw(self, *args, **kw):
+        """sdf_search_accept as it is: one round of the search driver's acceptance step on numpy arrays, run by the device
+        form on copies.  Arguments and result as search_accept_call's."""
+        return search_accept_call(self.lib.sdf_search_accept, (self.ctx,), *args, **kw)
+
+    def search_accept_device(self, d_round, d_found, nf, found_cap, d_out, n_out, out_cap, d_status, stream=None):
+        """The same over device pointers (ints), behind the second filter on one stream without a host read: d_round is what
+        accept_round makes of the round's device arrays; the status record (ACCEPT_STATUS_DTYPE) goes to d_status.  Three
+        launches, whatever the data."""
+        self._check(self.lib.sdf_search_accept_device(self.ctx, C.byref(d_round), d_found, int(nf), int(found_cap), d_out, int(n_out),
+                                                      int(out_cap), d_status, stream))
+
     def search_roll_raw(self, q, windows, first, intervals, r, len_r, init_len, limit):
         """sdf_search_roll as it is.  q, windows, first, intervals: as search_windows_raw takes and returns them; r: the
         reference's minimizers in loc order (MINIMIZER_DTYPE); limit: the same table.  Returns (rc, rolls): a
@@ -1367,6 +1432,84 @@ def search_hit_tasks_host(hits, len_q, len_r, q_off, q_rc, r_off, r_rc, out=None
     rc = load_library().sdf_search_hit_tasks_host(hits.ctypes.data if len(hits) else None, len(hits), int(len_q), int(len_r), int(q_off),
                                                   int(bool(q_rc)), int(r_off), int(bool(r_rc)), out.ctypes.data if len(out) else None)
     return rc, out
+
+
+ACCEPT_CANARY = 4  # records behind a capacity that search_accept_call leaves filled with 0xEE
+
+
+def search_accept_call(fn, head, q, act, windows, first, rolls, overlap, filt, hits, hit_filter, init_len, min_read_size, found, out,
+                       found_cap=None, out_cap=None, window_base=0, n_max=None, reserved=0):
+    """sdf_search_accept (head: its context) or sdf_search_accept_host (head: nothing) on numpy arrays: one round of the
+    acceptance step.  act: the ascending window indices that ran; windows, first, rolls, overlap (the is_overlap verdicts against
+    the list as it stood), filt, hits, hit_filter: what the stages wrote; found, out: the records so far (SEARCH_FOUND_DTYPE,
+    SEARCH_PAIR_HIT_DTYPE); found_cap, out_cap: the capacities (None: just enough for everything the round could add).
+    Returns (rc, status, found_buf, out_buf): the ACCEPT_STATUS_DTYPE record and the two lists in buffers of their capacity plus
+    ACCEPT_CANARY records that were 0xEE before the call."""
+    q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
+    act = np.ascontiguousarray(act, dtype=np.uint32)
+    windows = np.ascontiguousarray(windows, dtype=SEARCH_WINDOW_DTYPE)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    rolls = np.ascontiguousarray(rolls, dtype=SEARCH_ROLL_DTYPE)
+    overlap = np.ascontiguousarray(overlap, dtype=np.uint32)
+    filt = np.ascontiguousarray(filt, dtype=FILTER_REC_DTYPE)
+    hits = np.ascontiguousarray(hits, dtype=SEARCH_HIT_DTYPE)
+    hit_filter = np.ascontiguousarray(hit_filter, dtype=FILTER_REC_DTYPE)
+    found = np.ascontiguousarray(found, dtype=SEARCH_FOUND_DTYPE)
+    out = np.ascontiguousarray(out, dtype=SEARCH_PAIR_HIT_DTYPE)
+    n = len(rolls) if n_max is None else int(n_max)
+    assert min(len(rolls), len(overlap), len(filt), len(hits), len(hit_filter)) >= n
+    found_cap = len(found) + n if found_cap is None else int(found_cap)
+    out_cap = len(out) + n if out_cap is None else int(out_cap)
+    found_buf = np.frombuffer(bytearray(b"\xEE" * (16 * (found_cap + ACCEPT_CANARY))), SEARCH_FOUND_DTYPE)
+    out_buf = np.frombuffer(bytearray(b"\xEE" * (24 * (out_cap + ACCEPT_CANARY))), SEARCH_PAIR_HIT_DTYPE)
+    found_buf[:min(len(found), found_cap)] = found[:found_cap]
+    out_buf[:min(len(out), out_cap)] = out[:out_cap]
+    status = np.zeros(1, ACCEPT_STATUS_DTYPE)
+
+    def ptr(a):
+        return a.ctypes.data if len(a) else None
+    R = accept_round(ptr(q), len(q), ptr(act), len(act), ptr(windows), first.ctypes.data if len(first) else None, n, ptr(rolls),
+                     ptr(overlap), ptr(filt), ptr(hits), ptr(hit_filter), init_len, min_read_size, window_base, reserved)
+    rc = fn(*head, C.byref(R), found_buf.ctypes.data, len(found), found_cap, out_buf.ctypes.data, len(out), out_cap, status.ctypes.data)
+    return rc, status[0], found_buf, out_buf
+
+
+def search_accept_host(*args, **kw):
+    """sdf_search_accept_host: search_accept_raw without a context or a GPU, the same rules in plain C++."""
+    return search_accept_call(load_library().sdf_search_accept_host, (), *args, **kw)
+
+
+def search_pair_call(fn, head, q_range, r_range, k=12, w=16, separate_lowercase=True, uppercase_seeds=True, min_read_size=700,
+                     same_genome=False, limit=(), filter=None, extend=None, cap=None, round_windows=0, debug_host_every=0):
+    """sdf_search_pair (head: its context) or sdf_search_pair_host (head: the characters and their number).  Returns
+    (rc, hits, used, stats)."""
+    limit = np.ascontiguousarray(limit, dtype=np.int32)
+    P = _PairParams(int(k), int(w), int(bool(separate_lowercase)), int(bool(uppercase_seeds)), int(min_read_size), int(bool(same_genome)),
+                    filter_params() if filter is None else filter,
+                    extend_params(same_genome=bool(same_genome)) if extend is None else extend,
+                    limit.ctypes.data if len(limit) else None, len(limit), int(round_windows), int(debug_host_every))
+    ranges = [_MinimRange(int(r[0]), int(r[1]), int(r[2]) if len(r) > 2 else 0) for r in (q_range, r_range)]
+    stats = np.zeros(1, PAIR_STATS_DTYPE)
+    used = C.c_size_t(0)
+    room = 0 if cap is None else int(cap)
+    while True:
+        out = np.zeros(room, SEARCH_PAIR_HIT_DTYPE)
+        rc = fn(*head, C.byref(ranges[0]), C.byref(ranges[1]), C.byref(P), out.ctypes.data if room else None, room, C.byref(used),
+                stats.ctypes.data)
+        if rc != -5 or cap is not None:
+            break
+        room = int(used.value)
+    return rc, out[:int(used.value)] if rc == 0 else out[:0], int(used.value), stats[0]
+
+
+def search_pair_host(pool, q_range, r_range, pool_bytes=None, **kw):
+    """sdf_search_pair_host: initial_search window by window in plain C++ over the characters `pool` (bytes), no context and no
+    GPU.  q_range, r_range: (off, len) or (off, len, flags) with MINIM_RC.  limit: the table of
+    relaxed_jaccard_estimate(query_size).  cap: the hits `out` holds (None: retried with the need).  Returns (rc, hits, used,
+    stats): SEARCH_PAIR_HIT_DTYPE records, the need, a PAIR_STATS_DTYPE record."""
+    pool = bytes(pool)
+    return search_pair_call(load_library().sdf_search_pair_host, (pool, len(pool) if pool_bytes is None else int(pool_bytes)), q_range, r_range,
+                            **kw)
 
 
 _default_engine = None

@@ -1,8 +1,8 @@
 // Stand-alone host program for sanitizer runs of sdf_search_filter_host and sdf_search_filter_tasks_host (no GPU is touched, no
 // python is involved).  Build and run from the repository root:
 //   hipcc -std=c++17 -O1 -g --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Iinclude -Isedef_amd/csrc \
-//         -x hip profiles/search_filter_host_check.cc sedef_amd/csrc/sdf_filter_api.hip sedef_amd/csrc/search_filter.hip \
-//         -o /tmp/search_filter_host_check
+//         -x hip profiles/search_filter_host_check.cc sedef_amd/csrc/search_host.hip -o /tmp/search_filter_host_check
+// (search_host.hip holds the search family's host forms and needs no kernel source beside it)
 //   python tests/golden/make_golden_search_filter.py --dump-cases /tmp/cases.bin
 //   /tmp/search_filter_host_check /tmp/cases.bin
 // cases.bin holds fixture cases back to back, little endian: u64 pool_bytes, the pool, u64 n, n sdf_filter_task, one

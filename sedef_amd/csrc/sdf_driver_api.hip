@@ -1,50 +1,18 @@
-// The C ABI: the search driver (include/sedef_hip.h states the rules) -- the acceptance step of a round (search_accept.hip),
-// sdf_search_accept_host being the same rules in plain C++; sdf_search_pair_host, initial_search window by window on the host
-// over the per-window forms of the stages (sdf_search_api.hip) with minimizers and index computed here as tests/minim_model.py
-// states them; and sdf_search_pair, the stages and the acceptance step in rounds on the resident pool.
+// The C ABI: the search driver (include/sedef_hip.h states the rules) -- the device and uploading forms of a round's
+// acceptance step (search_accept.hip) with their launches, and sdf_search_pair, the stages and the acceptance step in rounds
+// on the resident pool.  sdf_search_accept_host, sdf_search_pair_host, the window that sdf_search_pair hands to the host
+// (pair_host_window) and the checks: search_host.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <deque>
-#include <map>
 #include <string>
 
 #include "sdf_entry.h"
+#include "search_host.h"
 
 using namespace sdf;
 
 namespace {
-// what every form of the acceptance step checks of its scalars and of the pointers a count makes necessary
-int accept_scalars(const sdf_search_accept_round *R, const void *found, size_t nf, size_t found_cap, const void *out, size_t n_out,
-                   size_t out_cap, const void *status, const char **why) {
-  if (!R || !status) return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
-  if (R->init_len < 1) return *why = "search accept: init_len < 1", SDF_ERR_INVALID;
-  if (R->min_read_size < 0) return *why = "search accept: min_read_size < 0", SDF_ERR_INVALID;
-  if (nf > found_cap || n_out > out_cap) return *why = "search accept: a count beyond its capacity", SDF_ERR_INVALID;
-  if ((found_cap && !found) || (out_cap && !out)) return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
-  if (R->na && (!R->act || !R->q || !R->windows || !R->first)) return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
-  if (R->na && R->n_max && (!R->rolls || !R->overlap || !R->filter || !R->hits || !R->hit_filter))
-    return *why = "search accept: invalid arguments", SDF_ERR_INVALID;
-  if (R->init_len > (1 << 30)) return *why = "search accept implements init_len up to 2^30", SDF_ERR_UNSUPPORTED;
-  if (R->nq > 0x3fffffffu) return *why = "search accept: more than 2^30 - 1 query minimizers in one call", SDF_ERR_UNSUPPORTED;
-  if (R->na > 0x7fffffffu || R->n_max > 0x7fffffffu || found_cap > 0x7fffffffu || out_cap > 0x7fffffffu)
-    return *why = "search accept: more than 2^31 - 1 round windows, intervals or records in one call", SDF_ERR_UNSUPPORTED;
-  if (R->reserved != 0) return *why = "search accept: reserved != 0", SDF_ERR_UNSUPPORTED;
-  return SDF_OK;
-}
-// ... and the forms that take host arrays of those
-int accept_arrays(const sdf_search_accept_round *R, const char **why) {
-  if (!R->na) return SDF_OK;
-  for (size_t j = 0; j < R->na; j++)
-    if (R->act[j] >= R->nq || (j && R->act[j] <= R->act[j - 1]))
-      return *why = "search accept: act[] does not ascend strictly inside [0, nq)", SDF_ERR_INVALID;
-  if (R->first[0] != 0) return *why = "search accept: first[0] != 0", SDF_ERR_INVALID;
-  for (size_t i = 0; i < R->nq; i++)
-    if (R->first[i + 1] < R->first[i]) return *why = "search accept: first[] does not ascend", SDF_ERR_INVALID;
-  return SDF_OK;
-}
-
 // the three launches on `st` (one when the round is empty)
 int accept_launch(sdf_ctx *ctx, const sdf_search_accept_round *R, sdf_search_found *d_found, size_t nf, size_t found_cap,
                   sdf_search_pair_hit *d_out, size_t n_out, size_t out_cap, sdf_search_accept_status *d_status, hipStream_t st) {
@@ -70,96 +38,6 @@ int accept_launch(sdf_ctx *ctx, const sdf_search_accept_round *R, sdf_search_fou
   return SDF_OK;
 }
 }  // namespace
-
-extern "C" int sdf_search_accept_host(const sdf_search_accept_round *R, sdf_search_found *found, size_t nf, size_t found_cap,
-                                      sdf_search_pair_hit *out, size_t n_out, size_t out_cap, sdf_search_accept_status *status) {
-  const char *why = nullptr;
-  if (int rc = accept_scalars(R, found, nf, found_cap, out, n_out, out_cap, status, &why)) return rc;
-  if (int rc = accept_arrays(R, &why)) return rc;
-  struct Kept {
-    uint64_t t;
-    bool dropped;
-  };
-  std::vector<Kept> kept;  // of the windows in front of the frontier, in order
-  std::vector<sdf_search_found> recs;
-  int64_t attempted = 0, jaccard_failed = 0, interval_failed = 0;
-  uint64_t n_found = 0, n_reported = 0;
-  int32_t reach = 0;
-  size_t frontier = R->na;
-  bool incomplete = false;
-  for (size_t j = 0; j < R->na; j++) {
-    const size_t i = R->act[j];
-    const long long pf_pos = R->q[i].loc, pf_end = pf_pos + R->init_len;
-    const uint64_t t0 = R->first[i], t1 = R->first[i + 1];
-    incomplete = t1 > R->n_max || (R->windows[i].flags & (SDF_SEARCH_WIDE | SDF_SEARCH_FOUND_WIDE));
-    int64_t att = 0, jf = 0, ivf = 0;
-    int32_t reach_w = 0;
-    recs.clear();
-    const size_t kept0 = kept.size();
-    for (uint64_t t = t0; t < t1 && t1 <= R->n_max; t++) {
-      const sdf_search_roll_rec &roll = R->rolls[t];
-      const sdf_search_hit &H = R->hits[t];
-      incomplete |= accept_unfinished(roll, H);
-      att += 1;
-      const int cls = accept_class(roll, R->overlap[t], R->filter[t], H, R->hit_filter[t]);
-      if (cls == 0) jf += 1;
-      if (cls == 1) ivf += 1;
-      if (cls < 2) continue;
-      bool hit = false;
-      for (size_t k = 0; k < recs.size() && !hit; k++)
-        hit = !found_empty(recs[k]) && found_covers(recs[k], pf_pos, roll.ref_start) &&
-              found_overlaps(recs[k], pf_pos, pf_end, roll.ref_start, roll.ref_end, R->min_read_size);
-      if (hit) {
-        ivf += 1;
-      } else if (cls == 3) {
-        if (recs.size() < SDF_ACCEPT_MAX_KEPT) {
-          recs.push_back(sdf_search_found{H.query_start, H.query_end, H.ref_start, H.ref_end});
-          kept.push_back(Kept{t, false});
-          reach_w = std::max(reach_w, H.query_end);
-        } else {
-          incomplete = true;
-        }
-      }
-    }
-    if (reach > pf_pos || incomplete) {
-      kept.resize(kept0);
-      frontier = j;
-      break;
-    }
-    incomplete = false;
-    uint64_t survivors = 0;
-    for (size_t h = 0; h < recs.size(); h++) {  // parse_hits
-      bool dropped = false;
-      for (size_t p = 0; p < recs.size() && !dropped; p++) dropped = p != h && accept_contains(recs[p], recs[h]);
-      kept[kept0 + h].dropped = dropped;
-      survivors += !dropped;
-    }
-    n_found += recs.size(), n_reported += survivors;
-    attempted += att, jaccard_failed += jf, interval_failed += ivf;
-    reach = std::max(reach, reach_w);
-  }
-  sdf_search_accept_status S;
-  S.need_found = nf + n_found, S.need_out = n_out + n_reported;
-  const bool over = S.need_found > found_cap || S.need_out > out_cap;
-  S.frontier = over ? 0u : (uint32_t)frontier;
-  S.flags = over ? SDF_ACCEPT_OVERFLOW : incomplete ? SDF_ACCEPT_INCOMPLETE : 0u;
-  S.nf = over ? nf : S.need_found, S.n_out = over ? n_out : S.need_out;
-  S.attempted = over ? 0 : attempted, S.jaccard_failed = over ? 0 : jaccard_failed, S.interval_failed = over ? 0 : interval_failed;
-  *status = S;
-  if (over) return SDF_OK;
-  // the append: window order, then interval order -- the order of `kept`
-  size_t w = 0;
-  for (size_t j = 0; j < frontier; j++) {
-    const size_t i = R->act[j];
-    for (; w < kept.size() && kept[w].t < R->first[i + 1]; w++) {
-      const sdf_search_hit &H = R->hits[kept[w].t];
-      found[nf++] = sdf_search_found{H.query_start, H.query_end, H.ref_start, H.ref_end};
-      if (!kept[w].dropped)
-        out[n_out++] = sdf_search_pair_hit{(int32_t)(R->window_base + (int32_t)i), H.query_start, H.query_end, H.ref_start, H.ref_end, H.jaccard};
-    }
-  }
-  return SDF_OK;
-}
 
 extern "C" int sdf_search_accept_device(sdf_ctx *ctx, const sdf_search_accept_round *R, sdf_search_found *d_found, size_t nf, size_t found_cap,
                                         sdf_search_pair_hit *d_out, size_t n_out, size_t out_cap, sdf_search_accept_status *d_status,
@@ -224,149 +102,6 @@ extern "C" int sdf_search_accept(sdf_ctx *ctx, const sdf_search_accept_round *R,
   return SDF_OK;
 }
 
-// ---- sdf_search_pair_host ----
-
-namespace {
-inline char host_rev_dna(const char c) {
-  switch (c) {
-    case 'A': return 'T';
-    case 'C': return 'G';
-    case 'G': return 'C';
-    case 'T': return 'A';
-    case 'a': return 't';
-    case 'c': return 'g';
-    case 'g': return 'c';
-    case 't': return 'a';
-    default: return 'N';
-  }
-}
-// the sequence of a range: its characters & 127, reverse-complemented by rev_dna under SDF_MINIM_RC
-std::string host_sequence(const char *pool, const sdf_minim_range &r) {
-  std::string s((size_t)r.len, 'N');
-  for (int32_t x = 0; x < r.len; x++) {
-    const char c = (char)(pool[r.off + x] & 127);
-    if (r.flags & SDF_MINIM_RC) s[(size_t)(r.len - 1 - x)] = host_rev_dna(c);
-    else s[(size_t)x] = c;
-  }
-  return s;
-}
-// get_minimizers (src/hash.cc:53-100) as tests/minim_model.py holds it, the deque loop as written
-std::vector<sdf_minimizer> host_minimizers(const std::string &s, int k, int w, bool separate_lowercase) {
-  std::vector<sdf_minimizer> out;
-  struct Item {
-    uint64_t key;
-    int64_t loc;
-  };
-  std::deque<Item> window;
-  const uint32_t mask = (uint32_t)((1ull << (2 * k)) - 1);
-  uint32_t h = 0;
-  int64_t last_n = -(int64_t)k - w, last_u = last_n;
-  for (int64_t i = 0; i < (int64_t)s.size(); i++) {
-    const char c = s[(size_t)i];
-    if (c == 'N' || c == 'n') last_n = i;
-    else if (c >= 'A' && c <= 'Z') last_u = i;
-    const uint32_t code = c == 'C' || c == 'c' ? 1u : c == 'G' || c == 'g' ? 2u : c == 'T' || c == 't' ? 3u : 0u;
-    h = ((h << 2) | code) & mask;
-    if (i < k - 1) continue;
-    const int64_t at = i - k + 1;
-    uint32_t status = last_n >= at ? 2u : last_u >= at ? 0u : 1u;
-    if (!separate_lowercase && status == 1u) status = 0u;
-    const uint64_t key = (uint64_t)status << 32 | h;
-    while (!window.empty() && !(window.back().key < key)) window.pop_back();
-    while (!window.empty() && window.back().loc < at - w) window.pop_front();
-    window.push_back(Item{key, at});
-    if (at < w) continue;
-    const Item &f = window.front();
-    if (out.empty() || !((int64_t)out.back().loc == f.loc && ((uint64_t)(uint32_t)out.back().status << 32 | out.back().hash) == f.key))
-      out.push_back(sdf_minimizer{(uint32_t)f.key, (int32_t)f.loc, (int32_t)(f.key >> 32), 0});
-  }
-  return out;
-}
-// Index::Index (src/hash.cc:113-141): the records in ascending (status, hash, loc), and the threshold
-uint32_t host_index(const std::vector<sdf_minimizer> &m, std::vector<sdf_minimizer> &sorted) {
-  const auto key = [](const sdf_minimizer &x) { return (uint64_t)(uint32_t)x.status << 32 | x.hash; };
-  sorted = m;
-  std::stable_sort(sorted.begin(), sorted.end(), [&](const sdf_minimizer &a, const sdf_minimizer &b) { return key(a) < key(b); });
-  std::map<uint64_t, uint64_t> hist;  // group size -> groups
-  for (size_t a = 0; a < sorted.size();) {
-    size_t b = a;
-    while (b < sorted.size() && key(sorted[b]) == key(sorted[a])) ++b;
-    hist[b - a] += 1;
-    a = b;
-  }
-  const int ignore = (int)(((double)m.size() * 0.001) / 100.0);
-  uint64_t total = 0;
-  uint32_t threshold = 0x80000000u;
-  for (auto it = hist.rbegin(); it != hist.rend(); ++it) {
-    total += it->second;
-    if (total > (uint64_t)ignore) break;
-    threshold = (uint32_t)it->first;
-  }
-  return threshold;
-}
-
-int pair_checks(size_t pool_bytes, const sdf_minim_range *Q, const sdf_minim_range *R, const sdf_search_pair_params *P) {
-  if (!Q || !R || !P || (P->n_limit && !P->limit)) return SDF_ERR_INVALID;
-  for (const sdf_minim_range *r : {Q, R})
-    if (!in_range(r->off, (int64_t)r->len, pool_bytes)) return SDF_ERR_INVALID;
-  if (P->min_read_size < 1) return SDF_ERR_INVALID;
-  if (P->same_genome && (Q->off != R->off || Q->len != R->len || Q->flags || R->flags)) return SDF_ERR_INVALID;
-  const sdf_filter_params &F = P->filter;
-  const sdf_extend_params &E = P->extend;
-  if (!std::isfinite(F.max_error) || !std::isfinite(F.max_edit_error) || !std::isfinite(F.gap_frequency) || !std::isfinite(E.max_error) ||
-      !std::isfinite(E.max_edit_error) || !(E.max_error - E.max_edit_error > 0))
-    return SDF_ERR_INVALID;
-  if (P->k < 1 || P->k > 15 || P->w < 1 || P->w > SDF_MINIM_MAX_W) return SDF_ERR_UNSUPPORTED;
-  if ((Q->flags | R->flags) & ~SDF_MINIM_RC) return SDF_ERR_UNSUPPORTED;
-  if (P->n_limit > 0x7fffffffu || P->min_read_size > (1 << 30)) return SDF_ERR_UNSUPPORTED;
-  for (size_t s = 1; s < P->n_limit; s++)
-    if (P->limit[s] < 1) return SDF_ERR_UNSUPPORTED;
-  if (F.reserved || E.reserved[0] || E.reserved[1]) return SDF_ERR_UNSUPPORTED;
-  return SDF_OK;
-}
-}  // namespace
-
-extern "C" int sdf_search_pair_host(const char *pool, size_t pool_bytes, const sdf_minim_range *q_range, const sdf_minim_range *r_range,
-                                    const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
-                                    sdf_search_pair_stats *stats) {
-  if (!used || !stats || (cap && !out) || (pool_bytes && !pool)) return SDF_ERR_INVALID;
-  if (int rc = pair_checks(pool_bytes, q_range, r_range, params)) return rc;
-  const sdf_search_pair_params &P = *params;
-  const std::string qs = host_sequence(pool, *q_range);
-  const std::vector<sdf_minimizer> q = host_minimizers(qs, P.k, P.w, P.separate_lowercase != 0);
-  std::vector<sdf_minimizer> r_own, r_sorted;
-  if (!P.same_genome) r_own = host_minimizers(host_sequence(pool, *r_range), P.k, P.w, P.separate_lowercase != 0);
-  const std::vector<sdf_minimizer> &r = P.same_genome ? q : r_own;
-  const uint32_t threshold = host_index(r, r_sorted);
-  sdf_extend_params E = P.extend;
-  E.same_genome = P.same_genome != 0;
-  const PairHostArgs A{pool,          pool_bytes,    q.data(),           q.size(),        r.data(),
-                       r_sorted.data(), r.size(),      threshold,          q_range->len,    r_range->len,
-                       q_range->off,  r_range->off,  (int)(q_range->flags & SDF_MINIM_RC), (int)(r_range->flags & SDF_MINIM_RC),
-                       P.min_read_size, P.same_genome != 0, P.uppercase_seeds != 0, P.limit, P.n_limit, P.filter, E};
-  std::vector<sdf_search_found> found;
-  std::vector<sdf_search_pair_hit> all;
-  PairHostWindow W;
-  sdf_search_pair_stats S{0, 0, 0, 0, 0, 0, 0};
-  int64_t next = 0;
-  for (size_t i = 0; i < q.size(); i++) {
-    if ((int64_t)q[i].loc < next) continue;
-    if (P.uppercase_seeds && q[i].status != 0) continue;
-    if (int rc = pair_host_window(A, i, found, W)) return rc;
-    S.attempted += W.attempted, S.jaccard_failed += W.jaccard_failed, S.interval_failed += W.interval_failed;
-    S.windows_run += 1, S.windows_scheduled += 1, S.windows_host += 1;
-    int64_t min_len = q_range->len;
-    for (const sdf_search_pair_hit &h : W.reported) min_len = std::min<int64_t>(min_len, (int64_t)h.query_end - h.query_start);
-    all.insert(all.end(), W.reported.begin(), W.reported.end());
-    next = min_len >= P.min_read_size ? (int64_t)(int)((double)q[i].loc + ((double)P.min_read_size * P.filter.max_error) / 2) : (int64_t)q[i].loc;
-  }
-  *stats = S;
-  *used = all.size();
-  if (all.size() > cap) return SDF_ERR_CIGAR_OVERFLOW;
-  if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(sdf_search_pair_hit));
-  return SDF_OK;
-}
-
 // ---- sdf_search_pair: the stages and the acceptance step in rounds, on the resident pool ----
 
 namespace {
@@ -377,6 +112,7 @@ struct PairDriver {
   sdf_ctx *ctx;
   hipStream_t st;
   const sdf_search_pair_params &P;
+  const sdf_extend_params E;  // P.extend as the stages take it
   sdf_minim_range Q, R;
   std::vector<sdf_minimizer> q, r_own, r_sorted;
   uint32_t threshold = 0x80000000u;
@@ -406,12 +142,6 @@ int pair_minimizers(sdf_ctx *ctx, const sdf_minim_range &range, const sdf_search
   return SDF_OK;
 }
 
-int pair_upload(sdf_ctx *ctx, DevBuf &buf, const void *src, size_t bytes, hipStream_t st) {
-  SDF_HIP(buf.reserve(bytes + 256));
-  if (bytes) SDF_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
-  return SDF_OK;
-}
-
 // the device list behind the host's mirror: room for `want` records, records [from, found.size()) uploaded
 int pair_sync_found(PairDriver &D, size_t want, size_t from) {
   sdf_ctx *ctx = D.ctx;
@@ -434,12 +164,9 @@ int pair_host_one(PairDriver &D, size_t i) {
     const sdf_pool_fetch F[2] = {{D.Q.off, D.Q.len, 0, 0}, {D.R.off, D.R.len, 0, D.Q.len}};
     if (int rc = sdf_pool_fetch_ranges(ctx, F, D.P.same_genome ? 1 : 2, &D.chars[0], D.chars.size())) return rc;
   }
-  sdf_extend_params E = D.P.extend;
-  E.same_genome = D.P.same_genome != 0;
-  const std::vector<sdf_minimizer> &r = D.r();
-  const PairHostArgs A{D.chars.data(), D.chars.size(), D.q.data(), D.q.size(), r.data(), D.r_sorted.data(), r.size(), D.threshold,
-                       D.Q.len, D.R.len, 0, D.P.same_genome ? 0 : (int64_t)D.Q.len, (int)(D.Q.flags & SDF_MINIM_RC), (int)(D.R.flags & SDF_MINIM_RC),
-                       D.P.min_read_size, D.P.same_genome != 0, D.P.uppercase_seeds != 0, D.P.limit, D.P.n_limit, D.P.filter, E};
+  // (the ranges as they lie in chars)
+  const sdf_minim_range Q{0, D.Q.len, D.Q.flags}, R{D.P.same_genome ? 0 : (int64_t)D.Q.len, D.R.len, D.R.flags};
+  const PairHostArgs A = pair_host_args(D.chars.data(), D.chars.size(), Q, R, D.P, D.E, D.q, D.r(), D.r_sorted, D.threshold);
   const size_t nf0 = D.found.size();
   if (int rc = pair_host_window(A, i, D.found, D.W)) return refuse(ctx, rc, "sdf_search_pair: the host step of a window failed");
   D.out.insert(D.out.end(), D.W.reported.begin(), D.W.reported.end());
@@ -475,7 +202,7 @@ int pair_round(PairDriver &D, const uint32_t *act, size_t na, sdf_search_accept_
   SDF_HIP(ctx->dr_hrec.reserve((n + 1) * sizeof(sdf_filter_rec)));
   SDF_HIP(ctx->dr_out.reserve((n + 1) * sizeof(sdf_search_pair_hit)));
   SDF_HIP(ctx->dr_status.reserve(sizeof(sdf_search_accept_status) + 16));
-  if (int rc = pair_upload(ctx, ctx->dr_act, act, na * 4, st)) return rc;
+  if (int rc = upload_all(ctx, st, {{ctx->dr_act, act, na * 4}})) return rc;
   const sdf_minimizer *d_q = (const sdf_minimizer *)ctx->dr_q.p, *d_r = P.same_genome ? d_q : (const sdf_minimizer *)ctx->dr_r.p;
   const sdf_minimizer *d_rs = (const sdf_minimizer *)ctx->dr_rs.p;
   const int32_t *d_limit = (const int32_t *)ctx->dr_limit.p;
@@ -490,8 +217,7 @@ int pair_round(PairDriver &D, const uint32_t *act, size_t na, sdf_search_accept_
   sdf_search_found *d_found = (sdf_search_found *)ctx->dr_found.p;
   sdf_search_accept_status *d_status = (sdf_search_accept_status *)ctx->dr_status.p;
   uint64_t *d_need = (uint64_t *)(d_status + 1);
-  sdf_extend_params E = P.extend;
-  E.same_genome = P.same_genome != 0;
+  const sdf_extend_params &E = D.E;
   void *s = (void *)st;
   // every window and interval of the round sees the whole list as it stands
   SDF_HIP(hipMemsetD32Async((hipDeviceptr_t)d_vis, (int)nf, std::max(nq, n), st));
@@ -561,7 +287,7 @@ extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, con
   if (!used || !stats || (cap && !out)) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair: invalid arguments");
   if (int rc = pair_checks(sdf_pool_bytes(ctx), q_range, r_range, params)) return refuse(ctx, rc, "sdf_search_pair: a range or a parameter is refused");
   SDF_HIP(hipSetDevice(ctx->device));
-  PairDriver D{ctx, ctx->stream, *params, *q_range, *r_range};
+  PairDriver D{ctx, ctx->stream, *params, pair_extend_params(*params), *q_range, *r_range};
   const sdf_search_pair_params &P = *params;
   // set-up: minimizers of both ranges, the reference's index; they stay in HBM for every round
   if (int rc = pair_minimizers(ctx, D.Q, P, false, D.q, nullptr)) return rc;
@@ -575,17 +301,20 @@ extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, con
     for (size_t i = 0; i < nq; i++) {
       if ((int64_t)D.q[i].loc < next || (P.uppercase_seeds && D.q[i].status != 0)) continue;
       sched.push_back((uint32_t)i);
-      next = (int64_t)(int)((double)D.q[i].loc + ((double)P.min_read_size * P.filter.max_error) / 2);
+      next = pair_next_loc(D.q[i].loc, P.min_read_size, P.filter.max_error);
     }
   }
   D.S.windows_scheduled = (int64_t)sched.size();
   if (!sched.empty()) {
     hipStream_t st = D.st;
-    if (int rc = pair_upload(ctx, ctx->dr_q, D.q.data(), nq * sizeof(sdf_minimizer), st)) return rc;
-    if (!P.same_genome)
-      if (int rc = pair_upload(ctx, ctx->dr_r, D.r_own.data(), D.r_own.size() * sizeof(sdf_minimizer), st)) return rc;
-    if (int rc = pair_upload(ctx, ctx->dr_rs, D.r_sorted.data(), D.r_sorted.size() * sizeof(sdf_minimizer), st)) return rc;
-    if (int rc = pair_upload(ctx, ctx->dr_limit, P.limit, P.n_limit * 4, st)) return rc;
+    // (an array without a record still gets a buffer: the device forms -- sdf_search_roll_device's d_r and d_limit first -- refuse a null
+    // pointer before they look at a count.  The 256 bytes these uploads used to add did no more: no kernel reads past its counts.)
+    for (DevBuf *b : {&ctx->dr_r, &ctx->dr_rs, &ctx->dr_limit}) SDF_HIP(b->reserve(16));
+    if (int rc = upload_all(ctx, st, {{ctx->dr_q, D.q.data(), nq * sizeof(sdf_minimizer)},
+                                     {ctx->dr_r, D.r_own.data(), D.r_own.size() * sizeof(sdf_minimizer)},  // (empty under same_genome)
+                                     {ctx->dr_rs, D.r_sorted.data(), D.r_sorted.size() * sizeof(sdf_minimizer)},
+                                     {ctx->dr_limit, P.limit, P.n_limit * 4}}))
+      return rc;
     SDF_HIP(ctx->dr_first.reserve((nq + 1) * 8));
     SDF_HIP(ctx->dr_win.reserve((nq + 1) * sizeof(sdf_search_window)));
     SDF_HIP(hipMemsetAsync(ctx->dr_win.p, 0, nq * sizeof(sdf_search_window), st));

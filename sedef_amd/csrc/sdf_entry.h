@@ -1,6 +1,10 @@
-// The checks the entry points of the C ABI share (sdf_pool_api.hip, sdf_stats_api.hip, sdf_minim_api.hip, sdf_search_api.hip, sdf_filter_api.hip): is a range inside
-// its pool, the tasks of the stats calls, and the tail of a call whose output the device counts first.
+// What the entry points of the C ABI share on the launch side (sdf_pool_api.hip, sdf_stats_api.hip, sdf_minim_api.hip and the
+// search family's sdf_*_api.hip): a refusal, the tasks of the stats calls, the tail of a call whose output the device counts
+// first, the bin index of the found records, and the uploads of a form that takes host arrays.  (in_range: sdf_internal.h;
+// the search family's own checks and host rules: search_host.h.)
 #pragma once
+#include <initializer_list>
+
 #include "sdf_ctx.h"
 
 namespace sdf {
@@ -9,11 +13,6 @@ inline int refuse(sdf_ctx *ctx, int code, std::string why) {
   ctx->err = std::move(why);
   return code;
 }
-
-// [off, off + len) lies inside [0, size) -- an empty range at `size` does -- without ever forming off + len (where that sum
-// cannot wrap, a task's 63-bit offset and 31-bit length, this is off + len <= size: what batch_host and batch_pairs asked before)
-inline bool in_range(uint64_t off, uint64_t len, uint64_t size) { return off <= size && len <= size - off; }
-inline bool in_range(int64_t off, int64_t len, size_t size) { return off >= 0 && len >= 0 && in_range((uint64_t)off, (uint64_t)len, (uint64_t)size); }
 
 // (the kernels that read the resident pool in aligned 16-byte units count them from its base)
 inline bool pool_base_aligned(const sdf_ctx *ctx) { return ((uintptr_t)ctx->an_pool.p & 15) == 0; }
@@ -65,31 +64,19 @@ int found_index(sdf_ctx *ctx, const sdf_search_found *d_found, size_t nf, size_t
                 hipStream_t st, FoundIndex *F);
 int found_index_need(sdf_ctx *ctx, size_t cap);
 
-// One window of initial_search on the host (sdf_search_api.hip, where the per-window forms of the stages live), for
-// sdf_search_pair_host (sdf_driver_api.hip): include/sedef_hip.h states the steps.  pair_host_window runs window i against the
-// whole of `found`, appends the records it keeps to it as it goes, and leaves the parse_hits survivors and the counters in W.
-struct PairHostArgs {
-  const char *pool;
-  size_t pool_bytes;
-  const sdf_minimizer *q;
-  size_t nq;
-  const sdf_minimizer *r, *r_sorted;  // ascending loc; ascending (status, hash, loc)
-  size_t nr;
-  uint32_t r_threshold;
-  int64_t len_q, len_r, q_off, r_off;
-  int q_rc, r_rc;
-  int32_t min_read_size;
-  bool same_genome, uppercase_seeds;
-  const int32_t *limit;
-  size_t n_limit;
-  sdf_filter_params filter;
-  sdf_extend_params extend;
+// The uploads of a form that takes host arrays: every buffer reserved and its copy enqueued on `st`, in order; an entry of no
+// bytes is skipped (its buffer stays as it is).
+struct Upload {
+  DevBuf &buf;
+  const void *src;
+  size_t bytes;
 };
-struct PairHostWindow {
-  std::vector<sdf_search_pair_hit> reported;
-  int64_t attempted = 0, jaccard_failed = 0, interval_failed = 0;
-  std::vector<sdf_search_window> windows;  // scratch: nq records, of which the call fills its own
-  std::vector<sdf_search_pair_hit> hits;
-};
-int pair_host_window(const PairHostArgs &A, size_t i, std::vector<sdf_search_found> &found, PairHostWindow &W);
+inline int upload_all(sdf_ctx *ctx, hipStream_t st, std::initializer_list<Upload> uploads) {
+  for (const Upload &u : uploads) {
+    if (!u.bytes) continue;
+    SDF_HIP(u.buf.reserve(u.bytes));
+    SDF_HIP(hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, st));
+  }
+  return SDF_OK;
+}
 }  // namespace sdf

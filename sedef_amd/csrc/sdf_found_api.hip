@@ -1,22 +1,15 @@
-// The C ABI: search against the SDs already found (search_found.hip; include/sedef_hip.h states the rules) -- the bin index of
-// the found records, which sdf_search_windows_found* (sdf_search_api.hip) reads too, and is_overlap for every rolled interval.
-// sdf_search_overlap_host is the statement in plain C++: a linear pass over found[0, visible).
+// The C ABI: search against the SDs already found (search_found.hip; include/sedef_hip.h states the rules) -- the launches of
+// the bin index of the found records, which sdf_search_windows_found* (sdf_search_api.hip) reads too, and the device and
+// uploading forms of is_overlap for every rolled interval.  sdf_search_overlap_host, sdf_search_found_entries and the
+// checks: search_host.hip.
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
 
 #include "sdf_entry.h"
+#include "search_host.h"
 
 using namespace sdf;
-
-extern "C" int sdf_search_found_entries(const sdf_search_found *found, size_t nf, uint64_t *entries) {
-  if (!entries || (nf && !found)) return SDF_ERR_INVALID;
-  uint64_t n = 0;
-  for (size_t f = 0; f < nf; f++)
-    if (!found_empty(found[f])) n += (uint64_t)(found_bin((long long)found[f].q_end - 1) - found_bin(found[f].q_start) + 1);
-  *entries = n;
-  return SDF_OK;
-}
 
 namespace sdf {
 int found_scalars(size_t nf, size_t cap, const char **why) {
@@ -65,34 +58,6 @@ int found_index_need(sdf_ctx *ctx, size_t cap) {
 }  // namespace sdf
 
 namespace {
-// what every form of the overlap call checks of its scalars (n: the intervals, or the lanes of the device form)
-int overlap_scalars(size_t nq, size_t n, int32_t init_len, int32_t min_read_size, const char **why) {
-  if (init_len < 1) return *why = "search overlap: init_len < 1", SDF_ERR_INVALID;
-  if (min_read_size < 0) return *why = "search overlap: min_read_size < 0", SDF_ERR_INVALID;
-  if (init_len > (1 << 30)) return *why = "search overlap implements init_len up to 2^30", SDF_ERR_UNSUPPORTED;
-  if (nq > 0x3fffffffu) return *why = "search overlap: more than 2^30 - 1 query minimizers in one call", SDF_ERR_UNSUPPORTED;
-  if (n > 0x7fffffffu) return *why = "search overlap: more than 2^31 - 1 intervals in one call", SDF_ERR_UNSUPPORTED;
-  return SDF_OK;
-}
-// ... and the forms that take host arrays of those; *entries: the bin entries of the list
-int overlap_arrays(const sdf_minimizer *q, size_t nq, const uint64_t *first, const sdf_search_roll_rec *rolls, const sdf_search_found *found,
-                   size_t nf, const uint32_t *visible_iv, int32_t init_len, int32_t min_read_size, const uint32_t *out, uint64_t *entries,
-                   const char **why) {
-  if (!q || !first || (nf && !found)) return *why = "search overlap: invalid arguments", SDF_ERR_INVALID;
-  if (first[0] != 0) return *why = "search overlap: first[0] != 0", SDF_ERR_INVALID;
-  for (size_t i = 0; i < nq; i++)
-    if (first[i + 1] < first[i]) return *why = "search overlap: first[] does not ascend", SDF_ERR_INVALID;
-  const uint64_t n = first[nq];
-  if (int rc = overlap_scalars(nq, n > 0x7fffffffu ? (size_t)0x80000000u : (size_t)n, init_len, min_read_size, why)) return rc;
-  if (nf > 0x7fffffffu) return *why = "search found: more than 2^31 - 1 found records in one call", SDF_ERR_UNSUPPORTED;
-  if (n && (!rolls || !visible_iv || !out)) return *why = "search overlap: invalid arguments", SDF_ERR_INVALID;
-  for (uint64_t t = 0; t < n; t++)
-    if (visible_iv[t] > nf) return *why = "search found: a prefix longer than the list", SDF_ERR_INVALID;
-  sdf_search_found_entries(found, nf, entries);
-  if (*entries > 0x7fffffffu) return *why = "search found: more than 2^31 - 1 bin entries in one call", SDF_ERR_UNSUPPORTED;
-  return SDF_OK;
-}
-
 int overlap_launch(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const uint64_t *d_first, const sdf_search_roll_rec *d_rolls, size_t n,
                    const FoundIndex &F, int32_t init_len, int32_t min_read_size, uint32_t *d_out, sdf_filter_task *d_tasks, hipStream_t st) {
   if (F.nf == 0) {  // no record: every verdict is 0, and no task changes
@@ -106,25 +71,6 @@ int overlap_launch(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const uint
   return SDF_OK;
 }
 }  // namespace
-
-extern "C" int sdf_search_overlap_host(const sdf_minimizer *q, size_t nq, const uint64_t *first, const sdf_search_roll_rec *rolls,
-                                       const sdf_search_found *found, size_t nf, const uint32_t *visible_iv, int32_t init_len,
-                                       int32_t min_read_size, uint32_t *out) {
-  if (nq == 0) return SDF_OK;
-  const char *why = nullptr;
-  uint64_t entries = 0;
-  if (int rc = overlap_arrays(q, nq, first, rolls, found, nf, visible_iv, init_len, min_read_size, out, &entries, &why)) return rc;
-  for (size_t i = 0; i < nq; i++)
-    for (uint64_t t = first[i]; t < first[i + 1]; t++) {
-      const long long pf_pos = q[i].loc, pf_end = pf_pos + init_len, pfp_pos = rolls[t].ref_start, pfp_end = rolls[t].ref_end;
-      bool hit = false;
-      for (size_t f = 0; f < visible_iv[t] && !hit; f++)
-        hit = !found_empty(found[f]) && found_covers(found[f], pf_pos, pfp_pos) &&
-              found_overlaps(found[f], pf_pos, pf_end, pfp_pos, pfp_end, min_read_size);
-      out[t] = hit ? 1u : 0u;
-    }
-  return SDF_OK;
-}
 
 extern "C" int sdf_search_overlap_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, const uint64_t *d_first,
                                          const sdf_search_roll_rec *d_rolls, size_t n_max, const sdf_search_found *d_found, size_t nf,
@@ -162,20 +108,10 @@ extern "C" int sdf_search_overlap(sdf_ctx *ctx, const sdf_minimizer *q, size_t n
   if (n == 0) return SDF_OK;
   SDF_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  struct Copy {
-    DevBuf &buf;
-    const void *src;
-    size_t bytes;
-  } copies[] = {{ctx->fo_q, q, nq * sizeof(sdf_minimizer)},
-                {ctx->fo_first, first, (nq + 1) * 8},
-                {ctx->fo_rolls, rolls, n * sizeof(sdf_search_roll_rec)},
-                {ctx->fo_found, found, nf * sizeof(sdf_search_found)},
-                {ctx->fo_vis, visible_iv, n * 4}};
-  for (Copy &c : copies) {
-    if (!c.bytes) continue;
-    SDF_HIP(c.buf.reserve(c.bytes));
-    SDF_HIP(hipMemcpyAsync(c.buf.p, c.src, c.bytes, hipMemcpyHostToDevice, st));
-  }
+  if (int rc = upload_all(ctx, st, {{ctx->fo_q, q, nq * sizeof(sdf_minimizer)}, {ctx->fo_first, first, (nq + 1) * 8},
+                                   {ctx->fo_rolls, rolls, n * sizeof(sdf_search_roll_rec)}, {ctx->fo_found, found, nf * sizeof(sdf_search_found)},
+                                   {ctx->fo_vis, visible_iv, n * 4}}))
+    return rc;
   SDF_HIP(ctx->fo_out.reserve(n * 4));
   FoundIndex F{};
   if (int rc = found_index(ctx, (const sdf_search_found *)ctx->fo_found.p, nf, (size_t)entries, nullptr, (const uint32_t *)ctx->fo_vis.p, st, &F))

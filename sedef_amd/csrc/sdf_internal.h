@@ -7,6 +7,11 @@
 
 namespace sdf {
 
+// [off, off + len) lies inside [0, size) -- an empty range at `size` does -- without ever forming off + len (where that sum
+// cannot wrap, a task's 63-bit offset and 31-bit length, this is off + len <= size: what batch_host and batch_pairs asked before)
+inline bool in_range(uint64_t off, uint64_t len, uint64_t size) { return off <= size && len <= size - off; }
+inline bool in_range(int64_t off, int64_t len, size_t size) { return off >= 0 && len >= 0 && in_range((uint64_t)off, (uint64_t)len, (uint64_t)size); }
+
 // Scoring constants in the form the kernels consume (bytes of the int8 difference domain).
 struct ScoreK {
   int32_t q, e;        // gap open / extend as int8 values

@@ -1185,7 +1185,16 @@ int sdf_search_hit_tasks_device(sdf_ctx *ctx, const sdf_search_hit *d_hits, size
  * differ between forms and round sizes.  Refusals as for sdf_search_pair_host, ranges against sdf_pool_bytes(ctx); every check
  * precedes the first launch.  Overflow of out as for sdf_pool_minimizers.  The host form scans the whole found list per
  * interval and keeps a window record per query minimizer: a statement to compare with, not to time at chromosome size.
- * What remains of `sedef search`: the command line (FASTA reading, BED text, the -r coordinate flip of to_bed, -t translation). */
+ * What remains of `sedef search`: the command line (FASTA reading, BED text, the -r coordinate flip of to_bed, -t translation).
+ * The driver's own sizes: SDF_PAIR_ROUND_WINDOWS, the round of round_windows == 0; SDF_PAIR_INTERVALS_START and
+ * SDF_PAIR_ENTRIES_START, the intervals a round's arrays and the bin entries its index hold at a call's start (a short one is
+ * raised to twice the need); SDF_PAIR_LONG_MAX and SDF_PAIR_LONG_BATCH, the n_long_max and batch a round gives
+ * sdf_search_extend_long_device -- a round's further long growths leave their windows to the host. */
+#define SDF_PAIR_ROUND_WINDOWS 64
+#define SDF_PAIR_INTERVALS_START 4096
+#define SDF_PAIR_ENTRIES_START 4096
+#define SDF_PAIR_LONG_MAX 16
+#define SDF_PAIR_LONG_BATCH 8
 #define SDF_ACCEPT_MAX_KEPT 512
 #define SDF_ACCEPT_INCOMPLETE 0x1
 #define SDF_ACCEPT_OVERFLOW 0x2

@@ -105,8 +105,9 @@ extern "C" int sdf_search_accept(sdf_ctx *ctx, const sdf_search_accept_round *R,
 // ---- sdf_search_pair: the stages and the acceptance step in rounds, on the resident pool ----
 
 namespace {
-constexpr size_t kPairRoundWindows = 64;  // round_windows == 0; not measured (profiles/search_driver.py has the sweep)
-constexpr size_t kPairLongMax = 16, kPairLongBatch = 8;  // long growths a round finishes on the device; the host takes the rest
+constexpr size_t kPairRoundWindows = SDF_PAIR_ROUND_WINDOWS;  // round_windows == 0; not measured (profiles/search_driver.py has the sweep)
+// long growths a round finishes on the device; the host takes the rest
+constexpr size_t kPairLongMax = SDF_PAIR_LONG_MAX, kPairLongBatch = SDF_PAIR_LONG_BATCH;
 
 struct PairDriver {
   sdf_ctx *ctx;
@@ -121,7 +122,7 @@ struct PairDriver {
   std::string chars;  // both ranges as they lie in the pool, fetched when the host first completes a window
   PairHostWindow W;
   sdf_search_pair_stats S{0, 0, 0, 0, 0, 0, 0};
-  size_t cap_iv = 4096, ent_cap = 4096, found_cap = 0;
+  size_t cap_iv = SDF_PAIR_INTERVALS_START, ent_cap = SDF_PAIR_ENTRIES_START, found_cap = 0;
   const std::vector<sdf_minimizer> &r() const { return P.same_genome ? q : r_own; }
 };
 

@@ -89,6 +89,8 @@ ACCEPT_STATUS_DTYPE = np.dtype([("frontier", "<u4"), ("flags", "<u4"), ("nf", "<
 PAIR_STATS_DTYPE = np.dtype([(f, "<i8") for f in ("attempted", "jaccard_failed", "interval_failed", "rounds", "windows_run",
                                                   "windows_scheduled", "windows_host")])
 ACCEPT_MAX_KEPT, ACCEPT_INCOMPLETE, ACCEPT_OVERFLOW = 512, 0x1, 0x2
+# SDF_PAIR_*: the driver's default round, its two starting capacities, the long growths a round finishes on the device
+PAIR_ROUND_WINDOWS, PAIR_INTERVALS_START, PAIR_ENTRIES_START, PAIR_LONG_MAX, PAIR_LONG_BATCH = 64, 4096, 4096, 16, 8
 assert SEARCH_PAIR_HIT_DTYPE.itemsize == 24 and ACCEPT_STATUS_DTYPE.itemsize == 64 and PAIR_STATS_DTYPE.itemsize == 56
 FILTER_Q_RC, FILTER_R_RC, FILTER_SKIP = 1, 2, 4
 FILTER_UPPER_FAIL, FILTER_QGRAM_FAIL, FILTER_SHORT, FILTER_SKIPPED = 1, 2, 4, 8

@@ -188,6 +188,10 @@ def test_the_driver_is_the_host_form_for_every_round_size(eng, which, round_wind
     assert int(stats["rounds"]) >= 1 and int(stats["windows_run"]) >= int(stats["windows_scheduled"])
     if round_windows == 1:
         assert int(stats["rounds"]) + int(stats["windows_host"]) >= int(stats["windows_scheduled"])
+    # ... and exactly the rounds of the model, which needs no more than the starting capacities here
+    R = DM.rounds(ex(), hosted(which)[0], round_windows)
+    assert all(p[2] <= DM.PAIR_INTERVALS_START and p[3] <= DM.PAIR_ENTRIES_START for p in R["per_round"])
+    assert {f: int(stats[f]) for f in ("rounds", "windows_run", "windows_host")} == {f: R[f] for f in ("rounds", "windows_run", "windows_host")}
     _driven[(which, round_windows)] = {f: int(stats[f]) for f in stats.dtype.names}
 
 

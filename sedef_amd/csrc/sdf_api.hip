@@ -859,16 +859,26 @@ extern "C" void sdf_ksw_extz2(void * /*km*/, int qlen, const uint8_t *query, int
   }
 }
 
-// ---- planner without a device (not part of the public header; tests/test_planner.py) -------------------------------
+// ---- planner without a device (not part of the public header; tests/test_planner.py, tests/test_plan_same.py) ------
 // Cuts and plans a batch exactly like sdf_extz2_batch_device does (same code, same settings -- the environment's, like a
-// context made now would get --, same thread pool; no lane kernel: its records need a device) and reports, per input
-// task: chunk index (-1: not run), launch class (LaunchClass::code), nreg, kind (TaskKind), dir_off, cig_slot, partner
-// (index of the task it shares a wavefront with, -1 none), and per chunk {heavy, tasks, launches, dir_bytes, region
-// capacity}.
-extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want, size_t ws_budget,
-                              int max_dyn_lds, int nthreads, int64_t *per_task /* n x 7 */, int64_t *per_chunk /* cap x 5 */,
-                              size_t chunk_cap, size_t *nchunks) {
-  sdf_config dcfg;
+// context made now would get --, same thread pool).  The lane kernel's records need a device: `with_lane` gives the scan a
+// host array for them instead (PlanEnv::lane_recs; lane_ok as plan_env sets it), so that the lane branch of the scan and
+// the re-accounting of too few lane tasks are planned as well.
+namespace {
+struct DebugPlan {
+  sdf_config cfg;
+  std::vector<sdf_task> handed;
+  std::vector<LaneRec> lane_recs;
+  PlanEnv env;
+  BatchCut cut;
+  std::vector<PlanTask> plan;
+  std::vector<int32_t> order;
+  double ms = 0;  // cut + chunk planning
+};
+
+int debug_plan_run(DebugPlan &d, const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want, size_t ws_budget,
+                   int max_dyn_lds, int nthreads, bool with_lane) {
+  sdf_config &dcfg = d.cfg;
   {
     char why[256];
     if (sdf_config_from_env(&dcfg, why, sizeof why) != SDF_OK) return SDF_ERR_INVALID;
@@ -877,7 +887,7 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
   ScoreK sk;
   if (int rc = make_scorek(&tmp, sc, sk)) return rc;
   // Tasks as sdf_extz2_batch_pairs takes them may carry strand bits: the planner gets the flag word that call hands over
-  std::vector<sdf_task> handed;
+  std::vector<sdf_task> &handed = d.handed;
   for (size_t k = 0; k < n; ++k)
     if (tasks[k].flag & kStrandBits) {
       handed.assign(tasks, tasks + n);
@@ -885,12 +895,17 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
       tasks = handed.data();
       break;
     }
-  const PlanEnv env = plan_env(dcfg, sc, tasks, n, want, max_dyn_lds);
-  BatchCut cut;
+  d.env = plan_env(dcfg, sc, tasks, n, want, max_dyn_lds);
+  if (with_lane && d.env.lane_ok) {
+    d.lane_recs.assign(n, LaneRec());
+    d.env.lane_recs = d.lane_recs.data();
+  }
+  const PlanEnv &env = d.env;
+  BatchCut &cut = d.cut;
   const char *msg = nullptr;
   const auto tc0 = std::chrono::steady_clock::now();
-  std::vector<PlanTask> plan;
-  std::vector<int32_t> order;
+  std::vector<PlanTask> &plan = d.plan;
+  std::vector<int32_t> &order = d.order;
   // SDF_DEBUG_PLAN_EARLY=1: the cut in two passes with the early start of the heavy chunks (batch_part's, minus the
   // device): buffers by their upper bounds, the heavy chunks planned from the callback
   PlanScratch early_scratch;
@@ -922,11 +937,28 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
     ChunkPlanner planner(env, cut, plan.data(), order.data(), &pool, nthreads, cut.n_early);
     for (size_t ci = cut.n_early; ci < cut.chunks.size(); ++ci) planner.wait(ci);
   }
+  d.ms = ms_since(tc0);
+  for (const ChunkPlan &c : cut.chunks)
+    if (c.err) return SDF_ERR_INVALID;
+  return SDF_OK;
+}
+}  // namespace
+
+// Reports, per input task: chunk index (-1: not run), launch class (LaunchClass::code), nreg, kind (TaskKind), dir_off,
+// cig_slot, partner (index of the task it shares a wavefront with, -1 none), and per chunk {heavy, tasks, launches,
+// dir_bytes, region capacity}.  No lane kernel.
+extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want, size_t ws_budget,
+                              int max_dyn_lds, int nthreads, int64_t *per_task /* n x 7 */, int64_t *per_chunk /* cap x 5 */,
+                              size_t chunk_cap, size_t *nchunks) {
+  DebugPlan d;
+  if (int rc = debug_plan_run(d, sc, tasks, n, want, ws_budget, max_dyn_lds, nthreads, false)) return rc;
+  const BatchCut &cut = d.cut;
+  const std::vector<PlanTask> &plan = d.plan;
+  const std::vector<int32_t> &order = d.order;
   for (size_t k = 0; k < n * 7; ++k) per_task[k] = -1;
   *nchunks = cut.chunks.size();
   for (size_t ci = 0; ci < cut.chunks.size(); ++ci) {
     const ChunkPlan &c = cut.chunks[ci];
-    if (c.err) return SDF_ERR_INVALID;
     if (ci < chunk_cap) {
       int64_t *o = per_chunk + 5 * ci;
       o[0] = c.heavy;
@@ -962,6 +994,80 @@ extern "C" int sdf_debug_plan(const sdf_scoring *sc, const sdf_task *tasks, size
       }
     }
   }
+  return SDF_OK;
+}
+
+// The whole plan, as the launcher reads it, in six digests: [0] the cut's figures with heavy_idx and the runnable tasks'
+// bound[] and cap[], [1] every PlanTask field by field, [2] order[0 .. order_total), [3] the chunks, [4] their launches,
+// [5] the lane figures, lane[] and the lane records.  `dump_path` (optional): every word that goes into the digests, in
+// that order, as 64-bit words into a file -- to find where two plans part.  `plan_ms` (optional): cut + chunk planning.
+extern "C" int sdf_debug_plan_dump(const sdf_scoring *sc, const sdf_task *tasks, size_t n, uint32_t want, size_t ws_budget,
+                                   int max_dyn_lds, int nthreads, int with_lane, uint64_t *digest /* 6 */,
+                                   const char *dump_path, double *plan_ms) {
+  DebugPlan d;
+  if (int rc = debug_plan_run(d, sc, tasks, n, want, ws_budget, max_dyn_lds, nthreads, with_lane != 0)) return rc;
+  if (plan_ms) *plan_ms = d.ms;
+  const BatchCut &cut = d.cut;
+  if (cut.bound.size() < n || cut.cap.size() < n || d.order.size() < cut.order_total) return SDF_ERR_INVALID;
+  FILE *f = dump_path ? fopen(dump_path, "wb") : nullptr;
+  if (dump_path && !f) return SDF_ERR_INVALID;
+  uint64_t h = 0;
+  auto add = [&](uint64_t v) {
+    h = (h ^ v) * 0x9E3779B97F4A7C15ull;
+    h ^= h >> 29;
+    if (f) fwrite(&v, 8, 1, f);
+  };
+  auto close = [&](int section) {
+    digest[section] = h;
+    h = (uint64_t)section + 1;
+    add(~0ull);  // (dump: a section mark)
+  };
+  for (uint64_t v : {(uint64_t)cut.pipelined, (uint64_t)cut.split_heavy, (uint64_t)cut.nch, (uint64_t)cut.max_regions,
+                     (uint64_t)cut.nreg_ws, (uint64_t)cut.n_heavy, (uint64_t)cut.region_need, (uint64_t)cut.heavy_need,
+                     (uint64_t)cut.stage_total, (uint64_t)cut.ntask_total, (uint64_t)cut.order_total, (uint64_t)cut.stage_upper,
+                     (uint64_t)cut.order_upper, (uint64_t)cut.n_early, (uint64_t)cut.chunks.size(), (uint64_t)cut.heavy_idx.size()})
+    add(v);
+  for (uint32_t k : cut.heavy_idx) add(k);
+  for (uint8_t b : cut.heavy) add(b);
+  for (size_t k = 0; k < n; ++k)
+    if (plan_detail::task_runs(d.env.tasks[k], d.env.degenerate)) add(((uint64_t)cut.bound[k] << 32) | cut.cap[k]);
+  close(0);
+  for (const ChunkPlan &c : cut.chunks) {
+    if (c.pb + c.cnt > d.plan.size()) return SDF_ERR_INVALID;
+    for (size_t k = 0; k < c.cnt; ++k) {
+      const PlanTask &p = d.plan[c.pb + k];
+      for (int64_t v : {p.q_word, p.t_word, p.dir_off, p.cig_slot, (int64_t)p.qlen, (int64_t)p.tlen, (int64_t)p.w, (int64_t)p.zdrop,
+                        (int64_t)p.flag, (int64_t)p.ncol16, (int64_t)p.out_idx, (int64_t)p.cig_cap, (int64_t)p.nreg, (int64_t)p.kind})
+        add((uint64_t)v);
+    }
+  }
+  close(1);
+  for (size_t k = 0; k < cut.order_total; ++k) add((uint32_t)d.order[k]);
+  close(2);
+  for (const ChunkPlan &c : cut.chunks)
+    for (uint64_t v : {(uint64_t)c.s, (uint64_t)c.e, (uint64_t)c.heavy, (uint64_t)c.pb, (uint64_t)c.ob, (uint64_t)c.order_cap,
+                       (uint64_t)c.stage0, (uint64_t)c.ntask, (uint64_t)c.stage_words, (uint64_t)c.cnt, (uint64_t)c.nord,
+                       (uint64_t)c.layouts, (uint64_t)c.paired, (uint64_t)c.dir_bytes, (uint64_t)c.launches.size()})
+      add(v);
+  close(3);
+  for (const ChunkPlan &c : cut.chunks)
+    for (const Launch &L : c.launches) {
+      uint64_t est;
+      memcpy(&est, &L.est, 8);
+      for (uint64_t v : {(uint64_t)L.lc.fam, (uint64_t)L.lc.nreg, (uint64_t)L.lc.stream, (uint64_t)L.lc.block, (uint64_t)L.lds,
+                         (uint64_t)L.off, (uint64_t)L.cnt, (uint64_t)(int64_t)L.rmax, est})
+        add(v);
+    }
+  close(4);
+  for (uint64_t v : {(uint64_t)cut.use_lane, (uint64_t)cut.n_lane, (uint64_t)cut.lane_cls[0], (uint64_t)cut.lane_cls[1],
+                     (uint64_t)cut.lane_cls[2], (uint64_t)cut.lane_cls[3], (uint64_t)cut.lane_stage_words, (uint64_t)cut.lane_dir_bytes})
+    add(v);
+  for (size_t k = 0; k < std::min(n, cut.lane.size()); ++k) add(cut.lane[k]);
+  for (const LaneRec &r : d.lane_recs)
+    for (uint64_t v : {(uint64_t)r.q_word, (uint64_t)r.t_word, (uint64_t)r.out_idx, (uint64_t)r.qlen_m1, (uint64_t)r.tlen_m1, (uint64_t)r.flag})
+      add(v);
+  close(5);
+  if (f) fclose(f);
   return SDF_OK;
 }
 

@@ -1185,7 +1185,8 @@ int sdf_search_hit_tasks_device(sdf_ctx *ctx, const sdf_search_hit *d_hits, size
  * differ between forms and round sizes.  Refusals as for sdf_search_pair_host, ranges against sdf_pool_bytes(ctx); every check
  * precedes the first launch.  Overflow of out as for sdf_pool_minimizers.  The host form scans the whole found list per
  * interval and keeps a window record per query minimizer: a statement to compare with, not to time at chromosome size.
- * What remains of `sedef search`: the command line (FASTA reading, BED text, the -r coordinate flip of to_bed, -t translation).
+ * The command line above it (FASTA reading, BED text, the -r coordinate flip of to_bed, -t translation) is `sedef search`,
+ * host/search_cmd.cc; it calls the indexed form below.
  * The driver's own sizes: SDF_PAIR_ROUND_WINDOWS, the round of round_windows == 0; SDF_PAIR_INTERVALS_START and
  * SDF_PAIR_ENTRIES_START, the intervals a round's arrays and the bin entries its index hold at a call's start (a short one is
  * raised to twice the need); SDF_PAIR_LONG_MAX and SDF_PAIR_LONG_BATCH, the n_long_max and batch a round gives
@@ -1244,6 +1245,62 @@ int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_mini
 int sdf_search_pair_host(const char *pool, size_t pool_bytes, const sdf_minim_range *q_range, const sdf_minim_range *r_range,
                          const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
                          sdf_search_pair_stats *stats);
+
+/* ---- the resident search index: a range's minimizers and index ONCE, for every pair that names the range ------------------
+ * The reference's search_single builds one Index per (chromosome, strand) and reuses it for every pair
+ * (src/search_main.cc:155-168); sdf_search_pair computes both ranges' minimizers and the reference's index in every call.
+ * A handle holds, for one range of the resident pool (SDF_MINIM_RC honoured) and one (k, w, separate_lowercase): the
+ * records of sdf_pool_minimizers in ascending loc and those of sdf_pool_minimizer_index with n_groups and threshold, each
+ * computed once by those two calls as they are; their device copies in HBM buffers of the handle's own (not the context's
+ * per-call dr_q / dr_r / dr_rs), and the host copies the driver's schedule and host step read.
+ *   sdf_search_index_build   checks and refusals are those of the two calls it makes, before the first launch; *out is NULL
+ *                            after a failure.  Returns after the copies have reached HBM.
+ *   sdf_search_index_free    frees the device and host copies.  NULL is SDF_OK.  Handles are recognised by ADDRESS, in the
+ *                            context's list of live ones: a pointer that is not in that list (another context's handle, one
+ *                            already freed) is SDF_ERR_INVALID and is not read -- in every call that takes a handle.  That is
+ *                            all an address can tell: once a later sdf_search_index_build has returned the same address, a
+ *                            stale copy of the freed pointer names the NEW handle.  Using a handle after freeing it is the
+ *                            caller's error, as with any freed pointer; the check catches it only until the address is reused.
+ *   LIFETIME, the one rule   a handle belongs to the context that built it.  sdf_destroy(ctx) frees every handle of ctx that
+ *                            is still live; after it those pointers are dead like ctx itself and must not be passed to any call,
+ *                            sdf_search_index_free included.  Nothing leaks, and nothing is freed twice by a caller that frees
+ *                            each handle at most once before the context goes.  sdf_device_bytes(ctx) counts the handles' buffers.
+ *   the pool                 a handle names bases by pool offset.  Appending to the pool (sdf_pool_append_fasta, reset == 0)
+ *                            keeps every handle valid, although the pool may move.  Replacing it -- sdf_pool_upload,
+ *                            sdf_pool_append_fasta(reset != 0), an anchors call with a host seq_pool, sdf_pool_share on this
+ *                            context, a view dropped -- makes the context's handles STALE: sdf_search_pair_indexed refuses them,
+ *                            sdf_search_index_info reports stale = 1, and all that remains is to free them.  A context that views
+ *                            another's pool builds handles of its own; the owner's are not its.
+ *   sdf_search_index_info    the range, k, w, separate_lowercase, the threshold, the records of both lists, n_groups, stale, and
+ *                            the device bytes the handle holds.  sdf_search_index_builds: the handles this context has built since
+ *                            it was made; sdf_search_index_live: those not yet freed.
+ * sdf_search_pair_indexed: the driver of sdf_search_pair on two handles; out, *used and the three counters equal what
+ * sdf_search_pair writes for (q's range, r's range, params), byte for byte, for every round_windows.  The query side reads q's
+ * loc-ordered list; the reference side r's loc-ordered list, r's index and r's threshold.  One handle may be the query of one
+ * call and the reference of the next, and both sides of one call; a call writes nothing into a handle's arrays -- first[] and
+ * the window records of a call (search_accept_tail_kernel, sdf_search_windows_found_device) lie in the context's per-call
+ * buffers.  Before the first launch:
+ *   SDF_ERR_INVALID      a null pointer (out may be null with cap == 0); q or r not a live handle of ctx; a stale handle;
+ *                        params->k, w or separate_lowercase (as 0 / not 0) different from a handle's; same_genome with q != r
+ *                        (same_genome names ONE handle, on the forward strand); then every refusal of sdf_search_pair on the
+ *                        handles' ranges, with its code.
+ * Calls on one context do not overlap, as for sdf_search_pair. */
+typedef struct sdf_search_index sdf_search_index;
+typedef struct {
+  sdf_minim_range range;
+  int32_t k, w, separate_lowercase;
+  uint32_t threshold;
+  uint64_t n_minimizers, n_sorted;
+  uint32_t n_groups, stale;
+  uint64_t device_bytes;
+} sdf_search_index_desc; /* 64 bytes */
+int sdf_search_index_build(sdf_ctx *ctx, const sdf_minim_range *range, int k, int w, int separate_lowercase, sdf_search_index **out);
+int sdf_search_index_free(sdf_ctx *ctx, sdf_search_index *index);
+int sdf_search_index_info(const sdf_ctx *ctx, const sdf_search_index *index, sdf_search_index_desc *info);
+long long sdf_search_index_builds(const sdf_ctx *ctx);
+size_t sdf_search_index_live(const sdf_ctx *ctx);
+int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                            sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats);
 
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is

@@ -98,32 +98,7 @@ std::vector<Hit> merge_hits(std::vector<Hit> &hits, int merge_dist) {
   return merged;
 }
 
-// chromosomes by (length, name) descending, packed greedily into groups of at most 100 MB
-std::vector<std::vector<std::string>> generate_translation(const std::string &ref_path) {  // src/search_main.cc:93-120
-  std::ifstream fai((ref_path + ".fai").c_str());
-  if (!fai.is_open()) throw "Index file " + ref_path + ".fai does not exist";
-  std::map<std::string, std::pair<size_t, std::string>> by_key;  // first token of the name -> (length, full name)
-  for (std::string line; std::getline(fai, line);) {
-    const auto f = split(line, '\t');
-    if (f.size() != 5) throw "Index file " + ref_path + ".fai is malformed";
-    by_key.insert({split(f[0], ' ').at(0), {(size_t)atoi(f[1].c_str()), f[0]}});
-  }
-  std::vector<std::pair<size_t, std::string>> chroms;
-  for (auto &e : by_key) chroms.push_back(e.second);
-  std::sort(chroms.begin(), chroms.end(), std::greater<std::pair<size_t, std::string>>());
-  std::vector<std::vector<std::string>> groups;
-  int filled = 0;  // (an int in the reference as well)
-  for (auto &c : chroms) {
-    if (groups.empty() || filled + c.first > (size_t)(100 * 1000 * 1000)) {
-      groups.push_back({c.second});
-      filled = (int)c.first;
-    } else {
-      groups.back().push_back(c.second);
-      filled += (int)c.first;
-    }
-  }
-  return groups;
-}
+// (generate_translation, the chromosome groups of `-t`: search_cmd.cc)
 
 static std::vector<std::string> seed_files(const std::string &path) {  // src/align_main.cc:44-62
   struct stat st;

@@ -579,4 +579,64 @@ int sdfh_sequence(const char *name, const char *seq, int is_rc, char *buf, size_
   return copy_out(s.name + "|" + s.seq + "|" + (s.is_rc ? "1" : "0"), buf, cap);
 }
 
+// ---- `sedef search` (search_cmd.cc) ----
+// the BED line of a search hit; ref_len: the reference record's length (read under ref_rc alone)
+int sdfh_search_hit_bed(const char *qname, const char *rname, int qs, int qe, int rs, int re, int ref_rc, long long ref_len, char *buf,
+                        size_t cap) {
+  return copy_out(search_hit_bed(qname, rname, qs, qe, rs, re, ref_rc != 0, (size_t)ref_len), buf, cap);
+}
+
+// limit[1 .. n] of (k, max_error, max_edit_error) into out[0, n): walk != 0 by the loop as the reference writes it
+int sdfh_limit_table(int kmer, double max_error, double max_edit_error, int n, int walk, int *out) {
+  for (int s = 1; s <= n; s++)
+    out[s - 1] = walk ? relaxed_jaccard_estimate_walk(s, kmer, max_error, max_edit_error) : relaxed_jaccard_estimate(s, kmer, max_error, max_edit_error);
+  return 0;
+}
+
+// --limit-table parsing: the entries (limit[0] = 0 first) into out[0, cap); returns their number, or -1 with the refusal
+int sdfh_read_limit_table(const char *path, int *out, int cap) {
+  try {
+    const std::vector<int32_t> t = read_limit_table(path);
+    for (size_t i = 0; i < t.size() && (int)i < cap; i++) out[i] = t[i];
+    return (int)t.size();
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  }
+}
+
+// the groups of `-t` over the records of genome.fa.fai at a group limit: "name, name|name|..." (groups separated by '|')
+int sdfh_translation(const char *ref_path, int max_size, char *buf, size_t cap) {
+  try {
+    std::string out;
+    for (auto &g : generate_translation(ref_path, max_size)) {
+      if (!out.empty()) out += "|";
+      for (size_t i = 0; i < g.size(); i++) out += (i ? "," : "") + g[i];
+    }
+    return copy_out(out, buf, cap);
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  }
+}
+
+// the arguments behind `sedef search`, separated by newlines -> "k w u e E g min_read_size transform reverse|limit table|pos..."
+int sdfh_search_args(const char *args, char *buf, size_t cap) {
+  try {
+    std::vector<std::string> a = split(args, '\n');
+    std::vector<char *> argv;
+    for (auto &s : a) argv.push_back(&s[0]);
+    const SearchParams p = parse_search_args((int)argv.size(), argv.data());
+    char head[256];
+    snprintf(head, sizeof head, "%d %d %d %.17g %.17g %.17g %d %d %d", p.kmer_size, p.window_size, p.min_uppercase, p.max_error, p.max_edit_error,
+             p.gap_frequency, p.min_read_size, (int)p.transform, (int)p.reverse);
+    std::string out = std::string(head) + "|" + p.limit_table;
+    for (auto &s : p.pos) out += "|" + s;
+    return copy_out(out, buf, cap);
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  }
+}
+
 }  // extern "C"

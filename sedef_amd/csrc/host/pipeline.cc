@@ -1103,6 +1103,7 @@ StageSettings StageSettings::from_env() {
   s.resident_dp = num("SDF_RESIDENT_DP", 0, 1, 1) != 0;
   s.anchor_parts = (int)num("SDF_ANCHOR_PARTS", 0, 16, 0);
   s.bucket_lanes = (int)num("SDF_BUCKET_LANES", 1, 4, 2);
+  s.translate_limit = (int)num("SDF_TEST_TRANSLATE_LIMIT", 1, 0x7fffffff, 100 * 1000 * 1000);
   s.stats_resident = num("SDF_STATS_RESIDENT", 0, 1, 0) != 0;
   s.stats_cuts_device = num("SDF_STATS_CUTS_DEVICE", 0, 1, 0) != 0;
   s.stage_resident = num("SDF_STAGE_RESIDENT", 0, 1, 0) != 0;

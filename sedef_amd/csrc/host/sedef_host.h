@@ -505,7 +505,46 @@ struct BucketParams {  // Globals::Extend (src/globals.cc:32-34)
   int merge_dist = 250;
 };
 std::vector<Hit> merge_hits(std::vector<Hit> &hits, int merge_dist);
+// the groups of `-t` (src/search_main.cc:93-120; search_cmd.cc): records by (length, name) descending, a new group when the
+// running sum -- an int, as there -- would exceed max_size (the reference's 100 MB in the one-argument form)
+std::vector<std::vector<std::string>> translation_groups(std::vector<std::pair<size_t, std::string>> records, int max_size);
+std::vector<std::vector<std::string>> generate_translation(const std::string &ref_path, int max_size);
 std::vector<std::vector<std::string>> generate_translation(const std::string &ref_path);
+
+// ---- `sedef search` / `sedef translate` (reference: src/search_main.cc, src/util.cc:52-113; search_cmd.cc) ------------------
+// tau, solve_inverse_jaccard and relaxed_jaccard_estimate without Boost; MAX_ERROR / MAX_EDIT_ERROR are arguments, not globals.
+double search_tau(double edit_error, int kmer_size, double max_error, double max_edit_error);
+double solve_inverse_jaccard(double j, int kmer_size, double max_error, double max_edit_error);
+int binomial_upper_quantile(int s, double p, double q);  // smallest x with P(X <= x) >= 1 - q, X ~ Binomial(s, p)
+int relaxed_jaccard_estimate_walk(int s, int kmer_size, double max_error, double max_edit_error);  // the loop as written there
+int relaxed_jaccard_estimate(int s, int kmer_size, double max_error, double max_edit_error);       // the same value, by bisection
+// limit[s] = relaxed_jaccard_estimate(s), memoised for one (k, MAX_ERROR, MAX_EDIT_ERROR) and grown on demand; limit[0] = 0
+class LimitTable {
+ public:
+  LimitTable(int kmer_size, double max_error, double max_edit_error)
+      : kmer_size_(kmer_size), max_error_(max_error), max_edit_error_(max_edit_error) {}
+  const std::vector<int32_t> &upto(size_t n);  // at least n entries
+ private:
+  int kmer_size_;
+  double max_error_, max_edit_error_;
+  std::vector<int32_t> table_;
+};
+// --limit-table FILE: one integer per line, line s (from 1) = limit[s]; throws on anything else, on a value below 1, on no line
+std::vector<int32_t> read_limit_table(const std::string &path);
+struct SearchParams {  // defaults: src/globals.cc
+  int kmer_size = 12, window_size = 16, min_uppercase = 12;
+  double max_error = 0.30, max_edit_error = 0.15, gap_frequency = 0.005;
+  int min_read_size = 700;  // (int)(KB * (1 - MAX_ERROR)), set by parse_search_args
+  int max_sd_size = 1 << 20, uppercase_seeds = 1, separate_lowercase = 1;
+  bool transform = false, reverse = false;
+  std::string limit_table;
+  std::vector<std::string> pos;  // genome.fa query ref
+};
+SearchParams parse_search_args(int argc, char **argv);  // the arguments behind `sedef search`
+std::string search_hit_bed(const std::string &qname, const std::string &rname, int qs, int qe, int ref_start, int ref_end, bool ref_rc,
+                           size_t ref_len);
+int search_command(const SearchParams &p, FILE *out, FILE *log);
+int translate_command(const std::string &ref_path, FILE *out, FILE *log);
 void bucket_alignments_extern(const std::string &bed_path, int nbins, const std::string &output_dir, bool extend,
                               const std::string &reference, const BucketParams &bp, FILE *log);
 
@@ -529,6 +568,7 @@ struct StageSettings {
   bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
   bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise
   int bucket_lanes = 2;      // SDF_BUCKET_LANES: buckets of a several-bucket run in flight, each on a device context of its own (1: one after the other)
+  int translate_limit = 100 * 1000 * 1000;  // SDF_TEST_TRANSLATE_LIMIT: TEST ONLY -- the size at which `search -t` / `translate` start a new group (the reference's 100 MB)
   static StageSettings from_env();
 };
 const StageSettings &stage_settings();             // the current run's

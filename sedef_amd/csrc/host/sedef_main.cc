@@ -128,8 +128,22 @@ int main(int argc, char **argv) {
               "  the per-alignment table of the final calls (--max-ok-gap, --min-split, --uppercase, --max-error)\n"
               "  SDF_STATS_CUTS_DEVICE=1 (default 0; only with SDF_STATS_RESIDENT=1 and without --max-ok-gap): the match counter,\n"
               "  the cuts at assembly gaps and the trims run on the resident chromosomes too (same output)\n"
-              "Other SEDEF stages (search, stats diff, translate) are not part of this build.\n");
+              "sedef search [-k kmer] [-w window] [-u uppercase] [-e error] [-E edit-error] [-g gap-freq] [-r] [-t] [genome.fa] [query] [ref]\n"
+              "  the seed SDs of chromosome [query] against [ref] (BED on stdout); -r/--reverse: [ref] reverse-complemented;\n"
+              "  -t/--transform: [query] and [ref] are group numbers of `sedef translate`, every chromosome of the one group\n"
+              "  against every one of the other.  Chromosomes are uploaded once and indexed once per strand.\n"
+              "  --limit-table FILE: one integer per line, line s (from 1) = relaxed_jaccard_estimate(s); replaces the table this\n"
+              "  build computes without Boost.  On stderr: the parameters, the totals and the attempts / Jaccard / interval fail\n"
+              "  counters; the reference's lowercase and q-grams counters are not kept.\n"
+              "sedef translate [genome.fa]\n"
+              "  the chromosome groups of -t on stderr, their number on stdout\n"
+              "  SDF_TEST_TRANSLATE_LIMIT (tests only): the group size limit in bases instead of 100 MB\n"
+              "Other SEDEF stages (stats diff) are not part of this build.\n");
       return 0;
+    } else if (command == "search") {
+      return search_command(parse_search_args(argc - 2, argv + 2), stdout, stderr);
+    } else if (command == "translate") {
+      return translate_command(argv[2], stdout, stderr);
     } else if (command == "align") {
       Args a(argc - 2, argv + 2);
       Params p;

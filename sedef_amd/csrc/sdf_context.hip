@@ -172,6 +172,7 @@ static void drop_view_locked(sdf_ctx *v) {
   }
   v->an_pool.drop_borrow();
   v->pool_bytes = 0;
+  v->pool_epoch += 1;
 }
 
 int pool_writable(sdf_ctx *ctx, bool keep_view) {
@@ -217,6 +218,7 @@ extern "C" int sdf_pool_share(sdf_ctx *dst, const sdf_ctx *src_c) {
   drop_view_locked(dst);  // (a view of another owner, if it held one)
   dst->an_pool.borrow(src->an_pool.p, src->an_pool.cap);
   dst->pool_bytes = src->pool_bytes;
+  dst->pool_epoch += 1;
   dst->view_of = src;
   src->views.push_back(dst);
   return SDF_OK;
@@ -234,6 +236,11 @@ extern "C" void sdf_destroy(sdf_ctx *ctx) {
     while (!ctx->views.empty()) drop_view_locked(ctx->views.back());
   }
   for (auto ev : ctx->events) (void)hipEventDestroy(ev);
+  for (sdf_search_index *h : ctx->indexes) {  // (the handles still live go with their context: include/sedef_hip.h)
+    h->d_loc.release(), h->d_sorted.release();
+    delete h;
+  }
+  ctx->indexes.clear();
   for_each_device_buffer(ctx, [](DevBuf &b) { b.release(); });
   for_each_host_buffer(ctx, [](HostBuf &b) { b.release(); });
   if (ctx->rerun_ctx) sdf_destroy(ctx->rerun_ctx);
@@ -372,6 +379,7 @@ extern "C" size_t sdf_device_bytes(const sdf_ctx *ctx) {
   if (!ctx) return 0;
   size_t sum = 0;
   for_each_device_buffer(ctx, [&](const DevBuf &b) { sum += b.held_bytes(); });
+  for (const sdf_search_index *h : ctx->indexes) sum += h->d_loc.held_bytes() + h->d_sorted.held_bytes();
   if (ctx->part_ctx) sum += sdf_device_bytes(ctx->part_ctx);
   if (ctx->rerun_ctx) sum += sdf_device_bytes(ctx->rerun_ctx);
   return sum;

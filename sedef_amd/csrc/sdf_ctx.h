@@ -364,6 +364,19 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(host_fetch) /* sdf_pool_fetch_ranges: a piece's output on its way back, its records behind it on their way up */  \
   X(host_an) /* pinned staging of the anchors call's output (sdf_reserve with SDF_RESERVE_ANCHORS; a pageable copy runs at ~3 GB/s) */
 
+// A resident search index (include/sedef_hip.h: sdf_search_index_build): one range's minimizers in ascending loc and its sorted
+// index, on the host (the driver's schedule and host step) and in HBM, in buffers of its own.  Its context lists it and frees
+// it with itself; pool_epoch: the context's when the handle was built -- a pool replaced since then makes the handle stale.
+struct sdf_search_index {
+  sdf_ctx *ctx = nullptr;
+  uint64_t pool_epoch = 0;
+  sdf_minim_range range{0, 0, 0};
+  int k = 0, w = 0, separate_lowercase = 0;
+  uint32_t threshold = 0x80000000u, n_groups = 0;
+  std::vector<sdf_minimizer> loc, sorted;
+  DevBuf d_loc, d_sorted;
+};
+
 struct sdf_ctx {
   sdf_config cfg;  // the context's settings, fixed when it is made (sdf_config.hip): every setting is read from here
   int device = 0;
@@ -382,6 +395,9 @@ struct sdf_ctx {
 #undef X
   std::vector<sdf_task> host_tasks;  // the task array of the host-buffer entry point with word offsets
   size_t pool_bytes = 0;   // characters resident in an_pool (sdf_pool_upload / sdf_anchors_batch): what sdf_extz2_batch_pairs may name
+  uint64_t pool_epoch = 0; // grows whenever the pool is REPLACED (an upload, a reset, a view taken or dropped), not when it is appended to
+  std::vector<sdf_search_index *> indexes;  // the live handles of sdf_search_index_build (sdf_driver_api.hip); sdf_destroy frees them
+  long long index_builds = 0;               // sdf_search_index_build calls that returned a handle
   long long lane_tasks = 0;   // tasks of the last batch call the lane kernel took
   // sdf_last_chain_classes: pairs of the last sdf_chain_batch per launch class -- [0..5] the LDS classes of chain_wave_kernel,
   // [6] chain_kernel --, [7] the LDS cap of class 5 in bytes (fixed in sdf_create: what the kernel was granted there)

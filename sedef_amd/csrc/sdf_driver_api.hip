@@ -1,6 +1,7 @@
 // The C ABI: the search driver (include/sedef_hip.h states the rules) -- the device and uploading forms of a round's
 // acceptance step (search_accept.hip) with their launches, and sdf_search_pair, the stages and the acceptance step in rounds
-// on the resident pool.  sdf_search_accept_host, sdf_search_pair_host, the window that sdf_search_pair hands to the host
+// on the resident pool; the resident search index (sdf_search_index_*) and sdf_search_pair_indexed, the same rounds on two
+// handles.  sdf_search_accept_host, sdf_search_pair_host, the window that sdf_search_pair hands to the host
 // (pair_host_window) and the checks: search_host.hip.
 #include <hip/hip_runtime.h>
 
@@ -115,7 +116,10 @@ struct PairDriver {
   const sdf_search_pair_params &P;
   const sdf_extend_params E;  // P.extend as the stages take it
   sdf_minim_range Q, R;
-  std::vector<sdf_minimizer> q, r_own, r_sorted;
+  // the query's minimizers and the reference's (the query's own under same_genome) in ascending loc, the reference's index:
+  // the host's copies and the device's -- the call's own (sdf_search_pair) or two handles' (sdf_search_pair_indexed)
+  const std::vector<sdf_minimizer> *q = nullptr, *r_loc = nullptr, *r_sorted = nullptr;
+  const sdf_minimizer *d_q = nullptr, *d_r = nullptr, *d_rs = nullptr;
   uint32_t threshold = 0x80000000u;
   std::vector<sdf_search_found> found;  // the host's mirror of the device list
   std::vector<sdf_search_pair_hit> out;
@@ -123,23 +127,24 @@ struct PairDriver {
   PairHostWindow W;
   sdf_search_pair_stats S{0, 0, 0, 0, 0, 0, 0};
   size_t cap_iv = SDF_PAIR_INTERVALS_START, ent_cap = SDF_PAIR_ENTRIES_START, found_cap = 0;
-  const std::vector<sdf_minimizer> &r() const { return P.same_genome ? q : r_own; }
+  const std::vector<sdf_minimizer> &r() const { return *r_loc; }
 };
 
-int pair_minimizers(sdf_ctx *ctx, const sdf_minim_range &range, const sdf_search_pair_params &P, bool index, std::vector<sdf_minimizer> &out,
-                    uint32_t *threshold) {
+int pair_minimizers(sdf_ctx *ctx, const sdf_minim_range &range, int k, int w, int separate_lowercase, bool index, std::vector<sdf_minimizer> &out,
+                    uint32_t *threshold, uint32_t *n_groups = nullptr) {
   uint64_t first[2] = {0, 0};
   uint32_t groups = 0, thr = 0;
   size_t used = 0;
   for (int pass = 0; pass < 2; pass++) {
-    const int rc = index ? sdf_pool_minimizer_index(ctx, &range, 1, P.k, P.w, P.separate_lowercase, first, out.data(), out.size(), &used, &groups, &thr)
-                         : sdf_pool_minimizers(ctx, &range, 1, P.k, P.w, P.separate_lowercase, first, out.data(), out.size(), &used);
+    const int rc = index ? sdf_pool_minimizer_index(ctx, &range, 1, k, w, separate_lowercase, first, out.data(), out.size(), &used, &groups, &thr)
+                         : sdf_pool_minimizers(ctx, &range, 1, k, w, separate_lowercase, first, out.data(), out.size(), &used);
     if (rc == SDF_OK) break;
     if (rc != SDF_ERR_CIGAR_OVERFLOW || pass) return rc;
     out.resize(used);
   }
   out.resize(used);
   if (threshold) *threshold = thr;
+  if (n_groups) *n_groups = groups;
   return SDF_OK;
 }
 
@@ -167,7 +172,7 @@ int pair_host_one(PairDriver &D, size_t i) {
   }
   // (the ranges as they lie in chars)
   const sdf_minim_range Q{0, D.Q.len, D.Q.flags}, R{D.P.same_genome ? 0 : (int64_t)D.Q.len, D.R.len, D.R.flags};
-  const PairHostArgs A = pair_host_args(D.chars.data(), D.chars.size(), Q, R, D.P, D.E, D.q, D.r(), D.r_sorted, D.threshold);
+  const PairHostArgs A = pair_host_args(D.chars.data(), D.chars.size(), Q, R, D.P, D.E, *D.q, D.r(), *D.r_sorted, D.threshold);
   const size_t nf0 = D.found.size();
   if (int rc = pair_host_window(A, i, D.found, D.W)) return refuse(ctx, rc, "sdf_search_pair: the host step of a window failed");
   D.out.insert(D.out.end(), D.W.reported.begin(), D.W.reported.end());
@@ -182,14 +187,15 @@ int pair_round(PairDriver &D, const uint32_t *act, size_t na, sdf_search_accept_
   sdf_ctx *ctx = D.ctx;
   hipStream_t st = D.st;
   const sdf_search_pair_params &P = D.P;
-  const size_t nq = D.q.size(), nr = D.r().size(), nf = D.found.size(), n = D.cap_iv;
+  const size_t nq = D.q->size(), nr = D.r().size(), nf = D.found.size(), n = D.cap_iv;
+  const std::vector<sdf_minimizer> &q = *D.q;
   const int32_t init_len = P.min_read_size;
   const int64_t len_q = D.Q.len, len_r = D.R.len;
   const int q_rc = (int)(D.Q.flags & SDF_MINIM_RC), r_rc = (int)(D.R.flags & SDF_MINIM_RC);
   // the slice of q the round's windows and their members lie in
   const size_t i0 = act[0];
   size_t e = act[na - 1];
-  while (e < nq && (int64_t)D.q[e].loc - D.q[act[na - 1]].loc <= init_len) ++e;
+  while (e < nq && (int64_t)q[e].loc - q[act[na - 1]].loc <= init_len) ++e;
   const size_t ns = e - i0;
   if (int rc = pair_sync_found(D, nf + n, nf)) return rc;
   SDF_HIP(ctx->dr_vis.reserve((std::max(nq, n) + 1) * 4));
@@ -204,8 +210,7 @@ int pair_round(PairDriver &D, const uint32_t *act, size_t na, sdf_search_accept_
   SDF_HIP(ctx->dr_out.reserve((n + 1) * sizeof(sdf_search_pair_hit)));
   SDF_HIP(ctx->dr_status.reserve(sizeof(sdf_search_accept_status) + 16));
   if (int rc = upload_all(ctx, st, {{ctx->dr_act, act, na * 4}})) return rc;
-  const sdf_minimizer *d_q = (const sdf_minimizer *)ctx->dr_q.p, *d_r = P.same_genome ? d_q : (const sdf_minimizer *)ctx->dr_r.p;
-  const sdf_minimizer *d_rs = (const sdf_minimizer *)ctx->dr_rs.p;
+  const sdf_minimizer *d_q = D.d_q, *d_r = D.d_r, *d_rs = D.d_rs;
   const int32_t *d_limit = (const int32_t *)ctx->dr_limit.p;
   uint64_t *d_first = (uint64_t *)ctx->dr_first.p;
   sdf_search_window *d_win = (sdf_search_window *)ctx->dr_win.p;
@@ -279,6 +284,71 @@ int pair_round(PairDriver &D, const uint32_t *act, size_t na, sdf_search_accept_
   D.S.attempted += back.status.attempted, D.S.jaccard_failed += back.status.jaccard_failed, D.S.interval_failed += back.status.interval_failed;
   return SDF_OK;
 }
+
+// fact 1: the windows that run, from loc and status alone
+void pair_schedule(PairDriver &D, std::vector<uint32_t> &sched) {
+  const sdf_search_pair_params &P = D.P;
+  const std::vector<sdf_minimizer> &q = *D.q;
+  int64_t next = 0;
+  for (size_t i = 0; i < q.size(); i++) {
+    if ((int64_t)q[i].loc < next || (P.uppercase_seeds && q[i].status != 0)) continue;
+    sched.push_back((uint32_t)i);
+    next = pair_next_loc(q[i].loc, P.min_read_size, P.filter.max_error);
+  }
+  D.S.windows_scheduled = (int64_t)sched.size();
+}
+
+// The rounds over a schedule that is not empty; D.d_q, D.d_r and D.d_rs name the device copies.  What a call writes per
+// window -- first[], the window records -- lies in the context's own buffers, never with the minimizers.
+int pair_rounds(PairDriver &D, const std::vector<uint32_t> &sched) {
+  sdf_ctx *ctx = D.ctx;
+  hipStream_t st = D.st;
+  const sdf_search_pair_params &P = D.P;
+  const size_t nq = D.q->size();
+  // (an array without a record still gets a buffer: the device forms -- sdf_search_roll_device's d_r and d_limit first -- refuse a null
+  // pointer before they look at a count)
+  SDF_HIP(ctx->dr_limit.reserve(16));
+  if (int rc = upload_all(ctx, st, {{ctx->dr_limit, P.limit, P.n_limit * 4}})) return rc;
+  SDF_HIP(ctx->dr_first.reserve((nq + 1) * 8));
+  SDF_HIP(ctx->dr_win.reserve((nq + 1) * sizeof(sdf_search_window)));
+  SDF_HIP(hipMemsetAsync(ctx->dr_win.p, 0, nq * sizeof(sdf_search_window), st));
+  const size_t round = P.round_windows ? P.round_windows : kPairRoundWindows, every = P.debug_host_every;
+  size_t s0 = 0;
+  while (s0 < sched.size()) {
+    if (every && s0 % every == every - 1) {  // debug: this window on the host
+      if (int rc = pair_host_one(D, sched[s0])) return rc;
+      ++s0;
+      continue;
+    }
+    size_t na = std::min(round, sched.size() - s0);
+    if (every) na = std::min(na, every - 1 - s0 % every);  // (the round ends in front of the next one the host takes)
+    sdf_search_accept_status status;
+    bool grew = false;
+    if (int rc = pair_round(D, sched.data() + s0, na, &status, &grew)) return rc;
+    if (grew) continue;  // the same round again, with room
+    s0 += status.frontier;
+    if (status.flags & SDF_ACCEPT_INCOMPLETE) {
+      if (int rc = pair_host_one(D, sched[s0])) return rc;
+      ++s0;
+    } else if (status.frontier == 0) {
+      return refuse(ctx, SDF_ERR_HIP, "sdf_search_pair: internal error, a round accepted nothing and handed nothing to the host");
+    }
+  }
+  return SDF_OK;
+}
+
+int pair_finish(PairDriver &D, sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
+  *stats = D.S;
+  *used = D.out.size();
+  if (D.out.size() > cap) return refuse(D.ctx, SDF_ERR_CIGAR_OVERFLOW, "the pair has " + std::to_string(D.out.size()) + " hits, more than cap");
+  if (!D.out.empty()) memcpy(out, D.out.data(), D.out.size() * sizeof(sdf_search_pair_hit));
+  return SDF_OK;
+}
+
+// a handle this context holds (looked up by address: a freed handle or another context's is not read)
+bool index_live(const sdf_ctx *ctx, const sdf_search_index *h) {
+  return h && std::find(ctx->indexes.begin(), ctx->indexes.end(), h) != ctx->indexes.end();
+}
 }  // namespace
 
 extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
@@ -291,60 +361,117 @@ extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, con
   PairDriver D{ctx, ctx->stream, *params, pair_extend_params(*params), *q_range, *r_range};
   const sdf_search_pair_params &P = *params;
   // set-up: minimizers of both ranges, the reference's index; they stay in HBM for every round
-  if (int rc = pair_minimizers(ctx, D.Q, P, false, D.q, nullptr)) return rc;
+  std::vector<sdf_minimizer> q, r_own, r_sorted;
+  if (int rc = pair_minimizers(ctx, D.Q, P.k, P.w, P.separate_lowercase, false, q, nullptr)) return rc;
   if (!P.same_genome)
-    if (int rc = pair_minimizers(ctx, D.R, P, false, D.r_own, nullptr)) return rc;
-  if (int rc = pair_minimizers(ctx, D.R, P, true, D.r_sorted, &D.threshold)) return rc;
-  const size_t nq = D.q.size();
-  std::vector<uint32_t> sched;  // fact 1: the windows that run, from loc and status alone
-  {
-    int64_t next = 0;
-    for (size_t i = 0; i < nq; i++) {
-      if ((int64_t)D.q[i].loc < next || (P.uppercase_seeds && D.q[i].status != 0)) continue;
-      sched.push_back((uint32_t)i);
-      next = pair_next_loc(D.q[i].loc, P.min_read_size, P.filter.max_error);
-    }
-  }
-  D.S.windows_scheduled = (int64_t)sched.size();
+    if (int rc = pair_minimizers(ctx, D.R, P.k, P.w, P.separate_lowercase, false, r_own, nullptr)) return rc;
+  if (int rc = pair_minimizers(ctx, D.R, P.k, P.w, P.separate_lowercase, true, r_sorted, &D.threshold)) return rc;
+  D.q = &q, D.r_loc = P.same_genome ? &q : &r_own, D.r_sorted = &r_sorted;
+  std::vector<uint32_t> sched;
+  pair_schedule(D, sched);
   if (!sched.empty()) {
-    hipStream_t st = D.st;
-    // (an array without a record still gets a buffer: the device forms -- sdf_search_roll_device's d_r and d_limit first -- refuse a null
-    // pointer before they look at a count.  The 256 bytes these uploads used to add did no more: no kernel reads past its counts.)
-    for (DevBuf *b : {&ctx->dr_r, &ctx->dr_rs, &ctx->dr_limit}) SDF_HIP(b->reserve(16));
-    if (int rc = upload_all(ctx, st, {{ctx->dr_q, D.q.data(), nq * sizeof(sdf_minimizer)},
-                                     {ctx->dr_r, D.r_own.data(), D.r_own.size() * sizeof(sdf_minimizer)},  // (empty under same_genome)
-                                     {ctx->dr_rs, D.r_sorted.data(), D.r_sorted.size() * sizeof(sdf_minimizer)},
-                                     {ctx->dr_limit, P.limit, P.n_limit * 4}}))
+    for (DevBuf *b : {&ctx->dr_r, &ctx->dr_rs}) SDF_HIP(b->reserve(16));
+    if (int rc = upload_all(ctx, D.st, {{ctx->dr_q, q.data(), q.size() * sizeof(sdf_minimizer)},
+                                       {ctx->dr_r, r_own.data(), r_own.size() * sizeof(sdf_minimizer)},  // (empty under same_genome)
+                                       {ctx->dr_rs, r_sorted.data(), r_sorted.size() * sizeof(sdf_minimizer)}}))
       return rc;
-    SDF_HIP(ctx->dr_first.reserve((nq + 1) * 8));
-    SDF_HIP(ctx->dr_win.reserve((nq + 1) * sizeof(sdf_search_window)));
-    SDF_HIP(hipMemsetAsync(ctx->dr_win.p, 0, nq * sizeof(sdf_search_window), st));
-    const size_t round = P.round_windows ? P.round_windows : kPairRoundWindows, every = P.debug_host_every;
-    size_t s0 = 0;
-    while (s0 < sched.size()) {
-      if (every && s0 % every == every - 1) {  // debug: this window on the host
-        if (int rc = pair_host_one(D, sched[s0])) return rc;
-        ++s0;
-        continue;
-      }
-      size_t na = std::min(round, sched.size() - s0);
-      if (every) na = std::min(na, every - 1 - s0 % every);  // (the round ends in front of the next one the host takes)
-      sdf_search_accept_status status;
-      bool grew = false;
-      if (int rc = pair_round(D, sched.data() + s0, na, &status, &grew)) return rc;
-      if (grew) continue;  // the same round again, with room
-      s0 += status.frontier;
-      if (status.flags & SDF_ACCEPT_INCOMPLETE) {
-        if (int rc = pair_host_one(D, sched[s0])) return rc;
-        ++s0;
-      } else if (status.frontier == 0) {
-        return refuse(ctx, SDF_ERR_HIP, "sdf_search_pair: internal error, a round accepted nothing and handed nothing to the host");
-      }
-    }
+    D.d_q = (const sdf_minimizer *)ctx->dr_q.p;
+    D.d_r = P.same_genome ? D.d_q : (const sdf_minimizer *)ctx->dr_r.p;
+    D.d_rs = (const sdf_minimizer *)ctx->dr_rs.p;
+    if (int rc = pair_rounds(D, sched)) return rc;
   }
-  *stats = D.S;
-  *used = D.out.size();
-  if (D.out.size() > cap) return refuse(ctx, SDF_ERR_CIGAR_OVERFLOW, "the pair has " + std::to_string(D.out.size()) + " hits, more than cap");
-  if (!D.out.empty()) memcpy(out, D.out.data(), D.out.size() * sizeof(sdf_search_pair_hit));
+  return pair_finish(D, out, cap, used, stats);
+}
+
+// ---- the resident search index: a range's minimizers and index once, for every pair that names the range ----
+
+extern "C" int sdf_search_index_build(sdf_ctx *ctx, const sdf_minim_range *range, int k, int w, int separate_lowercase, sdf_search_index **out) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (!range || !out) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_index_build: invalid arguments");
+  *out = nullptr;
+  SDF_HIP(hipSetDevice(ctx->device));
+  sdf_search_index *h = new sdf_search_index();
+  h->ctx = ctx, h->pool_epoch = ctx->pool_epoch, h->range = *range, h->k = k, h->w = w, h->separate_lowercase = separate_lowercase != 0;
+  auto fail = [&](int rc) {
+    h->d_loc.release(), h->d_sorted.release();
+    delete h;
+    return rc;
+  };
+  // (the two calls check the range, k and w and refuse before their first launch)
+  if (int rc = pair_minimizers(ctx, *range, k, w, separate_lowercase, false, h->loc, nullptr)) return fail(rc);
+  if (int rc = pair_minimizers(ctx, *range, k, w, separate_lowercase, true, h->sorted, &h->threshold, &h->n_groups)) return fail(rc);
+  // device copies of the handle's own, to the byte (never null: the device forms refuse a null pointer before they look at a count)
+  hipError_t e = h->d_loc.reserve_exact(std::max<size_t>(h->loc.size() * sizeof(sdf_minimizer), 16));
+  if (e == hipSuccess) e = h->d_sorted.reserve_exact(std::max<size_t>(h->sorted.size() * sizeof(sdf_minimizer), 16));
+  if (e == hipSuccess && !h->loc.empty())
+    e = hipMemcpyAsync(h->d_loc.p, h->loc.data(), h->loc.size() * sizeof(sdf_minimizer), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && !h->sorted.empty())
+    e = hipMemcpyAsync(h->d_sorted.p, h->sorted.data(), h->sorted.size() * sizeof(sdf_minimizer), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = std::string("sdf_search_index_build: ") + hipGetErrorString(e);
+    return fail(e == hipErrorOutOfMemory ? SDF_ERR_NOMEM : SDF_ERR_HIP);
+  }
+  ctx->indexes.push_back(h);
+  ctx->index_builds += 1;
+  *out = h;
   return SDF_OK;
+}
+
+extern "C" int sdf_search_index_free(sdf_ctx *ctx, sdf_search_index *h) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (!h) return SDF_OK;
+  if (!index_live(ctx, h)) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_index_free: not a live handle of this context");
+  SDF_HIP(hipSetDevice(ctx->device));
+  ctx->indexes.erase(std::find(ctx->indexes.begin(), ctx->indexes.end(), h));
+  h->d_loc.release(), h->d_sorted.release();
+  delete h;
+  return SDF_OK;
+}
+
+extern "C" int sdf_search_index_info(const sdf_ctx *ctx, const sdf_search_index *h, sdf_search_index_desc *info) {
+  if (!ctx || !info || !index_live(ctx, h)) return SDF_ERR_INVALID;
+  *info = sdf_search_index_desc{h->range,
+                                h->k,
+                                h->w,
+                                h->separate_lowercase,
+                                h->threshold,
+                                (uint64_t)h->loc.size(),
+                                (uint64_t)h->sorted.size(),
+                                h->n_groups,
+                                (uint32_t)(h->pool_epoch != ctx->pool_epoch),
+                                (uint64_t)(h->d_loc.held_bytes() + h->d_sorted.held_bytes())};
+  return SDF_OK;
+}
+
+extern "C" long long sdf_search_index_builds(const sdf_ctx *ctx) { return ctx ? ctx->index_builds : 0; }
+extern "C" size_t sdf_search_index_live(const sdf_ctx *ctx) { return ctx ? ctx->indexes.size() : 0; }
+
+extern "C" int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                                       sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
+  if (!ctx) return SDF_ERR_INVALID;
+  ctx->err.clear();
+  if (!used || !stats || !params || (cap && !out)) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: invalid arguments");
+  if (!index_live(ctx, q) || !index_live(ctx, r))
+    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: a handle that is null, freed or another context's");
+  if (q->pool_epoch != ctx->pool_epoch || r->pool_epoch != ctx->pool_epoch)
+    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: a handle built on a pool that has been replaced since");
+  for (const sdf_search_index *h : {q, r})
+    if (h->k != params->k || h->w != params->w || h->separate_lowercase != (params->separate_lowercase != 0))
+      return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: k, w or separate_lowercase differ from a handle's");
+  if (params->same_genome && q != r) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: same_genome takes one handle as both sides");
+  if (int rc = pair_checks(sdf_pool_bytes(ctx), &q->range, &r->range, params))
+    return refuse(ctx, rc, "sdf_search_pair_indexed: a range or a parameter is refused");
+  SDF_HIP(hipSetDevice(ctx->device));
+  PairDriver D{ctx, ctx->stream, *params, pair_extend_params(*params), q->range, r->range};
+  D.q = &q->loc, D.r_loc = &r->loc, D.r_sorted = &r->sorted, D.threshold = r->threshold;
+  D.d_q = (const sdf_minimizer *)q->d_loc.p, D.d_r = (const sdf_minimizer *)r->d_loc.p, D.d_rs = (const sdf_minimizer *)r->d_sorted.p;
+  std::vector<uint32_t> sched;
+  pair_schedule(D, sched);
+  if (!sched.empty())
+    if (int rc = pair_rounds(D, sched)) return rc;
+  return pair_finish(D, out, cap, used, stats);
 }

@@ -37,6 +37,7 @@ extern "C" int sdf_pool_upload(sdf_ctx *ctx, const char *chars, size_t bytes) {
   }
   if (pool_writable(ctx) != SDF_OK) return SDF_ERR_INVALID;  // (an owner with views keeps its pool as it is)
   ctx->pool_bytes = 0;
+  ctx->pool_epoch += 1;
   SDF_HIP(hipSetDevice(ctx->device));
   ctx->an_pool.new_call();
   SDF_HIP(ctx->an_pool.reserve(bytes + 64));
@@ -77,6 +78,7 @@ extern "C" int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nby
   if (nbytes < least || nbytes > least + gap) return invalid("nbytes does not fit n_bases bases in lines of this geometry");
   if (pool_writable(ctx, /*keep_view=*/reset == 0) != SDF_OK) return SDF_ERR_INVALID;
   const size_t at = reset ? 0 : ctx->pool_bytes, need = at + (size_t)n_bases;
+  if (reset) ctx->pool_epoch += 1;
   SDF_HIP(hipSetDevice(ctx->device));
   // pieces of whole lines, 64 MiB or so each (the gather's indices within a piece are 32-bit)
   const size_t piece_lines = std::max<size_t>(1, ((size_t)64 << 20) / (size_t)line_bytes);
@@ -102,6 +104,7 @@ extern "C" int sdf_pool_append_fasta(sdf_ctx *ctx, const char *bytes, size_t nby
     if (e != hipSuccess || (at && std::find(ctx->an_pool.retired.begin(), ctx->an_pool.retired.end(), old) == ctx->an_pool.retired.end())) {
       (void)hipGetLastError();
       ctx->err = "sdf_pool_append_fasta: out of device memory while growing the pool (the pool is empty now)";
+      ctx->pool_epoch += 1;
       return SDF_ERR_NOMEM;
     }
     if (at) SDF_HIP(hipMemcpyAsync(ctx->an_pool.p, old, at, hipMemcpyDeviceToDevice, ctx->stream));

@@ -175,6 +175,7 @@ extern "C" int sdf_anchors_batch_strand(sdf_ctx *ctx, const sdf_anchor_pair *pai
   if (!resident) {  // (the pool stays where it is after the call: sdf_extz2_batch_pairs may name ranges of it)
     if (pool_writable(ctx) != SDF_OK) return SDF_ERR_INVALID;
     ctx->pool_bytes = 0;
+    ctx->pool_epoch += 1;
     SDF_HIP(ctx->an_pool.reserve(pool_bytes + 64));
     SDF_HIP(hipMemcpyAsync(ctx->an_pool.p, seq_pool, pool_bytes, hipMemcpyHostToDevice, ctx->stream));
     ctx->pool_bytes = pool_bytes;

@@ -84,6 +84,11 @@ assert SEARCH_HIT_DTYPE.itemsize == 40
 # include/sedef_hip.h: sdf_search_pair_hit, sdf_search_accept_status, sdf_search_pair_stats (the search driver's section)
 SEARCH_PAIR_HIT_DTYPE = np.dtype([("window", "<i4"), ("query_start", "<i4"), ("query_end", "<i4"), ("ref_start", "<i4"),
                                   ("ref_end", "<i4"), ("jaccard", "<i4")])
+# sdf_search_index_desc (the resident search index)
+SEARCH_INDEX_DESC_DTYPE = np.dtype([("off", "<i8"), ("len", "<i4"), ("flags", "<i4"), ("k", "<i4"), ("w", "<i4"),
+                                    ("separate_lowercase", "<i4"), ("threshold", "<u4"), ("n_minimizers", "<u8"), ("n_sorted", "<u8"),
+                                    ("n_groups", "<u4"), ("stale", "<u4"), ("device_bytes", "<u8")])
+assert SEARCH_INDEX_DESC_DTYPE.itemsize == 64
 ACCEPT_STATUS_DTYPE = np.dtype([("frontier", "<u4"), ("flags", "<u4"), ("nf", "<u8"), ("n_out", "<u8"), ("need_found", "<u8"),
                                 ("need_out", "<u8"), ("attempted", "<i8"), ("jaccard_failed", "<i8"), ("interval_failed", "<i8")])
 PAIR_STATS_DTYPE = np.dtype([(f, "<i8") for f in ("attempted", "jaccard_failed", "interval_failed", "rounds", "windows_run",
@@ -353,6 +358,19 @@ def load_library():
     L.sdf_search_pair.restype = C.c_int  # ctx, q_range, r_range, params, out, cap, used, stats
     L.sdf_search_pair.argtypes = [C.c_void_p, C.POINTER(_MinimRange), C.POINTER(_MinimRange), C.POINTER(_PairParams), C.c_void_p,
                                   C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.sdf_search_index_build.restype = C.c_int  # ctx, range, k, w, separate_lowercase, out
+    L.sdf_search_index_build.argtypes = [C.c_void_p, C.POINTER(_MinimRange), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.sdf_search_index_free.restype = C.c_int
+    L.sdf_search_index_free.argtypes = [C.c_void_p, C.c_void_p]
+    L.sdf_search_index_info.restype = C.c_int
+    L.sdf_search_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sdf_search_index_builds.restype = C.c_longlong
+    L.sdf_search_index_builds.argtypes = [C.c_void_p]
+    L.sdf_search_index_live.restype = C.c_size_t
+    L.sdf_search_index_live.argtypes = [C.c_void_p]
+    L.sdf_search_pair_indexed.restype = C.c_int  # ctx, q, r, params, out, cap, used, stats
+    L.sdf_search_pair_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_PairParams), C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -1073,6 +1091,34 @@ class Extz2Engine:
         default) and debug_host_every (every n-th scheduled window on the host)."""
         return search_pair_call(self.lib.sdf_search_pair, (self.ctx,), q_range, r_range, **kw)
 
+    def search_index_build(self, rng, k=12, w=16, separate_lowercase=True):
+        """sdf_search_index_build: the minimizers and the index of one range (off, len) or (off, len, flags) of the resident
+        pool, computed once and kept in HBM.  Returns (rc, handle): an int for search_pair_indexed / search_index_info /
+        search_index_free, None after a refusal.  A handle dies with its engine (close) at the latest."""
+        r = _MinimRange(int(rng[0]), int(rng[1]), int(rng[2]) if len(rng) > 2 else 0)
+        h = C.c_void_p(0)
+        rc = self.lib.sdf_search_index_build(self.ctx, C.byref(r), int(k), int(w), int(bool(separate_lowercase)), C.byref(h))
+        return rc, (h.value if rc == 0 else None)
+
+    def search_index_free(self, handle):
+        """sdf_search_index_free -> rc (None is SDF_OK; a handle that is not live in this engine is -4)."""
+        return self.lib.sdf_search_index_free(self.ctx, handle)
+
+    def search_index_info(self, handle):
+        """sdf_search_index_info -> a SEARCH_INDEX_DESC_DTYPE record."""
+        d = np.zeros(1, SEARCH_INDEX_DESC_DTYPE)
+        self._check(self.lib.sdf_search_index_info(self.ctx, handle, d.ctypes.data))
+        return d[0]
+
+    def search_index_builds(self):
+        """(handles built since the engine was made, handles live now)"""
+        return int(self.lib.sdf_search_index_builds(self.ctx)), int(self.lib.sdf_search_index_live(self.ctx))
+
+    def search_pair_indexed(self, q_index, r_index, **kw):
+        """sdf_search_pair_indexed: search_pair on two handles of search_index_build (same_genome: one handle as both).
+        Keywords and result as search_pair's."""
+        return search_pair_call(self.lib.sdf_search_pair_indexed, (self.ctx,), q_index, r_index, **kw)
+
     def search_accept_raw(self, *args, **kw):
         """sdf_search_accept as it is: one round of the search driver's acceptance step on numpy arrays, run by the device
         form on copies.  Arguments and result as search_accept_call's."""
@@ -1490,13 +1536,16 @@ def search_pair_call(fn, head, q_range, r_range, k=12, w=16, separate_lowercase=
                     filter_params() if filter is None else filter,
                     extend_params(same_genome=bool(same_genome)) if extend is None else extend,
                     limit.ctypes.data if len(limit) else None, len(limit), int(round_windows), int(debug_host_every))
-    ranges = [_MinimRange(int(r[0]), int(r[1]), int(r[2]) if len(r) > 2 else 0) for r in (q_range, r_range)]
+    if isinstance(q_range, (tuple, list, np.ndarray)):
+        ranges = [C.byref(_MinimRange(int(r[0]), int(r[1]), int(r[2]) if len(r) > 2 else 0)) for r in (q_range, r_range)]
+    else:  # two handles of search_index_build (ints, or None)
+        ranges = [q_range, r_range]
     stats = np.zeros(1, PAIR_STATS_DTYPE)
     used = C.c_size_t(0)
     room = 0 if cap is None else int(cap)
     while True:
         out = np.zeros(room, SEARCH_PAIR_HIT_DTYPE)
-        rc = fn(*head, C.byref(ranges[0]), C.byref(ranges[1]), C.byref(P), out.ctypes.data if room else None, room, C.byref(used),
+        rc = fn(*head, ranges[0], ranges[1], C.byref(P), out.ctypes.data if room else None, room, C.byref(used),
                 stats.ctypes.data)
         if rc != -5 or cap is not None:
             break

@@ -12,7 +12,7 @@ HOST_SRC = os.path.join(_HERE, "csrc", "host")
 LIB = os.path.join(_HERE, "lib", "libsedef_host.so")
 CLI = os.path.join(_HERE, "bin", "sedef")
 MULTI = os.path.join(_HERE, "bin", "sdf_multi")
-_SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "pipeline.cc", "bucket.cc", "stats.cc", "host_cabi.cc"]
+_SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "pipeline.cc", "bucket.cc", "stats.cc", "search_cmd.cc", "host_cabi.cc"]
 
 
 def build_host(force=False):
@@ -295,3 +295,55 @@ def sequence(name, seq, is_rc=False):
     _err(lib, lib.sdfh_sequence(name.encode(), seq.encode(), int(is_rc), buf, len(buf)))
     n, s, r = buf.value.decode().split("|")
     return n, s, r == "1"
+
+
+def search_hit_bed(qname, rname, qs, qe, rs, re_, ref_rc=False, ref_len=0):
+    """The BED line `sedef search` prints for a hit (csrc/host/search_cmd.cc: Hit::to_bed() of a search hit, src/hit.cc:134-196);
+    rs / re_ as the driver reports them, flipped here under ref_rc by the record's length."""
+    lib, buf = load_host(), _buffer()
+    lib.sdfh_search_hit_bed.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_char_p,
+                                        C.c_size_t]
+    _err(lib, lib.sdfh_search_hit_bed(qname.encode(), rname.encode(), int(qs), int(qe), int(rs), int(re_), int(bool(ref_rc)),
+                                      int(ref_len), buf, len(buf)))
+    return buf.value.decode()
+
+
+def limit_table(n, kmer=12, max_error=0.30, max_edit_error=0.15, walk=False):
+    """limit[0 .. n]: relaxed_jaccard_estimate(s) as `sedef search` computes it (limit[0] = 0); walk=True: by the reference's
+    loop as written instead of the bisection."""
+    import numpy as np
+    lib = load_host()
+    out = np.zeros(n + 1, np.int32)
+    lib.sdfh_limit_table.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]
+    _err(lib, lib.sdfh_limit_table(int(kmer), float(max_error), float(max_edit_error), int(n), int(bool(walk)), out[1:].ctypes.data))
+    return out
+
+
+def read_limit_table(path, cap=1 << 20):
+    """--limit-table parsing (limit[0] = 0 first); raises RuntimeError with the refusal."""
+    import numpy as np
+    lib = load_host()
+    out = np.zeros(cap, np.int32)
+    lib.sdfh_read_limit_table.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
+    n = lib.sdfh_read_limit_table(path.encode(), out.ctypes.data, cap)
+    _err(lib, min(n, 0))
+    return out[:n].copy()
+
+
+def translation(ref_path, max_size=100 * 1000 * 1000):
+    """generate_translation over genome.fa.fai at a group limit -> [[name, ...], ...]."""
+    lib, buf = load_host(), _buffer()
+    lib.sdfh_translation.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
+    _err(lib, lib.sdfh_translation(ref_path.encode(), int(max_size), buf, len(buf)))
+    return [g.split(",") for g in buf.value.decode().split("|") if g]
+
+
+def search_args(args):
+    """parse_search_args over a list of strings -> dict; raises RuntimeError with the refusal."""
+    lib, buf = load_host(), _buffer()
+    lib.sdfh_search_args.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
+    _err(lib, lib.sdfh_search_args("\n".join(args).encode(), buf, len(buf)))
+    f = buf.value.decode().split("|")
+    h = f[0].split(" ")
+    return dict(k=int(h[0]), w=int(h[1]), u=int(h[2]), e=float(h[3]), E=float(h[4]), g=float(h[5]), min_read_size=int(h[6]),
+                transform=h[7] == "1", reverse=h[8] == "1", limit_table=f[1], pos=f[2:])

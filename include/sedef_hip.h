@@ -651,6 +651,8 @@ int sdf_pool_minimizer_index(sdf_ctx *ctx, const sdf_minim_range *r, size_t n, i
  * flag does not depend on who computes.  The device form flags such a window, fills its counts except n_candidates (0) and
  * writes no interval for it; sdf_search_windows completes it on the host (sdf_search_windows_host's code on the arrays it was
  * given), into the same first[] / out layout, and keeps the flag: its answer is complete for every input.
+ * sdf_search_windows_wide_device (behind the found records' section) finishes such a window on the device up to
+ * SDF_SEARCH_WIDE_MAX_GATHER gathered positions, and marks it SDF_SEARCH_WIDE_DONE in place of the flag.
  *
  * Overflow as for sdf_pool_minimizers: SDF_ERR_CIGAR_OVERFLOW when the windows have more than cap intervals -- *used holds the
  * need, first[] and windows[] are filled, nothing is written to out; no record is ever written at or behind out[cap].
@@ -753,6 +755,33 @@ int sdf_search_windows_found_host(const sdf_minimizer *q, size_t nq, int64_t len
                                   size_t n_limit, const sdf_search_found *found, size_t nf, const uint32_t *visible /* nq */,
                                   uint64_t *first /* nq + 1 */, sdf_search_window *windows /* nq */, sdf_search_interval *out,
                                   size_t cap, size_t *used);
+/* sdf_search_windows_wide_device: sdf_search_windows_found_device, and the windows it flags WIDE or FOUND_WIDE finished on the
+ * device by a second kernel (search_seeds_wide.hip: one workgroup of 256 lanes per window, 32-bit keys of
+ * SDF_SEARCH_WIDE_MAX_GATHER positions in LDS, the found records walked out of the bins in chunks of 256 -- any number of them).
+ *   eligible   a window of the existing device form with WIDE and/or FOUND_WIDE, without NOLIMIT, with n_members <=
+ *              SDF_SEARCH_MAX_MEMBERS and n_gathered <= SDF_SEARCH_WIDE_MAX_GATHER.  All read off the inputs.
+ *   listed     the LOWEST n_wide_max eligible window indices, in ascending order (an ordered compaction: which windows stay
+ *              behind does not depend on how the device ran).  *d_wide_total (HBM, or NULL) receives the number of eligible
+ *              windows, so a caller sees that the list was short.
+ *   completed  a listed window's record has WIDE and FOUND_WIDE CLEARED and SDF_SEARCH_WIDE_DONE set; every other field,
+ *              first[] and its intervals are byte for byte what sdf_search_windows_found_host / sdf_search_windows_found write
+ *              for it (those forms keep the WIDE bits, and stay as they are).  With the old bits cleared the acceptance step,
+ *              the roll and everything behind them take the window like any other.
+ *   the rest   a window that is not eligible, or not among the first n_wide_max, keeps exactly the record the existing device
+ *              form writes, and has no interval.
+ * Launches, on one stream without a host wait: the existing count pass, the list, the wide count, the scan of the counts, the
+ * existing emit pass (which writes nothing for a window it finds WIDE or FOUND_WIDE), the wide emit: the listed windows' intervals
+ * at first[i], nothing at or behind d_out[cap].  nf == 0 with d_visible == NULL runs the plain instantiations without an index.
+ * n_wide_max == 0 is sdf_search_windows_found_device byte for byte (*d_wide_total is not written).  Refusals are that form's,
+ * before the first launch, and SDF_ERR_UNSUPPORTED for n_wide_max > 2^20. */
+#define SDF_SEARCH_WIDE_DONE 0x10   /* window flag: finished by sdf_search_windows_wide_device */
+#define SDF_SEARCH_WIDE_MAX_GATHER 32768
+int sdf_search_windows_wide_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted,
+                                   size_t nr, uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                   const int32_t *d_limit, size_t n_limit, const sdf_search_found *d_found, size_t nf,
+                                   size_t found_entries_cap, uint64_t *d_found_entries /* or NULL */, const uint32_t *d_visible,
+                                   uint64_t *d_first, sdf_search_window *d_windows, sdf_search_interval *d_out, size_t cap,
+                                   size_t *used, size_t n_wide_max, uint64_t *d_wide_total /* or NULL */, void *stream);
 /* (sdf_search_overlap*, the tree's second query, stand behind the filter's section: they take its tasks) */
 
 /* ---- search roll: every reference interval rolled to its best initial match (search_roll.hip) ----------------------------------
@@ -1245,6 +1274,14 @@ int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_mini
 int sdf_search_pair_host(const char *pool, size_t pool_bytes, const sdf_minim_range *q_range, const sdf_minim_range *r_range,
                          const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
                          sdf_search_pair_stats *stats);
+/* sdf_search_pair_wide (and sdf_search_pair_indexed_wide, below): sdf_search_pair whose rounds seed with
+ * sdf_search_windows_wide_device(n_wide_max) -- a window that is WIDE or FOUND_WIDE for the seeding kernel alone is finished on
+ * the device and no longer ends the round for the host.  out, *used and the three counters equal sdf_search_pair_host's byte
+ * for byte for every round_windows; rounds, windows_run and windows_host may differ, as between any two forms.  n_wide_max == 0
+ * is sdf_search_pair itself; n_wide_max > 2^20: SDF_ERR_UNSUPPORTED before the first launch. */
+int sdf_search_pair_wide(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range,
+                         const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
+                         sdf_search_pair_stats *stats, size_t n_wide_max);
 
 /* ---- the resident search index: a range's minimizers and index ONCE, for every pair that names the range ------------------
  * The reference's search_single builds one Index per (chromosome, strand) and reuses it for every pair
@@ -1301,6 +1338,9 @@ long long sdf_search_index_builds(const sdf_ctx *ctx);
 size_t sdf_search_index_live(const sdf_ctx *ctx);
 int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
                             sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats);
+/* (sdf_search_pair_wide on two handles) */
+int sdf_search_pair_indexed_wide(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                                 sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats, size_t n_wide_max);
 
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is

@@ -383,6 +383,7 @@ int search_command(const SearchParams &p, FILE *out, FILE *log) {
   P.extend.max_error = p.max_error, P.extend.max_edit_error = p.max_edit_error, P.extend.max_sd_size = p.max_sd_size;
   P.limit = limit.data(), P.n_limit = limit.size();
   long long total = 0, attempted = 0, jaccard_failed = 0, interval_failed = 0, pairs = 0;
+  const size_t n_wide = (size_t)stage_settings().search_wide;
   std::vector<sdf_search_pair_hit> hits(1024);
   std::string text;
   for (auto &r : rr)
@@ -392,10 +393,11 @@ int search_command(const SearchParams &p, FILE *out, FILE *log) {
       const sdf_search_index *qh = indices[{q, false}], *rh = indices[{r, p.reverse}];
       size_t used = 0;
       sdf_search_pair_stats st;
-      int rc = sdf_search_pair_indexed(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st);
+      // (SDF_SEARCH_WIDE_DEVICE=N: the seeding's WIDE / FOUND_WIDE windows on the device; 0 is sdf_search_pair_indexed itself)
+      int rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
       if (rc == SDF_ERR_CIGAR_OVERFLOW) {
         hits.resize(used + used / 2);
-        rc = sdf_search_pair_indexed(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st);
+        rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
       }
       C.check(rc, "sdf_search_pair_indexed");
       text.clear();

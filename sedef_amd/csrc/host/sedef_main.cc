@@ -135,6 +135,8 @@ int main(int argc, char **argv) {
               "  --limit-table FILE: one integer per line, line s (from 1) = relaxed_jaccard_estimate(s); replaces the table this\n"
               "  build computes without Boost.  On stderr: the parameters, the totals and the attempts / Jaccard / interval fail\n"
               "  counters; the reference's lowercase and q-grams counters are not kept.\n"
+              "  SDF_SEARCH_WIDE_DEVICE=N (default 0): up to N windows a round that gather more than 4,096 positions or meet more\n"
+              "  than 256 found SDs are seeded on the device instead of one at a time on the host (same output)\n"
               "sedef translate [genome.fa]\n"
               "  the chromosome groups of -t on stderr, their number on stdout\n"
               "  SDF_TEST_TRANSLATE_LIMIT (tests only): the group size limit in bases instead of 100 MB\n"

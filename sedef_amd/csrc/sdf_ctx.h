@@ -329,6 +329,7 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(mz_sorted, None) X(mz_res, None) /* ... places (in, out), heads / ranks / starts, sort scratch, sorted records, results */ \
   X(sw_keys, None) X(sw_vals, None) X(sw_tmp, None) /* sdf_search_windows_device: sort keys and places (in, out), sort scratch, */ \
   X(sw_look, None) X(sw_counts, None) /* ... a SearchLook per query minimizer, intervals per window */                  \
+  X(sw_wide, None) X(sw_nwide, None) /* sdf_search_windows_wide_device: the listed window indices, the number of eligible windows */ \
   X(sw_q, None) X(sw_r, None) X(sw_limit, None) X(sw_first, None) X(sw_win, None) X(sw_out, None) /* sdf_search_windows: the host form's copies */ \
   X(fo_counts, None) X(fo_start, None) X(fo_ent, None) X(fo_need, None) X(fo_tmp, None) /* the bin index of the found records: counts / cursors, bin starts, entries, the need, hipCUB scratch */ \
   X(fo_found, None) X(fo_vis, None) X(fo_q, None) X(fo_first, None) X(fo_rolls, None) X(fo_out, None) /* sdf_search_windows_found, sdf_search_overlap: the host forms' copies */ \

@@ -127,6 +127,7 @@ struct PairDriver {
   PairHostWindow W;
   sdf_search_pair_stats S{0, 0, 0, 0, 0, 0, 0};
   size_t cap_iv = SDF_PAIR_INTERVALS_START, ent_cap = SDF_PAIR_ENTRIES_START, found_cap = 0;
+  size_t n_wide = 0;  // sdf_search_pair_wide: the n_wide_max of a round's seeding (0: the plain device form)
   const std::vector<sdf_minimizer> &r() const { return *r_loc; }
 };
 
@@ -228,8 +229,12 @@ int pair_round(PairDriver &D, const uint32_t *act, size_t na, sdf_search_accept_
   // every window and interval of the round sees the whole list as it stands
   SDF_HIP(hipMemsetD32Async((hipDeviceptr_t)d_vis, (int)nf, std::max(nq, n), st));
   if (i0) SDF_HIP(hipMemsetAsync(d_first, 0, i0 * 8, st));
-  if (int rc = sdf_search_windows_found_device(ctx, d_q + i0, ns, len_q, d_rs, nr, D.threshold, init_len, P.same_genome, P.uppercase_seeds, d_limit,
-                                               P.n_limit, d_found, nf, D.ent_cap, d_need, d_vis, d_first + i0, d_win + i0, d_iv, n, nullptr, s))
+  if (int rc = D.n_wide ? sdf_search_windows_wide_device(ctx, d_q + i0, ns, len_q, d_rs, nr, D.threshold, init_len, P.same_genome, P.uppercase_seeds,
+                                                         d_limit, P.n_limit, d_found, nf, D.ent_cap, d_need, d_vis, d_first + i0, d_win + i0, d_iv, n,
+                                                         nullptr, D.n_wide, nullptr, s)
+                        : sdf_search_windows_found_device(ctx, d_q + i0, ns, len_q, d_rs, nr, D.threshold, init_len, P.same_genome, P.uppercase_seeds,
+                                                          d_limit, P.n_limit, d_found, nf, D.ent_cap, d_need, d_vis, d_first + i0, d_win + i0, d_iv, n,
+                                                          nullptr, s))
     return rc;
   if (e < nq) {
     hipLaunchKernelGGL(search_accept_tail_kernel, dim3((unsigned)((nq - e + 255) / 256)), dim3(256), 0, st, d_first, (int)e, (int)nq);
@@ -351,14 +356,17 @@ bool index_live(const sdf_ctx *ctx, const sdf_search_index *h) {
 }
 }  // namespace
 
-extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
-                               sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
+// sdf_search_pair (n_wide_max == 0) and sdf_search_pair_wide
+static int pair_ranges(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
+                       sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats, size_t n_wide_max) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
   if (!used || !stats || (cap && !out)) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair: invalid arguments");
   if (int rc = pair_checks(sdf_pool_bytes(ctx), q_range, r_range, params)) return refuse(ctx, rc, "sdf_search_pair: a range or a parameter is refused");
+  if (n_wide_max > SEARCH_WIDE_MAX_LIST) return refuse(ctx, SDF_ERR_UNSUPPORTED, "sdf_search_pair_wide: n_wide_max > 2^20");
   SDF_HIP(hipSetDevice(ctx->device));
   PairDriver D{ctx, ctx->stream, *params, pair_extend_params(*params), *q_range, *r_range};
+  D.n_wide = n_wide_max;
   const sdf_search_pair_params &P = *params;
   // set-up: minimizers of both ranges, the reference's index; they stay in HBM for every round
   std::vector<sdf_minimizer> q, r_own, r_sorted;
@@ -381,6 +389,17 @@ extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, con
     if (int rc = pair_rounds(D, sched)) return rc;
   }
   return pair_finish(D, out, cap, used, stats);
+}
+
+extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
+                               sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
+  return pair_ranges(ctx, q_range, r_range, params, out, cap, used, stats, 0);
+}
+
+extern "C" int sdf_search_pair_wide(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range,
+                                    const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
+                                    sdf_search_pair_stats *stats, size_t n_wide_max) {
+  return pair_ranges(ctx, q_range, r_range, params, out, cap, used, stats, n_wide_max);
 }
 
 // ---- the resident search index: a range's minimizers and index once, for every pair that names the range ----
@@ -450,8 +469,9 @@ extern "C" int sdf_search_index_info(const sdf_ctx *ctx, const sdf_search_index 
 extern "C" long long sdf_search_index_builds(const sdf_ctx *ctx) { return ctx ? ctx->index_builds : 0; }
 extern "C" size_t sdf_search_index_live(const sdf_ctx *ctx) { return ctx ? ctx->indexes.size() : 0; }
 
-extern "C" int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
-                                       sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
+// sdf_search_pair_indexed (n_wide_max == 0) and sdf_search_pair_indexed_wide
+static int pair_handles(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                        sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats, size_t n_wide_max) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
   if (!used || !stats || !params || (cap && !out)) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: invalid arguments");
@@ -465,8 +485,10 @@ extern "C" int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, 
   if (params->same_genome && q != r) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: same_genome takes one handle as both sides");
   if (int rc = pair_checks(sdf_pool_bytes(ctx), &q->range, &r->range, params))
     return refuse(ctx, rc, "sdf_search_pair_indexed: a range or a parameter is refused");
+  if (n_wide_max > SEARCH_WIDE_MAX_LIST) return refuse(ctx, SDF_ERR_UNSUPPORTED, "sdf_search_pair_indexed_wide: n_wide_max > 2^20");
   SDF_HIP(hipSetDevice(ctx->device));
   PairDriver D{ctx, ctx->stream, *params, pair_extend_params(*params), q->range, r->range};
+  D.n_wide = n_wide_max;
   D.q = &q->loc, D.r_loc = &r->loc, D.r_sorted = &r->sorted, D.threshold = r->threshold;
   D.d_q = (const sdf_minimizer *)q->d_loc.p, D.d_r = (const sdf_minimizer *)r->d_loc.p, D.d_rs = (const sdf_minimizer *)r->d_sorted.p;
   std::vector<uint32_t> sched;
@@ -474,4 +496,15 @@ extern "C" int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, 
   if (!sched.empty())
     if (int rc = pair_rounds(D, sched)) return rc;
   return pair_finish(D, out, cap, used, stats);
+}
+
+extern "C" int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                                       sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
+  return pair_handles(ctx, q, r, params, out, cap, used, stats, 0);
+}
+
+extern "C" int sdf_search_pair_indexed_wide(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r,
+                                            const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
+                                            sdf_search_pair_stats *stats, size_t n_wide_max) {
+  return pair_handles(ctx, q, r, params, out, cap, used, stats, n_wide_max);
 }

@@ -230,6 +230,23 @@ template <bool EMIT, bool FOUND>
 __global__ void search_window_kernel(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, int, int,
                                      const int32_t *, int, sdf_search_window *, uint32_t *, const uint64_t *, sdf_search_interval *,
                                      uint64_t, FoundIndex);
+// search_seeds_wide.hip: a workgroup of SEARCH_WIDE_THREADS lanes per window that search_window_kernel flags and leaves; its
+// LDS: 32-bit keys of SEARCH_WIDE_MAX_GATHER positions, 32-bit offsets of the members, a chunk of SEARCH_WIDE_CHUNK found records
+constexpr int SEARCH_WIDE_MAX_GATHER = SDF_SEARCH_WIDE_MAX_GATHER, SEARCH_WIDE_THREADS = 256, SEARCH_WIDE_CHUNK = 256;
+constexpr size_t SEARCH_WIDE_MAX_LIST = (size_t)1 << 20;  // n_wide_max: a workgroup per list entry is launched without a host wait
+static_assert((SEARCH_WIDE_MAX_GATHER & (SEARCH_WIDE_MAX_GATHER - 1)) == 0 && SEARCH_WIDE_CHUNK == SEARCH_WIDE_THREADS &&
+                  4 * SEARCH_WIDE_MAX_GATHER + 4 * (SEARCH_MAX_MEMBERS + 1) + 16 * SEARCH_WIDE_CHUNK + 256 <= 160 * 1024,
+              "search_seeds_wide.hip: one workgroup's LDS is a CU's 160 KB at most; a round of entries fits an empty chunk");
+// a window of the count pass that search_window_wide_kernel can take (include/sedef_hip.h: SDF_SEARCH_WIDE_DONE)
+__host__ __device__ inline bool search_wide_eligible(const sdf_search_window &W) {
+  return (W.flags & (SDF_SEARCH_WIDE | SDF_SEARCH_FOUND_WIDE)) && !(W.flags & SDF_SEARCH_NOLIMIT) && W.n_members <= SEARCH_MAX_MEMBERS &&
+         W.n_gathered <= SEARCH_WIDE_MAX_GATHER;
+}
+__global__ void search_wide_list_kernel(const sdf_search_window *, int, uint32_t, uint32_t *, unsigned long long *, unsigned long long *);
+template <bool EMIT, bool FOUND>
+__global__ void search_window_wide_kernel(const sdf_minimizer *, int, long long, const sdf_minimizer *, const SearchLook *, int, int,
+                                          const int32_t *, int, sdf_search_window *, uint32_t *, const uint64_t *, sdf_search_interval *,
+                                          uint64_t, FoundIndex, const uint32_t *, const unsigned long long *, uint32_t);
 // search_roll.hip
 constexpr int ROLL_MAX_SPAN = SDF_ROLL_MAX_SPAN, ROLL_MAX_KEYS = SEARCH_MAX_MEMBERS + ROLL_MAX_SPAN;  // a wavefront's LDS: 32-bit keys, 16-bit slots
 static_assert(ROLL_MAX_KEYS < 65535 && sizeof(sdf_search_roll_rec) == 24, "search_roll.hip: slots are 16 bits wide; include/sedef_hip.h");

@@ -11,11 +11,34 @@
 
 using namespace sdf;
 
-// The launches in front of the intervals, on `st`: keys, their sort, prev, lookup, the windows' records and counts, d_first.
+// What sdf_search_windows_wide_device adds to a call: the list's room, and where the caller wants the number of eligible windows.
+struct WideRun {
+  size_t n_max;
+  uint64_t *d_total;
+};
+template <bool EMIT>
+static void wide_launch(sdf_ctx *ctx, const WideRun &wide, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r,
+                        int32_t init_len, int same_genome, const int32_t *d_limit, size_t n_limit, sdf_search_window *d_windows,
+                        const uint64_t *d_first, sdf_search_interval *d_out, size_t cap, hipStream_t st, const FoundIndex *F) {
+  const auto kernel = F ? search_window_wide_kernel<EMIT, true> : search_window_wide_kernel<EMIT, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)wide.n_max), dim3(SEARCH_WIDE_THREADS), 0, st, d_q, (int)nq, (long long)len_q, d_r,
+                     (const SearchLook *)ctx->sw_look.p, (int)init_len, same_genome, d_limit, (int)n_limit, d_windows, (uint32_t *)ctx->sw_counts.p,
+                     d_first, d_out, (uint64_t)cap, F ? *F : FoundIndex{}, (const uint32_t *)ctx->sw_wide.p,
+                     (const unsigned long long *)ctx->sw_nwide.p, (uint32_t)wide.n_max);
+  ctx->launches += 1;
+}
+
+// The launches in front of the intervals, on `st`: keys, their sort, prev, lookup, the windows' records and counts (wide: the list
+// and the listed windows' records and counts behind them), d_first.
 static int search_count(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r, size_t nr,
                         uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *d_limit, size_t n_limit,
-                        uint64_t *d_first, sdf_search_window *d_windows, hipStream_t st, const FoundIndex *F = nullptr) {
+                        uint64_t *d_first, sdf_search_window *d_windows, hipStream_t st, const FoundIndex *F = nullptr,
+                        const WideRun *wide = nullptr) {
   const int n = (int)nq;
+  if (wide) {
+    SDF_HIP(ctx->sw_wide.reserve(wide->n_max * 4));
+    SDF_HIP(ctx->sw_nwide.reserve(8));
+  }
   SDF_HIP(ctx->sw_keys.reserve(2 * nq * 8));
   SDF_HIP(ctx->sw_vals.reserve(2 * nq * 4));
   SDF_HIP(ctx->sw_look.reserve(nq * sizeof(SearchLook)));
@@ -36,6 +59,12 @@ static int search_count(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64
   hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(64), 0, st, d_q, n, (long long)len_q, d_r, (const SearchLook *)d_look, (int)init_len,
                      same_genome, d_limit, (int)n_limit, d_windows, d_counts, (const uint64_t *)nullptr, (sdf_search_interval *)nullptr,
                      (uint64_t)0, F ? *F : FoundIndex{});
+  if (wide) {
+    hipLaunchKernelGGL(search_wide_list_kernel, dim3(1), dim3(1024), 0, st, (const sdf_search_window *)d_windows, n, (uint32_t)wide->n_max,
+                       (uint32_t *)ctx->sw_wide.p, (unsigned long long *)ctx->sw_nwide.p, (unsigned long long *)wide->d_total);
+    ctx->launches += 1;
+    wide_launch<false>(ctx, *wide, d_q, nq, len_q, d_r, init_len, same_genome, d_limit, n_limit, d_windows, nullptr, nullptr, 0, st, F);
+  }
   hipLaunchKernelGGL(stats_cuts_scan_kernel, dim3(1), dim3(1024), 0, st, d_counts, n, d_first);
   SDF_HIP(hipGetLastError());
   ctx->launches += 5;
@@ -44,22 +73,24 @@ static int search_count(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64
 // the intervals (after search_count on the same stream)
 static int search_emit(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r, int32_t init_len,
                        int same_genome, const int32_t *d_limit, size_t n_limit, const uint64_t *d_first, sdf_search_interval *d_out,
-                       size_t cap, hipStream_t st, const FoundIndex *F = nullptr) {
+                       size_t cap, hipStream_t st, const FoundIndex *F = nullptr, const WideRun *wide = nullptr) {
   const auto kernel = F ? search_window_kernel<true, true> : search_window_kernel<true, false>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(64), 0, st, d_q, (int)nq, (long long)len_q, d_r,
                      (const SearchLook *)ctx->sw_look.p, (int)init_len, same_genome, d_limit, (int)n_limit, (sdf_search_window *)nullptr,
                      (uint32_t *)nullptr, d_first, d_out, (uint64_t)cap, F ? *F : FoundIndex{});
-  SDF_HIP(hipGetLastError());
   ctx->launches += 1;
+  if (wide) wide_launch<true>(ctx, *wide, d_q, nq, len_q, d_r, init_len, same_genome, d_limit, n_limit, nullptr, d_first, d_out, cap, st, F);
+  SDF_HIP(hipGetLastError());
   return SDF_OK;
 }
 
-// sdf_search_windows_device, and with_found sdf_search_windows_found_device (a list without a record runs the plain kernels)
+// sdf_search_windows_device, and with_found sdf_search_windows_found_device (a list without a record runs the plain kernels);
+// n_wide_max > 0: sdf_search_windows_wide_device
 static int windows_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted, size_t nr,
                           uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds, const int32_t *d_limit, size_t n_limit,
                           bool with_found, const sdf_search_found *d_found, size_t nf, size_t found_entries_cap, uint64_t *d_found_entries,
                           const uint32_t *d_visible, uint64_t *d_first, sdf_search_window *d_windows, sdf_search_interval *d_out, size_t cap,
-                          size_t *used, void *stream) {
+                          size_t *used, void *stream, size_t n_wide_max = 0, uint64_t *d_wide_total = nullptr) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
   if (nq == 0) {
@@ -73,6 +104,8 @@ static int windows_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int
   if (int rc = search_scalars(nq, nr, init_len, n_limit, &why)) return refuse(ctx, rc, why);
   if (with_found)
     if (int rc = found_scalars(nf, found_entries_cap, &why)) return refuse(ctx, rc, why);
+  if (n_wide_max > SEARCH_WIDE_MAX_LIST) return refuse(ctx, SDF_ERR_UNSUPPORTED, "sdf_search_windows_wide_device: n_wide_max > 2^20");
+  const WideRun wide{n_wide_max, d_wide_total}, *Wp = n_wide_max ? &wide : nullptr;
   SDF_HIP(hipSetDevice(ctx->device));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   FoundIndex F{};
@@ -80,9 +113,9 @@ static int windows_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int
     if (int rc = found_index(ctx, d_found, nf, found_entries_cap, d_found_entries, d_visible, st, &F)) return rc;
   const FoundIndex *Fp = with_found && nf ? &F : nullptr;
   if (int rc = search_count(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome != 0, uppercase_seeds != 0, d_limit,
-                            n_limit, d_first, d_windows, st, Fp))
+                            n_limit, d_first, d_windows, st, Fp, Wp))
     return rc;
-  if (int rc = search_emit(ctx, d_q, nq, len_q, d_r_sorted, init_len, same_genome != 0, d_limit, n_limit, d_first, d_out, cap, st, Fp)) return rc;
+  if (int rc = search_emit(ctx, d_q, nq, len_q, d_r_sorted, init_len, same_genome != 0, d_limit, n_limit, d_first, d_out, cap, st, Fp, Wp)) return rc;
   if (stream) return SDF_OK;
   const int rc = counted_need(ctx, d_first, nq, nullptr, st, cap, used, "the windows have ", " intervals, more than cap");
   if (rc == SDF_ERR_HIP || !with_found) return rc;
@@ -108,6 +141,18 @@ extern "C" int sdf_search_windows_found_device(sdf_ctx *ctx, const sdf_minimizer
                                                void *stream) {
   return windows_device(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome, uppercase_seeds, d_limit, n_limit, true,
                         d_found, nf, found_entries_cap, d_found_entries, d_visible, d_first, d_windows, d_out, cap, used, stream);
+}
+
+extern "C" int sdf_search_windows_wide_device(sdf_ctx *ctx, const sdf_minimizer *d_q, size_t nq, int64_t len_q, const sdf_minimizer *d_r_sorted,
+                                              size_t nr, uint32_t r_threshold, int32_t init_len, int same_genome, int uppercase_seeds,
+                                              const int32_t *d_limit, size_t n_limit, const sdf_search_found *d_found, size_t nf,
+                                              size_t found_entries_cap, uint64_t *d_found_entries, const uint32_t *d_visible,
+                                              uint64_t *d_first, sdf_search_window *d_windows, sdf_search_interval *d_out, size_t cap,
+                                              size_t *used, size_t n_wide_max, uint64_t *d_wide_total, void *stream) {
+  // (no record and no prefixes: the plain form, without an index)
+  return windows_device(ctx, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome, uppercase_seeds, d_limit, n_limit,
+                        nf != 0 || d_visible != nullptr, d_found, nf, found_entries_cap, d_found_entries, d_visible, d_first, d_windows, d_out, cap,
+                        used, stream, n_wide_max, d_wide_total);
 }
 
 // sdf_search_windows, and with_found sdf_search_windows_found: the device form on copies, what it left completed on the host

@@ -1,10 +1,18 @@
 // Device helpers the search kernels share (search_seeds.hip, search_roll.hip, search_extend.hip): a workgroup is ONE wavefront, its keys lie in LDS.
+// The `_wg` forms at the end serve search_seeds_wide.hip, whose workgroup is several wavefronts: they take the thread index and
+// the thread count, and every lane of the workgroup calls them together.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "sdf_kernels.h"
+#include "stats_dev.h"
 
 namespace sdf {
+
+// a loc as a sort key whose unsigned order is the locs' signed order, and back; kSearchGone: a filtered loc (sorts last)
+constexpr uint32_t kSearchGone = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t search_loc_key(int loc) { return (uint32_t)loc ^ 0x80000000u; }
+__device__ __forceinline__ long long search_key_loc(uint32_t k) { return (long long)(int)(k ^ 0x80000000u); }
 
 // ascending sort of a[0 .. n) in LDS by the workgroup's single wavefront: chain_sort_u64's network (chain.hip) on 32-bit keys
 __device__ __forceinline__ void search_sort_u32(uint32_t *a, const int n, const int lane) {
@@ -194,6 +202,84 @@ __device__ __forceinline__ void search_roll_walk(SearchMap &S, Slots slot, Locs 
     if (eval(s, e, ws, we)) return;
     s++, e++;
   }
+}
+
+// ---- a workgroup of nt lanes (a multiple of 64), tid its thread index ----
+
+// The exclusive prefix sum of v over the workgroup, *all its sum: stats_wave_scan inside a wavefront, the wavefronts' totals
+// through ws[0 .. nt / 64) in LDS.  Two barriers: what the lanes read before the call is read before anything written after it.
+__device__ __forceinline__ int search_wg_scan(const int v, int *all, int *ws, const int tid, const int nt) {
+  const int in = stats_wave_scan(v), wave = tid >> 6;
+  __syncthreads();  // (ws[] of the call before has been read)
+  if ((tid & 63) == 63) ws[wave] = in;
+  __syncthreads();
+  int before = 0, sum = 0;
+  for (int k = 0; k < nt >> 6; k++) {
+    const int s = ws[k];
+    before += k < wave ? s : 0;
+    sum += s;
+  }
+  *all = sum;
+  return before + in - v;
+}
+
+// the exact sum of v over the workgroup, through ws[0 .. nt / 64)
+__device__ __forceinline__ long long search_wg_sum64(const long long v, long long *ws, const int tid, const int nt) {
+  long long s = v;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+  __syncthreads();
+  if ((tid & 63) == 0) ws[tid >> 6] = s;
+  __syncthreads();
+  long long sum = 0;
+  for (int k = 0; k < nt >> 6; k++) sum += ws[k];
+  return sum;
+}
+
+// search_sort_u32 by the whole workgroup: the same network, nt compare-exchanges a step
+__device__ __forceinline__ void search_sort_u32_wg(uint32_t *a, const int n, const int tid, const int nt) {
+  int np2 = 1;
+  while (np2 < n) np2 <<= 1;
+  for (int k = 2; k <= np2; k <<= 1) {
+    for (int idx = tid; idx < np2 / 2; idx += nt) {
+      const int blk = idx / (k / 2), off = idx % (k / 2);
+      const int i = blk * k + off, j = blk * k + k - 1 - off;
+      if (j < n) {
+        const uint32_t x = a[i], y = a[j];
+        if (x > y) a[i] = y, a[j] = x;
+      }
+    }
+    __syncthreads();
+    for (int jj = k / 4; jj >= 1; jj >>= 1) {
+      for (int idx = tid; idx < np2 / 2; idx += nt) {
+        const int i = (idx / jj) * 2 * jj + idx % jj, j = i + jj;
+        if (j < n) {
+          const uint32_t x = a[i], y = a[j];
+          if (x > y) a[i] = y, a[j] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// search_compact_u32 by the whole workgroup, nt keys a round: a round reads its keys and the one in front of them before it
+// writes (search_wg_scan's barriers), and never writes behind what it read -- the key in front of a round, c[s0 - 1], is either
+// untouched by the rounds before or was rewritten with itself (every key before it was distinct).  Returns the distinct keys.
+__device__ __forceinline__ int search_compact_u32_wg(uint32_t *c, const int nv, int *ws, const int tid, const int nt) {
+  int nc = 0;
+  for (int s0 = 0; s0 < nv; s0 += nt) {
+    const int s = s0 + tid;
+    const bool in = s < nv;
+    const uint32_t mine = in ? c[s] : 0u, left = in && s > 0 ? c[s - 1] : 0u;
+    const bool fresh = in && (s == 0 || mine != left);
+    int all;
+    const int at = search_wg_scan(fresh ? 1 : 0, &all, ws, tid, nt);
+    if (fresh) c[nc + at] = mine;
+    nc += all;
+    __syncthreads();
+  }
+  return nc;
 }
 
 }  // namespace sdf

@@ -85,11 +85,7 @@ __global__ __launch_bounds__(256) void search_lookup_kernel(const sdf_minimizer 
   look[j].size = size;
 }
 
-// a loc as a sort key whose unsigned order is the locs' signed order, and back; kSearchGone: a filtered loc (sorts last)
-constexpr uint32_t kSearchGone = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t search_loc_key(int loc) { return (uint32_t)loc ^ 0x80000000u; }
-__device__ __forceinline__ long long search_key_loc(uint32_t k) { return (long long)(int)(k ^ 0x80000000u); }
-
+// (search_dev.h: a loc as a sort key and back, kSearchGone)
 // EMIT false: windows[i] and counts[i] (the window's intervals); true: the intervals, from out[first[i]], none at or behind out[cap].
 // FOUND (include/sedef_hip.h, the section of the found records): the visible records that meet the window are staged in LDS
 // from the bins the window touches, and a gathered position that one of them covers at its member's loc is dropped like one

@@ -63,6 +63,8 @@ assert SEARCH_WINDOW_DTYPE.itemsize == 20 and SEARCH_INTERVAL_DTYPE.itemsize == 
 # include/sedef_hip.h: sdf_search_found (search_windows_found, search_overlap; SEARCH_FOUND_WIDE in a window's `flags`)
 SEARCH_FOUND_DTYPE = np.dtype([("q_start", "<i4"), ("q_end", "<i4"), ("r_start", "<i4"), ("r_end", "<i4")])
 SEARCH_FOUND_WIDE, SEARCH_MAX_FOUND, SEARCH_FOUND_BIN_SHIFT = 0x8, 256, 12
+# include/sedef_hip.h: a window search_windows_wide_device finished (WIDE and FOUND_WIDE cleared), and the positions it gathers
+SEARCH_WIDE_DONE, SEARCH_WIDE_MAX_GATHER = 0x10, 32768
 assert SEARCH_FOUND_DTYPE.itemsize == 16
 # include/sedef_hip.h: sdf_search_roll_rec (search_roll; ROLL_* in `flags`)
 SEARCH_ROLL_DTYPE = np.dtype([("ref_start", "<i4"), ("ref_end", "<i4"), ("winnow_start", "<i4"), ("winnow_end", "<i4"),
@@ -294,6 +296,8 @@ def load_library():
     L.sdf_search_windows_found.argtypes = [C.c_void_p] + _search[:11] + _found + _search[11:]
     L.sdf_search_windows_found_device.restype = C.c_int
     L.sdf_search_windows_found_device.argtypes = [C.c_void_p] + _search[:11] + _found_dev + _search[11:] + [C.c_void_p]
+    L.sdf_search_windows_wide_device.restype = C.c_int  # ... used, n_wide_max, d_wide_total, stream
+    L.sdf_search_windows_wide_device.argtypes = [C.c_void_p] + _search[:11] + _found_dev + _search[11:] + [C.c_size_t, C.c_void_p, C.c_void_p]
     L.sdf_search_windows_found_host.restype = C.c_int
     L.sdf_search_windows_found_host.argtypes = _search[:11] + _found + _search[11:]
     _overlap = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]  # q, nq, first, rolls
@@ -358,6 +362,8 @@ def load_library():
     L.sdf_search_pair.restype = C.c_int  # ctx, q_range, r_range, params, out, cap, used, stats
     L.sdf_search_pair.argtypes = [C.c_void_p, C.POINTER(_MinimRange), C.POINTER(_MinimRange), C.POINTER(_PairParams), C.c_void_p,
                                   C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.sdf_search_pair_wide.restype = C.c_int  # ... stats, n_wide_max
+    L.sdf_search_pair_wide.argtypes = L.sdf_search_pair.argtypes + [C.c_size_t]
     L.sdf_search_index_build.restype = C.c_int  # ctx, range, k, w, separate_lowercase, out
     L.sdf_search_index_build.argtypes = [C.c_void_p, C.POINTER(_MinimRange), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.sdf_search_index_free.restype = C.c_int
@@ -371,6 +377,8 @@ def load_library():
     L.sdf_search_pair_indexed.restype = C.c_int  # ctx, q, r, params, out, cap, used, stats
     L.sdf_search_pair_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_PairParams), C.c_void_p, C.c_size_t,
                                           C.POINTER(C.c_size_t), C.c_void_p]
+    L.sdf_search_pair_indexed_wide.restype = C.c_int  # ... stats, n_wide_max
+    L.sdf_search_pair_indexed_wide.argtypes = L.sdf_search_pair_indexed.argtypes + [C.c_size_t]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -1069,6 +1077,60 @@ class Extz2Engine:
             d_out, cap, C.byref(used), stream))
         return int(used.value)
 
+    def search_windows_wide_device(self, d_q, nq, len_q, d_r_sorted, nr, r_threshold, init_len, same_genome, uppercase_seeds, d_limit,
+                                   n_limit, d_found, nf, found_entries_cap, d_found_entries, d_visible, d_first, d_windows, d_out, cap,
+                                   n_wide_max, d_wide_total=None, stream=None):
+        """sdf_search_windows_wide_device: search_windows_found_device, and the lowest n_wide_max windows it flags WIDE or
+        FOUND_WIDE and that fit the wide kernel (at most SEARCH_MAX_MEMBERS members and SEARCH_WIDE_MAX_GATHER gathered
+        positions, no NOLIMIT) finished on the device: SEARCH_WIDE_DONE instead of the two flags, the counts and intervals of
+        the host form.  d_wide_total: eight bytes that receive the number of such windows, or None."""
+        used = C.c_size_t(0)
+        self._check(self.lib.sdf_search_windows_wide_device(
+            self.ctx, d_q, nq, int(len_q), d_r_sorted, nr, int(r_threshold), int(init_len), int(bool(same_genome)),
+            int(bool(uppercase_seeds)), d_limit, n_limit, d_found, nf, found_entries_cap, d_found_entries, d_visible, d_first, d_windows,
+            d_out, cap, C.byref(used), int(n_wide_max), d_wide_total, stream))
+        return int(used.value)
+
+    def search_windows_wide(self, q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, found=None,
+                            visible=None, n_wide_max=64):
+        """search_windows_wide_device on numpy arrays: uploads them, runs the call on the context's stream (a second time when
+        the first found the intervals' room short) and brings the answer back.  Returns (first, windows, intervals, wide_total):
+        wide_total the windows the wide kernel could take, of which the lowest n_wide_max are SEARCH_WIDE_DONE."""
+        import torch
+        q = np.ascontiguousarray(q, dtype=MINIMIZER_DTYPE)
+        r_sorted = np.ascontiguousarray(r_sorted, dtype=MINIMIZER_DTYPE)
+        limit = np.ascontiguousarray(limit, dtype=np.int32)
+        found = np.zeros(0, SEARCH_FOUND_DTYPE) if found is None else np.ascontiguousarray(found, dtype=SEARCH_FOUND_DTYPE)
+        visible = np.zeros(len(q), np.uint32) if visible is None else np.ascontiguousarray(visible, dtype=np.uint32)
+        assert len(visible) == len(q)
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+        def ptr(t):
+            return t.data_ptr() if t.numel() else None
+        d_q, d_r, d_limit, d_found, d_vis = up(q), up(r_sorted), up(limit), up(found), up(visible)
+        d_first = torch.zeros(len(q) + 1, dtype=torch.int64, device="cuda")
+        d_win = torch.zeros(len(q) * SEARCH_WINDOW_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        cap = 4096
+        while True:
+            d_out = torch.zeros(cap * SEARCH_INTERVAL_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()  # (the tensors were filled on torch's stream)
+            used = C.c_size_t(0)
+            rc = self.lib.sdf_search_windows_wide_device(
+                self.ctx, ptr(d_q), len(q), int(len_q), ptr(d_r), len(r_sorted), int(r_threshold), int(init_len), int(bool(same_genome)),
+                int(bool(uppercase_seeds)), ptr(d_limit), len(limit), ptr(d_found), len(found), found_entries(found), None, ptr(d_vis),
+                d_first.data_ptr(), ptr(d_win), d_out.data_ptr(), cap, C.byref(used), int(n_wide_max), d_total.data_ptr(), None)
+            if rc != -5 or int(used.value) <= cap:
+                break
+            cap = int(used.value)
+        self._check(rc)
+        n = int(used.value)
+        return (d_first.cpu().numpy(), np.frombuffer(d_win.cpu().numpy().tobytes(), SEARCH_WINDOW_DTYPE),
+                np.frombuffer(d_out.cpu().numpy().tobytes()[:n * SEARCH_INTERVAL_DTYPE.itemsize], SEARCH_INTERVAL_DTYPE),
+                int(d_total.cpu()[0]) if len(q) and n_wide_max else 0)
+
     def search_overlap_raw(self, q, first, rolls, found, visible_iv, init_len, min_read_size):
         """sdf_search_overlap as it is: the reference's is_overlap for every rolled interval.  q, first: as search_windows_raw
         takes and returns them; rolls: search_roll_raw's records; found: a SEARCH_FOUND_DTYPE array; visible_iv: per interval
@@ -1090,6 +1152,11 @@ class Extz2Engine:
         acceptance step run in rounds on the device.  Arguments and result as search_pair_host's, and round_windows (0: the
         default) and debug_host_every (every n-th scheduled window on the host)."""
         return search_pair_call(self.lib.sdf_search_pair, (self.ctx,), q_range, r_range, **kw)
+
+    def search_pair_wide(self, q_range, r_range, n_wide_max=64, **kw):
+        """sdf_search_pair_wide: search_pair whose rounds finish up to n_wide_max WIDE / FOUND_WIDE windows of the seeding on
+        the device (search_windows_wide_device) where search_pair hands them to the host."""
+        return search_pair_call(self.lib.sdf_search_pair_wide, (self.ctx,), q_range, r_range, tail=(int(n_wide_max),), **kw)
 
     def search_index_build(self, rng, k=12, w=16, separate_lowercase=True):
         """sdf_search_index_build: the minimizers and the index of one range (off, len) or (off, len, flags) of the resident
@@ -1118,6 +1185,10 @@ class Extz2Engine:
         """sdf_search_pair_indexed: search_pair on two handles of search_index_build (same_genome: one handle as both).
         Keywords and result as search_pair's."""
         return search_pair_call(self.lib.sdf_search_pair_indexed, (self.ctx,), q_index, r_index, **kw)
+
+    def search_pair_indexed_wide(self, q_index, r_index, n_wide_max=64, **kw):
+        """sdf_search_pair_indexed_wide: search_pair_wide on two handles of search_index_build."""
+        return search_pair_call(self.lib.sdf_search_pair_indexed_wide, (self.ctx,), q_index, r_index, tail=(int(n_wide_max),), **kw)
 
     def search_accept_raw(self, *args, **kw):
         """sdf_search_accept as it is: one round of the search driver's acceptance step on numpy arrays, run by the device
@@ -1528,9 +1599,9 @@ def search_accept_host(*args, **kw):
 
 
 def search_pair_call(fn, head, q_range, r_range, k=12, w=16, separate_lowercase=True, uppercase_seeds=True, min_read_size=700,
-                     same_genome=False, limit=(), filter=None, extend=None, cap=None, round_windows=0, debug_host_every=0):
-    """sdf_search_pair (head: its context) or sdf_search_pair_host (head: the characters and their number).  Returns
-    (rc, hits, used, stats)."""
+                     same_genome=False, limit=(), filter=None, extend=None, cap=None, round_windows=0, debug_host_every=0, tail=()):
+    """sdf_search_pair (head: its context) or sdf_search_pair_host (head: the characters and their number); tail: what a form
+    takes behind stats (the _wide forms' n_wide_max).  Returns (rc, hits, used, stats)."""
     limit = np.ascontiguousarray(limit, dtype=np.int32)
     P = _PairParams(int(k), int(w), int(bool(separate_lowercase)), int(bool(uppercase_seeds)), int(min_read_size), int(bool(same_genome)),
                     filter_params() if filter is None else filter,
@@ -1546,7 +1617,7 @@ def search_pair_call(fn, head, q_range, r_range, k=12, w=16, separate_lowercase=
     while True:
         out = np.zeros(room, SEARCH_PAIR_HIT_DTYPE)
         rc = fn(*head, ranges[0], ranges[1], C.byref(P), out.ctypes.data if room else None, room, C.byref(used),
-                stats.ctypes.data)
+                stats.ctypes.data, *tail)
         if rc != -5 or cap is not None:
             break
         room = int(used.value)

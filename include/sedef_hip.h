@@ -1342,6 +1342,48 @@ int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, const sdf_s
 int sdf_search_pair_indexed_wide(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
                                  sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats, size_t n_wide_max);
 
+/* ---- several pairs in flight: lanes ------------------------------------------------------------------------------------------
+ * The rounds of ONE pair cannot overlap -- each needs the found list the round before it left --, and a round is a few dozen
+ * wavefronts behind about twenty launches and one wait.  The rounds of DIFFERENT pairs are independent (the reference makes a
+ * fresh Tree per initial_search call and keeps one Index per chromosome and strand for all of them, src/search.cc), so a run
+ * over many pairs keeps several of them in flight.
+ *   sdf_search_lanes_open   n_lanes (1 .. SDF_SEARCH_LANES_MAX, else SDF_ERR_INVALID) child contexts of ctx on ctx's device, with
+ *                           ctx's sdf_config.  A lane holds a VIEW of ctx's pool (sdf_pool_share), a stream of its own and its
+ *                           own per-call buffers, reserved by need: it costs what its rounds reserve.  While lanes are open ctx's
+ *                           pool is shared, and the rule of sdf_pool_share holds unchanged: ctx cannot grow or replace its pool
+ *                           (SDF_ERR_INVALID, "pool is shared").  sdf_device_bytes(ctx) counts the lanes' buffers.  A lanes
+ *                           object is recognised by ADDRESS in a list ctx keeps, as handles are.
+ *   sdf_search_lanes_close  destroys the lanes and drops their views: appending to the pool works again, and ctx's handles stay
+ *                           valid, as after any append.  NULL is SDF_OK; lanes that are not live lanes of ctx: SDF_ERR_INVALID.
+ *                           sdf_destroy(ctx) closes the lanes that are still open.
+ *   sdf_search_pairs_indexed  job j is sdf_search_pair_indexed_wide(jobs[j].q, jobs[j].r, params with same_genome and
+ *                           extend.same_genome taken from jobs[j].same_genome, n_wide_max).  Its hits are out[first[j],
+ *                           first[j + 1]), in job order, first[0] == 0 and *used == first[n_jobs]; stats[j] is that call's stats.
+ *                           The hits and the counters attempted, jaccard_failed, interval_failed and windows_scheduled equal the
+ *                           single-pair call's byte for byte, for every n_lanes, every round_windows and whatever order the lanes
+ *                           took the jobs in.  The handles are ctx's: a lane reads them (their liveness and pool_epoch are
+ *                           checked against ctx) and never builds, frees or writes one, so the same (q, r) may appear in several
+ *                           jobs and one handle may serve several lanes at once.  One host thread per lane lives inside the
+ *                           call and is joined before it returns; the jobs come off one shared queue, those with the most query
+ *                           minimizers first; with n_jobs < n_lanes the spare lanes stay idle.  n_jobs == 0: SDF_OK, first[0] = 0.
+ * Before the first launch, for ALL jobs -- nothing is written, the context stays usable --: SDF_ERR_INVALID for a null pointer (out
+ * may be null with cap == 0; jobs and stats with n_jobs == 0), lanes that are not live lanes of ctx, a job with a null, freed,
+ * foreign or stale handle, k, w or separate_lowercase different from a handle's, same_genome with q != r; then the refusals of
+ * sdf_search_pair_indexed_wide on each job's ranges and on n_wide_max, with their codes.  sdf_last_error names the job.
+ * SDF_ERR_CIGAR_OVERFLOW: the jobs' hits exceed cap; *used and all of first[] are right, out is unspecified, and a second call
+ * with cap >= *used succeeds.  A job that fails in flight: jobs not yet started are not started (after a HIP error nothing more
+ * is started on the device in the call), those running finish; the call returns the code of the failed job with the lowest
+ * index, *used = 0, and sdf_last_error gives that lane's message behind the job's index.
+ * Calls on one context do not overlap; a lanes object serves one call at a time. */
+#define SDF_SEARCH_LANES_MAX 16
+typedef struct sdf_search_lanes sdf_search_lanes;
+typedef struct { const sdf_search_index *q, *r; int32_t same_genome, reserved; } sdf_search_pair_job; /* 24 bytes */
+int sdf_search_lanes_open(sdf_ctx *ctx, int n_lanes, sdf_search_lanes **out);
+int sdf_search_lanes_close(sdf_ctx *ctx, sdf_search_lanes *lanes);
+int sdf_search_pairs_indexed(sdf_ctx *ctx, sdf_search_lanes *lanes, const sdf_search_pair_job *jobs, size_t n_jobs,
+                             const sdf_search_pair_params *params, size_t n_wide_max, sdf_search_pair_hit *out, size_t cap,
+                             size_t *used, uint64_t *first /* n_jobs + 1 */, sdf_search_pair_stats *stats /* n_jobs */);
+
 /* ---- multi-GPU: the one exchange step of the path.  DP tasks are independent (the reference runs one
  * single-threaded process per bucket file and concatenates their output files, sedef.sh:187-190,218-221), so a batch is
  * sharded over the GPUs of a node with no data-path collective; after the DP an RCCL all-gatherv over xGMI gives every GPU

@@ -1107,6 +1107,7 @@ StageSettings StageSettings::from_env() {
   s.stats_resident = num("SDF_STATS_RESIDENT", 0, 1, 0) != 0;
   s.stats_cuts_device = num("SDF_STATS_CUTS_DEVICE", 0, 1, 0) != 0;
   s.search_wide = (int)num("SDF_SEARCH_WIDE_DEVICE", 0, 1 << 20, 0);
+  s.search_lanes = (int)num("SDF_SEARCH_LANES", 1, 16, 1);
   s.stage_resident = num("SDF_STAGE_RESIDENT", 0, 1, 0) != 0;
   s.fetch_device = num("SDF_STAGE_FETCH_DEVICE", 0, 1, 0) != 0;
   if (const char *e = getenv("SDF_DEVICES"))

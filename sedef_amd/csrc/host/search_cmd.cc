@@ -1,5 +1,6 @@
 // `sedef search` and `sedef translate` (restates the CLI contract of reference src/search_main.cc:93-241): the pair loop over
-// resident chromosomes and their search indexes (include/sedef_hip.h: sdf_search_index_build, sdf_search_pair_indexed), the BED
+// resident chromosomes and their search indexes (include/sedef_hip.h: sdf_search_index_build, sdf_search_pair_indexed; with
+// SDF_SEARCH_LANES=N the pairs as one sdf_search_pairs_indexed call, N in flight), the BED
 // text of a search hit, the translation groups, and the caller's table of the search entry points --
 // relaxed_jaccard_estimate(query_size), src/util.cc:52-113 -- stated without Boost.
 #include <chrono>
@@ -386,33 +387,69 @@ int search_command(const SearchParams &p, FILE *out, FILE *log) {
   const size_t n_wide = (size_t)stage_settings().search_wide;
   std::vector<sdf_search_pair_hit> hits(1024);
   std::string text;
-  for (auto &r : rr)
-    for (auto &q : qr) {
-      P.same_genome = (q == r) && !p.reverse;
-      P.extend.same_genome = P.same_genome;
-      const sdf_search_index *qh = indices[{q, false}], *rh = indices[{r, p.reverse}];
-      size_t used = 0;
-      sdf_search_pair_stats st;
-      // (SDF_SEARCH_WIDE_DEVICE=N: the seeding's WIDE / FOUND_WIDE windows on the device; 0 is sdf_search_pair_indexed itself)
-      int rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
-      if (rc == SDF_ERR_CIGAR_OVERFLOW) {
-        hits.resize(used + used / 2);
-        rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
-      }
-      C.check(rc, "sdf_search_pair_indexed");
-      text.clear();
-      for (size_t i = 0; i < used; i++)
-        text += search_hit_bed(q, r, hits[i].query_start, hits[i].query_end, hits[i].ref_start, hits[i].ref_end, p.reverse,
-                               (size_t)chroms[r].len) + "\n";
-      fwrite(text.data(), 1, text.size(), out);
-      total += (long long)used, attempted += st.attempted, jaccard_failed += st.jaccard_failed, interval_failed += st.interval_failed;
-      pairs += 1;
+  const int n_lanes = stage_settings().search_lanes;
+  if (n_lanes > 1) {
+    // SDF_SEARCH_LANES=N: every pair of the loop below as one job of one call, N of them in flight; the lines in the loop's order
+    sdf_search_lanes *lanes = nullptr;
+    C.check(sdf_search_lanes_open(C.ctx, n_lanes, &lanes), "sdf_search_lanes_open");
+    std::vector<sdf_search_pair_job> jobs;
+    for (auto &r : rr)
+      for (auto &q : qr) jobs.push_back(sdf_search_pair_job{indices[{q, false}], indices[{r, p.reverse}], (q == r) && !p.reverse, 0});
+    std::vector<uint64_t> first(jobs.size() + 1);
+    std::vector<sdf_search_pair_stats> stats(jobs.size());
+    // (an overflow costs a second run of EVERY pair, where the loop repeats one: room for 4,096 hits a pair from the start)
+    hits.resize(std::max(hits.size(), 4096 * jobs.size()));
+    size_t used = 0;
+    int rc = sdf_search_pairs_indexed(C.ctx, lanes, jobs.data(), jobs.size(), &P, n_wide, hits.data(), hits.size(), &used, first.data(), stats.data());
+    if (rc == SDF_ERR_CIGAR_OVERFLOW) {
+      hits.resize(used + used / 2);
+      rc = sdf_search_pairs_indexed(C.ctx, lanes, jobs.data(), jobs.size(), &P, n_wide, hits.data(), hits.size(), &used, first.data(), stats.data());
     }
+    C.check(rc, "sdf_search_pairs_indexed");
+    C.check(sdf_search_lanes_close(C.ctx, lanes), "sdf_search_lanes_close");
+    size_t j = 0;
+    for (auto &r : rr)
+      for (auto &q : qr) {
+        text.clear();
+        for (size_t i = (size_t)first[j]; i < (size_t)first[j + 1]; i++)
+          text += search_hit_bed(q, r, hits[i].query_start, hits[i].query_end, hits[i].ref_start, hits[i].ref_end, p.reverse,
+                                 (size_t)chroms[r].len) + "\n";
+        fwrite(text.data(), 1, text.size(), out);
+        attempted += stats[j].attempted, jaccard_failed += stats[j].jaccard_failed, interval_failed += stats[j].interval_failed;
+        j += 1;
+      }
+    total = (long long)used, pairs = (long long)jobs.size();
+  } else {
+    for (auto &r : rr)
+      for (auto &q : qr) {
+        P.same_genome = (q == r) && !p.reverse;
+        P.extend.same_genome = P.same_genome;
+        const sdf_search_index *qh = indices[{q, false}], *rh = indices[{r, p.reverse}];
+        size_t used = 0;
+        sdf_search_pair_stats st;
+        // (SDF_SEARCH_WIDE_DEVICE=N: the seeding's WIDE / FOUND_WIDE windows on the device; 0 is sdf_search_pair_indexed itself)
+        int rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
+        if (rc == SDF_ERR_CIGAR_OVERFLOW) {
+          hits.resize(used + used / 2);
+          rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
+        }
+        C.check(rc, "sdf_search_pair_indexed");
+        text.clear();
+        for (size_t i = 0; i < used; i++)
+          text += search_hit_bed(q, r, hits[i].query_start, hits[i].query_end, hits[i].ref_start, hits[i].ref_end, p.reverse,
+                                 (size_t)chroms[r].len) + "\n";
+        fwrite(text.data(), 1, text.size(), out);
+        total += (long long)used, attempted += st.attempted, jaccard_failed += st.jaccard_failed, interval_failed += st.interval_failed;
+        pairs += 1;
+      }
+  }
   fflush(out);
   fprintf(log, "Total:           = %10lld\n", total);
   fprintf(log, "Fails: attempts  = %10lld\n       Jaccard   = %10lld\n       interval  = %10lld\n", attempted, jaccard_failed, interval_failed);
-  fprintf(log, "Indexes built: %lld for %lld pairs (%zu chromosomes resident, limit table of %zu entries) in %.1fs\n",
-          sdf_search_index_builds(C.ctx), pairs, chroms.size(), limit.size() - 1, std::chrono::duration<double>(Clock::now() - T).count());
+  const std::string in_lanes = n_lanes > 1 ? ", " + std::to_string(n_lanes) + " lanes" : "";  // (lanes build no index: the counts stay)
+  fprintf(log, "Indexes built: %lld for %lld pairs%s (%zu chromosomes resident, limit table of %zu entries) in %.1fs\n",
+          sdf_search_index_builds(C.ctx), pairs, in_lanes.c_str(), chroms.size(), limit.size() - 1,
+          std::chrono::duration<double>(Clock::now() - T).count());
   return 0;
 }
 

@@ -568,6 +568,7 @@ struct StageSettings {
   bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
   bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise
   int search_wide = 0;       // SDF_SEARCH_WIDE_DEVICE=N: `search` finishes up to N WIDE / FOUND_WIDE windows of a round's seeding on the device (sdf_search_pair_indexed_wide's n_wide_max; 0: they go to the host)
+  int search_lanes = 1;      // SDF_SEARCH_LANES=N (1 .. 16): `search` keeps N chromosome pairs in flight (sdf_search_lanes_open, sdf_search_pairs_indexed; 1: the pair loop, one sdf_search_pair_indexed_wide call after the other)
   int bucket_lanes = 2;      // SDF_BUCKET_LANES: buckets of a several-bucket run in flight, each on a device context of its own (1: one after the other)
   int translate_limit = 100 * 1000 * 1000;  // SDF_TEST_TRANSLATE_LIMIT: TEST ONLY -- the size at which `search -t` / `translate` start a new group (the reference's 100 MB)
   static StageSettings from_env();

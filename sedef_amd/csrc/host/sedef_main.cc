@@ -137,6 +137,8 @@ int main(int argc, char **argv) {
               "  counters; the reference's lowercase and q-grams counters are not kept.\n"
               "  SDF_SEARCH_WIDE_DEVICE=N (default 0): up to N windows a round that gather more than 4,096 positions or meet more\n"
               "  than 256 found SDs are seeded on the device instead of one at a time on the host (same output)\n"
+              "  SDF_SEARCH_LANES=N (1..16, default 1): N chromosome pairs of a -t run in flight on the GPU at once, each on a\n"
+              "  lane of its own; the chromosomes and their indexes are shared (same output)\n"
               "sedef translate [genome.fa]\n"
               "  the chromosome groups of -t on stderr, their number on stdout\n"
               "  SDF_TEST_TRANSLATE_LIMIT (tests only): the group size limit in bases instead of 100 MB\n"

@@ -44,6 +44,10 @@ extern "C" const sdf_config *sdf_get_config(const sdf_ctx *ctx) { return ctx ? &
 extern "C" sdf_ctx *sdf_create(int device, size_t workspace_bytes) { return sdf_create_cfg(device, workspace_bytes, nullptr); }
 
 extern "C" sdf_ctx *sdf_create_cfg(int device, size_t workspace_bytes, const sdf_config *cfg_in) {
+  return create_context(device, workspace_bytes, cfg_in, true);
+}
+
+sdf_ctx *create_context(int device, size_t workspace_bytes, const sdf_config *cfg_in, bool pipeline_streams) {
   sdf_config cfg;
   if (cfg_in) {
     if (cfg_in->size != sizeof(sdf_config)) {
@@ -140,9 +144,11 @@ extern "C" sdf_ctx *sdf_create_cfg(int device, size_t workspace_bytes, const sdf
   ctx->chain_classes[7] = chain_lds_ok ? chain_lds : 65536;
   (void)hipGetLastError();
   lap.at("attributes");
-  if (hipStreamCreateWithFlags(&ctx->dp_stream[0], hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->dp_stream[1], hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->tb_stream, hipStreamNonBlocking) != hipSuccess) {
+  if (!pipeline_streams) {
+    ctx->pipeline_ok = false;
+  } else if (hipStreamCreateWithFlags(&ctx->dp_stream[0], hipStreamNonBlocking) != hipSuccess ||
+             hipStreamCreateWithFlags(&ctx->dp_stream[1], hipStreamNonBlocking) != hipSuccess ||
+             hipStreamCreateWithFlags(&ctx->tb_stream, hipStreamNonBlocking) != hipSuccess) {
     (void)hipGetLastError();
     ctx->pipeline_ok = false;
   }
@@ -228,6 +234,7 @@ extern "C" void sdf_destroy(sdf_ctx *ctx) {
   if (!ctx) return;
   if (!ctx->is_part) g_live_contexts.fetch_sub(1);
   (void)hipSetDevice(ctx->device);
+  while (!ctx->lanes.empty()) close_lanes(ctx, ctx->lanes.back());  // (lanes still open go first: they are views of this pool)
   for_each_stream(ctx, [](hipStream_t q) { if (q) (void)hipStreamSynchronize(q); });
   {  // a view leaves its owner's list; an owner's views (the caller's error: the owner outlives its views) are left with an
      // empty pool, so that their later calls answer SDF_ERR_INVALID instead of reading freed memory
@@ -382,6 +389,8 @@ extern "C" size_t sdf_device_bytes(const sdf_ctx *ctx) {
   for (const sdf_search_index *h : ctx->indexes) sum += h->d_loc.held_bytes() + h->d_sorted.held_bytes();
   if (ctx->part_ctx) sum += sdf_device_bytes(ctx->part_ctx);
   if (ctx->rerun_ctx) sum += sdf_device_bytes(ctx->rerun_ctx);
+  for (const sdf_search_lanes *l : ctx->lanes)
+    for (const sdf_ctx *lane : l->lane) sum += sdf_device_bytes(lane);
   return sum;
 }
 

@@ -378,6 +378,14 @@ struct sdf_search_index {
   DevBuf d_loc, d_sorted;
 };
 
+// The lanes of sdf_search_pairs_indexed (include/sedef_hip.h: sdf_search_lanes_open; sdf_lanes_api.hip): child contexts of
+// `owner`, each a view of the owner's pool with a stream and per-call buffers of its own.  The owner lists the object and
+// closes it with itself.
+struct sdf_search_lanes {
+  sdf_ctx *owner = nullptr;
+  std::vector<sdf_ctx *> lane;
+};
+
 struct sdf_ctx {
   sdf_config cfg;  // the context's settings, fixed when it is made (sdf_config.hip): every setting is read from here
   int device = 0;
@@ -399,6 +407,7 @@ struct sdf_ctx {
   uint64_t pool_epoch = 0; // grows whenever the pool is REPLACED (an upload, a reset, a view taken or dropped), not when it is appended to
   std::vector<sdf_search_index *> indexes;  // the live handles of sdf_search_index_build (sdf_driver_api.hip); sdf_destroy frees them
   long long index_builds = 0;               // sdf_search_index_build calls that returned a handle
+  std::vector<sdf_search_lanes *> lanes;    // the open lanes of sdf_search_lanes_open (sdf_lanes_api.hip); sdf_destroy closes them
   long long lane_tasks = 0;   // tasks of the last batch call the lane kernel took
   // sdf_last_chain_classes: pairs of the last sdf_chain_batch per launch class -- [0..5] the LDS classes of chain_wave_kernel,
   // [6] chain_kernel --, [7] the LDS cap of class 5 in bytes (fixed in sdf_create: what the kernel was granted there)
@@ -455,6 +464,11 @@ inline void for_each_stream(sdf_ctx *ctx, F &&f) {
 // a context another context owns (the first part of a split batch, the re-run of abandoned stripe tasks): not another
 // user of the process's CPUs (sdf_context.hip, like the two below)
 void mark_internal_context(sdf_ctx *c);
+// sdf_create_cfg with a say on the chunk pipeline's three streams: a context that never runs a DP batch (a search lane) does
+// without them
+sdf_ctx *create_context(int device, size_t workspace_bytes, const sdf_config *cfg_in, bool pipeline_streams);
+// the lanes of a list entry destroyed, the entry gone from its owner's list (sdf_lanes_api.hip)
+void close_lanes(sdf_ctx *owner, sdf_search_lanes *lanes);
 // In front of everything that replaces or grows a context's resident pool.  SDF_ERR_INVALID ("pool is shared"): other
 // contexts view this one's pool, or -- keep_view -- this context holds a view and the caller wants to add to it.  Otherwise
 // SDF_OK, and a context that held a view holds none any more: an empty pool of its own.

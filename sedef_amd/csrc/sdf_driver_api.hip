@@ -342,11 +342,10 @@ int pair_rounds(PairDriver &D, const std::vector<uint32_t> &sched) {
   return SDF_OK;
 }
 
-int pair_finish(PairDriver &D, sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
-  *stats = D.S;
-  *used = D.out.size();
-  if (D.out.size() > cap) return refuse(D.ctx, SDF_ERR_CIGAR_OVERFLOW, "the pair has " + std::to_string(D.out.size()) + " hits, more than cap");
-  if (!D.out.empty()) memcpy(out, D.out.data(), D.out.size() * sizeof(sdf_search_pair_hit));
+int pair_finish(sdf_ctx *ctx, const std::vector<sdf_search_pair_hit> &hits, sdf_search_pair_hit *out, size_t cap, size_t *used) {
+  *used = hits.size();
+  if (hits.size() > cap) return refuse(ctx, SDF_ERR_CIGAR_OVERFLOW, "the pair has " + std::to_string(hits.size()) + " hits, more than cap");
+  if (!hits.empty()) memcpy(out, hits.data(), hits.size() * sizeof(sdf_search_pair_hit));
   return SDF_OK;
 }
 
@@ -355,6 +354,52 @@ bool index_live(const sdf_ctx *ctx, const sdf_search_index *h) {
   return h && std::find(ctx->indexes.begin(), ctx->indexes.end(), h) != ctx->indexes.end();
 }
 }  // namespace
+
+// ---- two handles as a pair: the checks and the rounds, for the single-pair calls below and for the lanes (sdf_lanes_api.hip).
+// `owner` holds the handles; the rounds run on `ctx` -- the owner itself, or a lane that views the owner's pool.
+namespace sdf {
+int pair_handles_valid(const sdf_ctx *owner, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                       const char **why) {
+  if (!index_live(owner, q) || !index_live(owner, r))
+    return *why = "sdf_search_pair_indexed: a handle that is null, freed or another context's", SDF_ERR_INVALID;
+  if (q->pool_epoch != owner->pool_epoch || r->pool_epoch != owner->pool_epoch)
+    return *why = "sdf_search_pair_indexed: a handle built on a pool that has been replaced since", SDF_ERR_INVALID;
+  for (const sdf_search_index *h : {q, r})
+    if (h->k != params->k || h->w != params->w || h->separate_lowercase != (params->separate_lowercase != 0))
+      return *why = "sdf_search_pair_indexed: k, w or separate_lowercase differ from a handle's", SDF_ERR_INVALID;
+  if (params->same_genome && q != r) return *why = "sdf_search_pair_indexed: same_genome takes one handle as both sides", SDF_ERR_INVALID;
+  return SDF_OK;
+}
+
+int pair_handles_ranges(size_t pool_bytes, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                        size_t n_wide_max, const char **why) {
+  if (int rc = pair_checks(pool_bytes, &q->range, &r->range, params))
+    return *why = "sdf_search_pair_indexed: a range or a parameter is refused", rc;
+  if (n_wide_max > SEARCH_WIDE_MAX_LIST) return *why = "sdf_search_pair_indexed_wide: n_wide_max > 2^20", SDF_ERR_UNSUPPORTED;
+  return SDF_OK;
+}
+
+int pair_handles_run(sdf_ctx *ctx, const sdf_ctx *owner, const sdf_search_index *q, const sdf_search_index *r,
+                     const sdf_search_pair_params *params, size_t n_wide_max, std::vector<sdf_search_pair_hit> &hits,
+                     sdf_search_pair_stats *stats) {
+  ctx->err.clear();
+  const char *why = nullptr;
+  if (int rc = pair_handles_valid(owner, q, r, params, &why)) return refuse(ctx, rc, why);
+  if (int rc = pair_handles_ranges(sdf_pool_bytes(ctx), q, r, params, n_wide_max, &why)) return refuse(ctx, rc, why);
+  SDF_HIP(hipSetDevice(ctx->device));
+  PairDriver D{ctx, ctx->stream, *params, pair_extend_params(*params), q->range, r->range};
+  D.n_wide = n_wide_max;
+  D.q = &q->loc, D.r_loc = &r->loc, D.r_sorted = &r->sorted, D.threshold = r->threshold;
+  D.d_q = (const sdf_minimizer *)q->d_loc.p, D.d_r = (const sdf_minimizer *)r->d_loc.p, D.d_rs = (const sdf_minimizer *)r->d_sorted.p;
+  std::vector<uint32_t> sched;
+  pair_schedule(D, sched);
+  if (!sched.empty())
+    if (int rc = pair_rounds(D, sched)) return rc;
+  *stats = D.S;
+  hits.swap(D.out);
+  return SDF_OK;
+}
+}  // namespace sdf
 
 // sdf_search_pair (n_wide_max == 0) and sdf_search_pair_wide
 static int pair_ranges(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
@@ -388,7 +433,8 @@ static int pair_ranges(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_m
     D.d_rs = (const sdf_minimizer *)ctx->dr_rs.p;
     if (int rc = pair_rounds(D, sched)) return rc;
   }
-  return pair_finish(D, out, cap, used, stats);
+  *stats = D.S;
+  return pair_finish(ctx, D.out, out, cap, used);
 }
 
 extern "C" int sdf_search_pair(sdf_ctx *ctx, const sdf_minim_range *q_range, const sdf_minim_range *r_range, const sdf_search_pair_params *params,
@@ -469,42 +515,27 @@ extern "C" int sdf_search_index_info(const sdf_ctx *ctx, const sdf_search_index 
 extern "C" long long sdf_search_index_builds(const sdf_ctx *ctx) { return ctx ? ctx->index_builds : 0; }
 extern "C" size_t sdf_search_index_live(const sdf_ctx *ctx) { return ctx ? ctx->indexes.size() : 0; }
 
-// sdf_search_pair_indexed (n_wide_max == 0) and sdf_search_pair_indexed_wide
-static int pair_handles(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+// sdf_search_pair_indexed (n_wide_max == 0) and sdf_search_pair_indexed_wide: the rounds on `ctx`, the handles `owner`'s (the public
+// calls name one context as both)
+static int pair_handles(sdf_ctx *ctx, const sdf_ctx *owner, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
                         sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats, size_t n_wide_max) {
   if (!ctx) return SDF_ERR_INVALID;
   ctx->err.clear();
   if (!used || !stats || !params || (cap && !out)) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: invalid arguments");
-  if (!index_live(ctx, q) || !index_live(ctx, r))
-    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: a handle that is null, freed or another context's");
-  if (q->pool_epoch != ctx->pool_epoch || r->pool_epoch != ctx->pool_epoch)
-    return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: a handle built on a pool that has been replaced since");
-  for (const sdf_search_index *h : {q, r})
-    if (h->k != params->k || h->w != params->w || h->separate_lowercase != (params->separate_lowercase != 0))
-      return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: k, w or separate_lowercase differ from a handle's");
-  if (params->same_genome && q != r) return refuse(ctx, SDF_ERR_INVALID, "sdf_search_pair_indexed: same_genome takes one handle as both sides");
-  if (int rc = pair_checks(sdf_pool_bytes(ctx), &q->range, &r->range, params))
-    return refuse(ctx, rc, "sdf_search_pair_indexed: a range or a parameter is refused");
-  if (n_wide_max > SEARCH_WIDE_MAX_LIST) return refuse(ctx, SDF_ERR_UNSUPPORTED, "sdf_search_pair_indexed_wide: n_wide_max > 2^20");
-  SDF_HIP(hipSetDevice(ctx->device));
-  PairDriver D{ctx, ctx->stream, *params, pair_extend_params(*params), q->range, r->range};
-  D.n_wide = n_wide_max;
-  D.q = &q->loc, D.r_loc = &r->loc, D.r_sorted = &r->sorted, D.threshold = r->threshold;
-  D.d_q = (const sdf_minimizer *)q->d_loc.p, D.d_r = (const sdf_minimizer *)r->d_loc.p, D.d_rs = (const sdf_minimizer *)r->d_sorted.p;
-  std::vector<uint32_t> sched;
-  pair_schedule(D, sched);
-  if (!sched.empty())
-    if (int rc = pair_rounds(D, sched)) return rc;
-  return pair_finish(D, out, cap, used, stats);
+  std::vector<sdf_search_pair_hit> hits;
+  sdf_search_pair_stats S;
+  if (int rc = pair_handles_run(ctx, owner, q, r, params, n_wide_max, hits, &S)) return rc;
+  *stats = S;
+  return pair_finish(ctx, hits, out, cap, used);
 }
 
 extern "C" int sdf_search_pair_indexed(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
                                        sdf_search_pair_hit *out, size_t cap, size_t *used, sdf_search_pair_stats *stats) {
-  return pair_handles(ctx, q, r, params, out, cap, used, stats, 0);
+  return pair_handles(ctx, ctx, q, r, params, out, cap, used, stats, 0);
 }
 
 extern "C" int sdf_search_pair_indexed_wide(sdf_ctx *ctx, const sdf_search_index *q, const sdf_search_index *r,
                                             const sdf_search_pair_params *params, sdf_search_pair_hit *out, size_t cap, size_t *used,
                                             sdf_search_pair_stats *stats, size_t n_wide_max) {
-  return pair_handles(ctx, q, r, params, out, cap, used, stats, n_wide_max);
+  return pair_handles(ctx, ctx, q, r, params, out, cap, used, stats, n_wide_max);
 }

@@ -64,6 +64,19 @@ int found_index(sdf_ctx *ctx, const sdf_search_found *d_found, size_t nf, size_t
                 hipStream_t st, FoundIndex *F);
 int found_index_need(sdf_ctx *ctx, size_t cap);
 
+// Two handles as a pair (sdf_driver_api.hip), for the single-pair calls and for the lanes (sdf_lanes_api.hip).  `owner` holds
+// the handles; the rounds run on `ctx`, the owner itself or a lane that views its pool.  pair_handles_valid: what
+// sdf_search_pair_indexed asks of the handles against the owner and the parameters (SDF_ERR_INVALID); pair_handles_ranges: behind
+// it, sdf_search_pair's refusals on the handles' ranges and on n_wide_max, with their codes; neither reads a handle that is not
+// live, neither launches.  pair_handles_run: both checks, then the rounds; the pair's hits to `hits`.
+int pair_handles_valid(const sdf_ctx *owner, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                       const char **why);
+int pair_handles_ranges(size_t pool_bytes, const sdf_search_index *q, const sdf_search_index *r, const sdf_search_pair_params *params,
+                        size_t n_wide_max, const char **why);
+int pair_handles_run(sdf_ctx *ctx, const sdf_ctx *owner, const sdf_search_index *q, const sdf_search_index *r,
+                     const sdf_search_pair_params *params, size_t n_wide_max, std::vector<sdf_search_pair_hit> &hits,
+                     sdf_search_pair_stats *stats);
+
 // The uploads of a form that takes host arrays: every buffer reserved and its copy enqueued on `st`, in order; an entry of no
 // bytes is skipped (its buffer stays as it is).
 struct Upload {

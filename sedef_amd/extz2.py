@@ -99,6 +99,10 @@ ACCEPT_MAX_KEPT, ACCEPT_INCOMPLETE, ACCEPT_OVERFLOW = 512, 0x1, 0x2
 # SDF_PAIR_*: the driver's default round, its two starting capacities, the long growths a round finishes on the device
 PAIR_ROUND_WINDOWS, PAIR_INTERVALS_START, PAIR_ENTRIES_START, PAIR_LONG_MAX, PAIR_LONG_BATCH = 64, 4096, 4096, 16, 8
 assert SEARCH_PAIR_HIT_DTYPE.itemsize == 24 and ACCEPT_STATUS_DTYPE.itemsize == 64 and PAIR_STATS_DTYPE.itemsize == 56
+# sdf_search_pair_job (the lanes' section): two handles of search_index_build and same_genome
+PAIR_JOB_DTYPE = np.dtype([("q", "<u8"), ("r", "<u8"), ("same_genome", "<i4"), ("reserved", "<i4")])
+SEARCH_LANES_MAX = 16  # SDF_SEARCH_LANES_MAX
+assert PAIR_JOB_DTYPE.itemsize == 24
 FILTER_Q_RC, FILTER_R_RC, FILTER_SKIP = 1, 2, 4
 FILTER_UPPER_FAIL, FILTER_QGRAM_FAIL, FILTER_SHORT, FILTER_SKIPPED = 1, 2, 4, 8
 FILTER_WAVE_MAX_LEN = 4096
@@ -379,6 +383,13 @@ def load_library():
                                           C.POINTER(C.c_size_t), C.c_void_p]
     L.sdf_search_pair_indexed_wide.restype = C.c_int  # ... stats, n_wide_max
     L.sdf_search_pair_indexed_wide.argtypes = L.sdf_search_pair_indexed.argtypes + [C.c_size_t]
+    L.sdf_search_lanes_open.restype = C.c_int  # ctx, n_lanes, out
+    L.sdf_search_lanes_open.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.sdf_search_lanes_close.restype = C.c_int
+    L.sdf_search_lanes_close.argtypes = [C.c_void_p, C.c_void_p]
+    L.sdf_search_pairs_indexed.restype = C.c_int  # ctx, lanes, jobs, n_jobs, params, n_wide_max, out, cap, used, first, stats
+    L.sdf_search_pairs_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_PairParams), C.c_size_t, C.c_void_p,
+                                           C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]
     L.sdf_last_ms.restype = C.c_float
     L.sdf_last_ms.argtypes = [C.c_void_p, C.c_int]
     L.sdf_last_launches.restype = C.c_int
@@ -1190,6 +1201,42 @@ class Extz2Engine:
         """sdf_search_pair_indexed_wide: search_pair_wide on two handles of search_index_build."""
         return search_pair_call(self.lib.sdf_search_pair_indexed_wide, (self.ctx,), q_index, r_index, tail=(int(n_wide_max),), **kw)
 
+    def search_lanes_open(self, n):
+        """sdf_search_lanes_open: n (1 .. 16) lanes for search_pairs_indexed -- child contexts that view this engine's pool, so
+        the pool cannot grow or be replaced until they are closed.  Returns (rc, lanes): an int for search_pairs_indexed and
+        search_lanes_close, None after a refusal.  Lanes die with their engine (close) at the latest."""
+        h = C.c_void_p(0)
+        rc = self.lib.sdf_search_lanes_open(self.ctx, int(n), C.byref(h))
+        return rc, (h.value if rc == 0 else None)
+
+    def search_lanes_close(self, lanes):
+        """sdf_search_lanes_close -> rc (None is SDF_OK; lanes that are not live in this engine are -4)."""
+        return self.lib.sdf_search_lanes_close(self.ctx, lanes)
+
+    def search_pairs_indexed(self, lanes, jobs, n_wide_max=0, cap=None, **kw):
+        """sdf_search_pairs_indexed: every job (q_handle, r_handle, same_genome) as search_pair_indexed_wide(q, r, n_wide_max,
+        same_genome=..., **kw), several in flight on the lanes.  Keywords as search_pair's (same_genome and extend's own come
+        from the job); cap: the hits `out` holds (None: retried with the need).  Returns (rc, hits, first, stats): job j's hits
+        are hits[first[j]:first[j + 1]], stats[j] its PAIR_STATS_DTYPE record; after -5 hits is empty and first[-1] the need."""
+        J = np.zeros(len(jobs), PAIR_JOB_DTYPE)
+        for j, (q, r, same) in enumerate(jobs):
+            J[j] = (q or 0, r or 0, int(bool(same)), 0)
+        P, keep = pair_params(**kw)
+        first = np.zeros(len(jobs) + 1, np.uint64)
+        stats = np.zeros(len(jobs), PAIR_STATS_DTYPE)
+        used = C.c_size_t(0)
+        room = 0 if cap is None else int(cap)
+        while True:
+            out = np.zeros(room, SEARCH_PAIR_HIT_DTYPE)
+            rc = self.lib.sdf_search_pairs_indexed(self.ctx, lanes, J.ctypes.data if len(jobs) else None, len(jobs), C.byref(P),
+                                                   int(n_wide_max), out.ctypes.data if room else None, room, C.byref(used),
+                                                   first.ctypes.data, stats.ctypes.data if len(jobs) else None)
+            if rc != -5 or cap is not None:
+                break
+            room = int(used.value)
+        del keep
+        return rc, out[:int(used.value)] if rc == 0 else out[:0], first, stats
+
     def search_accept_raw(self, *args, **kw):
         """sdf_search_accept as it is: one round of the search driver's acceptance step on numpy arrays, run by the device
         form on copies.  Arguments and result as search_accept_call's."""
@@ -1598,15 +1645,21 @@ def search_accept_host(*args, **kw):
     return search_accept_call(load_library().sdf_search_accept_host, (), *args, **kw)
 
 
-def search_pair_call(fn, head, q_range, r_range, k=12, w=16, separate_lowercase=True, uppercase_seeds=True, min_read_size=700,
-                     same_genome=False, limit=(), filter=None, extend=None, cap=None, round_windows=0, debug_host_every=0, tail=()):
-    """sdf_search_pair (head: its context) or sdf_search_pair_host (head: the characters and their number); tail: what a form
-    takes behind stats (the _wide forms' n_wide_max).  Returns (rc, hits, used, stats)."""
+def pair_params(k=12, w=16, separate_lowercase=True, uppercase_seeds=True, min_read_size=700, same_genome=False, limit=(), filter=None,
+                extend=None, round_windows=0, debug_host_every=0):
+    """sdf_search_pair_params from keywords -> (the struct, the limit table it points into: keep it until the call has returned)."""
     limit = np.ascontiguousarray(limit, dtype=np.int32)
     P = _PairParams(int(k), int(w), int(bool(separate_lowercase)), int(bool(uppercase_seeds)), int(min_read_size), int(bool(same_genome)),
                     filter_params() if filter is None else filter,
                     extend_params(same_genome=bool(same_genome)) if extend is None else extend,
                     limit.ctypes.data if len(limit) else None, len(limit), int(round_windows), int(debug_host_every))
+    return P, limit
+
+
+def search_pair_call(fn, head, q_range, r_range, cap=None, tail=(), **kw):
+    """sdf_search_pair (head: its context) or sdf_search_pair_host (head: the characters and their number); tail: what a form
+    takes behind stats (the _wide forms' n_wide_max); the other keywords: pair_params'.  Returns (rc, hits, used, stats)."""
+    P, limit = pair_params(**kw)
     if isinstance(q_range, (tuple, list, np.ndarray)):
         ranges = [C.byref(_MinimRange(int(r[0]), int(r[1]), int(r[2]) if len(r) > 2 else 0)) for r in (q_range, r_range)]
     else:  # two handles of search_index_build (ints, or None)

@@ -343,6 +343,45 @@ int sdf_pool_fetch_plan(const sdf_pool_fetch *r, size_t n, size_t pool_bytes, si
 int sdf_pool_fetch_ranges_device(sdf_ctx *ctx, const sdf_pool_fetch_rec *d_recs /* HBM */, size_t n, int any_rc, long long n_seg,
                                  char *d_dst, void *stream);
 
+/* ---- coverage of ranges of the resident pool ------------------------------------------------------------------------------
+ * How two sets of intervals cover ranges of the pool: `stats diff` (the reference's get_differences, src/stats_main.cc:397-509)
+ * with a chromosome per region, the SDs found as set 0 and the gold standard as set 1.  (pool_cover.hip.)
+ *
+ * A REGION is a range of the pool.  An INTERVAL is bases [start, start + len) of region `region` -- start counts from the
+ * region's first byte -- in set 0 or 1, with a `partner`: another interval's index, or -1.  Two predicates on a pool byte c, both
+ * decided on the WHOLE byte as it lies in HBM:
+ *   upper(c)     'A' <= c <= 'Z'                the reference's isupper() in the C locale: N and the IUPAC letters count, n and
+ *                                               every byte of 128 and above do not
+ *   upper_base(c) 'A' <= c <= 'Z' && c != 'N'   the reference's isupper(c) && toupper(c) != 'N': R counts, N and n do not
+ * Neither depends on strand: both count bytes of a range, whatever order they are read in, and no interval carries a strand.
+ *   1. iv_upper[i] = the bytes of interval i with upper(c).
+ *   2. Interval i is PAINTED when partner < 0, or when iv_upper[i] >= min_upper and iv_upper[partner] >= min_upper (the
+ *      reference's `qa < 100 || qb < 100` on the two sides of a hit; a partner need not name i back, and may lie in another
+ *      region or set).  A painted interval sets its bases in its set's bitmap of its region; iv_painted[i] = 1, else 0.
+ *   3. Per region, over its bases x with A / B = x is set in the bitmap of set 0 / 1:  a = |A|, b = |B|, both = |A & B|,
+ *      a_only = |A & ~B|, b_only = |B & ~A|, a_only_upper / b_only_upper = the bases of a_only / b_only with upper_base(c).
+ * Regions may overlap or repeat: each has bitmaps of its own, one bit a base, in a buffer of the context that
+ * sdf_device_bytes() counts (2 bits a base of all regions, zeroed on the stream in front of every call).
+ * Before any launch, with the context usable afterwards:
+ *   SDF_ERR_INVALID      a region outside sdf_pool_bytes(ctx) or with len < 0, an interval whose region is not in [0, n_regions),
+ *                        with len < 0 or not inside [0, region.len), a partner that is neither -1 nor in [0, n_iv), set not 0 or
+ *                        1, regions / out == NULL with n_regions > 0, iv == NULL with n_iv > 0, bitmaps that do not fit the
+ *                        device's free memory
+ *   SDF_ERR_UNSUPPORTED  reserved != 0 (region or interval), more than 2^31 - 1 regions or intervals
+ * Legal: intervals and regions with len == 0, n_iv == 0 (all counts zero), n_regions == 0 (with n_iv == 0: nothing is done).
+ * iv_upper and iv_painted may be NULL.  Three launches on the context's stream, behind the pool's uploads, with no host wait
+ * between them; the call returns with its outputs filled.
+ * sdf_pool_coverage_host: the same checks, codes and results in plain C++ over the characters pool[0, pool_bytes), without a
+ * context or a device (it has no error text; "free memory" is not asked). */
+typedef struct { int32_t region; int32_t start; int32_t len; int32_t set; int32_t partner; int32_t reserved; /* must be 0 */ } sdf_cover_interval;
+typedef struct { int64_t a, b, both, a_only, b_only, a_only_upper, b_only_upper; } sdf_cover_counts;
+int sdf_pool_coverage(sdf_ctx *ctx, const sdf_pool_range *regions, size_t n_regions, const sdf_cover_interval *iv, size_t n_iv,
+                      int32_t min_upper, sdf_cover_counts *out /* n_regions */, int32_t *iv_upper /* n_iv, may be NULL */,
+                      uint8_t *iv_painted /* n_iv, may be NULL */);
+int sdf_pool_coverage_host(const char *pool, size_t pool_bytes, const sdf_pool_range *regions, size_t n_regions,
+                           const sdf_cover_interval *iv, size_t n_iv, int32_t min_upper, sdf_cover_counts *out, int32_t *iv_upper,
+                           uint8_t *iv_painted);
+
 /* ---- one resident pool read by several contexts of a device ---------------------------------------------------------
  * dst reads src's resident pool: dst's pool is replaced by a VIEW of src's (same device; SDF_ERR_INVALID otherwise, or when
  * src == dst, or when src is itself a view, or when dst's own pool has views).  sdf_pool_bytes(dst) == sdf_pool_bytes(src) at

@@ -434,6 +434,13 @@ long stats_generate(const std::string &ref_path, const std::string &bed_path, FI
                     test_cols_fn test, int device, long long *stats, test_cuts_fn test_cuts = nullptr);
 std::string format_double(double x);  // fmt 4.0.1 "{}" of a double, as the reference prints columns 22-25 and 35
 
+// ---- `sedef stats diff` (reference: src/stats_main.cc:397-509, get_differences; stats_diff.cc) ---------------------
+// The coverage of the chromosomes final.bed names by its hits and by the WGAC table's, in the reference's lines on `log`:
+// every such chromosome is uploaded once and ONE sdf_pool_coverage call on `device` paints and counts (pool_cover.hip).
+// host (SDF_STATS_DIFF_HOST=1, StageSettings::stats_diff_host): sdf_pool_coverage_host instead, no device.  Returns 0; throws
+// std::string for a file that is missing, a line with too few fields, a chromosome the index does not know.
+int stats_diff(const std::string &ref_path, const std::string &bed_path, const std::string &wgac_path, bool host, int device, FILE *log);
+
 // ---- utilities (reference: src/util.cc:33-48, src/common.h:56-99) ----------------------------------
 void set_alignment_scoring(const Params &p);  // Align::MATCH and co. are process-wide (src/globals.cc:25-28)
 std::vector<std::string> split(const std::string &s, char delim);
@@ -565,6 +572,7 @@ struct StageSettings {
   bool resident_dp = true;   // SDF_RESIDENT_DP=0: the DP rounds cut their bases out on the host again instead of naming ranges of the characters the anchors call left in HBM
   bool stats_resident = false;  // SDF_STATS_RESIDENT=1: `stats generate` counts on resident chromosomes (StatsParams::resident)
   bool stats_cuts_device = false;  // SDF_STATS_CUTS_DEVICE=1: with stats_resident, the cuts and trims of `stats generate` run on the device too (StatsParams::cuts_device)
+  bool stats_diff_host = false;  // SDF_STATS_DIFF_HOST=1: `stats diff` paints and counts on the host (sdf_pool_coverage_host), no device
   bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
   bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise
   int search_wide = 0;       // SDF_SEARCH_WIDE_DEVICE=N: `search` finishes up to N WIDE / FOUND_WIDE windows of a round's seeding on the device (sdf_search_pair_indexed_wide's n_wide_max; 0: they go to the host)

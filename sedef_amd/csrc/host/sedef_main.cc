@@ -142,7 +142,10 @@ int main(int argc, char **argv) {
               "sedef translate [genome.fa]\n"
               "  the chromosome groups of -t on stderr, their number on stdout\n"
               "  SDF_TEST_TRANSLATE_LIMIT (tests only): the group size limit in bases instead of 100 MB\n"
-              "Other SEDEF stages (stats diff) are not part of this build.\n");
+              "sedef stats diff [genome.fa] [final.bed] [wgac.tab]\n"
+              "  how the SDs of final.bed and of the WGAC table cover the chromosomes final.bed names (seven figures on stderr);\n"
+              "  painted and counted on the resident chromosomes in one device call\n"
+              "  SDF_STATS_DIFF_HOST=1 (default 0): the same figures from the host form of that call, without a device\n");
       return 0;
     } else if (command == "search") {
       return search_command(parse_search_args(argc - 2, argv + 2), stdout, stderr);
@@ -221,7 +224,7 @@ int main(int argc, char **argv) {
       }
     } else if (command == "stats") {
       // `sedef stats generate [--max-ok-gap N --min-split N --uppercase N --max-error X] genome.fa final.bed`
-      // (reference: src/stats_main.cc:482-510); `stats diff` (WGAC comparison) is not part of this build
+      // (reference: src/stats_main.cc:482-510), and `sedef stats diff genome.fa final.bed wgac.tab` (:397-509; stats_diff.cc)
       Args a(argc - 2, argv + 2);
       StatsParams sp;
       a.get({"max-ok-gap"}, sp.max_ok_gap);
@@ -231,6 +234,10 @@ int main(int argc, char **argv) {
       sp.resident = stage_settings().stats_resident;  // (SDF_STATS_RESIDENT=1)
       sp.cuts_device = stage_settings().stats_cuts_device;  // (SDF_STATS_CUTS_DEVICE=1)
       if (a.pos.size() < 3) throw std::string("Not enough arguments to stats");
+      if (a.pos[0] == "diff") {
+        if (a.pos.size() < 4) throw std::string("Not enough arguments to stats");
+        return stats_diff(a.pos[1], a.pos[2], a.pos[3], stage_settings().stats_diff_host, stage_settings().device, stderr);
+      }
       if (a.pos[0] != "generate") throw std::string("Unknown stats command");
       long long st[3] = {0, 0, 0};
       const long lines = stats_generate(a.pos[1], a.pos[2], stdout, sp, nullptr, stage_settings().device, st);

@@ -347,6 +347,8 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(pk_recs, Pairs)     /* one PackRec per task of an sdf_extz2_batch_pairs call (seq_pack.hip) */                    \
   X(cl_ranges, Pairs) X(cl_out, Pairs) /* sdf_pool_range_classes: a ClassRange and a record of four counts per range */ \
   X(pf_recs, None) X(pf_out, None) /* sdf_pool_fetch_ranges: a piece's FetchRec records and its output bytes (fetch_stage_bytes) */ \
+  X(cv_regions, None) X(cv_iv, None) X(cv_upper, None) X(cv_out, None) /* sdf_pool_coverage: a CoverRegion per region, a CoverIv and a count per interval, seven counters per region */ \
+  X(cv_bits, None) /* ... the bitmaps: a bit per base of every region, set 0 then set 1 (pool_cover.hip), zeroed per call */ \
   X(fa_raw, Pool) /* a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta) */           \
   /* lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch */ \
   X(ln_recs, BatchCall) X(ln_keys, BatchCall) X(ln_vals, BatchCall) X(ln_sizes, BatchCall) X(ln_tmp, BatchCall)       \

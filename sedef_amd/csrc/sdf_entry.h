@@ -40,6 +40,30 @@ inline int check_stats_tasks(sdf_ctx *ctx, const sdf_stats_task *tasks, size_t n
   return SDF_OK;
 }
 
+// The regions and intervals of a coverage call (include/sedef_hip.h: sdf_pool_coverage / sdf_pool_coverage_host), in order; the
+// first refusal is the call's, and *why its sentence.  Both forms ask this before they do anything.
+inline int check_cover(const sdf_pool_range *regions, size_t n_regions, const sdf_cover_interval *iv, size_t n_iv, size_t pool_bytes,
+                       const sdf_cover_counts *out, std::string *why) {
+  const std::string who = "sdf_pool_coverage: ";
+  if ((n_regions && (!regions || !out)) || (n_iv && !iv)) return *why = who + "invalid arguments", SDF_ERR_INVALID;
+  if (n_regions > 0x7fffffffu || n_iv > 0x7fffffffu) return *why = who + "more than 2^31 - 1 regions or intervals in one call", SDF_ERR_UNSUPPORTED;
+  for (size_t r = 0; r < n_regions; r++) {
+    if (regions[r].reserved != 0) return *why = who + "region " + std::to_string(r) + ": reserved must be 0", SDF_ERR_UNSUPPORTED;
+    if (!in_range(regions[r].off, (int64_t)regions[r].len, pool_bytes))
+      return *why = who + "region " + std::to_string(r) + ": range outside the resident pool", SDF_ERR_INVALID;
+  }
+  for (size_t i = 0; i < n_iv; i++) {
+    const sdf_cover_interval &v = iv[i];
+    const auto refuse_iv = [&](int code, const char *what) { return *why = who + "interval " + std::to_string(i) + ": " + what, code; };
+    if (v.reserved != 0) return refuse_iv(SDF_ERR_UNSUPPORTED, "reserved must be 0");
+    if (v.set != 0 && v.set != 1) return refuse_iv(SDF_ERR_INVALID, "set must be 0 or 1");
+    if (v.region < 0 || (size_t)v.region >= n_regions) return refuse_iv(SDF_ERR_INVALID, "region out of range");
+    if (!in_range((int64_t)v.start, (int64_t)v.len, (size_t)regions[v.region].len)) return refuse_iv(SDF_ERR_INVALID, "not inside its region");
+    if (v.partner < -1 || (v.partner >= 0 && (size_t)v.partner >= n_iv)) return refuse_iv(SDF_ERR_INVALID, "partner out of range");
+  }
+  return SDF_OK;
+}
+
 // The tail of a counted output, behind the launches that filled d_first[0 .. n] on `st`: first[0 .. n] back (a host form), or
 // d_first[n] alone (first == nullptr: a device form), one wait, *used = the need, and SDF_ERR_CIGAR_OVERFLOW -- "<before>
 // <need> <after>" -- when the need exceeds cap.

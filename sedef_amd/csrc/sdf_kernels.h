@@ -98,6 +98,32 @@ static_assert(sizeof(FetchRec) == 32, "FetchRec: two records per 64-byte line");
 // REV: some record of the launch has rc set; <false> never reads the word and is the plain copy
 template <bool REV>
 __global__ void pool_fetch_kernel(const FetchRec *, int, long long, const char *, char *);
+// pool_cover.hip
+constexpr int kCoverPieceBytes = 8192;  // bytes (and bitmap bits) of an interval that one wavefront counts or paints
+struct CoverRegion {  // one region of sdf_pool_coverage (32 bytes)
+  int64_t off;        // first byte of the region in the pool
+  int64_t word0;      // first word of the region's bitmap within a set's half of the buffer: the words of the regions before it
+  int64_t wave0;      // wavefronts of the count launch before this region's: ceil(words / 64) each
+  int32_t len, pad;
+};
+struct CoverIv {    // one interval (32 bytes)
+  int64_t off;      // first byte of the interval in the pool
+  int64_t bit0;     // its first bit within a set's half of the buffer: 32 * word0 of its region + start
+  int32_t len, set, partner;
+  int32_t piece0;   // pieces of the intervals before this one: the launch's wavefront g takes piece g - piece0 of its interval
+};
+static_assert(sizeof(CoverRegion) == 32 && sizeof(CoverIv) == 32 && sizeof(sdf_cover_counts) == 56 && sizeof(sdf_cover_interval) == 24,
+              "include/sedef_hip.h");
+// the two predicates of include/sedef_hip.h on one byte, and the rule of the paint launch: the one form the kernels' word forms
+// are checked against and the host form uses
+__host__ __device__ inline bool cover_upper(const unsigned char c) { return c >= 'A' && c <= 'Z'; }
+__host__ __device__ inline bool cover_upper_base(const unsigned char c) { return c >= 'A' && c <= 'Z' && c != 'N'; }
+__host__ __device__ inline bool cover_painted(const int32_t partner, const int32_t own, const int32_t partners, const int32_t min_upper) {
+  return partner < 0 || (own >= min_upper && partners >= min_upper);
+}
+__global__ void cover_upper_kernel(const CoverIv *, int, long long, const char *, int32_t *);
+__global__ void cover_paint_kernel(const CoverIv *, int, long long, const int32_t *, int32_t, long long, uint32_t *);
+__global__ void cover_count_kernel(const CoverRegion *, int, long long, const char *, const uint32_t *, long long, sdf_cover_counts *);
 // anchors.hip
 struct AnchorPairDev {
   int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool

@@ -34,6 +34,10 @@ POOL_FETCH_DTYPE = np.dtype([("off", "<i8"), ("len", "<i4"), ("flags", "<i4"), (
 POOL_FETCH_REC_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("rc", "<i4"), ("seg0", "<i8")])
 FETCH_RC, FETCH_SEG_BYTES = 0x1, 16384
 assert POOL_FETCH_DTYPE.itemsize == 24 and POOL_FETCH_REC_DTYPE.itemsize == 32
+# include/sedef_hip.h: sdf_cover_interval / sdf_cover_counts (pool_coverage, pool_coverage_host)
+COVER_INTERVAL_DTYPE = np.dtype([(f, "<i4") for f in ("region", "start", "len", "set", "partner", "reserved")])
+COVER_COUNTS_DTYPE = np.dtype([(f, "<i8") for f in ("a", "b", "both", "a_only", "b_only", "a_only_upper", "b_only_upper")])
+assert COVER_INTERVAL_DTYPE.itemsize == 24 and COVER_COUNTS_DTYPE.itemsize == 56
 RESERVE_BRIEF, RESERVE_ANCHORS = 1, 2
 assert BRIEF_DTYPE.itemsize == 16
 assert TASK_DTYPE.itemsize == 40 and RESULT_DTYPE.itemsize == 64 and ANCHOR_PAIR_DTYPE.itemsize == 32
@@ -222,6 +226,11 @@ def load_library():
     L.sdf_pool_sync.argtypes = [C.c_void_p]
     L.sdf_pool_range_classes.restype = C.c_int
     L.sdf_pool_range_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _cover = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sdf_pool_coverage.restype = C.c_int  # ctx, regions, n_regions, iv, n_iv, min_upper, out, iv_upper, iv_painted
+    L.sdf_pool_coverage.argtypes = [C.c_void_p] + _cover
+    L.sdf_pool_coverage_host.restype = C.c_int  # pool, pool_bytes, then the same
+    L.sdf_pool_coverage_host.argtypes = [C.c_char_p, C.c_size_t] + _cover
     L.sdf_pool_fetch_ranges.restype = C.c_int
     L.sdf_pool_fetch_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.sdf_pool_fetch_plan.restype = C.c_int
@@ -623,6 +632,17 @@ class Extz2Engine:
         n = len(ranges)
         out = np.zeros(n, RANGE_CLASSES_DTYPE)
         rc = self.lib.sdf_pool_range_classes(self.ctx, ranges.ctypes.data if n else None, n, out.ctypes.data if n else None)
+        if not check:
+            return rc, out, self.lib.sdf_last_error(self.ctx).decode()
+        self._check(rc)
+        return out
+
+    def pool_coverage(self, regions, intervals, min_upper, check=True):
+        """sdf_pool_coverage: how two interval sets cover ranges of the resident pool.  regions: a POOL_RANGE_DTYPE array, or
+        (off, len) pairs; intervals: a COVER_INTERVAL_DTYPE array, or (region, start, len, set, partner) rows.  Returns (counts,
+        upper, painted): a COVER_COUNTS_DTYPE record per region, the uppercase bytes of every interval (int32) and whether it was
+        painted (uint8); check=False: (rc, that tuple, sdf_last_error) instead of raising."""
+        rc, out = pool_coverage_call(self.lib.sdf_pool_coverage, (self.ctx,), regions, intervals, min_upper)
         if not check:
             return rc, out, self.lib.sdf_last_error(self.ctx).decode()
         self._check(rc)
@@ -1418,6 +1438,34 @@ class Extz2Engine:
     def last_reran(self):
         """Tasks of the last batch that a stripe kernel gave up and the call ran again on another kernel."""
         return int(self.lib.sdf_last_reran(self.ctx))
+
+
+def pool_coverage_call(fn, head, regions, intervals, min_upper):
+    """sdf_pool_coverage (head: its context) or sdf_pool_coverage_host (head: the characters and their number) on numpy arrays.
+    Returns (rc, (counts, upper, painted))."""
+    if not (isinstance(regions, np.ndarray) and regions.dtype == POOL_RANGE_DTYPE):
+        pairs = np.asarray(regions, dtype=np.int64).reshape(-1, 2)
+        regions = np.zeros(len(pairs), POOL_RANGE_DTYPE)
+        regions["off"], regions["len"] = pairs[:, 0], pairs[:, 1]
+    if not (isinstance(intervals, np.ndarray) and intervals.dtype == COVER_INTERVAL_DTYPE):
+        rows = np.asarray(intervals, dtype=np.int64).reshape(-1, 5)
+        intervals = np.zeros(len(rows), COVER_INTERVAL_DTYPE)
+        for k, f in enumerate(("region", "start", "len", "set", "partner")):
+            intervals[f] = rows[:, k]
+    regions, intervals = np.ascontiguousarray(regions), np.ascontiguousarray(intervals)
+    nr, ni = len(regions), len(intervals)
+    counts, upper, painted = np.zeros(nr, COVER_COUNTS_DTYPE), np.zeros(ni, np.int32), np.zeros(ni, np.uint8)
+    ptr = lambda a: a.ctypes.data if len(a) else None  # noqa: E731
+    rc = fn(*head, ptr(regions), nr, ptr(intervals), ni, int(min_upper), ptr(counts), ptr(upper), ptr(painted))
+    return rc, (counts, upper, painted)
+
+
+def pool_coverage_host(pool, regions, intervals, min_upper, pool_bytes=None):
+    """sdf_pool_coverage_host: Extz2Engine.pool_coverage without a context or a GPU, over the characters `pool` (bytes or a
+    uint8 array).  Returns (rc, (counts, upper, painted))."""
+    pool = bytes(pool) if not isinstance(pool, bytes) else pool
+    return pool_coverage_call(load_library().sdf_pool_coverage_host, (pool, len(pool) if pool_bytes is None else int(pool_bytes)),
+                              regions, intervals, min_upper)
 
 
 def search_windows_call(fn, head, q, r_sorted, r_threshold, len_q, init_len, same_genome, uppercase_seeds, limit, cap=None, out=None,

@@ -12,7 +12,7 @@ HOST_SRC = os.path.join(_HERE, "csrc", "host")
 LIB = os.path.join(_HERE, "lib", "libsedef_host.so")
 CLI = os.path.join(_HERE, "bin", "sedef")
 MULTI = os.path.join(_HERE, "bin", "sdf_multi")
-_SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "pipeline.cc", "bucket.cc", "stats.cc", "search_cmd.cc", "host_cabi.cc"]
+_SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "pipeline.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "search_cmd.cc", "host_cabi.cc"]
 
 
 def build_host(force=False):

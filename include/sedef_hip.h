@@ -171,7 +171,7 @@ const sdf_config *sdf_get_config(const sdf_ctx *ctx);
  * buffers.  Call it where a context is set up: pinning takes the process's memory-map lock, and a pageable upload that
  * runs meanwhile (sdf_anchors_batch) waits for it -- measured: 46-78 ms for a 34-54 MB upload next to a reserve on another
  * thread, 4 ms without.  It must have returned before the context's first batch call.  (The stage driver: once per lane,
- * with the lane's context, host/pipeline.cc.) */
+ * with the lane's context, host/dp_provider.cc.) */
 #define SDF_RESERVE_BRIEF 1u /* the caller reads results through sdf_extz2_batch_brief: 16 bytes of result staging per task */
 #define SDF_RESERVE_ANCHORS 2u /* the caller will use sdf_anchors_batch: one tiny call now, so that the first real one does not
                                   pay for the first launch of its kernels and of the library sort behind it */
@@ -285,7 +285,7 @@ int sdf_extz2_batch_pairs_view(sdf_ctx *ctx, const sdf_scoring *sc, const sdf_ta
 /* ---- character classes of ranges of the resident pool ----------------------------------------------------------------
  * How many bytes of pool[off, off + len), as they lie in HBM, are ACGT, acgt, 'N' or 'n', and anything else; the four counts
  * add up to len.  The class of a byte is decided on the WHOLE byte: one of 128 or more is `other` (the stage driver's own
- * scan, PairJob in host/pipeline.cc, indexes its table by the unsigned char -- unlike rev_dna and align_dna, which look at
+ * scan, PairJob in host/pair_job.cc, indexes its table by the unsigned char -- unlike rev_dna and align_dna, which look at
  * c & 127).  The counts are strand-free: rev_dna maps every class onto itself or onto 'N' (A <-> T and C <-> G keep their
  * case, N and n become N, everything else becomes N), so `other == 0` holds for a range exactly when it holds for its
  * reverse complement, and a pair of the stage driver is "plain" -- nothing but ACGTNacgtn -- exactly when other == 0 on both

@@ -5,11 +5,9 @@
 #include <cstring>
 #include <string>
 
-#include "sedef_host.h"
+#include "stage_internal.h"
 
 using namespace sdfh;
-
-namespace sdfh { void set_alignment_scoring(const Params &p); }
 
 static thread_local std::string g_err;
 
@@ -63,7 +61,7 @@ int sdfh_generate(const char *ref_path, const char *bed_path, int kmer, const ch
   }
 }
 
-// several buckets, one provider (host/pipeline.cc: generate_many): `beds` = bucket paths separated by newlines; every
+// several buckets, one provider (host/stage_driver.cc: generate_many): `beds` = bucket paths separated by newlines; every
 // bucket's lines go to `<bucket><out_suffix>`.  stats: per bucket {lines, hits} (2 x buckets entries).
 // `totals`: behind them the four totals of the process (stage_totals).  resident: StageSettings::stage_resident for this
 // run -- the lanes' providers are then set up side by side, as the CLI does, and the chromosomes loaded before the stage.
@@ -117,12 +115,19 @@ int sdfh_generate_many_resident(const char *ref_path, const char *beds, int kmer
   return generate_many_impl(ref_path, beds, kmer, out_suffix, log_dir, test_dp, device,
                             resident != 0 || StageSettings::from_env().stage_resident, true, stats);
 }
-// resident_range (host/pipeline.cc; test hook): 0 and *off, or -1 when the request is not inside the host's copy
+// resident_range (host/stage_driver.cc; test hook): 0 and *off, or -1 when the request is not inside the host's copy
 int sdfh_resident_range(long long base, long long start, long long seq_len, long long s, long long len, int rc, long long *off) {
   int64_t o = 0;
   if (!resident_range(base, start, seq_len, s, len, rc != 0, &o)) return -1;
   *off = o;
   return 0;
+}
+// the DP tasks a request of qlen x tlen bases is cut into, `step` bases at a time (host/dp_provider.cc: for_each_chunk; test
+// hook): per chunk {first query base, first byte of the target in pool order -- of a target that starts at t_off and, with t_rc,
+// is read reversed --, query length, target length} into out[0, 4 * cap); returns the number of chunks, or -1
+long sdfh_dp_chunks(int qlen, int tlen, int step, int t_rc, long long t_off, long long *out, long cap) {
+  if (qlen < 0 || tlen < 0 || step < 1 || cap < 0) return -1;
+  return (long)dp_chunks(qlen, tlen, (size_t)step, t_rc != 0, t_off, out, (size_t)cap);
 }
 
 // `sedef stats generate genome.fa final.bed > out` (reference: src/stats_main.cc:339-389); test_cols: the oracle's column

@@ -12,13 +12,14 @@ HOST_SRC = os.path.join(_HERE, "csrc", "host")
 LIB = os.path.join(_HERE, "lib", "libsedef_host.so")
 CLI = os.path.join(_HERE, "bin", "sedef")
 MULTI = os.path.join(_HERE, "bin", "sdf_multi")
-_SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "pipeline.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "search_cmd.cc", "host_cabi.cc"]
+_SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "host_threads.cc", "stage_settings.cc", "dp_provider.cc", "pair_job.cc",
+            "stage_driver.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "search_cmd.cc", "host_cabi.cc"]
 
 
 def build_host(force=False):
     """g++ build of the host library and the `sedef` CLI (needs libsedef_hip.so next to it)."""
     srcs = [os.path.join(HOST_SRC, f) for f in _SOURCES]
-    deps = srcs + [os.path.join(HOST_SRC, "sedef_host.h"), os.path.join(HOST_SRC, "sedef_main.cc"),
+    deps = srcs + [os.path.join(HOST_SRC, "sedef_host.h"), os.path.join(HOST_SRC, "stage_internal.h"), os.path.join(HOST_SRC, "sedef_main.cc"),
                    os.path.join(HOST_SRC, "multi_gpu.cc")]
     multi_ok = os.path.exists(MULTI) or os.path.exists(MULTI + ".skipped")
     built = [LIB, CLI] + ([MULTI] if os.path.exists(MULTI) else [])
@@ -82,7 +83,7 @@ def generate(ref_path, bed_path, kmer, out_path, match=5, mismatch=-4, gap_open=
 
 
 def generate_many(ref_path, beds, kmer, out_suffix=".aligned.bed", log_dir=None, test_dp=None, device=0):
-    """Several buckets through ONE provider (csrc/host/pipeline.cc: generate_many): bucket b's lines go to b + out_suffix.
+    """Several buckets through ONE provider (csrc/host/stage_driver.cc: generate_many): bucket b's lines go to b + out_suffix.
     `beds`: bucket files or directories of bucket_???? files.  Returns [(lines, hits)] per bucket."""
     lib = load_host()
     # (two figures per bucket; a directory stands for the bucket_???? files in it)
@@ -108,6 +109,20 @@ def generate_many_resident(ref_path, beds, kmer, out_suffix=".aligned.bed", log_
                                         log_dir.encode() if log_dir else None, test_dp, device, int(bool(resident)), stats)
     _err(lib, min(n, 0))
     return [(int(stats[2 * k]), int(stats[2 * k + 1])) for k in range(n)], tuple(int(stats[2 * n + i]) for i in range(4))
+
+
+def dp_chunks(qlen, tlen, step, t_rc=False, t_off=0):
+    """Test hook: the DP tasks a request of qlen x tlen bases is cut into, `step` bases at a time (csrc/host/dp_provider.cc:
+    for_each_chunk) -> [(first query base, first byte of the target in pool order, query length, target length)]; the target
+    starts at pool byte t_off and, with t_rc, is read reversed."""
+    lib = load_host()
+    lib.sdfh_dp_chunks.restype = C.c_long
+    lib.sdfh_dp_chunks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_longlong), C.c_long]
+    cap = min(qlen, tlen) // step + 2
+    out = (C.c_longlong * (4 * cap))()
+    n = lib.sdfh_dp_chunks(qlen, tlen, step, int(bool(t_rc)), t_off, out, cap)
+    assert 0 <= n <= cap, n
+    return [tuple(int(x) for x in out[4 * k:4 * k + 4]) for k in range(n)]
 
 
 _buf = None

@@ -183,7 +183,7 @@ class ChainCheck:
 # calls into the reference's own classes compiled unmodified (oracle/_ref/libref_align.so through
 # oracle.binding.ReferenceAlign: oracle/ref_hit_table.cc).  Seed anchors come from the brute-force definition above.
 # The three reference files themselves cannot be compiled in this image (Boost.ICL); this is the independent check
-# their restatement in sedef_amd/csrc/host/pipeline.cc is held to (tests/golden/make_golden_stage_pairs.py).
+# their restatement in sedef_amd/csrc/host/pair_job.cc is held to (tests/golden/make_golden_stage_pairs.py).
 # ======================================================================================================================
 import math
 

@@ -1481,7 +1481,7 @@ def test_resident_pool_after_anchors_call(oracle):
 
 
 def test_view_entries_and_anchors_in_two_halves(oracle):
-    """The entry points the stage driver binds since round 6 (host/pipeline.cc: GpuProvider): sdf_anchors_batch_view on the
+    """The entry points the stage driver binds since round 6 (host/dp_provider.cc: GpuProvider): sdf_anchors_batch_view on the
     first half of a super-batch's pairs, sdf_anchors_batch_more on the second half BEHIND the first half's anchors (which must
     stay what they were), sdf_extz2_batch_pairs_view -- against the copying forms of the same calls on the same resident pool."""
     import ctypes as C

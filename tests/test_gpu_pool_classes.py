@@ -1,7 +1,7 @@
 """Character classes of ranges of the resident pool on the GPU (sdf_pool_range_classes; seq_pack.hip: pool_classes_kernel).
 
 The expected counts are numpy's on the same bytes, compared exactly.  The class of a byte is decided on the whole byte, as the
-table of the stage driver's PairJob does (sedef_amd/csrc/host/pipeline.cc): ACGT, acgt, N or n, everything else -- a byte of 128
+table of the stage driver's PairJob does (sedef_amd/csrc/host/pair_job.cc): ACGT, acgt, N or n, everything else -- a byte of 128
 or more is `other`."""
 import os
 import sys

@@ -1,4 +1,4 @@
-"""Where a DP request of the stage driver finds its bases in a resident chromosome (host/pipeline.cc: resident_range, exported
+"""Where a DP request of the stage driver finds its bases in a resident chromosome (host/stage_driver.cc: resident_range, exported
 as sdfh_resident_range): the rule of INTEGRATION.md section 2 against a brute-force model and against real bytes."""
 import ctypes as C
 

@@ -4,7 +4,7 @@ tests/golden/stage_pairs_kat.json.xz (generator: tests/golden/make_golden_stage_
 model of src/chain.cc:103-268, src/refine.cc:23-193 and src/align_main.cc:200-337 (tests/bruteforce.py: StageModel, control
 flow only) produces when every alignment, merge, guide alignment, tree query, FASTA fetch and BED line on the way is made by
 the reference's Alignment / Hit / SegmentTree / FastaReference classes compiled unmodified.  The product's host pipeline
-(sedef_amd/csrc/host/pipeline.cc, chain.cc) has to reproduce it byte for byte: with the CPU test hook here, through the GPU
+(sedef_amd/csrc/host/pair_job.cc, stage_driver.cc, chain.cc) has to reproduce it byte for byte: with the CPU test hook here, through the GPU
 provider and the CLI under -m gpu."""
 import ctypes as C
 import json

@@ -7,7 +7,7 @@ code (sedef_amd/csrc/host) and the HIP kernels can be checked against something 
     (src/chain.cc:24-101) streams query k-mers through a hash join and keeps, per diagonal, the query position up to
     which matches are already covered (`slide[]`, src/chain.cc:42,70-99).  Net effect per diagonal and per maximal
     case-insensitive N-free match run [s, e): ONE anchor, starting at the first position of the run whose k-mer is
-    eligible (fewer than 1000 occurrences in the reference sequence, src/chain.cc:61; not within k of the main diagonal
+    eligible (fewer than 1000 occurrences of its hash in the reference sequence, src/chain.cc:61; not within k of the main diagonal
     of a same-chromosome pair, src/chain.cc:67-69) and reaching to e; `has_u` is "any uppercase base in either
     sequence" (a bool accumulated with +=, src/chain.cc:74,84).  Order: query position, then reference position.
 
@@ -32,7 +32,16 @@ def _codes(s):
     return a
 
 
+# hash_dna (src/common.h:56-69,89): C, G, T in either case -> 1, 2, 3; A and every other byte -> 0
+_CODE2 = bytes(1 if c in b"Cc" else 2 if c in b"Gg" else 3 if c in b"Tt" else 0 for c in range(256))
+
+
 def anchors_bruteforce(q, r, k, same_chr=False, qstart=0, rstart=0, max_occ=1000):
+    """Occurrences are counted as the reference counts them: by the window's 2-bit code sequence (the hash of
+    src/chain.cc:34,54 with hash_dna of src/common.h:56-69,89, where every byte other than C, G, T of either case codes as
+    A does), over the reference windows without an N or n (src/chain.cc:28-40); a query window is looked up the same way and
+    skipped if it holds an N or at `max_occ` occurrences and more (src/chain.cc:54-62).  The match runs themselves are
+    comparisons of characters, case-insensitive (src/chain.cc:77-83)."""
     n, m = len(q), len(r)
     if n < k or m < k:
         return []
@@ -41,19 +50,18 @@ def anchors_bruteforce(q, r, k, same_chr=False, qstart=0, rstart=0, max_occ=1000
     ru = np.frombuffer(r.encode(), dtype=np.uint8)
     q_upper = (qu >= 65) & (qu <= 90)
     r_upper = (ru >= 65) & (ru <= 90)
-    # occurrences of every N-free reference k-mer
+    # occurrences of every N-free reference window, by its codes
     occ = {}
-    R_str = r.upper()
+    R_str, R_code = r.upper(), r.encode().translate(_CODE2)
     for i in range(m - k + 1):
-        w = R_str[i:i + k]
-        if "N" not in w:
+        if "N" not in R_str[i:i + k]:
+            w = R_code[i:i + k]
             occ[w] = occ.get(w, 0) + 1
-    Q_str = q.upper()
+    Q_str, Q_code = q.upper(), q.encode().translate(_CODE2)
     q_ok = np.zeros(n, bool)  # k-mer starting here is eligible by frequency
     for i in range(n - k + 1):
-        w = Q_str[i:i + k]
-        c = occ.get(w, 0)
-        q_ok[i] = ("N" not in w) and 0 < c < max_occ
+        c = occ.get(Q_code[i:i + k], 0)
+        q_ok[i] = ("N" not in Q_str[i:i + k]) and 0 < c < max_occ
     out = []
     for d in range(-(n - 1), m):  # r = q + d
         if same_chr and abs(rstart + d - qstart) <= k:

@@ -426,7 +426,7 @@ def test_gpu_anchors_equal_host_anchors(host):
         q = hostgen.rseq(rng, int(rng.integers(5, 4000)), 0.004 if it % 2 else 0.0)
         r = hostgen.rseq(rng, int(rng.integers(0, 300))) + hostgen.mut(rng, q, rng.random() * 0.1) + \
             hostgen.rseq(rng, int(rng.integers(0, 300)))
-        if it % 5 == 0:  # low-complexity stretch: k-mers with >= 1000 occurrences are skipped
+        if it % 5 == 0:  # low-complexity stretch below the cap: at most 258 occurrences of a k-mer (the cap: test_gpu_anchor_edges.py)
             rep = "ACGTTGCAACGT" * 200
             q, r = q[:500] + rep + q[500:], r[:300] + rep + rep[:700] + r[300:]
         same = it % 3 == 0

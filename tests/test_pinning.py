@@ -94,7 +94,7 @@ def _anchor_cases(rng, n):
         q = hostgen.rseq(rng, int(rng.integers(5, 1500)), 0.004 if it % 2 else 0.0)
         r = hostgen.rseq(rng, int(rng.integers(0, 200))) + hostgen.mut(rng, q, rng.random() * 0.1) + \
             hostgen.rseq(rng, int(rng.integers(0, 200)))
-        if it % 5 == 0:  # k-mers with >= 1000 reference occurrences are skipped (src/chain.cc:61)
+        if it % 5 == 0:  # a repeat BELOW the cap of src/chain.cc:61: at most 142 occurrences of a k-mer (the cap: test_anchor_edges_cpu.py)
             rep = "ACGTTGCAACGT" * 100
             q, r = q[:300] + rep[:700] + q[300:], r[:200] + rep + rep[:500] + r[200:]
         if it % 7 == 0:  # a soft-masked stretch: has_u == 0 anchors

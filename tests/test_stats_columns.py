@@ -118,10 +118,7 @@ def test_gpu_stats_columns_equal_oracle_on_golden(oracle, stats_golden):
         assert [int(g[f]) for f in ("matches", "mismatches", "gaps", "gap_bases", "span")] == c["counts"]
 
 
-@pytest.mark.gpu
-def test_gpu_stats_columns_fuzz_and_edges(oracle):
-    import sedef_amd
-    eng = sedef_amd.Extz2Engine(0)
+def fuzz_cases():
     rng = np.random.default_rng(5)
     cases = [random_stats_case(rng, k) for k in range(1200)]
     # edges: nothing at all, empty CIGAR over sequences, only gaps, one column, zero-length runs only, all N, exactly
@@ -137,8 +134,42 @@ def test_gpu_stats_columns_fuzz_and_edges(oracle):
               (bytes(range(1, 256)), bytes(reversed(range(1, 256))), [(0, 100), (2, 55), (1, 55), (0, 100)]),
               (bytes(range(33, 128)) * 3, (bytes(range(33, 128)) * 3).swapcase(), [(0, 285)]),
               ("@[`{AZaz" * 9, "@[`{azAZ" * 9, [(0, 72)])]
-    _check_batch(eng, oracle, cases)
+    return cases
+
+
+def grouped_quads(cases):
+    """(grouped quads, those of them that hold a row of 17..32 runs: a second chunk of sixteen), by the kernel's rule."""
+    from stats_path_cases import paths
+    n = [len(runs) for _, _, runs in cases]
+    ps = paths(n)
+    grouped = [q for q in range(0, len(n), 4) if ps[q] == "group"]
+    return len(grouped), sum(any(17 <= c <= 32 for c in n[q:q + 4]) for q in grouped)
+
+
+def fuzz_cases_by_run_count():
+    """The same cases in a stable order by run count, so that the short ones are consecutive and share wavefronts (in the
+    generator's own order every quad holds an alignment of 40 runs or more); rows of 17..32 runs are added until twenty
+    grouped quads hold one."""
+    cases = fuzz_cases()
+    rng = np.random.default_rng(55)
+    k = len(cases)
+    while grouped_quads(sorted(cases, key=lambda c: len(c[2])))[1] < 20:
+        cases.append(random_stats_case(rng, k, n_runs=int(rng.integers(17, 33))))
+        k += 1
+    return sorted(cases, key=lambda c: len(c[2]))
+
+
+@pytest.mark.gpu
+def test_gpu_stats_columns_fuzz_and_edges(oracle):
+    import sedef_amd
+    eng = sedef_amd.Extz2Engine(0)
+    _check_batch(eng, oracle, fuzz_cases())
     assert len(eng.stats_columns_batch([])) == 0
+    # once more with the short ones side by side: four to a wavefront (tests/test_stats_paths_cpu.py counts them without a GPU)
+    by_count = fuzz_cases_by_run_count()
+    grouped, second_chunk = grouped_quads(by_count)
+    assert grouped >= 100 and second_chunk >= 20
+    _check_batch(eng, oracle, by_count)
 
 
 @pytest.mark.gpu

@@ -24,14 +24,16 @@ def check_case(got, case):
     assert cigar_to_str(got["cigar"]) == exp["cigar"], case["tag"]
 
 
-def random_stats_case(rng, k):
+def random_stats_case(rng, k, n_runs=None):
     """One (a, b, runs) alignment for the stats-columns tests: runs = [(op, len)] with op 0 'M', 1 'D' (a only),
     2 'I' (b only).  Mixed case, N runs, zero-length runs, more than 64 / 128 runs, long runs, a CIGAR that stops
-    short of the sequences, empty CIGARs -- chosen by k so that every generator run holds every kind."""
+    short of the sequences, empty CIGARs -- chosen by k so that every generator run holds every kind.
+    n_runs: that many runs instead of the count that k chooses (k still chooses everything else)."""
     kind = k % 8
-    n_runs = [0, 1, 3, 40, 64, 65, 150, 400][kind]
-    if k % 29 == 0:
-        n_runs = int(rng.integers(0, 700))
+    if n_runs is None:
+        n_runs = [0, 1, 3, 40, 64, 65, 150, 400][kind]
+        if k % 29 == 0:
+            n_runs = int(rng.integers(0, 700))
     max_len = [1, 5000, 300, 60, 8, 130, 40, 25][kind]
     if n_runs * max_len > 40000:
         max_len = max(1, 40000 // n_runs)

@@ -1451,6 +1451,63 @@ int sdf_allgatherv_results(sdf_comm *c, const sdf_result *d_out, size_t n_tasks,
                            sdf_result *d_all_out, size_t all_out_cap, uint32_t *d_all_cig, size_t all_cig_cap,
                            uint64_t *counts, void *stream);
 
+/* ---- `align bucket`: seed hits extended, sorted, merged and dealt into buckets (bucket_merge.hip) -------------------------------
+ * What bucket_alignments_extern does between `sedef search` and `sedef align generate` (src/align_main.cc:38-198, merge() of
+ * src/merge.cc:35-109), on records: a SEED HIT is a query range and a reference range of two chromosomes, both [start, end),
+ * with the strand of its reference side in bit 0 of `flags` (the query side of a seed is always forward).  Chromosome ids are
+ * the caller's numbering IN BYTE-WISE LEXICOGRAPHIC ORDER OF THE NAMES ("chr10" < "chr2"), so that every name comparison of
+ * the reference is an integer comparison here.  Two small tables come with them:
+ *   chr_group[n_chr]                       the translation group of each chromosome (`sedef translate`), in [0, n_groups)
+ *   group_pair_order[n_groups * n_groups]  entry gq * n_groups + gr: the rank of the string "tmp_<gq>_<gr>.tmp" among all such
+ *                                          strings -- the order the reference reads its temporary files in ("tmp_10_2" sorts
+ *                                          before "tmp_2_1"); a permutation of [0, n_groups^2)
+ * The steps, in the reference's arithmetic:
+ *   1. Hit::extend (src/hit.cc:200-207): w = max(q_end - q_start, r_end - r_start); w = min(max_extend, (int)(extend_ratio * w))
+ *      in fp64; starts = max(0, start - w), ends += w.
+ *   2. The sides are ordered: when (q_chr, q_start, q_end) > (r_chr, r_start, r_end) ids and coordinates change sides; the
+ *      strand bit stays where it is.  A hit is SELF when ids, starts and ends of its sides agree and the strand bit is clear;
+ *      self hits are dropped.
+ *   3. The hits are sorted by (group_pair_order of the two chromosomes' groups, strand, q_chr, r_chr, q_start, r_start) and swept
+ *      in that order: a hit opens a new RUN when one of the first four changes or when the largest q_end of the run so far +
+ *      merge_dist < its q_start; else it swallows every surviving hit W of its run that is not APART from it --
+ *      W.q_end + merge_dist < q_start, W.r_end < r_start - merge_dist or W.r_start > r_end + merge_dist --, grows to the union
+ *      and looks again until nothing more is swallowed.  A run's survivors leave in the order of (r_end, position in the sort).
+ *   4. The deal: cls = (int)sqrt((double)(q_end - q_start) * (double)(r_end - r_start)) / 1000; every class goes round the nbins
+ *      buckets on its own, starting where the class below it stopped (src/align_main.cc:147-175).
+ * out[0 .. *n_out) holds the merged hits in the order the reference deals them, each with its bucket: bucket file b is the
+ * hits with bucket == b in this order.  On seeds as `sedef search` prints them (no name, forward query) the result does not
+ * depend on how hits of equal sort key are ordered, which is what lets the device sort them stably.
+ * Before anything else, the same in all three forms (sdf_bucket_merge_device: what the host can see -- the first two, the last
+ * five and the pointers; a record or table entry that fails the rest there is dropped and counted in d_n_out[1]):
+ *   SDF_ERR_INVALID      n_chr > 2^19 or n_groups > 4096 or either < 1 with n > 0; an id or a group outside its range, a
+ *                        group_pair_order entry outside [0, n_groups^2); start < 0 or start > end; a coordinate above
+ *                        2^31 - 1 - max_extend - merge_dist (no int sum of the reference wraps); extend_ratio that is negative,
+ *                        not a number, or with extend_ratio * max(len) >= 2^31; max_extend < 0; nbins < 1; merge_dist < 0;
+ *                        out_cap < n; a null pointer with n > 0; a flags bit other than SDF_SEED_RC or pad != 0
+ *   SDF_ERR_UNSUPPORTED  n > 2^30
+ * n == 0 is SDF_OK with *n_out = 0 and no launch.
+ *   sdf_bucket_merge_host    plain C++ with the reference's containers: no context, no device, no error text
+ *   sdf_bucket_merge         host arrays in and out: uploads, the launches below, one wait
+ *   sdf_bucket_merge_device  everything in HBM (the tables too) on the context's stream, no host wait inside and nothing read
+ *                            back: d_n_out[0] = the number of records, d_n_out[1] = the records and table entries dropped as
+ *                            said above (0 for a call the other forms would accept); d_out holds out_cap >= n records
+ * The launches: bucket_prepare_kernel (steps 1-2 and the sort keys, a lane a seed), two stable radix sorts, a segmented
+ * max-scan and a sum for the runs, bucket_sweep_kernel (a wavefront per run of two or more hits), one radix sort by
+ * (run, r_end) for the order of step 3, one by class for step 4.  Buffers of the context that sdf_device_bytes() counts:
+ * about 150 bytes a seed. */
+#define SDF_SEED_RC 1u /* sdf_seed_hit::flags, sdf_bucket_hit::flags: the reference side is the reverse strand */
+typedef struct { int32_t q_chr, q_start, q_end, r_chr, r_start, r_end; uint32_t flags; uint32_t pad; /* must be 0 */ } sdf_seed_hit;
+typedef struct { int32_t q_chr, q_start, q_end, r_chr, r_start, r_end; uint32_t flags; int32_t bucket; } sdf_bucket_hit;
+typedef struct { double extend_ratio; int32_t max_extend, merge_dist, nbins; } sdf_bucket_params;
+int sdf_bucket_merge_host(const sdf_seed_hit *hits, size_t n, const int32_t *chr_group, size_t n_chr, const int32_t *group_pair_order,
+                          size_t n_groups, const sdf_bucket_params *params, sdf_bucket_hit *out, size_t out_cap, size_t *n_out);
+int sdf_bucket_merge(sdf_ctx *ctx, const sdf_seed_hit *hits, size_t n, const int32_t *chr_group, size_t n_chr,
+                     const int32_t *group_pair_order, size_t n_groups, const sdf_bucket_params *params, sdf_bucket_hit *out,
+                     size_t out_cap, size_t *n_out);
+int sdf_bucket_merge_device(sdf_ctx *ctx, const sdf_seed_hit *d_hits /* HBM */, size_t n, const int32_t *d_chr_group, size_t n_chr,
+                            const int32_t *d_group_pair_order, size_t n_groups, const sdf_bucket_params *params /* host */,
+                            sdf_bucket_hit *d_out, size_t out_cap, uint64_t *d_n_out /* two words */);
+
 /* ---- one-task drop-in: same contract as ksw_extz2_sse (extern/ksw2.h:50).  `km` is ignored
  * like in the reference build (no HAVE_KALLOC).  Uses a process-wide context on device 0 (or
  * the device named by SDF_DEVICE).  On a fatal error prints to stderr and exits with 120, the

@@ -18,6 +18,7 @@
 #include <map>
 #include <tuple>
 
+#include "../../../include/sedef_hip.h"
 #include "sedef_host.h"
 
 namespace sdfh {
@@ -120,8 +121,112 @@ static std::vector<std::string> seed_files(const std::string &path) {  // src/al
   return files;
 }
 
+// SDF_BUCKET_DEVICE=1: the seeds as records through ONE sdf_bucket_merge call (include/sedef_hip.h; form 2: through
+// sdf_bucket_merge_host, no device) and the bucket files from its records.  The records hold coordinates, ids and the strand of
+// the reference side and nothing else, which is all that survives of a seed as `sedef search` writes it (no name, forward
+// query; the comment and the jaccard column are lost in the BED round trips of the host path): any other seed keeps the whole
+// run on the host path -- false, with one line on stderr.
+bool bucket_alignments_records(const std::string &bed_path, int nbins, const std::string &output_dir, const std::string &reference,
+                               const BucketParams &bp, FILE *log, int form, int device) {
+  const auto ignored = [](const std::string &why) {
+    fprintf(stderr, "[sedef_amd] SDF_BUCKET_DEVICE=1 ignored: %s, the host path buckets this run\n", why.c_str());
+    return false;
+  };
+  // the seeds, and the chromosomes numbered in the order of their names (std::string compares bytes)
+  std::vector<Hit> seeds;
+  std::vector<std::pair<std::string, int>> read;
+  std::map<std::string, int> id_of;
+  for (auto &file : seed_files(bed_path)) {
+    std::ifstream fin(file.c_str());
+    if (!fin.is_open()) throw "BED file " + bed_path + " does not exist";
+    int count = 0;
+    for (std::string line; std::getline(fin, line); count++) {
+      seeds.push_back(Hit::from_bed(line));
+      const Hit &h = seeds.back();
+      if (!h.name.empty() || h.query->is_rc) return ignored("a seed with a name or a reverse query strand (" + file + ")");
+      id_of[h.query->name] = 0, id_of[h.ref->name] = 0;
+    }
+    read.emplace_back(file, count);
+  }
+  std::vector<std::string> names;
+  for (auto &kv : id_of) kv.second = (int)names.size(), names.push_back(kv.first);
+  const auto groups = generate_translation(reference);
+  const size_t n_groups = std::max<size_t>(groups.size(), 1);
+  if (n_groups > 4096 || names.size() > ((size_t)1 << 19)) return ignored("more than 4096 chromosome groups or 2^19 chromosomes");
+  std::vector<int32_t> chr_group(names.size(), 0);  // (a chromosome the index does not hold: group 0, as group_of[] answers)
+  for (size_t g = 0; g < groups.size(); g++)
+    for (auto &name : groups[g])
+      if (id_of.count(name)) chr_group[(size_t)id_of[name]] = (int32_t)g;
+  // the order the reference reads its temporary files in: that of their names
+  std::vector<int32_t> pair_order(n_groups * n_groups);
+  {
+    std::vector<std::pair<std::string, int32_t>> tmp;
+    for (size_t a = 0; a < n_groups; a++)
+      for (size_t b = 0; b < n_groups; b++) tmp.emplace_back("tmp_" + std::to_string(a) + "_" + std::to_string(b) + ".tmp", (int32_t)(a * n_groups + b));
+    std::sort(tmp.begin(), tmp.end());
+    for (size_t k = 0; k < tmp.size(); k++) pair_order[(size_t)tmp[k].second] = (int32_t)k;
+  }
+  std::vector<sdf_seed_hit> in(seeds.size());
+  for (size_t i = 0; i < seeds.size(); i++) {
+    const Hit &h = seeds[i];
+    in[i] = sdf_seed_hit{id_of[h.query->name], h.query_start, h.query_end, id_of[h.ref->name], h.ref_start, h.ref_end, h.ref->is_rc ? SDF_SEED_RC : 0u, 0u};
+  }
+  seeds.clear();
+  const sdf_bucket_params P{bp.extend_ratio, bp.max_extend, bp.merge_dist, nbins};
+  std::vector<sdf_bucket_hit> out(in.size());
+  size_t n_out = 0;
+  if (form == 2) {
+    if (sdf_bucket_merge_host(in.data(), in.size(), chr_group.data(), chr_group.size(), pair_order.data(), n_groups, &P, out.data(), out.size(), &n_out))
+      return ignored("sdf_bucket_merge_host does not take these seeds or parameters");
+  } else {
+    sdf_ctx *ctx = sdf_create(device, 0);
+    if (!ctx) throw std::string("no usable HIP device: ") + sdf_last_error(nullptr);
+    const int rc = sdf_bucket_merge(ctx, in.data(), in.size(), chr_group.data(), chr_group.size(), pair_order.data(), n_groups, &P, out.data(),
+                                    out.size(), &n_out);
+    const std::string why = rc ? sdf_last_error(ctx) : "";
+    sdf_destroy(ctx);
+    if (rc == SDF_ERR_INVALID || rc == SDF_ERR_UNSUPPORTED) return ignored(why);
+    if (rc) throw "sdf_bucket_merge: " + why;
+  }
+  int total = 0;
+  for (auto &r : read) {
+    total += r.second;
+    fprintf(log, "\rRead %10d alignments in %s         ", r.second, r.first.c_str());
+  }
+  fprintf(log, "\nRead total %d alignments\n", total);
+  fprintf(log, "\nFinished with sorting\n");
+  std::vector<FILE *> files;
+  for (int b = 0; b < nbins; b++) {
+    char name[64];
+    snprintf(name, sizeof name, "/bucket_%04d", b);
+    FILE *f = fopen((output_dir + name).c_str(), "w");
+    if (!f) throw "Cannot open file " + output_dir + name + " for writing";
+    files.push_back(f);
+  }
+  std::vector<std::shared_ptr<Sequence>> fwd(names.size()), rev(names.size());  // a chromosome's name on either strand
+  const auto side = [&](int32_t id, bool is_rc) {
+    std::shared_ptr<Sequence> &s = (is_rc ? rev : fwd)[(size_t)id];
+    if (!s) s = std::make_shared<Sequence>(names[(size_t)id], "", is_rc);
+    return s;
+  };
+  for (size_t j = 0; j < n_out; j++) {
+    const sdf_bucket_hit &r = out[j];
+    Hit h;
+    h.query = side(r.q_chr, false);
+    h.ref = side(r.r_chr, (r.flags & SDF_SEED_RC) != 0);
+    h.query_start = r.q_start, h.query_end = r.q_end, h.ref_start = r.r_start, h.ref_end = r.r_end;
+    fputs(h.to_bed(false).c_str(), files[(size_t)r.bucket]);
+    fputs("\n", files[(size_t)r.bucket]);
+  }
+  for (auto f : files) fclose(f);
+  return true;
+}
+
 void bucket_alignments_extern(const std::string &bed_path, int nbins, const std::string &output_dir, bool extend,
                               const std::string &reference, const BucketParams &bp, FILE *log) {
+  if (extend && stage_settings().bucket_device &&
+      bucket_alignments_records(bed_path, nbins, output_dir, reference, bp, log, 1, stage_settings().device))
+    return;
   std::map<std::string, int> group_of;
   {
     const auto groups = generate_translation(reference);

@@ -485,6 +485,18 @@ int sdfh_bucket(const char *bed_path, int nbins, const char *out_dir, const char
   }
 }
 
+// ... through the records of include/sedef_hip.h (bucket_alignments_records) -- form 1: sdf_bucket_merge on `device`, form 2:
+// sdf_bucket_merge_host.  Returns 1 when the bucket files were written, 0 when the seeds keep the host path (nothing written).
+int sdfh_bucket_records(const char *bed_path, int nbins, const char *out_dir, const char *reference, int form, int device) {
+  try {
+    BucketParams bp;
+    return bucket_alignments_records(bed_path, nbins, out_dir, reference, bp, stderr, form, device) ? 1 : 0;
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  }
+}
+
 // generate_anchors on the host (reference: src/chain.cc:24-101): "q r l has_u;" per anchor, in order
 int sdfh_anchors(const char *query, const char *ref, int kmer, int same_chr, int qstart, int rstart, char *buf,
                  size_t cap) {

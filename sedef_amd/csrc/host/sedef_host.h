@@ -554,6 +554,12 @@ int search_command(const SearchParams &p, FILE *out, FILE *log);
 int translate_command(const std::string &ref_path, FILE *out, FILE *log);
 void bucket_alignments_extern(const std::string &bed_path, int nbins, const std::string &output_dir, bool extend,
                               const std::string &reference, const BucketParams &bp, FILE *log);
+// The same through the records of include/sedef_hip.h (StageSettings::bucket_device; bucket.cc) -- form 1: one sdf_bucket_merge
+// call on `device`; form 2: sdf_bucket_merge_host, no device -- with byte-identical bucket files.  false, with one line on stderr:
+// the seeds carry what the records do not (a name, a reverse query strand) or the call does not take them; nothing is written
+// and the caller buckets on the host path.
+bool bucket_alignments_records(const std::string &bed_path, int nbins, const std::string &output_dir, const std::string &reference,
+                               const BucketParams &bp, FILE *log, int form, int device);
 
 // ---- the stage driver's own settings ---------------------------------------------------------------------
 // (the DP library's are include/sedef_hip.h: sdf_config).  Read from the environment in ONE place -- StageSettings::from_env,
@@ -577,6 +583,7 @@ struct StageSettings {
   bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise
   int search_wide = 0;       // SDF_SEARCH_WIDE_DEVICE=N: `search` finishes up to N WIDE / FOUND_WIDE windows of a round's seeding on the device (sdf_search_pair_indexed_wide's n_wide_max; 0: they go to the host)
   int search_lanes = 1;      // SDF_SEARCH_LANES=N (1 .. 16): `search` keeps N chromosome pairs in flight (sdf_search_lanes_open, sdf_search_pairs_indexed; 1: the pair loop, one sdf_search_pair_indexed_wide call after the other)
+  bool bucket_device = false;  // SDF_BUCKET_DEVICE=1: `align bucket` extends, sorts, merges and deals the seeds in one sdf_bucket_merge call (bucket_alignments_records); seeds with a name or a reverse query strand keep the host path
   int bucket_lanes = 2;      // SDF_BUCKET_LANES: buckets of a several-bucket run in flight, each on a device context of its own (1: one after the other)
   int translate_limit = 100 * 1000 * 1000;  // SDF_TEST_TRANSLATE_LIMIT: TEST ONLY -- the size at which `search -t` / `translate` start a new group (the reference's 100 MB)
   static StageSettings from_env();

@@ -124,6 +124,8 @@ int main(int argc, char **argv) {
               "  the resident chromosomes in one device call instead of cutting them out of the FASTA file (same output)\n"
               "sedef align bucket -n [count] [bed_directory(/)] [buckets/] [genome.fa]\n"
               "  bucket BEDs into [count] files for the alignment stage (--extend-ratio, --max-extend, --merge-dist)\n"
+              "  SDF_BUCKET_DEVICE=1 (default 0): the seeds are extended, sorted, merged and dealt on the device in one call (same\n"
+              "  files); seeds with a name or a reverse query strand keep the host path, said in one line on stderr\n"
               "sedef stats generate [genome.fa] [final.bed]\n"
               "  the per-alignment table of the final calls (--max-ok-gap, --min-split, --uppercase, --max-error)\n"
               "  SDF_STATS_CUTS_DEVICE=1 (default 0; only with SDF_STATS_RESIDENT=1 and without --max-ok-gap): the match counter,\n"

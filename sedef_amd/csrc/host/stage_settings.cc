@@ -30,6 +30,7 @@ StageSettings StageSettings::from_env() {
   s.translate_limit = (int)num("SDF_TEST_TRANSLATE_LIMIT", 1, 0x7fffffff, 100 * 1000 * 1000);
   s.stats_resident = num("SDF_STATS_RESIDENT", 0, 1, 0) != 0;
   s.stats_cuts_device = num("SDF_STATS_CUTS_DEVICE", 0, 1, 0) != 0;
+  s.bucket_device = num("SDF_BUCKET_DEVICE", 0, 1, 0) != 0;
   s.stats_diff_host = num("SDF_STATS_DIFF_HOST", 0, 1, 0) != 0;
   s.search_wide = (int)num("SDF_SEARCH_WIDE_DEVICE", 0, 1 << 20, 0);
   s.search_lanes = (int)num("SDF_SEARCH_LANES", 1, 16, 1);

@@ -349,6 +349,8 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(pf_recs, None) X(pf_out, None) /* sdf_pool_fetch_ranges: a piece's FetchRec records and its output bytes (fetch_stage_bytes) */ \
   X(cv_regions, None) X(cv_iv, None) X(cv_upper, None) X(cv_out, None) /* sdf_pool_coverage: a CoverRegion per region, a CoverIv and a count per interval, seven counters per region */ \
   X(cv_bits, None) /* ... the bitmaps: a bit per base of every region, set 0 then set 1 (pool_cover.hip), zeroed per call */ \
+  X(bk_ws, None) X(bk_tmp, None) /* sdf_bucket_merge_device: records, sort keys and places, scan items, runs, slots (sdf_bucket_api.hip: bucket_launch); hipCUB scratch */ \
+  X(bk_in, None) X(bk_chr, None) X(bk_pairs, None) X(bk_out, None) /* sdf_bucket_merge: the host form's copies (the two counts in front of the records) */ \
   X(fa_raw, Pool) /* a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta) */           \
   /* lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch */ \
   X(ln_recs, BatchCall) X(ln_keys, BatchCall) X(ln_vals, BatchCall) X(ln_sizes, BatchCall) X(ln_tmp, BatchCall)       \

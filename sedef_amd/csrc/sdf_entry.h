@@ -64,6 +64,44 @@ inline int check_cover(const sdf_pool_range *regions, size_t n_regions, const sd
   return SDF_OK;
 }
 
+// What every form of the bucket family asks of its scalars (include/sedef_hip.h: sdf_bucket_merge), in order; the first refusal
+// is the call's.  The pointers are the caller's arrays wherever they lie.
+inline int check_bucket_scalars(const void *hits, size_t n, const void *chr_group, size_t n_chr, const void *group_pair_order, size_t n_groups,
+                                const sdf_bucket_params *P, const void *out, size_t out_cap, const void *n_out, const char **why) {
+  if (!P || !n_out) return *why = "invalid arguments", SDF_ERR_INVALID;
+  if (P->nbins < 1) return *why = "nbins < 1", SDF_ERR_INVALID;
+  if (P->merge_dist < 0 || P->max_extend < 0) return *why = "merge_dist or max_extend below 0", SDF_ERR_INVALID;
+  if (!(P->extend_ratio >= 0)) return *why = "extend_ratio is negative or not a number", SDF_ERR_INVALID;
+  if (n > ((size_t)1 << 30)) return *why = "more than 2^30 seed hits in one call", SDF_ERR_UNSUPPORTED;
+  if (out_cap < n) return *why = "out_cap < n", SDF_ERR_INVALID;
+  if (n == 0) return SDF_OK;
+  if (!hits || !chr_group || !group_pair_order || !out) return *why = "invalid arguments", SDF_ERR_INVALID;
+  if (n_chr < 1 || n_chr > ((size_t)1 << 19)) return *why = "n_chr outside 1 .. 2^19", SDF_ERR_INVALID;
+  if (n_groups < 1 || n_groups > 4096) return *why = "n_groups outside 1 .. 4096", SDF_ERR_INVALID;
+  return SDF_OK;
+}
+// ... and, where the arrays are the host's, of every table entry and record: recs[i] = hit i behind bucket_prepare
+// (sdf_kernels.h: the record's own checks, Hit::extend, the ordered sides).
+inline int check_bucket(const sdf_seed_hit *hits, size_t n, const int32_t *chr_group, size_t n_chr, const int32_t *group_pair_order,
+                        size_t n_groups, const sdf_bucket_params *P, const void *out, size_t out_cap, const void *n_out,
+                        std::vector<BucketRec> *recs, std::string *why) {
+  const char *w = "";
+  if (int rc = check_bucket_scalars(hits, n, chr_group, n_chr, group_pair_order, n_groups, P, out, out_cap, n_out, &w)) return *why = w, rc;
+  recs->resize(n);
+  if (n == 0) return SDF_OK;
+  for (size_t c = 0; c < n_chr; c++)
+    if (chr_group[c] < 0 || (size_t)chr_group[c] >= n_groups) return *why = "chromosome " + std::to_string(c) + ": group out of range", SDF_ERR_INVALID;
+  for (size_t g = 0; g < n_groups * n_groups; g++)
+    if (group_pair_order[g] < 0 || (size_t)group_pair_order[g] >= n_groups * n_groups)
+      return *why = "group_pair_order entry " + std::to_string(g) + " out of range", SDF_ERR_INVALID;
+  for (size_t i = 0; i < n; i++) {
+    (*recs)[i] = bucket_prepare(hits[i], chr_group, (int32_t)n_chr, group_pair_order, (int32_t)n_groups, P->extend_ratio, P->max_extend, P->merge_dist);
+    if ((*recs)[i].flags & kBucketBad)
+      return *why = "seed hit " + std::to_string(i) + ": an id, a coordinate, a flag or its extension is outside what the call takes", SDF_ERR_INVALID;
+  }
+  return SDF_OK;
+}
+
 // The tail of a counted output, behind the launches that filled d_first[0 .. n] on `st`: first[0 .. n] back (a host form), or
 // d_first[n] alone (first == nullptr: a device form), one wait, *used = the need, and SDF_ERR_CIGAR_OVERFLOW -- "<before>
 // <need> <after>" -- when the need exceeds cap.

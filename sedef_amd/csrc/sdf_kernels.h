@@ -124,6 +124,98 @@ __host__ __device__ inline bool cover_painted(const int32_t partner, const int32
 __global__ void cover_upper_kernel(const CoverIv *, int, long long, const char *, int32_t *);
 __global__ void cover_paint_kernel(const CoverIv *, int, long long, const int32_t *, int32_t, long long, uint32_t *);
 __global__ void cover_count_kernel(const CoverRegion *, int, long long, const char *, const uint32_t *, long long, sdf_cover_counts *);
+// bucket_merge.hip
+struct BucketRec {  // a seed hit behind steps 1 and 2 of include/sedef_hip.h (sdf_bucket_merge): extended, sides ordered (32 bytes)
+  int32_t q_chr, q_start, q_end, r_chr, r_start, r_end;
+  uint32_t flags;  // SDF_SEED_RC | kBucketSelf | kBucketBad
+  int32_t pair;    // group_pair_order of the two chromosomes' groups
+};
+struct BucketBox {  // a window of the sweep (16 bytes)
+  int32_t q_start, q_end, r_start, r_end;
+};
+struct BucketSeg {  // an item of the segmented max-scan: head of a segment, largest q_end so far
+  int32_t head, val;
+};
+struct BucketSegMax {
+  __host__ __device__ BucketSeg operator()(const BucketSeg &a, const BucketSeg &b) const {
+    return b.head ? b : BucketSeg{a.head, a.val > b.val ? a.val : b.val};
+  }
+};
+static_assert(sizeof(BucketRec) == 32 && sizeof(sdf_seed_hit) == 32 && sizeof(sdf_bucket_hit) == 32 && sizeof(sdf_bucket_params) == 24,
+              "include/sedef_hip.h");
+constexpr uint32_t kBucketSelf = 2;  // a region against itself: takes no part in the sweep
+constexpr uint32_t kBucketBad = 4;   // fails a check of include/sedef_hip.h (the device form drops and counts it)
+constexpr uint32_t kBucketDeadClass = 1u << 22;  // sort key of a slot that does not leave; above every class (2^31 / 1000 < 2^22)
+// The checks of one record and steps 1 and 2, the one form the kernel and the host forms share.  A record that fails a check
+// comes back as kBucketBad with nothing else defined.
+__host__ __device__ inline BucketRec bucket_prepare(const sdf_seed_hit &h, const int32_t *chr_group, const int32_t n_chr,
+                                                    const int32_t *group_pair_order, const int32_t n_groups, const double extend_ratio,
+                                                    const int32_t max_extend, const int32_t merge_dist) {
+#pragma clang fp contract(off)
+  BucketRec r{h.q_chr, h.q_start, h.q_end, h.r_chr, h.r_start, h.r_end, h.flags, 0};
+  const int64_t top = (int64_t)0x7fffffff - max_extend - merge_dist;
+  bool ok = (h.flags & ~SDF_SEED_RC) == 0 && h.pad == 0 && h.q_chr >= 0 && h.q_chr < n_chr && h.r_chr >= 0 && h.r_chr < n_chr;
+  ok = ok && h.q_start >= 0 && h.r_start >= 0 && h.q_start <= h.q_end && h.r_start <= h.r_end && h.q_end <= top && h.r_end <= top;
+  int32_t w = ok ? (h.q_end - h.q_start > h.r_end - h.r_start ? h.q_end - h.q_start : h.r_end - h.r_start) : 0;
+  const double grown = extend_ratio * w;
+  ok = ok && grown < 2147483648.0;
+  int32_t gq = 0, gr = 0;
+  if (ok) {
+    gq = chr_group[h.q_chr], gr = chr_group[h.r_chr];
+    ok = gq >= 0 && gq < n_groups && gr >= 0 && gr < n_groups;
+  }
+  if (!ok) return r.flags = kBucketBad, r;
+  w = (int32_t)grown;  // Hit::extend, operation by operation
+  w = max_extend < w ? max_extend : w;
+  r.q_start = r.q_start - w > 0 ? r.q_start - w : 0;
+  r.q_end += w;
+  r.r_start = r.r_start - w > 0 ? r.r_start - w : 0;
+  r.r_end += w;
+  // order_sides: std::tie(name, start, end) of the query > that of the reference
+  const bool swap = r.q_chr != r.r_chr ? r.q_chr > r.r_chr : r.q_start != r.r_start ? r.q_start > r.r_start : r.q_end > r.r_end;
+  if (swap) {
+    int32_t t;
+    t = r.q_chr, r.q_chr = r.r_chr, r.r_chr = t;
+    t = r.q_start, r.q_start = r.r_start, r.r_start = t;
+    t = r.q_end, r.q_end = r.r_end, r.r_end = t;
+    t = gq, gq = gr, gr = t;
+  }
+  r.pair = group_pair_order[(int64_t)gq * n_groups + gr];
+  if (r.pair < 0 || r.pair >= n_groups * n_groups) return r.flags = kBucketBad, r;
+  if (r.q_chr == r.r_chr && r.q_start == r.r_start && r.q_end == r.r_end && !(r.flags & SDF_SEED_RC)) r.flags |= kBucketSelf;
+  return r;
+}
+// the two sort keys of a prepared record: key_hi first, key_lo among equals
+__host__ __device__ inline uint64_t bucket_key_hi(const BucketRec &r) {
+  return (uint64_t)r.pair << 39 | (uint64_t)(r.flags & SDF_SEED_RC) << 38 | (uint64_t)r.q_chr << 19 | (uint64_t)r.r_chr;
+}
+__host__ __device__ inline uint64_t bucket_key_lo(const BucketRec &r) { return (uint64_t)r.q_start << 32 | (uint32_t)r.r_start; }
+// merge()'s test of a window against the growing hit (src/merge.cc:73-76 with its lower_bound: the second clause)
+__host__ __device__ inline bool bucket_apart(const BucketBox &w, const BucketBox &h, const int32_t merge_dist) {
+  return w.q_end + merge_dist < h.q_start || w.r_end < h.r_start - merge_dist || w.r_start > h.r_end + merge_dist;
+}
+// the complexity class of a merged hit (src/align_main.cc:128-130): a correctly rounded product and root on both sides
+__host__ __device__ inline int32_t bucket_class(const BucketBox &b) {
+#pragma clang fp contract(off)
+  const double area = (double)(b.q_end - b.q_start) * (double)(b.r_end - b.r_start);
+#ifdef __HIP_DEVICE_COMPILE__
+  return (int32_t)__dsqrt_rn(area) / 1000;
+#else
+  return (int32_t)__builtin_sqrt(area) / 1000;
+#endif
+}
+__global__ void bucket_prepare_kernel(const sdf_seed_hit *, int, const int32_t *, int, const int32_t *, int, double, int, int, BucketRec *,
+                                      unsigned long long *, unsigned long long *, uint32_t *, unsigned long long *);
+__global__ void bucket_key_gather_kernel(const unsigned long long *, const uint32_t *, int, unsigned long long *);
+__global__ void bucket_runs_kernel(const BucketRec *, const uint32_t *, const unsigned long long *, int, BucketRec *, BucketSeg *);
+__global__ void bucket_new_run_kernel(const BucketRec *, const BucketSeg *, int, int, uint32_t *, BucketBox *, uint32_t *);
+__global__ void bucket_run_starts_kernel(const uint32_t *, const uint32_t *, int, uint32_t *);
+__global__ void bucket_sweep_kernel(BucketBox *, uint32_t *, const uint32_t *, const uint32_t *, int);
+__global__ void bucket_flush_keys_kernel(const BucketBox *, const uint32_t *, const uint32_t *, const uint32_t *, int,
+                                         unsigned long long *, uint32_t *);
+__global__ void bucket_class_kernel(const unsigned long long *, const uint32_t *, const BucketRec *, const BucketBox *, int,
+                                    sdf_bucket_hit *, uint32_t *, uint32_t *, unsigned long long *);
+__global__ void bucket_deal_kernel(const uint32_t *, const uint32_t *, int, int, sdf_bucket_hit *);
 // anchors.hip
 struct AnchorPairDev {
   int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool

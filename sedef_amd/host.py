@@ -287,6 +287,16 @@ def bucket(bed_path, nbins, out_dir, reference):
     _err(lib, lib.sdfh_bucket(bed_path.encode(), nbins, out_dir.encode(), reference.encode()))
 
 
+def bucket_records(bed_path, nbins, out_dir, reference, form=2, device=0):
+    """`sedef align bucket` through the records of include/sedef_hip.h (csrc/host/bucket.cc: bucket_alignments_records) -- form 1:
+    one sdf_bucket_merge call on `device` (what SDF_BUCKET_DEVICE=1 selects), form 2: sdf_bucket_merge_host, no device.  True:
+    the bucket files are written; False: the seeds keep the host path (one line on stderr, nothing written)."""
+    lib = load_host()
+    rc = lib.sdfh_bucket_records(bed_path.encode(), int(nbins), out_dir.encode(), reference.encode(), int(form), int(device))
+    _err(lib, min(rc, 0))
+    return rc == 1
+
+
 def anchors(q, r, kmer=11, same_chr=False, qstart=0, rstart=0):
     """Host generate_anchors (reference: src/chain.cc:24-101) -> list of (q, r, l, has_u)."""
     lib, buf = load_host(), _buffer()

@@ -1508,6 +1508,45 @@ int sdf_bucket_merge_device(sdf_ctx *ctx, const sdf_seed_hit *d_hits /* HBM */, 
                             const int32_t *d_group_pair_order, size_t n_groups, const sdf_bucket_params *params /* host */,
                             sdf_bucket_hit *d_out, size_t out_cap, uint64_t *d_n_out /* two words */);
 
+/* ---- search hits to seed records (seed_records.hip): the seam between `sedef search` and `align bucket` --------------------------
+ * The hits of sdf_search_pairs_indexed -- hits[first[j], first[j + 1]) are job j's -- become the sdf_seed_hit records that their
+ * BED lines would give `align bucket` (Hit::from_bed of search_hit_bed, csrc/host/search_cmd.cc), without the text.  jobs[j] says
+ * what the hits of job j do not: the ids of the query and the reference chromosome (the numbering of sdf_bucket_merge: byte order
+ * of the names), the reference's length and, in bit 0 of `flags` (SDF_SEED_RC), whether the reference was searched on the reverse
+ * strand.  Record t, of job j = the last job with first[j] <= t (jobs without hits repeat a value of first[] and are stepped over):
+ *   q_chr = jobs[j].q_chr, q_start = query_start, q_end = query_end, r_chr = jobs[j].r_chr, pad = 0
+ *   forward:  r_start = ref_start, r_end = ref_end, flags = 0
+ *   reverse:  r_start = (int)(ref_len - ref_end + 1), r_end = (int)(ref_len - ref_start + 1), flags = SDF_SEED_RC
+ *             (the low 32 bits of the difference, as the BED text has them: a flip may come out negative, and sdf_bucket_merge
+ *             then refuses the record)
+ * window and jaccard of a hit are not read.  Before anything else, the same in all three forms (sdf_seed_records_device: what
+ * the host can see -- n, n_jobs and the pointers; a first[] or a job it cannot read is the caller's to have checked):
+ *   SDF_ERR_UNSUPPORTED  n > 2^30; a job with reserved != 0 or a flags bit other than SDF_SEED_RC
+ *   SDF_ERR_INVALID      a null pointer with n > 0; first[0] != 0, first[] decreasing somewhere, first[n_jobs] != n (so n > 0 with
+ *                        n_jobs == 0)
+ * n == 0 is SDF_OK with no launch (first and jobs are still checked where they are given).
+ *   sdf_seed_records_host    plain C++: no context, no device, no error text
+ *   sdf_seed_records         host arrays in and out: uploads, the launch, one wait
+ *   sdf_seed_records_device  everything in HBM on the context's stream, no host wait inside and nothing read back, so that
+ *                            sdf_bucket_merge_device can follow on the same stream with d_out as its d_hits
+ * One launch, seed_records_kernel: a lane a hit, its job by a binary search of first[]. */
+typedef struct { int32_t q_chr, r_chr; int64_t ref_len; uint32_t flags /* SDF_SEED_RC */, reserved /* must be 0 */; } sdf_seed_job; /* 24 bytes */
+int sdf_seed_records_host(const sdf_search_pair_hit *hits, size_t n, const uint64_t *first /* n_jobs + 1 */, const sdf_seed_job *jobs,
+                          size_t n_jobs, sdf_seed_hit *out /* n */);
+int sdf_seed_records(sdf_ctx *ctx, const sdf_search_pair_hit *hits, size_t n, const uint64_t *first, const sdf_seed_job *jobs,
+                     size_t n_jobs, sdf_seed_hit *out);
+int sdf_seed_records_device(sdf_ctx *ctx, const sdf_search_pair_hit *d_hits /* HBM */, size_t n, const uint64_t *d_first,
+                            const sdf_seed_job *d_jobs, size_t n_jobs, sdf_seed_hit *d_out);
+/* The chain `sedef seeds` runs, from host arrays: hits, first[] and the job table go up in one piece with the two tables of the
+ * merge, sdf_seed_records_device and sdf_bucket_merge_device follow each other on the context's stream, then the two words of
+ * d_n_out come back and, behind them, the merged records.  Refusals: those of sdf_seed_records, then those sdf_bucket_merge_device
+ * makes; a null n_dropped is SDF_ERR_INVALID.  *n_dropped = d_n_out[1]: when it is not 0 -- a flipped coordinate below 0 or beyond
+ * what the merge takes, a table entry out of range -- the call is SDF_OK with *n_out = 0 and nothing in out, and the caller
+ * buckets these hits another way.  Buffers of the context that sdf_device_bytes() counts. */
+int sdf_seeds_bucket_merge(sdf_ctx *ctx, const sdf_search_pair_hit *hits, size_t n, const uint64_t *first, const sdf_seed_job *jobs,
+                           size_t n_jobs, const int32_t *chr_group, size_t n_chr, const int32_t *group_pair_order, size_t n_groups,
+                           const sdf_bucket_params *params, sdf_bucket_hit *out, size_t out_cap, size_t *n_out, size_t *n_dropped);
+
 /* ---- one-task drop-in: same contract as ksw_extz2_sse (extern/ksw2.h:50).  `km` is ignored
  * like in the reference build (no HAVE_KALLOC).  Uses a process-wide context on device 0 (or
  * the device named by SDF_DEVICE).  On a fatal error prints to stderr and exits with 120, the

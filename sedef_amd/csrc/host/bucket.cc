@@ -15,11 +15,12 @@
 #include <cmath>
 #include <cstdio>
 #include <fstream>
+#include <functional>
+#include <istream>
 #include <map>
 #include <tuple>
 
-#include "../../../include/sedef_hip.h"
-#include "sedef_host.h"
+#include "search_run.h"
 
 namespace sdfh {
 
@@ -121,6 +122,62 @@ static std::vector<std::string> seed_files(const std::string &path) {  // src/al
   return files;
 }
 
+// The two tables sdf_bucket_merge takes beside its records (include/sedef_hip.h), for chromosomes numbered in the order of `names`
+// (sorted: std::string compares bytes): the group of each by generate_translation(reference), and the order the reference reads its
+// temporary files in -- that of their names.  false: more groups or chromosomes than the call takes.
+bool bucket_tables(const std::vector<std::string> &names, const std::string &reference, BucketTables *t) {
+  std::map<std::string, int> id_of;
+  for (size_t i = 0; i < names.size(); i++) id_of[names[i]] = (int)i;
+  const auto groups = generate_translation(reference);
+  const size_t n_groups = std::max<size_t>(groups.size(), 1);
+  if (n_groups > 4096 || names.size() > ((size_t)1 << 19)) return false;
+  t->n_groups = n_groups;
+  t->chr_group.assign(names.size(), 0);  // (a chromosome the index does not hold: group 0, as group_of[] answers)
+  for (size_t g = 0; g < groups.size(); g++)
+    for (auto &name : groups[g])
+      if (id_of.count(name)) t->chr_group[(size_t)id_of[name]] = (int32_t)g;
+  t->pair_order.assign(n_groups * n_groups, 0);
+  std::vector<std::pair<std::string, int32_t>> tmp;
+  for (size_t a = 0; a < n_groups; a++)
+    for (size_t b = 0; b < n_groups; b++) tmp.emplace_back("tmp_" + std::to_string(a) + "_" + std::to_string(b) + ".tmp", (int32_t)(a * n_groups + b));
+  std::sort(tmp.begin(), tmp.end());
+  for (size_t k = 0; k < tmp.size(); k++) t->pair_order[(size_t)tmp[k].second] = (int32_t)k;
+  return true;
+}
+
+static std::vector<FILE *> open_buckets(int nbins, const std::string &output_dir) {
+  std::vector<FILE *> files;
+  for (int b = 0; b < nbins; b++) {
+    char name[64];
+    snprintf(name, sizeof name, "/bucket_%04d", b);
+    FILE *f = fopen((output_dir + name).c_str(), "w");
+    if (!f) throw "Cannot open file " + output_dir + name + " for writing";
+    files.push_back(f);
+  }
+  return files;
+}
+
+// The bucket files from the records of a merge call, out[0, n_out) in deal order: record j goes to file out[j].bucket.
+void write_bucket_records(const std::vector<std::string> &names, const sdf_bucket_hit *out, size_t n_out, int nbins, const std::string &output_dir) {
+  std::vector<FILE *> files = open_buckets(nbins, output_dir);
+  std::vector<std::shared_ptr<Sequence>> fwd(names.size()), rev(names.size());  // a chromosome's name on either strand
+  const auto side = [&](int32_t id, bool is_rc) {
+    std::shared_ptr<Sequence> &s = (is_rc ? rev : fwd)[(size_t)id];
+    if (!s) s = std::make_shared<Sequence>(names[(size_t)id], "", is_rc);
+    return s;
+  };
+  for (size_t j = 0; j < n_out; j++) {
+    const sdf_bucket_hit &r = out[j];
+    Hit h;
+    h.query = side(r.q_chr, false);
+    h.ref = side(r.r_chr, (r.flags & SDF_SEED_RC) != 0);
+    h.query_start = r.q_start, h.query_end = r.q_end, h.ref_start = r.r_start, h.ref_end = r.r_end;
+    fputs(h.to_bed(false).c_str(), files[(size_t)r.bucket]);
+    fputs("\n", files[(size_t)r.bucket]);
+  }
+  for (auto f : files) fclose(f);
+}
+
 // SDF_BUCKET_DEVICE=1: the seeds as records through ONE sdf_bucket_merge call (include/sedef_hip.h; form 2: through
 // sdf_bucket_merge_host, no device) and the bucket files from its records.  The records hold coordinates, ids and the strand of
 // the reference side and nothing else, which is all that survives of a seed as `sedef search` writes it (no name, forward
@@ -150,22 +207,10 @@ bool bucket_alignments_records(const std::string &bed_path, int nbins, const std
   }
   std::vector<std::string> names;
   for (auto &kv : id_of) kv.second = (int)names.size(), names.push_back(kv.first);
-  const auto groups = generate_translation(reference);
-  const size_t n_groups = std::max<size_t>(groups.size(), 1);
-  if (n_groups > 4096 || names.size() > ((size_t)1 << 19)) return ignored("more than 4096 chromosome groups or 2^19 chromosomes");
-  std::vector<int32_t> chr_group(names.size(), 0);  // (a chromosome the index does not hold: group 0, as group_of[] answers)
-  for (size_t g = 0; g < groups.size(); g++)
-    for (auto &name : groups[g])
-      if (id_of.count(name)) chr_group[(size_t)id_of[name]] = (int32_t)g;
-  // the order the reference reads its temporary files in: that of their names
-  std::vector<int32_t> pair_order(n_groups * n_groups);
-  {
-    std::vector<std::pair<std::string, int32_t>> tmp;
-    for (size_t a = 0; a < n_groups; a++)
-      for (size_t b = 0; b < n_groups; b++) tmp.emplace_back("tmp_" + std::to_string(a) + "_" + std::to_string(b) + ".tmp", (int32_t)(a * n_groups + b));
-    std::sort(tmp.begin(), tmp.end());
-    for (size_t k = 0; k < tmp.size(); k++) pair_order[(size_t)tmp[k].second] = (int32_t)k;
-  }
+  BucketTables tab;
+  if (!bucket_tables(names, reference, &tab)) return ignored("more than 4096 chromosome groups or 2^19 chromosomes");
+  const std::vector<int32_t> &chr_group = tab.chr_group, &pair_order = tab.pair_order;
+  const size_t n_groups = tab.n_groups;
   std::vector<sdf_seed_hit> in(seeds.size());
   for (size_t i = 0; i < seeds.size(); i++) {
     const Hit &h = seeds[i];
@@ -195,30 +240,7 @@ bool bucket_alignments_records(const std::string &bed_path, int nbins, const std
   }
   fprintf(log, "\nRead total %d alignments\n", total);
   fprintf(log, "\nFinished with sorting\n");
-  std::vector<FILE *> files;
-  for (int b = 0; b < nbins; b++) {
-    char name[64];
-    snprintf(name, sizeof name, "/bucket_%04d", b);
-    FILE *f = fopen((output_dir + name).c_str(), "w");
-    if (!f) throw "Cannot open file " + output_dir + name + " for writing";
-    files.push_back(f);
-  }
-  std::vector<std::shared_ptr<Sequence>> fwd(names.size()), rev(names.size());  // a chromosome's name on either strand
-  const auto side = [&](int32_t id, bool is_rc) {
-    std::shared_ptr<Sequence> &s = (is_rc ? rev : fwd)[(size_t)id];
-    if (!s) s = std::make_shared<Sequence>(names[(size_t)id], "", is_rc);
-    return s;
-  };
-  for (size_t j = 0; j < n_out; j++) {
-    const sdf_bucket_hit &r = out[j];
-    Hit h;
-    h.query = side(r.q_chr, false);
-    h.ref = side(r.r_chr, (r.flags & SDF_SEED_RC) != 0);
-    h.query_start = r.q_start, h.query_end = r.q_end, h.ref_start = r.r_start, h.ref_end = r.r_end;
-    fputs(h.to_bed(false).c_str(), files[(size_t)r.bucket]);
-    fputs("\n", files[(size_t)r.bucket]);
-  }
-  for (auto f : files) fclose(f);
+  write_bucket_records(names, out.data(), n_out, nbins, output_dir);
   return true;
 }
 
@@ -227,6 +249,21 @@ void bucket_alignments_extern(const std::string &bed_path, int nbins, const std:
   if (extend && stage_settings().bucket_device &&
       bucket_alignments_records(bed_path, nbins, output_dir, reference, bp, log, 1, stage_settings().device))
     return;
+  bucket_alignments_streams(
+      [&](const SeedStreamVisitor &visit) {
+        for (auto &file : seed_files(bed_path)) {
+          std::ifstream fin(file.c_str());
+          if (!fin.is_open()) throw "BED file " + bed_path + " does not exist";
+          visit(file, fin);
+        }
+      },
+      nbins, output_dir, extend, reference, bp, log);
+}
+
+// The host path on seed lines wherever they come from: each_file calls its visitor once per seeds file, in the order the files
+// are read, with the file's name and its lines.
+void bucket_alignments_streams(const std::function<void(const SeedStreamVisitor &)> &each_file, int nbins, const std::string &output_dir, bool extend,
+                               const std::string &reference, const BucketParams &bp, FILE *log) {
   std::map<std::string, int> group_of;
   {
     const auto groups = generate_translation(reference);
@@ -237,9 +274,7 @@ void bucket_alignments_extern(const std::string &bed_path, int nbins, const std:
   //    temporary file name: groups are processed in the order of these strings.
   std::map<std::string, std::vector<std::string>> group_lines;
   int total = 0;
-  for (auto &file : seed_files(bed_path)) {
-    std::ifstream fin(file.c_str());
-    if (!fin.is_open()) throw "BED file " + bed_path + " does not exist";
+  each_file([&](const std::string &file, std::istream &fin) {
     int count = 0;
     for (std::string line; std::getline(fin, line); count++) {
       Hit h = Hit::from_bed(line);
@@ -251,7 +286,7 @@ void bucket_alignments_extern(const std::string &bed_path, int nbins, const std:
     }
     total += count;
     fprintf(log, "\rRead %10d alignments in %s         ", count, file.c_str());
-  }
+  });
   fprintf(log, "\nRead total %d alignments\n", total);
 
   // 2. merge every group; count the hits per complexity class (sqrt of the area, in thousands)
@@ -275,14 +310,7 @@ void bucket_alignments_extern(const std::string &bed_path, int nbins, const std:
   //    (src/align_main.cc:147-175), so that each bucket gets its share of cheap and of expensive pairs
   std::vector<int> next_bucket(1, 0);
   for (int c = 1; c <= max_complexity / 1000; c++) next_bucket.push_back((next_bucket[(size_t)c - 1] + per_class[c - 1]) % nbins);
-  std::vector<FILE *> out;
-  for (int b = 0; b < nbins; b++) {
-    char name[64];
-    snprintf(name, sizeof name, "/bucket_%04d", b);
-    FILE *f = fopen((output_dir + name).c_str(), "w");
-    if (!f) throw "Cannot open file " + output_dir + name + " for writing";
-    out.push_back(f);
-  }
+  std::vector<FILE *> out = open_buckets(nbins, output_dir);
   for (auto &g : group_lines)
     for (auto &line : g.second) {
       Hit h = Hit::from_bed(line);

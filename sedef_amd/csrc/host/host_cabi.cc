@@ -656,4 +656,51 @@ int sdfh_search_args(const char *args, char *buf, size_t cap) {
   }
 }
 
+// ---- `sedef seeds` (seeds_cmd.cc) ----
+// the pairs of a run over genome.fa.fai at a group limit, in order: "i j reverse q r same_genome" per pair, separated by '|'
+int sdfh_seeds_pairs(const char *ref_path, int max_size, char *buf, size_t cap) {
+  try {
+    std::string out;
+    for (auto &p : seeds_pairs(generate_translation(ref_path, max_size)))
+      out += (out.empty() ? "" : "|") + std::to_string(p.i) + " " + std::to_string(p.j) + " " + (p.reverse ? "1 " : "0 ") + p.q + " " + p.r +
+             ((p.q == p.r && !p.reverse) ? " 1" : " 0");
+    return copy_out(out, buf, cap);
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  }
+}
+
+// the arguments behind `sedef seeds`, separated by newlines -> "k w u nbins extend_ratio max_extend merge_dist|seeds dir|pos..."
+int sdfh_seeds_args(const char *args, char *buf, size_t cap) {
+  try {
+    std::vector<std::string> a = split(args, '\n');
+    std::vector<char *> argv;
+    for (auto &s : a) argv.push_back(&s[0]);
+    const SeedsParams p = parse_seeds_args((int)argv.size(), argv.data());
+    char head[256];
+    snprintf(head, sizeof head, "%d %d %d %d %.17g %d %d", p.search.kmer_size, p.search.window_size, p.search.min_uppercase, p.nbins,
+             p.bucket.extend_ratio, p.bucket.max_extend, p.bucket.merge_dist);
+    std::string out = std::string(head) + "|" + p.seeds_dir;
+    for (auto &s : p.search.pos) out += "|" + s;
+    return copy_out(out, buf, cap);
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  }
+}
+
+// Hit::from_bed of a line as `align bucket` reads a seed: out = {query_start, query_end, ref_start, ref_end, query is_rc, ref is_rc};
+// buf: "query name|reference name"
+int sdfh_hit_from_bed(const char *line, int *out, char *buf, size_t cap) {
+  try {
+    const Hit h = Hit::from_bed(line);
+    out[0] = h.query_start, out[1] = h.query_end, out[2] = h.ref_start, out[3] = h.ref_end, out[4] = h.query->is_rc, out[5] = h.ref->is_rc;
+    return copy_out(h.query->name + "|" + h.ref->name, buf, cap);
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  }
+}
+
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include <set>
 
 #include "../../../include/sedef_hip.h"
+#include "search_run.h"
 #include "sedef_host.h"
 
 namespace sdfh {
@@ -237,7 +238,7 @@ std::string search_hit_bed(const std::string &qname, const std::string &rname, i
 // ---- the arguments ----------------------------------------------------------------------------------------------------
 // The reference's parser takes a value for the options it has registered and reads every other option as a flag; a token
 // that is a number is never an option.  -l / --min-read-size is registered there and never read: its value is dropped here too.
-SearchParams parse_search_args(int argc, char **argv) {
+SearchParams parse_search_options(int argc, char **argv) {
   static const char *const with_value[] = {"k", "kmer", "w", "window", "u", "uppercase", "e", "error", "E", "edit-error",
                                            "g", "gap-freq", "l", "min-read-size", "limit-table"};
   SearchParams p;
@@ -281,30 +282,151 @@ SearchParams parse_search_args(int argc, char **argv) {
     else throw "Unknown option " + a;
   }
   p.min_read_size = (int)(1000 * (1 - p.max_error));  // KB * (1 - MAX_ERROR), in double as written
+  return p;
+}
+SearchParams parse_search_args(int argc, char **argv) {
+  SearchParams p = parse_search_options(argc, argv);
   if (p.pos.size() < 3) throw std::string("Not enough arguments to search");
   return p;
 }
 
-// ---- the command ------------------------------------------------------------------------------------------------------
+
+// ---- a run on one device context (search_run.h) -----------------------------------------------------------------------------
 namespace {
-struct Ctx {  // the device context of a run
-  sdf_ctx *ctx = nullptr;
-  explicit Ctx(int device) : ctx(sdf_create(device, 0)) {
-    if (!ctx) throw std::string("no usable HIP device: ") + sdf_last_error(nullptr);
-  }
-  ~Ctx() { sdf_destroy(ctx); }  // (with the handles still live: include/sedef_hip.h)
-  void check(int rc, const char *what) const {
-    if (rc != SDF_OK) throw std::string(what) + ": " + sdf_last_error(ctx);
-  }
-};
+std::map<std::string, long long> fai_lengths(const std::string &ref_path) {
+  std::map<std::string, long long> out;
+  for (auto &r : read_fai(ref_path)) out[r.key] = r.length;
+  return out;
+}
 }  // namespace
 
-int search_command(const SearchParams &p, FILE *out, FILE *log) {
-  using Clock = std::chrono::steady_clock;
+SearchRun::SearchRun(const SearchParams &p, const std::string &ref_path, int device)
+    : p_(p), fai_len_(fai_lengths(ref_path)), fr_(ref_path), computed_(p.kmer_size, p.max_error, p.max_edit_error) {
+  memset(&P_, 0, sizeof P_);
+  ctx_ = sdf_create(device, 0);
+  if (!ctx_) throw std::string("no usable HIP device: ") + sdf_last_error(nullptr);
+}
+SearchRun::~SearchRun() { sdf_destroy(ctx_); }
+
+void SearchRun::check(int rc, const char *what) const {
+  if (rc != SDF_OK) throw std::string(what) + ": " + sdf_last_error(ctx_);
+}
+
+void SearchRun::upload(const std::string &name) {
+  if (chroms_.count(name)) return;
+  const auto it = fai_len_.find(name);
+  if (it == fai_len_.end()) throw "Chromosome " + name + " does not exist";
+  if (it->second > 0x7fffffffLL) throw "Chromosome " + name + " is longer than 2^31 - 1 bases: not supported";
+  const FastaReference::Record rec = fr_.record(name);
+  int64_t off = 0;
+  check(sdf_pool_append_fasta(ctx_, rec.bytes, rec.nbytes, rec.entry->length, rec.entry->line_blen, rec.entry->line_len, chroms_.empty(), &off),
+        "sdf_pool_append_fasta");
+  chroms_[name] = Chrom{off, (int32_t)rec.entry->length};
+}
+void SearchRun::uploaded() { check(sdf_pool_sync(ctx_), "sdf_pool_sync"); }
+
+void SearchRun::index(const std::string &name, bool rc) {
+  if (indices_.count({name, rc})) return;
+  const sdf_minim_range range{chroms_.at(name).off, chroms_.at(name).len, rc ? SDF_MINIM_RC : 0};
+  sdf_search_index *h = nullptr;
+  check(sdf_search_index_build(ctx_, &range, p_.kmer_size, p_.window_size, p_.separate_lowercase, &h), "sdf_search_index_build");
+  indices_[{name, rc}] = h;
+}
+
+void SearchRun::prepare(const std::vector<std::string> &queries) {
+  size_t most = 0;  // the most minimizers a query has: no window holds more
+  for (auto &q : queries) {
+    sdf_search_index_desc d;
+    check(sdf_search_index_info(ctx_, indices_.at({q, false}), &d), "sdf_search_index_info");
+    most = std::max(most, (size_t)d.n_minimizers);
+  }
+  if (!p_.limit_table.empty()) given_ = read_limit_table(p_.limit_table);
+  const std::vector<int32_t> &limit = given_.empty() ? computed_.upto(most + 1) : given_;
+  if (!given_.empty() && given_.size() < most + 1)
+    throw "Limit table " + p_.limit_table + " has " + std::to_string(given_.size() - 1) + " lines; this run needs " + std::to_string(most);
+  for (size_t s = 1; s < limit.size(); s++)
+    if (limit[s] < 1) throw "The limit table has " + std::to_string(limit[s]) + " at " + std::to_string(s) + ": the search needs 1 or more";
+  limit_ = &limit;
+  memset(&P_, 0, sizeof P_);
+  P_.k = p_.kmer_size, P_.w = p_.window_size, P_.separate_lowercase = p_.separate_lowercase, P_.uppercase_seeds = p_.uppercase_seeds;
+  P_.min_read_size = p_.min_read_size;
+  P_.filter.min_uppercase = p_.min_uppercase, P_.filter.max_error = p_.max_error, P_.filter.max_edit_error = p_.max_edit_error;
+  P_.filter.gap_frequency = p_.gap_frequency;
+  P_.extend.max_error = p_.max_error, P_.extend.max_edit_error = p_.max_edit_error, P_.extend.max_sd_size = p_.max_sd_size;
+  P_.limit = limit.data(), P_.n_limit = limit.size();
+}
+
+void SearchRun::run(const std::vector<SearchPair> &pairs, int n_lanes, std::vector<sdf_search_pair_hit> &hits, std::vector<uint64_t> &first) {
+  const size_t n_wide = (size_t)stage_settings().search_wide;
+  first.assign(pairs.size() + 1, 0);
+  if (n_lanes > 1) {
+    // SDF_SEARCH_LANES=N: every pair as one job of one call, N of them in flight; the hits in the pairs' order
+    sdf_search_lanes *lanes = nullptr;
+    check(sdf_search_lanes_open(ctx_, n_lanes, &lanes), "sdf_search_lanes_open");
+    std::vector<sdf_search_pair_job> jobs;
+    for (auto &pr : pairs)
+      jobs.push_back(sdf_search_pair_job{indices_.at({pr.q, false}), indices_.at({pr.r, pr.reverse}), (pr.q == pr.r) && !pr.reverse, 0});
+    std::vector<sdf_search_pair_stats> stats(jobs.size());
+    // (an overflow costs a second run of EVERY pair, where the loop repeats one: room for 4,096 hits a pair from the start)
+    hits.resize(std::max<size_t>(1024, 4096 * jobs.size()));
+    size_t used = 0;
+    int rc = sdf_search_pairs_indexed(ctx_, lanes, jobs.data(), jobs.size(), &P_, n_wide, hits.data(), hits.size(), &used, first.data(), stats.data());
+    if (rc == SDF_ERR_CIGAR_OVERFLOW) {
+      hits.resize(used + used / 2);
+      rc = sdf_search_pairs_indexed(ctx_, lanes, jobs.data(), jobs.size(), &P_, n_wide, hits.data(), hits.size(), &used, first.data(), stats.data());
+    }
+    check(rc, "sdf_search_pairs_indexed");
+    check(sdf_search_lanes_close(ctx_, lanes), "sdf_search_lanes_close");
+    hits.resize(used);
+    for (auto &st : stats) attempted_ += st.attempted, jaccard_failed_ += st.jaccard_failed, interval_failed_ += st.interval_failed;
+  } else {
+    hits.clear();
+    std::vector<sdf_search_pair_hit> one(1024);
+    for (size_t j = 0; j < pairs.size(); j++) {
+      const SearchPair &pr = pairs[j];
+      P_.same_genome = (pr.q == pr.r) && !pr.reverse;
+      P_.extend.same_genome = P_.same_genome;
+      const sdf_search_index *qh = indices_.at({pr.q, false}), *rh = indices_.at({pr.r, pr.reverse});
+      size_t used = 0;
+      sdf_search_pair_stats st;
+      // (SDF_SEARCH_WIDE_DEVICE=N: the seeding's WIDE / FOUND_WIDE windows on the device; 0 is sdf_search_pair_indexed itself)
+      int rc = sdf_search_pair_indexed_wide(ctx_, qh, rh, &P_, one.data(), one.size(), &used, &st, n_wide);
+      if (rc == SDF_ERR_CIGAR_OVERFLOW) {
+        one.resize(used + used / 2);
+        rc = sdf_search_pair_indexed_wide(ctx_, qh, rh, &P_, one.data(), one.size(), &used, &st, n_wide);
+      }
+      check(rc, "sdf_search_pair_indexed");
+      hits.insert(hits.end(), one.begin(), one.begin() + (long)used);
+      first[j + 1] = hits.size();
+      attempted_ += st.attempted, jaccard_failed_ += st.jaccard_failed, interval_failed_ += st.interval_failed;
+    }
+  }
+  total_ += (long long)hits.size(), pairs_ += (long long)pairs.size();
+}
+
+std::string SearchRun::bed(const SearchPair &pair, const sdf_search_pair_hit &h) const {
+  return search_hit_bed(pair.q, pair.r, h.query_start, h.query_end, h.ref_start, h.ref_end, pair.reverse, (size_t)chroms_.at(pair.r).len);
+}
+
+void SearchRun::log_totals(FILE *log, int n_lanes, double seconds) const {
+  fprintf(log, "Total:           = %10lld\n", total_);
+  fprintf(log, "Fails: attempts  = %10lld\n       Jaccard   = %10lld\n       interval  = %10lld\n", attempted_, jaccard_failed_, interval_failed_);
+  const std::string in_lanes = n_lanes > 1 ? ", " + std::to_string(n_lanes) + " lanes" : "";  // (lanes build no index: the counts stay)
+  fprintf(log, "Indexes built: %lld for %lld pairs%s (%zu chromosomes resident, limit table of %zu entries) in %.1fs\n",
+          sdf_search_index_builds(ctx_), pairs_, in_lanes.c_str(), chroms_.size(), limit_ ? limit_->size() - 1 : (size_t)0, seconds);
+}
+
+void log_search_parameters(const SearchParams &p, FILE *log) {
   fprintf(log,
           "        Parameters: READ_SIZE      = %d\n"
           "                    MAX_ERROR      = %.2f (%.2f EDIT + %.2f GAP; GAPFREQ=%.3f)\n",
           p.min_read_size, p.max_error, p.max_edit_error, p.max_error - p.max_edit_error, p.gap_frequency);
+}
+
+// ---- the command ------------------------------------------------------------------------------------------------------
+int search_command(const SearchParams &p, FILE *out, FILE *log) {
+  using Clock = std::chrono::steady_clock;
+  log_search_parameters(p, log);
   fprintf(log, "Reverse complement: %s\nk-mer size:         %d\nWindow size:        %d\n\n", p.reverse ? "true" : "false", p.kmer_size,
           p.window_size);
   auto T = Clock::now();
@@ -324,132 +446,31 @@ int search_command(const SearchParams &p, FILE *out, FILE *log) {
     }
   }
   // every chromosome the run names goes to the device once
-  std::map<std::string, long long> fai_len;
-  for (auto &r : read_fai(ref_path)) fai_len[r.key] = r.length;
-  FastaReference fr(ref_path);
-  Ctx C(stage_settings().device);
-  struct Chrom {
-    int64_t off;
-    int32_t len;
-  };
-  std::map<std::string, Chrom> chroms;
-  auto upload = [&](const std::string &name) {
-    if (chroms.count(name)) return;
-    const auto it = fai_len.find(name);
-    if (it == fai_len.end()) throw "Chromosome " + name + " does not exist";
-    if (it->second > 0x7fffffffLL) throw "Chromosome " + name + " is longer than 2^31 - 1 bases: not supported";
-    const FastaReference::Record rec = fr.record(name);
-    int64_t off = 0;
-    C.check(sdf_pool_append_fasta(C.ctx, rec.bytes, rec.nbytes, rec.entry->length, rec.entry->line_blen, rec.entry->line_len, chroms.empty(), &off),
-            "sdf_pool_append_fasta");
-    chroms[name] = Chrom{off, (int32_t)rec.entry->length};
-  };
-  for (auto &r : rr) upload(r);
-  for (auto &q : qr) upload(q);
-  C.check(sdf_pool_sync(C.ctx), "sdf_pool_sync");
+  SearchRun R(p, ref_path, stage_settings().device);
+  for (auto &r : rr) R.upload(r);
+  for (auto &q : qr) R.upload(q);
+  R.uploaded();
   // one index per (name, strand): the references on the strand of -r, then the queries that are not there yet, forward
-  std::map<std::pair<std::string, bool>, sdf_search_index *> indices;
-  size_t most = 0;  // the most minimizers a query has: no window holds more
-  auto build = [&](const std::string &name, bool rc) {
-    if (indices.count({name, rc})) return;
-    const sdf_minim_range range{chroms[name].off, chroms[name].len, rc ? SDF_MINIM_RC : 0};
-    sdf_search_index *h = nullptr;
-    C.check(sdf_search_index_build(C.ctx, &range, p.kmer_size, p.window_size, p.separate_lowercase, &h), "sdf_search_index_build");
-    indices[{name, rc}] = h;
-  };
-  for (auto &r : rr) build(r, p.reverse);
-  for (auto &q : qr) build(q, false);
-  for (auto &q : qr) {
-    sdf_search_index_desc d;
-    C.check(sdf_search_index_info(C.ctx, indices[{q, false}], &d), "sdf_search_index_info");
-    most = std::max(most, (size_t)d.n_minimizers);
-  }
+  for (auto &r : rr) R.index(r, p.reverse);
+  for (auto &q : qr) R.index(q, false);
   fprintf(log, "Building index took %.1fs\n", std::chrono::duration<double>(Clock::now() - T).count());
   T = Clock::now();
-  // the caller's table, sized up front: limit[s] for every s a window of this run can have
-  LimitTable computed(p.kmer_size, p.max_error, p.max_edit_error);
-  std::vector<int32_t> given;
-  if (!p.limit_table.empty()) given = read_limit_table(p.limit_table);
-  const std::vector<int32_t> &limit = given.empty() ? computed.upto(most + 1) : given;
-  if (!given.empty() && given.size() < most + 1)
-    throw "Limit table " + p.limit_table + " has " + std::to_string(given.size() - 1) + " lines; this run needs " + std::to_string(most);
-  for (size_t s = 1; s < limit.size(); s++)
-    if (limit[s] < 1) throw "The limit table has " + std::to_string(limit[s]) + " at " + std::to_string(s) + ": the search needs 1 or more";
-  sdf_search_pair_params P;
-  memset(&P, 0, sizeof P);
-  P.k = p.kmer_size, P.w = p.window_size, P.separate_lowercase = p.separate_lowercase, P.uppercase_seeds = p.uppercase_seeds;
-  P.min_read_size = p.min_read_size;
-  P.filter.min_uppercase = p.min_uppercase, P.filter.max_error = p.max_error, P.filter.max_edit_error = p.max_edit_error;
-  P.filter.gap_frequency = p.gap_frequency;
-  P.extend.max_error = p.max_error, P.extend.max_edit_error = p.max_edit_error, P.extend.max_sd_size = p.max_sd_size;
-  P.limit = limit.data(), P.n_limit = limit.size();
-  long long total = 0, attempted = 0, jaccard_failed = 0, interval_failed = 0, pairs = 0;
-  const size_t n_wide = (size_t)stage_settings().search_wide;
-  std::vector<sdf_search_pair_hit> hits(1024);
-  std::string text;
+  R.prepare(qr);
+  std::vector<SearchPair> pairs;
+  for (auto &r : rr)
+    for (auto &q : qr) pairs.push_back(SearchPair{q, r, p.reverse});
   const int n_lanes = stage_settings().search_lanes;
-  if (n_lanes > 1) {
-    // SDF_SEARCH_LANES=N: every pair of the loop below as one job of one call, N of them in flight; the lines in the loop's order
-    sdf_search_lanes *lanes = nullptr;
-    C.check(sdf_search_lanes_open(C.ctx, n_lanes, &lanes), "sdf_search_lanes_open");
-    std::vector<sdf_search_pair_job> jobs;
-    for (auto &r : rr)
-      for (auto &q : qr) jobs.push_back(sdf_search_pair_job{indices[{q, false}], indices[{r, p.reverse}], (q == r) && !p.reverse, 0});
-    std::vector<uint64_t> first(jobs.size() + 1);
-    std::vector<sdf_search_pair_stats> stats(jobs.size());
-    // (an overflow costs a second run of EVERY pair, where the loop repeats one: room for 4,096 hits a pair from the start)
-    hits.resize(std::max(hits.size(), 4096 * jobs.size()));
-    size_t used = 0;
-    int rc = sdf_search_pairs_indexed(C.ctx, lanes, jobs.data(), jobs.size(), &P, n_wide, hits.data(), hits.size(), &used, first.data(), stats.data());
-    if (rc == SDF_ERR_CIGAR_OVERFLOW) {
-      hits.resize(used + used / 2);
-      rc = sdf_search_pairs_indexed(C.ctx, lanes, jobs.data(), jobs.size(), &P, n_wide, hits.data(), hits.size(), &used, first.data(), stats.data());
-    }
-    C.check(rc, "sdf_search_pairs_indexed");
-    C.check(sdf_search_lanes_close(C.ctx, lanes), "sdf_search_lanes_close");
-    size_t j = 0;
-    for (auto &r : rr)
-      for (auto &q : qr) {
-        text.clear();
-        for (size_t i = (size_t)first[j]; i < (size_t)first[j + 1]; i++)
-          text += search_hit_bed(q, r, hits[i].query_start, hits[i].query_end, hits[i].ref_start, hits[i].ref_end, p.reverse,
-                                 (size_t)chroms[r].len) + "\n";
-        fwrite(text.data(), 1, text.size(), out);
-        attempted += stats[j].attempted, jaccard_failed += stats[j].jaccard_failed, interval_failed += stats[j].interval_failed;
-        j += 1;
-      }
-    total = (long long)used, pairs = (long long)jobs.size();
-  } else {
-    for (auto &r : rr)
-      for (auto &q : qr) {
-        P.same_genome = (q == r) && !p.reverse;
-        P.extend.same_genome = P.same_genome;
-        const sdf_search_index *qh = indices[{q, false}], *rh = indices[{r, p.reverse}];
-        size_t used = 0;
-        sdf_search_pair_stats st;
-        // (SDF_SEARCH_WIDE_DEVICE=N: the seeding's WIDE / FOUND_WIDE windows on the device; 0 is sdf_search_pair_indexed itself)
-        int rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
-        if (rc == SDF_ERR_CIGAR_OVERFLOW) {
-          hits.resize(used + used / 2);
-          rc = sdf_search_pair_indexed_wide(C.ctx, qh, rh, &P, hits.data(), hits.size(), &used, &st, n_wide);
-        }
-        C.check(rc, "sdf_search_pair_indexed");
-        text.clear();
-        for (size_t i = 0; i < used; i++)
-          text += search_hit_bed(q, r, hits[i].query_start, hits[i].query_end, hits[i].ref_start, hits[i].ref_end, p.reverse,
-                                 (size_t)chroms[r].len) + "\n";
-        fwrite(text.data(), 1, text.size(), out);
-        total += (long long)used, attempted += st.attempted, jaccard_failed += st.jaccard_failed, interval_failed += st.interval_failed;
-        pairs += 1;
-      }
+  std::vector<sdf_search_pair_hit> hits;
+  std::vector<uint64_t> first;
+  R.run(pairs, n_lanes, hits, first);
+  std::string text;
+  for (size_t j = 0; j < pairs.size(); j++) {
+    text.clear();
+    for (size_t i = (size_t)first[j]; i < (size_t)first[j + 1]; i++) text += R.bed(pairs[j], hits[i]) + "\n";
+    fwrite(text.data(), 1, text.size(), out);
   }
   fflush(out);
-  fprintf(log, "Total:           = %10lld\n", total);
-  fprintf(log, "Fails: attempts  = %10lld\n       Jaccard   = %10lld\n       interval  = %10lld\n", attempted, jaccard_failed, interval_failed);
-  const std::string in_lanes = n_lanes > 1 ? ", " + std::to_string(n_lanes) + " lanes" : "";  // (lanes build no index: the counts stay)
-  fprintf(log, "Indexes built: %lld for %lld pairs%s (%zu chromosomes resident, limit table of %zu entries) in %.1fs\n",
-          sdf_search_index_builds(C.ctx), pairs, in_lanes.c_str(), chroms.size(), limit.size() - 1,
-          std::chrono::duration<double>(Clock::now() - T).count());
+  R.log_totals(log, n_lanes, std::chrono::duration<double>(Clock::now() - T).count());
   return 0;
 }
 

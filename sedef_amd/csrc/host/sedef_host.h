@@ -547,7 +547,8 @@ struct SearchParams {  // defaults: src/globals.cc
   std::string limit_table;
   std::vector<std::string> pos;  // genome.fa query ref
 };
-SearchParams parse_search_args(int argc, char **argv);  // the arguments behind `sedef search`
+SearchParams parse_search_options(int argc, char **argv);  // the options and whatever positionals there are
+SearchParams parse_search_args(int argc, char **argv);     // the arguments behind `sedef search`: ... and its three positionals
 std::string search_hit_bed(const std::string &qname, const std::string &rname, int qs, int qe, int ref_start, int ref_end, bool ref_rc,
                            size_t ref_len);
 int search_command(const SearchParams &p, FILE *out, FILE *log);
@@ -560,6 +561,30 @@ void bucket_alignments_extern(const std::string &bed_path, int nbins, const std:
 // and the caller buckets on the host path.
 bool bucket_alignments_records(const std::string &bed_path, int nbins, const std::string &output_dir, const std::string &reference,
                                const BucketParams &bp, FILE *log, int form, int device);
+// The host path of bucket_alignments_extern on seed lines wherever they lie: each_file calls its visitor once per seeds file, in
+// the order the files are read (that of their names), with the file's name and its lines.
+using SeedStreamVisitor = std::function<void(const std::string &file, std::istream &lines)>;
+void bucket_alignments_streams(const std::function<void(const SeedStreamVisitor &)> &each_file, int nbins, const std::string &output_dir, bool extend,
+                               const std::string &reference, const BucketParams &bp, FILE *log);
+
+// ---- `sedef seeds` (seeds_cmd.cc): what sedef.sh:133-140,169 run as two `sedef search -t` processes per pair of groups and one
+// `sedef align bucket`, in one process and one device context ------------------------------------------------------------------
+struct SeedsPair {  // one chromosome pair of the run, as `search [-r] -t i j` takes it
+  int i, j;         // query group, reference group: the pair's lines belong to <i>_<j>_<n|y>.bed
+  bool reverse;
+  std::string q, r;  // same_genome = (q == r) && !reverse
+};
+// Every pair of the run in sedef.sh's order: reference group j = 0 .., query group i = j .., forward then reverse, and within a
+// job r over group j outside q over group i (for i == j the full square, both orders of a pair).
+std::vector<SeedsPair> seeds_pairs(const std::vector<std::vector<std::string>> &groups);
+struct SeedsParams {
+  SearchParams search;  // pos: genome.fa, buckets/
+  BucketParams bucket;
+  int nbins = 0;
+  std::string seeds_dir;  // --seeds-dir: also the files sedef.sh would have
+};
+SeedsParams parse_seeds_args(int argc, char **argv);  // throws for -r / -t, a missing -n, a missing positional
+int seeds_command(const SeedsParams &p, FILE *log);
 
 // ---- the stage driver's own settings ---------------------------------------------------------------------
 // (the DP library's are include/sedef_hip.h: sdf_config).  Read from the environment in ONE place -- StageSettings::from_env,

@@ -141,6 +141,14 @@ int main(int argc, char **argv) {
               "  than 256 found SDs are seeded on the device instead of one at a time on the host (same output)\n"
               "  SDF_SEARCH_LANES=N (1..16, default 1): N chromosome pairs of a -t run in flight on the GPU at once, each on a\n"
               "  lane of its own; the chromosomes and their indexes are shared (same output)\n"
+              "sedef seeds [search options] -n [count] [--seeds-dir dir] [genome.fa] [buckets/]\n"
+              "  the whole seeding phase in one process: every pair of `sedef translate` groups on both strands (what two\n"
+              "  `sedef search [-r] -t i j` per pair of groups print) and `sedef align bucket -n [count]` of those hits, which go\n"
+              "  from the search to the bucket files as records on the device; every chromosome is uploaded once and indexed once\n"
+              "  per strand.  Search options: -k -w -u -e -E -g --limit-table (-r and -t are refused); bucket options:\n"
+              "  --extend-ratio, --max-extend, --merge-dist.  --seeds-dir dir: also dir/<i>_<j>_<n|y>.bed, byte for byte what the\n"
+              "  search processes print.  SDF_SEARCH_LANES and SDF_SEARCH_WIDE_DEVICE as for `sedef search`.  Hits the records do not\n"
+              "  take (a flipped coordinate below 0, more than 4096 groups) are bucketed on the host path, said in one line on stderr\n"
               "sedef translate [genome.fa]\n"
               "  the chromosome groups of -t on stderr, their number on stdout\n"
               "  SDF_TEST_TRANSLATE_LIMIT (tests only): the group size limit in bases instead of 100 MB\n"
@@ -151,6 +159,8 @@ int main(int argc, char **argv) {
       return 0;
     } else if (command == "search") {
       return search_command(parse_search_args(argc - 2, argv + 2), stdout, stderr);
+    } else if (command == "seeds") {
+      return seeds_command(parse_seeds_args(argc - 2, argv + 2), stderr);
     } else if (command == "translate") {
       return translate_command(argv[2], stdout, stderr);
     } else if (command == "align") {

@@ -102,6 +102,29 @@ inline int check_bucket(const sdf_seed_hit *hits, size_t n, const int32_t *chr_g
   return SDF_OK;
 }
 
+// What every form of sdf_seed_records asks (include/sedef_hip.h), in order; the first refusal is the call's.  The pointers are the
+// caller's arrays wherever they lie ...
+inline int check_seed_scalars(const void *hits, size_t n, const void *first, const void *jobs, size_t n_jobs, const void *out, const char **why) {
+  if (n > ((size_t)1 << 30)) return *why = "more than 2^30 hits in one call", SDF_ERR_UNSUPPORTED;
+  if (n > 0 && (!hits || !first || !jobs || !out)) return *why = "invalid arguments", SDF_ERR_INVALID;
+  if (n > 0 && n_jobs == 0) return *why = "first[n_jobs] != n", SDF_ERR_INVALID;
+  return SDF_OK;
+}
+// ... and, where first[] and the job table are the host's, of every entry (with n == 0 too, where they are given).
+inline int check_seed(const void *hits, size_t n, const uint64_t *first, const sdf_seed_job *jobs, size_t n_jobs, const void *out, std::string *why) {
+  const char *w = "";
+  if (int rc = check_seed_scalars(hits, n, first, jobs, n_jobs, out, &w)) return *why = w, rc;
+  for (size_t j = 0; jobs && j < n_jobs; j++)
+    if (jobs[j].reserved != 0 || (jobs[j].flags & ~SDF_SEED_RC))
+      return *why = "job " + std::to_string(j) + ": reserved must be 0, flags SDF_SEED_RC or 0", SDF_ERR_UNSUPPORTED;
+  if (!first) return SDF_OK;  // (n == 0 and no table)
+  if (first[0] != 0) return *why = "first[0] != 0", SDF_ERR_INVALID;
+  for (size_t j = 0; j < n_jobs; j++)
+    if (first[j + 1] < first[j]) return *why = "first[] decreases at job " + std::to_string(j), SDF_ERR_INVALID;
+  if (first[n_jobs] != n) return *why = "first[n_jobs] != n", SDF_ERR_INVALID;
+  return SDF_OK;
+}
+
 // The tail of a counted output, behind the launches that filled d_first[0 .. n] on `st`: first[0 .. n] back (a host form), or
 // d_first[n] alone (first == nullptr: a device form), one wait, *used = the need, and SDF_ERR_CIGAR_OVERFLOW -- "<before>
 // <need> <after>" -- when the need exceeds cap.

@@ -216,6 +216,29 @@ __global__ void bucket_flush_keys_kernel(const BucketBox *, const uint32_t *, co
 __global__ void bucket_class_kernel(const unsigned long long *, const uint32_t *, const BucketRec *, const BucketBox *, int,
                                     sdf_bucket_hit *, uint32_t *, uint32_t *, unsigned long long *);
 __global__ void bucket_deal_kernel(const uint32_t *, const uint32_t *, int, int, sdf_bucket_hit *);
+// seed_records.hip
+static_assert(sizeof(sdf_seed_job) == 24 && sizeof(sdf_search_pair_hit) == 24, "include/sedef_hip.h");
+// The job of hit t: the last j in [0, n_jobs) with first[j] <= t (n_jobs >= 1).  Jobs without hits repeat a value of first[] and
+// are stepped over; whatever first[] holds, the answer is inside the job table.
+__host__ __device__ inline size_t seed_job_of(const uint64_t *first, const size_t n_jobs, const uint64_t t) {
+  size_t lo = 0, hi = n_jobs;  // (the answer is in [lo, hi))
+  while (hi - lo > 1) {
+    const size_t mid = lo + (hi - lo) / 2;
+    if (first[mid] <= t) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+// The record of a hit of job `job` (include/sedef_hip.h: sdf_seed_records), the one form the kernel and the host form share: the
+// flip of search_hit_bed in the low 32 bits of its size_t arithmetic.
+__host__ __device__ inline sdf_seed_hit seed_record(const sdf_search_pair_hit &h, const sdf_seed_job &job) {
+  const bool rc = (job.flags & SDF_SEED_RC) != 0;
+  const uint32_t len = (uint32_t)(uint64_t)job.ref_len;
+  const int32_t r_start = rc ? (int32_t)(len - (uint32_t)h.ref_end + 1u) : h.ref_start;
+  const int32_t r_end = rc ? (int32_t)(len - (uint32_t)h.ref_start + 1u) : h.ref_end;
+  return sdf_seed_hit{job.q_chr, h.query_start, h.query_end, job.r_chr, r_start, r_end, rc ? SDF_SEED_RC : 0u, 0u};
+}
+__global__ void seed_records_kernel(const sdf_search_pair_hit *, uint32_t, const uint64_t *, const sdf_seed_job *, size_t, sdf_seed_hit *);
 // anchors.hip
 struct AnchorPairDev {
   int64_t q_off, r_off;    // byte offsets of the raw sequences in the pool

@@ -13,13 +13,14 @@ LIB = os.path.join(_HERE, "lib", "libsedef_host.so")
 CLI = os.path.join(_HERE, "bin", "sedef")
 MULTI = os.path.join(_HERE, "bin", "sdf_multi")
 _SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "host_threads.cc", "stage_settings.cc", "dp_provider.cc", "pair_job.cc",
-            "stage_driver.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "search_cmd.cc", "host_cabi.cc"]
+            "stage_driver.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "search_cmd.cc", "seeds_cmd.cc", "host_cabi.cc"]
 
 
 def build_host(force=False):
     """g++ build of the host library and the `sedef` CLI (needs libsedef_hip.so next to it)."""
     srcs = [os.path.join(HOST_SRC, f) for f in _SOURCES]
-    deps = srcs + [os.path.join(HOST_SRC, "sedef_host.h"), os.path.join(HOST_SRC, "stage_internal.h"), os.path.join(HOST_SRC, "sedef_main.cc"),
+    deps = srcs + [os.path.join(HOST_SRC, "sedef_host.h"), os.path.join(HOST_SRC, "stage_internal.h"), os.path.join(HOST_SRC, "search_run.h"),
+                   os.path.join(HOST_SRC, "sedef_main.cc"),
                    os.path.join(HOST_SRC, "multi_gpu.cc")]
     multi_ok = os.path.exists(MULTI) or os.path.exists(MULTI + ".skipped")
     built = [LIB, CLI] + ([MULTI] if os.path.exists(MULTI) else [])

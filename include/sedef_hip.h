@@ -1547,6 +1547,49 @@ int sdf_seeds_bucket_merge(sdf_ctx *ctx, const sdf_search_pair_hit *hits, size_t
                            size_t n_jobs, const int32_t *chr_group, size_t n_chr, const int32_t *group_pair_order, size_t n_groups,
                            const sdf_bucket_params *params, sdf_bucket_hit *out, size_t out_cap, size_t *n_out, size_t *n_dropped);
 
+/* ---- pair recall: which records of a gold standard a set of found pairs hits, and how much of them (pair_recall.hip) ----------
+ * The per-pair comparison `sedef stats recall` prints (the reference's scratch/check-overlap.py over `bedtools pairtopair -type
+ * both`; bedtools is no part of this build, so THIS is the project's statement of that join).  A RECORD of either set is two ENDS,
+ * bases [start1, end1) of chromosome chr1 and [start2, end2) of chr2; bit 0 of `flags` is the strand of end 1, bit 1 that of
+ * end 2 (set: reverse).  Chromosome ids are any numbering the two sets share.
+ *   Two ends MEET when they lie on the same chromosome id, min(end) - max(start) >= 1 (ends that touch do not meet, an empty
+ *   end meets nothing) and their strand bits are equal; the call flag SDF_RECALL_IGNORE_STRAND drops the last clause.
+ *   A found record f HITS a gold record g DIRECTLY when g.1 meets f.1 and g.2 meets f.2, CROSSWISE when g.1 meets f.2 and g.2
+ *   meets f.1; a record that does both is one hit.
+ * Per gold record g, out[g] holds
+ *   n_hits       the found records that hit g, each once
+ *   cov1, cov2   the bases of g's end 1 / end 2 inside the union of the hitting records' matching ends, clipped to that end of
+ *                g: a direct hit gives f.1 to end 1 and f.2 to end 2, a crosswise hit f.2 to end 1 and f.1 to end 2, a record
+ *                that hits both ways gives both
+ *   flags        SDF_RECALL_WIDE: the direct and crosswise hits of g together are more than SDF_RECALL_CAP (a property of the
+ *                inputs, the same in every form).  sdf_pair_recall_host and sdf_pair_recall answer such a record in full;
+ *                sdf_pair_recall_device answers its n_hits, leaves cov1 = cov2 = 0 and leaves the rest to its caller.
+ * Before anything else, in sdf_pair_recall_host and sdf_pair_recall, the first failing record's refusal (gold first):
+ *   SDF_ERR_INVALID      start > end, a start below 0, a chromosome id below 0, reserved != 0, a flags bit above bit 1; a null
+ *                        pointer with a count above 0
+ *   SDF_ERR_UNSUPPORTED  a call flag other than SDF_RECALL_IGNORE_STRAND; more than 2^30 gold or 2^29 found records
+ * sdf_pair_recall_device makes the refusals the host can see (pointers, counts, call flags); a FOUND record that fails the rest
+ * there hits nothing and is counted in d_status[0], a GOLD record that fails it is answered {0, 0, 0, SDF_RECALL_BAD} and counted
+ * in d_status[1]; both words are 0 for a call the other forms accept.  With n_gold == 0 nothing is launched and both are 0.
+ *   sdf_pair_recall_host    plain C++: no context, no device, no error text
+ *   sdf_pair_recall         host arrays in and out: uploads, the launches, one wait, the WIDE records completed on the host
+ *   sdf_pair_recall_device  everything in HBM on the context's stream; nothing is read back and nothing waited for
+ * The launches: recall_entries_kernel (a lane a found record: a sort key (chromosome, start) per end, the longest end), one
+ * radix sort, recall_kernel (a wavefront a gold record).  Buffers of the context that sdf_device_bytes() counts: 48 bytes a
+ * found record and the sort's scratch. */
+#define SDF_RECALL_IGNORE_STRAND 1u /* call flag */
+#define SDF_RECALL_WIDE 1u          /* sdf_pair_recall_rec::flags */
+#define SDF_RECALL_BAD 2u           /* sdf_pair_recall_rec::flags, sdf_pair_recall_device only */
+#define SDF_RECALL_CAP 1024         /* clipped intervals per end that recall_kernel keeps in LDS */
+typedef struct { int32_t chr1, start1, end1, chr2, start2, end2; uint32_t flags; uint32_t reserved; /* must be 0 */ } sdf_pair_rec;
+typedef struct { uint32_t n_hits; int32_t cov1, cov2; uint32_t flags; } sdf_pair_recall_rec;
+int sdf_pair_recall_host(const sdf_pair_rec *gold, size_t n_gold, const sdf_pair_rec *found, size_t n_found, uint32_t flags,
+                         sdf_pair_recall_rec *out /* n_gold */);
+int sdf_pair_recall(sdf_ctx *ctx, const sdf_pair_rec *gold, size_t n_gold, const sdf_pair_rec *found, size_t n_found, uint32_t flags,
+                    sdf_pair_recall_rec *out /* n_gold */);
+int sdf_pair_recall_device(sdf_ctx *ctx, const sdf_pair_rec *d_gold /* HBM */, size_t n_gold, const sdf_pair_rec *d_found, size_t n_found,
+                           uint32_t flags, sdf_pair_recall_rec *d_out /* n_gold */, uint64_t *d_status /* two words */);
+
 /* ---- one-task drop-in: same contract as ksw_extz2_sse (extern/ksw2.h:50).  `km` is ignored
  * like in the reference build (no HAVE_KALLOC).  Uses a process-wide context on device 0 (or
  * the device named by SDF_DEVICE).  On a fatal error prints to stderr and exits with 120, the

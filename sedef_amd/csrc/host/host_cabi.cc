@@ -497,6 +497,30 @@ int sdfh_bucket_records(const char *bed_path, int nbins, const char *out_dir, co
   }
 }
 
+// `sedef stats recall final.bed wgac.tab out.txt` (stats_recall.cc): the MISS and PART lines to out_path, the four summary lines
+// of the command's stdout to buf.  host != 0: sdf_pair_recall_host, no device.
+int sdfh_stats_recall(const char *bed_path, const char *wgac_path, const char *out_path, int host, int ignore_strand, int device, char *buf,
+                      size_t cap) {
+  char *text = nullptr;
+  size_t len = 0;
+  FILE *report = open_memstream(&text, &len);
+  if (!report) {
+    g_err = "open_memstream failed";
+    return -1;
+  }
+  int rc = 0;
+  try {
+    stats_recall(bed_path, wgac_path, out_path, host != 0, ignore_strand != 0, device, report, stderr);
+  } catch (std::string &s) {
+    g_err = s;
+    rc = -1;
+  }
+  fclose(report);
+  if (rc == 0) rc = copy_out(std::string(text, len), buf, cap);
+  free(text);
+  return rc;
+}
+
 // generate_anchors on the host (reference: src/chain.cc:24-101): "q r l has_u;" per anchor, in order
 int sdfh_anchors(const char *query, const char *ref, int kmer, int same_chr, int qstart, int rstart, char *buf,
                  size_t cap) {

@@ -441,6 +441,15 @@ std::string format_double(double x);  // fmt 4.0.1 "{}" of a double, as the refe
 // std::string for a file that is missing, a line with too few fields, a chromosome the index does not know.
 int stats_diff(const std::string &ref_path, const std::string &bed_path, const std::string &wgac_path, bool host, int device, FILE *log);
 
+// ---- `sedef stats recall` (reference: scratch/check-overlap.py; stats_recall.cc) -----------------------------------------
+// Which SDs of the WGAC table final.bed finds: the MISS and PART lines to the file `out_path`, the script's four summary lines
+// to `report`, notes to `log`.  ONE sdf_pair_recall call on `device` joins the two tables (pair_recall.hip); host
+// (SDF_STATS_RECALL_HOST=1, StageSettings::stats_recall_host): sdf_pair_recall_host instead, no device.  ignore_strand
+// (--ignore-strand, StageSettings::stats_recall_ignore_strand): SDF_RECALL_IGNORE_STRAND.  Needs no genome.  Returns 0; throws
+// std::string for a file that is missing or cannot be written, a line with too few fields or a side that starts behind its end.
+int stats_recall(const std::string &bed_path, const std::string &wgac_path, const std::string &out_path, bool host, bool ignore_strand,
+                 int device, FILE *report, FILE *log);
+
 // ---- utilities (reference: src/util.cc:33-48, src/common.h:56-99) ----------------------------------
 void set_alignment_scoring(const Params &p);  // Align::MATCH and co. are process-wide (src/globals.cc:25-28)
 std::vector<std::string> split(const std::string &s, char delim);
@@ -604,6 +613,8 @@ struct StageSettings {
   bool stats_resident = false;  // SDF_STATS_RESIDENT=1: `stats generate` counts on resident chromosomes (StatsParams::resident)
   bool stats_cuts_device = false;  // SDF_STATS_CUTS_DEVICE=1: with stats_resident, the cuts and trims of `stats generate` run on the device too (StatsParams::cuts_device)
   bool stats_diff_host = false;  // SDF_STATS_DIFF_HOST=1: `stats diff` paints and counts on the host (sdf_pool_coverage_host), no device
+  bool stats_recall_host = false;  // SDF_STATS_RECALL_HOST=1: `stats recall` joins the two tables on the host (sdf_pair_recall_host), no device
+  bool stats_recall_ignore_strand = false;  // SDF_STATS_RECALL_IGNORE_STRAND=1, or --ignore-strand on the command line: `stats recall` passes SDF_RECALL_IGNORE_STRAND
   bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
   bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise
   int search_wide = 0;       // SDF_SEARCH_WIDE_DEVICE=N: `search` finishes up to N WIDE / FOUND_WIDE windows of a round's seeding on the device (sdf_search_pair_indexed_wide's n_wide_max; 0: they go to the host)

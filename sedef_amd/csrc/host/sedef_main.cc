@@ -155,7 +155,12 @@ int main(int argc, char **argv) {
               "sedef stats diff [genome.fa] [final.bed] [wgac.tab]\n"
               "  how the SDs of final.bed and of the WGAC table cover the chromosomes final.bed names (seven figures on stderr);\n"
               "  painted and counted on the resident chromosomes in one device call\n"
-              "  SDF_STATS_DIFF_HOST=1 (default 0): the same figures from the host form of that call, without a device\n");
+              "  SDF_STATS_DIFF_HOST=1 (default 0): the same figures from the host form of that call, without a device\n"
+              "sedef stats recall [--ignore-strand] [final.bed] [wgac.tab] [out.txt]\n"
+              "  which SDs of the WGAC table final.bed finds (scratch/check-overlap.py): MISS and PART lines to [out.txt], the\n"
+              "  WGAC / Missed / Partial / Full summary on stdout; the two tables are joined in one device call, no genome needed\n"
+              "  --ignore-strand: ends meet whatever their strands (bedtools' -is)\n"
+              "  SDF_STATS_RECALL_HOST=1 (default 0): the same lines from the host form of that call, without a device\n");
       return 0;
     } else if (command == "search") {
       return search_command(parse_search_args(argc - 2, argv + 2), stdout, stderr);
@@ -237,7 +242,14 @@ int main(int argc, char **argv) {
     } else if (command == "stats") {
       // `sedef stats generate [--max-ok-gap N --min-split N --uppercase N --max-error X] genome.fa final.bed`
       // (reference: src/stats_main.cc:482-510), and `sedef stats diff genome.fa final.bed wgac.tab` (:397-509; stats_diff.cc)
-      Args a(argc - 2, argv + 2);
+      // (`stats recall` (stats_recall.cc) has the one option without a value: taken out before the parser gives it the next token)
+      std::vector<char *> rest;
+      bool ignore_strand = stage_settings().stats_recall_ignore_strand;
+      for (int i = 2; i < argc; i++) {
+        if (std::string(argv[i]) == "--ignore-strand") ignore_strand = true;
+        else rest.push_back(argv[i]);
+      }
+      Args a((int)rest.size(), rest.data());
       StatsParams sp;
       a.get({"max-ok-gap"}, sp.max_ok_gap);
       a.get({"min-split"}, sp.min_split);
@@ -249,6 +261,11 @@ int main(int argc, char **argv) {
       if (a.pos[0] == "diff") {
         if (a.pos.size() < 4) throw std::string("Not enough arguments to stats");
         return stats_diff(a.pos[1], a.pos[2], a.pos[3], stage_settings().stats_diff_host, stage_settings().device, stderr);
+      }
+      if (a.pos[0] == "recall") {
+        if (a.pos.size() < 4) throw std::string("Not enough arguments to stats");
+        return stats_recall(a.pos[1], a.pos[2], a.pos[3], stage_settings().stats_recall_host, ignore_strand, stage_settings().device, stdout,
+                            stderr);
       }
       if (a.pos[0] != "generate") throw std::string("Unknown stats command");
       long long st[3] = {0, 0, 0};

@@ -352,6 +352,8 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(bk_ws, None) X(bk_tmp, None) /* sdf_bucket_merge_device: records, sort keys and places, scan items, runs, slots (sdf_bucket_api.hip: bucket_launch); hipCUB scratch */ \
   X(bk_in, None) X(bk_chr, None) X(bk_pairs, None) X(bk_out, None) /* sdf_bucket_merge: the host form's copies (the two counts in front of the records) */ \
   X(sd_in, None) X(sd_out, None) /* sdf_seed_records: the host form's copies (hits, first[], the job table in one piece; the records) */ \
+  X(rc_ws, None) X(rc_tmp, None) /* sdf_pair_recall_device: the longest end, the entries as made and as sorted (sdf_recall_api.hip: recall_launch); hipCUB scratch */ \
+  X(rc_gold, None) X(rc_found, None) X(rc_out, None) /* sdf_pair_recall: the host form's copies (the two status words in front of the results) */ \
   X(sd_tab, None) X(sd_merged, None) /* sdf_seeds_bucket_merge: the two tables of the merge in one piece; the two counts in front of the merged records */ \
   X(fa_raw, Pool) /* a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta) */           \
   /* lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch */ \

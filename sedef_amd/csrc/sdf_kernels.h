@@ -590,5 +590,48 @@ __global__ void search_accept_tail_kernel(uint64_t *, int, int);
 __global__ void search_accept_append_kernel(AcceptRound, const AcceptWin *, const uint32_t *, const AcceptOff *, const uint32_t *,
                                             sdf_search_found *, unsigned long long, unsigned long long, sdf_search_pair_hit *,
                                             unsigned long long, unsigned long long);
+// pair_recall.hip (include/sedef_hip.h: sdf_pair_recall): the rule, once, for the host form and the kernels
+constexpr int kRecallCap = SDF_RECALL_CAP;
+constexpr unsigned long long kRecallNoKey = ~0ull;  // the sort key of an end that can meet nothing: behind every key of an id
+struct RecallEnd {
+  int32_t chr, start, end;
+  uint32_t strand;
+};
+__host__ __device__ inline RecallEnd recall_end(const sdf_pair_rec &r, const int e) {
+  return e ? RecallEnd{r.chr2, r.start2, r.end2, (r.flags >> 1) & 1u} : RecallEnd{r.chr1, r.start1, r.end1, r.flags & 1u};
+}
+__host__ __device__ inline bool recall_rec_bad(const sdf_pair_rec &r) {
+  return r.chr1 < 0 || r.chr2 < 0 || r.start1 < 0 || r.start2 < 0 || r.start1 > r.end1 || r.start2 > r.end2 || r.reserved != 0 || (r.flags & ~3u);
+}
+// (ends of checked records: 0 <= start <= end, so neither difference leaves an int)
+__host__ __device__ inline bool recall_meets(const RecallEnd &a, const RecallEnd &b, const bool ignore_strand) {
+  const int32_t lo = a.start > b.start ? a.start : b.start, hi = a.end < b.end ? a.end : b.end;
+  return a.chr == b.chr && hi - lo >= 1 && (ignore_strand || a.strand == b.strand);
+}
+// end f of a hitting record clipped to the gold end g it meets, counted from g's first base: start << 32 | end, 0 <= start < end
+__host__ __device__ inline unsigned long long recall_clip(const RecallEnd &g, const RecallEnd &f) {
+  const int32_t lo = (f.start > g.start ? f.start : g.start) - g.start, hi = (f.end < g.end ? f.end : g.end) - g.start;
+  return (unsigned long long)(uint32_t)lo << 32 | (uint32_t)hi;
+}
+__host__ __device__ inline unsigned long long recall_key(const int32_t chr, const long long start) {
+  return (unsigned long long)(uint32_t)chr << 32 | (uint32_t)(start < 0 ? 0 : start);
+}
+// The candidates of a gold end [start, end) among ends sorted by recall_key, none longer than max_len: the keys in
+// [recall_key(chr, start - max_len + 1), recall_key(chr, end)) -- an end that starts at or below start - max_len stops at or
+// below start, one that starts at `end` or behind it starts behind the gold end.
+// What entry (record F, end p) says about gold record G, whose end 1 the entry is a candidate of: *hit -- F's end p meets G.1 and
+// its other end G.2 (p == 0: directly, p == 1: crosswise) --, *counts -- this entry is the one of F's that n_hits counts: the
+// direct one, or the crosswise one of a record without a direct hit --, and the two clipped intervals.
+__host__ __device__ inline void recall_entry(const sdf_pair_rec &G, const sdf_pair_rec &F, const int p, const bool ignore_strand, bool *hit,
+                                             bool *counts, unsigned long long *iv1, unsigned long long *iv2) {
+  const RecallEnd g1 = recall_end(G, 0), g2 = recall_end(G, 1), a = recall_end(F, p), b = recall_end(F, 1 - p);
+  *hit = recall_meets(g1, a, ignore_strand) && recall_meets(g2, b, ignore_strand);
+  *counts = *hit && (p == 0 || !(recall_meets(g1, b, ignore_strand) && recall_meets(g2, a, ignore_strand)));
+  *iv1 = *hit ? recall_clip(g1, a) : 0ull;
+  *iv2 = *hit ? recall_clip(g2, b) : 0ull;
+}
+__global__ void recall_entries_kernel(const sdf_pair_rec *, int, unsigned long long *, uint32_t *, int32_t *, unsigned long long *);
+__global__ void recall_kernel(const sdf_pair_rec *, const sdf_pair_rec *, const unsigned long long *, const uint32_t *, int, const int32_t *,
+                              uint32_t, sdf_pair_recall_rec *, unsigned long long *);
 
 }  // namespace sdf

@@ -13,7 +13,7 @@ LIB = os.path.join(_HERE, "lib", "libsedef_host.so")
 CLI = os.path.join(_HERE, "bin", "sedef")
 MULTI = os.path.join(_HERE, "bin", "sdf_multi")
 _SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "host_threads.cc", "stage_settings.cc", "dp_provider.cc", "pair_job.cc",
-            "stage_driver.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "search_cmd.cc", "seeds_cmd.cc", "host_cabi.cc"]
+            "stage_driver.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "stats_recall.cc", "search_cmd.cc", "seeds_cmd.cc", "host_cabi.cc"]
 
 
 def build_host(force=False):
@@ -280,6 +280,17 @@ def format_double(x):
     lib, buf = load_host(), _buffer()
     lib.sdfh_format_double.argtypes = [C.c_double, C.c_char_p, C.c_size_t]
     _err(lib, lib.sdfh_format_double(float(x), buf, len(buf)))
+    return buf.value.decode()
+
+
+def stats_recall(bed_path, wgac_path, out_path, host=False, ignore_strand=False, device=0):
+    """`sedef stats recall` (csrc/host/stats_recall.cc; reference: scratch/check-overlap.py): which SDs of the WGAC table final.bed
+    finds.  The MISS and PART lines go to out_path; returns the four summary lines the command prints on stdout.  host=True:
+    sdf_pair_recall_host instead of the device call."""
+    lib, buf = load_host(), _buffer()
+    lib.sdfh_stats_recall.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    _err(lib, lib.sdfh_stats_recall(bed_path.encode(), wgac_path.encode(), out_path.encode(), int(bool(host)), int(bool(ignore_strand)),
+                                    int(device), buf, len(buf)))
     return buf.value.decode()
 
 

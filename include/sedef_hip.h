@@ -1590,6 +1590,65 @@ int sdf_pair_recall(sdf_ctx *ctx, const sdf_pair_rec *gold, size_t n_gold, const
 int sdf_pair_recall_device(sdf_ctx *ctx, const sdf_pair_rec *d_gold /* HBM */, size_t n_gold, const sdf_pair_rec *d_found, size_t n_found,
                            uint32_t flags, sdf_pair_recall_rec *d_out /* n_gold */, uint64_t *d_status /* two words */);
 
+/* ---- line order: text lines by eight keys and, inside equal keys, by their bytes; duplicates flagged (line_order.hip) ---------
+ * What `sort -k1,1V -k9,9r -k10,10r -k4,4V -k2,2n -k3,3n -k5,5n -k6,6n | uniq` (LC_ALL=C; sedef.sh:218-229) does with lines the
+ * caller has parsed: `sedef report` is the command over it.  The LINES lie in one byte pool, line i in [off, off + len) -- without
+ * its newline, len 0 is a line --, `off` a multiple of 16 (what lies between a line's end and the next line's start is never
+ * compared, and nothing behind pool_bytes is read).  key[0 .. 7] are eight ASCENDING unsigned keys, most significant first: the
+ * caller has turned the eight sort fields, in the order k1 k9 k10 k4 k2 k3 k5 k6, into ranks or values such that a smaller key
+ * sorts in front (the reversed fields' ranks already reversed).
+ *   The order: by key[0], then key[1], ... key[7]; lines whose eight keys are equal (a RUN) by memcmp over the shorter length,
+ *   the shorter line first when one is a prefix of the other; identical lines in the order of their indices.
+ * order[p] is the index of the line at place p.  flags[p] holds
+ *   SDF_LINE_DUP   the line at place p is byte for byte the line at place p - 1 (what `uniq` drops)
+ *   SDF_LINE_WIDE  place p lies in a run of more than SDF_LINE_RUN lines (a property of the inputs, the same in every form).
+ *                  sdf_line_order_host and sdf_line_order answer such a run in full; sdf_line_order_device leaves its places in
+ *                  index order without SDF_LINE_DUP and leaves the rest to its caller.
+ * *n_kept counts the places without SDF_LINE_DUP.
+ * Refusals of sdf_line_order_host and sdf_line_order, before anything else:
+ *   SDF_ERR_INVALID      a line whose off is no multiple of 16, whose reserved is not 0 or whose range runs past pool_bytes (the
+ *                        first such line's); a null pointer with a count above 0; n_kept missing
+ *   SDF_ERR_UNSUPPORTED  more than 2^30 lines or a pool of 2^40 bytes or more
+ * sdf_line_order_device makes the refusals the host can see (pointers, counts); a line that fails the rest there is ordered by
+ * its keys as a line of no bytes and counted in d_counts[2], which is 0 for a call the other forms accept.  d_counts: three
+ * words -- [0] the places without SDF_LINE_DUP (every place of a WIDE run counts), [1] the WIDE runs, [2] the lines refused.
+ * With n == 0 nothing is launched but the clearing of d_counts.
+ *   sdf_line_order_host    plain C++: no context, no device, no error text
+ *   sdf_line_order         host arrays in and out: uploads, the launches, one wait, the WIDE runs completed on the host
+ *   sdf_line_order_device  everything in HBM on `stream` (NULL: the context's stream); nothing is read back, nothing waited for
+ * The launches: four times line_keys_kernel and a radix sort (least significant pair of keys first, stable), line_heads_kernel
+ * (where a run starts, the runs of two lines and more listed), line_tie_kernel (a wavefront a listed run).  Buffers of the
+ * context that sdf_device_bytes() counts: about 27 bytes a line and the sort's scratch, and in sdf_line_order the pool and records. */
+#define SDF_LINE_DUP 1u  /* flags[p] */
+#define SDF_LINE_WIDE 2u /* flags[p] */
+#define SDF_LINE_RUN 64  /* lines of equal keys that line_tie_kernel orders */
+typedef struct { uint64_t off; uint32_t len; uint32_t reserved; /* must be 0 */ uint32_t key[8]; } sdf_line_rec; /* 48 bytes */
+int sdf_line_order_host(const uint8_t *pool, size_t pool_bytes, const sdf_line_rec *lines, size_t n, uint32_t *order /* n */,
+                        uint32_t *flags /* n */, size_t *n_kept);
+int sdf_line_order(sdf_ctx *ctx, const uint8_t *pool, size_t pool_bytes, const sdf_line_rec *lines, size_t n, uint32_t *order,
+                   uint32_t *flags, size_t *n_kept);
+/* The parse in front of it, on the host: `text` holds lines that end in '\n' (a last line without one counts, an empty text has
+ * none).  Line i goes to pool[lines[i].off ...), each start a multiple of 16, and lines[i].key[] become the eight keys of
+ *   sort -k1,1V -k9,9r -k10,10r -k4,4V -k2,2n -k3,3n -k5,5n -k6,6n     under LC_ALL=C, GNU sort's rules taken literally:
+ *   fields    no -t: a field ends where a non-blank (not ' ', '\t') is followed by a blank, and KEEPS its leading blanks; so two
+ *             tabs in a row do not make an empty field -- a line of `align generate` whose name column is empty has one field
+ *             fewer, and its "field 9" is the second strand.  A field the line does not have is empty.
+ *   V (1, 4)  version order (this file's restatement of the coreutils manual's "version sort": runs of non-digits by the order
+ *             '~' < end < letters < everything else by byte value, runs of digits by value, a file suffix
+ *             (\.[A-Za-z~][A-Za-z0-9~]*)*$ set aside unless the rest is equal, a leading '.' first, equal strings by strcmp):
+ *             key = the rank among the call's distinct values
+ *   r (9, 10) byte strings, the shorter first when one is a prefix: key = the REVERSED rank among the distinct values
+ *   n         the number in front after blanks -- [-]digits[.digits], anything else counts as 0 --: key = its value
+ * *plain = 0 when some n field has a sign or a decimal point in front, more than ten digits or a value of 2^32 or more: the
+ * four n keys are then ranks among the distinct values by numeric comparison, which orders the same on every form, and the
+ * caller keeps to the host form by convention (`sedef report` says so on stderr).  pool == NULL or lines == NULL: only
+ * *pool_bytes and *n, the sizes a second call needs.  SDF_ERR_INVALID: a capacity too small, text missing with text_bytes > 0,
+ * a size pointer missing; SDF_ERR_UNSUPPORTED: more than 2^30 lines, a line of 2^32 bytes or more. */
+int sdf_line_records(const uint8_t *text, size_t text_bytes, uint8_t *pool, size_t pool_cap, size_t *pool_bytes, sdf_line_rec *lines,
+                     size_t lines_cap, size_t *n, int *plain);
+int sdf_line_order_device(sdf_ctx *ctx, const uint8_t *d_pool /* HBM */, size_t pool_bytes, const sdf_line_rec *d_lines, size_t n,
+                          uint32_t *d_order /* n */, uint32_t *d_flags /* n */, uint32_t *d_counts /* three words */, void *stream /* a hipStream_t */);
+
 /* ---- one-task drop-in: same contract as ksw_extz2_sse (extern/ksw2.h:50).  `km` is ignored
  * like in the reference build (no HAVE_KALLOC).  Uses a process-wide context on device 0 (or
  * the device named by SDF_DEVICE).  On a fatal error prints to stderr and exits with 120, the

@@ -521,6 +521,31 @@ int sdfh_stats_recall(const char *bed_path, const char *wgac_path, const char *o
   return rc;
 }
 
+// `sedef report genome.fa inputs... out_dir` (report_cmd.cc): `inputs` is a newline-separated list of *.aligned.bed files or
+// directories of them; counts: the lines of out_dir/aligned.bed and out_dir/final.bed.  host != 0, or SDF_REPORT_HOST=1 in the
+// environment: the two orderings by sdf_line_order_host.  The stats parameters and SDF_STATS_RESIDENT / SDF_STATS_CUTS_DEVICE as
+// for sdfh_stats_generate_cuts.
+int sdfh_report(const char *ref_path, const char *inputs, const char *out_dir, int max_ok_gap, int min_split, int min_uppercase,
+                double max_error, int host, int device, long long *counts) {
+  try {
+    const StageSettings env = StageSettings::from_env();
+    StatsParams sp;
+    sp.resident = env.stats_resident;
+    sp.cuts_device = env.stats_cuts_device;
+    sp.max_ok_gap = max_ok_gap;
+    sp.min_split = min_split;
+    sp.min_uppercase = min_uppercase;
+    sp.max_scaled_error = max_error;
+    return report_command(ref_path, split(inputs, '\n'), out_dir, sp, host != 0 || env.report_host, device, stderr, counts);
+  } catch (std::string &s) {
+    g_err = s;
+    return -1;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 // generate_anchors on the host (reference: src/chain.cc:24-101): "q r l has_u;" per anchor, in order
 int sdfh_anchors(const char *query, const char *ref, int kmer, int same_chr, int qstart, int rstart, char *buf,
                  size_t cap) {

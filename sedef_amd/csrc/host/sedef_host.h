@@ -450,6 +450,17 @@ int stats_diff(const std::string &ref_path, const std::string &bed_path, const s
 int stats_recall(const std::string &bed_path, const std::string &wgac_path, const std::string &out_path, bool host, bool ignore_strand,
                  int device, FILE *report, FILE *log);
 
+// ---- `sedef report` (reference: sedef.sh:218-229; report_cmd.cc) -----------------------------------------------------------
+// The aligned buckets to out_dir/aligned.bed and out_dir/final.bed: every *.aligned.bed of `inputs` (files, or directories of
+// them) ordered and deduplicated as `sort -k1,1V -k9,9r -k10,10r -k4,4V -k2,2n -k3,3n -k5,5n -k6,6n | uniq` does under LC_ALL=C,
+// stats_generate on that file with `sp`, its output ordered and deduplicated the same way.  Each ordering is ONE sdf_line_order
+// call on `device` (line_order.hip); host (SDF_REPORT_HOST=1, StageSettings::report_host): sdf_line_order_host instead, as for
+// a call whose number columns the records do not take (one line on `log`).  counts (may be null): the lines of the two files,
+// which also go to `log`.  Returns 0; throws std::string for an input that is missing, no *.aligned.bed among them, a file that
+// cannot be written, and what stats_generate throws.
+int report_command(const std::string &ref_path, const std::vector<std::string> &inputs, const std::string &out_dir, const StatsParams &sp,
+                   bool host, int device, FILE *log, long long *counts);
+
 // ---- utilities (reference: src/util.cc:33-48, src/common.h:56-99) ----------------------------------
 void set_alignment_scoring(const Params &p);  // Align::MATCH and co. are process-wide (src/globals.cc:25-28)
 std::vector<std::string> split(const std::string &s, char delim);
@@ -614,6 +625,7 @@ struct StageSettings {
   bool stats_cuts_device = false;  // SDF_STATS_CUTS_DEVICE=1: with stats_resident, the cuts and trims of `stats generate` run on the device too (StatsParams::cuts_device)
   bool stats_diff_host = false;  // SDF_STATS_DIFF_HOST=1: `stats diff` paints and counts on the host (sdf_pool_coverage_host), no device
   bool stats_recall_host = false;  // SDF_STATS_RECALL_HOST=1: `stats recall` joins the two tables on the host (sdf_pair_recall_host), no device
+  bool report_host = false;  // SDF_REPORT_HOST=1: `report` orders and deduplicates its lines on the host (sdf_line_order_host), no device for the two orderings
   bool stats_recall_ignore_strand = false;  // SDF_STATS_RECALL_IGNORE_STRAND=1, or --ignore-strand on the command line: `stats recall` passes SDF_RECALL_IGNORE_STRAND
   bool stage_resident = false;  // SDF_STAGE_RESIDENT=1: `align generate` runs on chromosomes uploaded once per process (load_stage_genome)
   bool fetch_device = false;    // SDF_STAGE_FETCH_DEVICE=1: while chromosomes are resident, a super-batch reads its sequences back from the device pool (one sdf_pool_fetch_ranges call) instead of cutting them out of the mapped FASTA; no effect otherwise

@@ -160,12 +160,33 @@ int main(int argc, char **argv) {
               "  which SDs of the WGAC table final.bed finds (scratch/check-overlap.py): MISS and PART lines to [out.txt], the\n"
               "  WGAC / Missed / Partial / Full summary on stdout; the two tables are joined in one device call, no genome needed\n"
               "  --ignore-strand: ends meet whatever their strands (bedtools' -is)\n"
-              "  SDF_STATS_RECALL_HOST=1 (default 0): the same lines from the host form of that call, without a device\n");
+              "  SDF_STATS_RECALL_HOST=1 (default 0): the same lines from the host form of that call, without a device\n"
+              "sedef report [genome.fa] [align directory | bucket.aligned.bed ...] [out directory]\n"
+              "  the aligned buckets to the SD calls (sedef.sh:218-229): every *.aligned.bed ordered as `sort -k1,1V -k9,9r -k10,10r\n"
+              "  -k4,4V -k2,2n -k3,3n -k5,5n -k6,6n | uniq` orders it (LC_ALL=C) to [out]/aligned.bed, `stats generate` of that file\n"
+              "  ordered the same way to [out]/final.bed; both orderings on the device, the two line counts on stderr\n"
+              "  params: --max-ok-gap, --min-split, --uppercase, --max-error, SDF_STATS_RESIDENT and SDF_STATS_CUTS_DEVICE as for\n"
+              "  `stats generate`.  SDF_REPORT_HOST=1 (default 0): the two orderings from the host form, without a device; a file\n"
+              "  whose number columns hold a sign, a decimal point or more than ten digits takes it too, said in one line on stderr\n");
       return 0;
     } else if (command == "search") {
       return search_command(parse_search_args(argc - 2, argv + 2), stdout, stderr);
     } else if (command == "seeds") {
       return seeds_command(parse_seeds_args(argc - 2, argv + 2), stderr);
+    } else if (command == "report") {
+      // `sedef report [--max-ok-gap N --min-split N --uppercase N --max-error X] genome.fa <align dir | *.aligned.bed ...> out_dir`
+      // (report_cmd.cc; the parameters are those of `stats generate`, which runs between the two orderings)
+      Args a(argc - 2, argv + 2);
+      StatsParams sp;
+      a.get({"max-ok-gap"}, sp.max_ok_gap);
+      a.get({"min-split"}, sp.min_split);
+      a.get({"uppercase"}, sp.min_uppercase);
+      a.getd({"max-error"}, sp.max_scaled_error);
+      sp.resident = stage_settings().stats_resident;
+      sp.cuts_device = stage_settings().stats_cuts_device;
+      if (a.pos.size() < 3) throw std::string("Not enough arguments to report");
+      return report_command(a.pos[0], std::vector<std::string>(a.pos.begin() + 1, a.pos.end() - 1), a.pos.back(), sp,
+                            stage_settings().report_host, stage_settings().device, stderr, nullptr);
     } else if (command == "translate") {
       return translate_command(argv[2], stdout, stderr);
     } else if (command == "align") {

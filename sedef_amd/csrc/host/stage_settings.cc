@@ -33,6 +33,7 @@ StageSettings StageSettings::from_env() {
   s.bucket_device = num("SDF_BUCKET_DEVICE", 0, 1, 0) != 0;
   s.stats_diff_host = num("SDF_STATS_DIFF_HOST", 0, 1, 0) != 0;
   s.stats_recall_host = num("SDF_STATS_RECALL_HOST", 0, 1, 0) != 0;
+  s.report_host = num("SDF_REPORT_HOST", 0, 1, 0) != 0;
   s.stats_recall_ignore_strand = num("SDF_STATS_RECALL_IGNORE_STRAND", 0, 1, 0) != 0;
   s.search_wide = (int)num("SDF_SEARCH_WIDE_DEVICE", 0, 1 << 20, 0);
   s.search_lanes = (int)num("SDF_SEARCH_LANES", 1, 16, 1);

@@ -354,6 +354,8 @@ enum class BufGroup { Any, None, BatchCall, Pairs, Pool };
   X(sd_in, None) X(sd_out, None) /* sdf_seed_records: the host form's copies (hits, first[], the job table in one piece; the records) */ \
   X(rc_ws, None) X(rc_tmp, None) /* sdf_pair_recall_device: the longest end, the entries as made and as sorted (sdf_recall_api.hip: recall_launch); hipCUB scratch */ \
   X(rc_gold, None) X(rc_found, None) X(rc_out, None) /* sdf_pair_recall: the host form's copies (the two status words in front of the results) */ \
+  X(lo_ws, None) X(lo_tmp, None) /* sdf_line_order_device: the listed runs' count, sort keys and places twice, head bytes, the list (sdf_report_api.hip: lines_launch); hipCUB scratch */ \
+  X(lo_pool, None) X(lo_lines, None) X(lo_out, None) /* sdf_line_order: the host form's copies (the three counts in front of order and flags) */ \
   X(sd_tab, None) X(sd_merged, None) /* sdf_seeds_bucket_merge: the two tables of the merge in one piece; the two counts in front of the merged records */ \
   X(fa_raw, Pool) /* a piece of a FASTA record's lines on their way into an_pool (sdf_pool_append_fasta) */           \
   /* lane kernel (extz2_lane.hip): records as uploaded, sort keys / values (in, out), sizes and their scans, hipCUB scratch */ \

@@ -633,5 +633,20 @@ __host__ __device__ inline void recall_entry(const sdf_pair_rec &G, const sdf_pa
 __global__ void recall_entries_kernel(const sdf_pair_rec *, int, unsigned long long *, uint32_t *, int32_t *, unsigned long long *);
 __global__ void recall_kernel(const sdf_pair_rec *, const sdf_pair_rec *, const unsigned long long *, const uint32_t *, int, const int32_t *,
                               uint32_t, sdf_pair_recall_rec *, unsigned long long *);
+// line_order.hip (include/sedef_hip.h: sdf_line_order): what the host form and the kernels ask of a line, once
+constexpr int kLineRun = SDF_LINE_RUN;
+__host__ __device__ inline bool line_rec_bad(const sdf_line_rec &r, const unsigned long long pool_bytes) {
+  return (r.off & 15u) != 0 || r.reserved != 0 || r.off > pool_bytes || r.len > pool_bytes - r.off;
+}
+__host__ __device__ inline bool line_keys_equal(const sdf_line_rec &a, const sdf_line_rec &b) {
+  bool same = true;
+  for (int k = 0; k < 8; k++) same &= a.key[k] == b.key[k];
+  return same;
+}
+__global__ void line_keys_kernel(const sdf_line_rec *, const uint32_t *, uint32_t *, unsigned long long *, int, int, unsigned long long,
+                                 uint32_t *);
+__global__ void line_heads_kernel(const sdf_line_rec *, const uint32_t *, int, uint8_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *);
+__global__ void line_tie_kernel(const uint8_t *, unsigned long long, const sdf_line_rec *, int, const uint8_t *, const uint32_t *,
+                                const uint32_t *, uint32_t *, uint32_t *, uint32_t *);
 
 }  // namespace sdf

@@ -13,7 +13,7 @@ LIB = os.path.join(_HERE, "lib", "libsedef_host.so")
 CLI = os.path.join(_HERE, "bin", "sedef")
 MULTI = os.path.join(_HERE, "bin", "sdf_multi")
 _SOURCES = ["alignment.cc", "hit_fasta.cc", "chain.cc", "host_threads.cc", "stage_settings.cc", "dp_provider.cc", "pair_job.cc",
-            "stage_driver.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "stats_recall.cc", "search_cmd.cc", "seeds_cmd.cc", "host_cabi.cc"]
+            "stage_driver.cc", "bucket.cc", "stats.cc", "stats_diff.cc", "stats_recall.cc", "report_cmd.cc", "search_cmd.cc", "seeds_cmd.cc", "host_cabi.cc"]
 
 
 def build_host(force=False):
@@ -292,6 +292,18 @@ def stats_recall(bed_path, wgac_path, out_path, host=False, ignore_strand=False,
     _err(lib, lib.sdfh_stats_recall(bed_path.encode(), wgac_path.encode(), out_path.encode(), int(bool(host)), int(bool(ignore_strand)),
                                     int(device), buf, len(buf)))
     return buf.value.decode()
+
+
+def report(ref_path, inputs, out_dir, max_ok_gap=-1, min_split=1000, min_uppercase=100, max_error=0.5, host=False, device=0):
+    """`sedef report` (csrc/host/report_cmd.cc; reference: sedef.sh:218-229): the *.aligned.bed files of `inputs` (files or
+    directories) ordered and deduplicated to out_dir/aligned.bed, `stats generate` of that file ordered and deduplicated to
+    out_dir/final.bed.  Returns the two files' line counts.  host=True: sdf_line_order_host instead of the device call."""
+    lib = load_host()
+    counts = (C.c_longlong * 2)()
+    lib.sdfh_report.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
+    _err(lib, lib.sdfh_report(ref_path.encode(), "\n".join(inputs).encode(), out_dir.encode(), int(max_ok_gap), int(min_split),
+                              int(min_uppercase), float(max_error), int(bool(host)), int(device), counts))
+    return int(counts[0]), int(counts[1])
 
 
 def bucket(bed_path, nbins, out_dir, reference):
